@@ -1,7 +1,22 @@
 #!/usr/bin/env python
 """bench.py — headline benchmark of the FOCNeRF hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (`metric`, `value`, `unit`, `ms_per_step` = milliseconds per
+timed step, ...). Everything else it can measure — the per-kernel timings and the roofline, the other paths and configurations, the
+combined-render leg, the CPU baselines — runs with `--full` only (and there `--no-extras` / `--no-cpu-baseline` leave parts of it out).
+In every run the training state from before the wall-time-bounded initialisation (seeded model, Adam at step 0, GradScaler at its initial
+scale, RNGs) is restored in place after it, so the W + K steps start from the same state whatever that initialisation did. The per-op
+event pairs inside the timed region (KernelTimer, which `roofline` / `kernels` read) are installed with `--full` only.
+`--dump-outputs DIR` writes what the timed path computed in its last timed step (rank 0) as DIR/<name>.npy (float32; the sampled rows'
+indices float64): the image, depth and weights_sum its render returned, the loss, and the parameters' gradients (the hash-grid table's
+as a fixed, seeded sample of rows).
+With the same arguments the inputs are the same from run to run: seeded model, rays, targets and noise, and the last timed step starts
+from the seeded state the W + K steps start from (restored in place, off the clock), whatever the wall-time-bounded initialisation and
+the earlier steps did. What it computes is then the same in every run up to the rounding of the hash-grid backward, which adds its
+partial sums into the table gradient with atomics in no fixed order. That step starts from a drained queue, so a dump run's ms_per_step
+can come out slightly above a plain run's.
 
 N > 1: one rank per GPU, one OBJECT per rank (weak scaling). Either launched by torch.distributed.run (RANK / WORLD_SIZE in the
 environment), or — `python bench.py --gpus N` on its own — this process starts the N ranks itself (torch.distributed.run as a CHILD
@@ -12,7 +27,7 @@ drawn from synthetic 800x800 views, FOC's default fixed-step renderer (num_steps
 upsample_steps=0, nerf/renderer.py:126-238): one STEP = 4096 rays x 512 samples = 2 097 152 samples
 through R1 -> G1 -> M1(sigma) -> weights -> M1(colour, masked) -> composite -> loss -> backward
 (M2, G2) -> Adam. `value` = samples completed per second, whole job (sum over ranks), inputs resident
-in HBM. Extra keys: `combined_render` (EVERY N: K = N objects, one per rank, full 800x800 view — per-rank field evaluation + exchange by
+in HBM. Extra keys, with `--full`: `combined_render` (EVERY N: K = N objects, one per rank, full 800x800 view — per-rank field evaluation + exchange by
 ray + select/composite + gather, COMBINED.py:592-618 — rays/s, bytes on the wire, share of xGMI and of the field evaluation),
 `render` (full 800x800 view, rays/s), `occupancy_path` (config[2]: march + composite kernels), `roofline` (dominant kernel, timed with
 events on the launch stream), `cpu_baseline` (rank 0 / N=1 only: the CPU oracle port on a bounded sample, and configs[0] — the
@@ -403,13 +418,17 @@ def sample_batch(poses, intr, device, gen):
     return rays_o, rays_d, target
 
 
-def train_step(model, opt, scaler, rays_o, rays_d, target, fused=True, sched=None):
+def train_step(model, opt, scaler, rays_o, rays_d, target, fused=True, sched=None, outputs=None):
     """One iteration of the reference trainer's loop (nerf/utils.py:1108-1119): zero_grad, autocast forward + loss, scaled backward,
-    GradScaler step + update, per-step LR schedule (its EMA update runs once per epoch, :1124, not per step)."""
+    GradScaler step + update, per-step LR schedule (its EMA update runs once per epoch, :1124, not per step). `outputs` (a dict): filled
+    with what the render returned to its caller and the loss, detached (--dump-outputs)."""
     opt.zero_grad(set_to_none=True)
     with torch.autocast("cuda", dtype=torch.float16):
         out = model.render(rays_o, rays_d, staged=False, num_steps=NUM_STEPS, upsample_steps=0, perturb=True, bg_color=None, fused=fused)
         loss = torch.nn.functional.mse_loss(out["image"], target)
+    if outputs is not None:
+        outputs.update({k: out[k].detach() for k in ("image", "depth", "weights_sum") if torch.is_tensor(out.get(k))})
+        outputs["loss"] = loss.detach()
     scaler.scale(loss).backward()
     scaler.step(opt)
     scaler.update()
@@ -427,6 +446,64 @@ def cuda_ray_train_step(model, opt, scaler, rays_o, rays_d, target):
     scaler.step(opt)
     scaler.update()
     return loss
+
+
+def save_training_state(model, opt, sched, scaler, device):
+    """Copies of everything a training step reads besides its batch: parameters and buffers, optimizer state and hyperparameters, LR schedule,
+    GradScaler, the CPU and device RNGs (the step's perturbation noise)."""
+    import copy
+    return {"model": {k: v.detach().clone() for k, v in model.state_dict().items()},
+            "opt": {p: {k: (v.clone() if torch.is_tensor(v) else v) for k, v in s.items()} for p, s in opt.state.items()},
+            "groups": [{k: copy.deepcopy(v) for k, v in g.items() if k != "params"} for g in opt.param_groups],
+            "sched": copy.deepcopy(sched.state_dict()), "scaler": copy.deepcopy(scaler.state_dict()),
+            "rng": (torch.get_rng_state(), torch.cuda.get_rng_state(device))}
+
+
+def restore_training_state(saved, model, opt, sched, scaler, device):
+    """Back to `saved` (save_training_state), in place: the same tensors and allocations, the values they had then. Optimizer state made
+    since then is zeroed in place: for Adam that is its state before the first step (step 0, both moments 0)."""
+    with torch.no_grad():
+        for k, v in model.state_dict().items():
+            v.copy_(saved["model"][k])
+        for p, s in opt.state.items():
+            for k, v in s.items():
+                old = saved["opt"].get(p, {}).get(k)
+                if torch.is_tensor(v) and old is not None:
+                    v.copy_(old)
+                elif torch.is_tensor(v):
+                    v.zero_()
+                elif old is not None:
+                    s[k] = old
+    for g, h in zip(opt.param_groups, saved["groups"]):
+        g.update(h)
+    sched.load_state_dict(saved["sched"])
+    scaler.load_state_dict(saved["scaler"])
+    torch.set_rng_state(saved["rng"][0])
+    torch.cuda.set_rng_state(saved["rng"][1], device)
+
+
+DUMP_TABLE_ROWS = 1 << 18        # rows of the hash-grid table (and of its gradient) written by --dump-outputs: a fixed, seeded sample
+
+
+def dump_outputs(out_dir, outputs, model):
+    """--dump-outputs: the last timed step's results as <out_dir>/<name>.npy, float32 (about 3 MB in all): what its render returned, the
+    loss, and the parameters' gradients (unscaled by the GradScaler) that the optimizer step consumed; the sampled rows' indices float64."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v for k, v in outputs.items()}
+    for name, p in model.named_parameters():
+        if p.grad is None:
+            continue
+        key = name.replace(".", "_") + "_grad"
+        if p.dim() == 2 and p.shape[0] > DUMP_TABLE_ROWS:
+            rows = np.sort(np.random.default_rng(0).choice(p.shape[0], DUMP_TABLE_ROWS, replace=False))
+            arrays[key + "_sample"] = p.grad.index_select(0, torch.from_numpy(rows).to(p.device))
+            arrays[key + "_sample_rows"] = rows.astype(np.float64)            # float64: exact for any row count
+        else:
+            arrays[key] = p.grad
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t if isinstance(t, np.ndarray) else t.detach().float().cpu().numpy())
+    return sorted(arrays)
 
 
 def cpu_baseline(budget_s=10.0, one_core_s=4.0):
@@ -701,8 +778,11 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--render-views", type=int, default=8)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the render / occupancy-path extras")
+    ap.add_argument("--full", action="store_true", help="beyond the headline: per-kernel timings + roofline, the other paths (renders, occupancy "
+                                                         "path, FOC network), the combined-render leg and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path computed in its last step as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the render / occupancy-path extras and the combined-render leg")
     ap.add_argument("--no-fused", action="store_true", help="headline step through the torch glue of NeRFRenderer.run instead of csrc/fixedstep.hip")
     ap.add_argument("--dry-run-cpu", action="store_true", help="no GPU: gloo ranks, combined-render leg on injected CPU ops (launch / collective logic only)")
     ap.add_argument("--combined-views", type=int, default=2)
@@ -766,7 +846,8 @@ def main():
     batches = [sample_batch(poses, intr, device, gen) for _ in range(max(4, min(args.steps + args.warmup, 256)))]
 
     timer = KernelTimer()
-    timer.install()
+    if args.full:
+        timer.install()
     import gc
     gc.collect()
     gc.disable()                      # see progress(): collections happen between the legs, not inside a timed loop
@@ -775,6 +856,9 @@ def main():
     # Initialisation, before the W warm-up steps: the first steps create the persistent scratch buffers (2 GB of records), size the
     # caching allocator's blocks and bring the device out of its idle power state; on a freshly started process the first few hundred
     # milliseconds of work have been seen to run 3-10x slower than steady state. Bounded by wall time, not part of W or K.
+    # How many steps that takes varies from run to run: the training state from before it is restored afterwards (in place: the buffers
+    # stay allocated), so that the W + K steps start from the same seeded state, RNGs included, in every run with the same arguments.
+    state0 = save_training_state(model, opt, sched, scaler, device)
     t_init = time.perf_counter()
     i = 0
     while i < 8 or (time.perf_counter() - t_init < 0.75 and i < 400):
@@ -783,6 +867,9 @@ def main():
         if i % 8 == 0:
             torch.cuda.synchronize()
     init_steps = i
+    restore_training_state(state0, model, opt, sched, scaler, device)
+    if not args.dump_outputs:
+        del state0
     for i in range(args.warmup):
         train_step(model, opt, scaler, *batches[i % len(batches)], fused=fused, sched=sched)
     barrier()
@@ -793,17 +880,36 @@ def main():
     t0 = time.perf_counter()                                 # step is the host's: the region starts from an empty queue, the host's lead grows by ~0.6 ms per step)
     host_marks[0] = t0
     step_marks[0].record()
+    last_step = {} if args.dump_outputs else None
+    paused, resumed = 0.0, None
     for i in range(args.steps):
-        train_step(model, opt, scaler, *batches[(args.warmup + i) % len(batches)], fused=fused, sched=sched)
+        if last_step is not None and i == args.steps - 1:
+            # --dump-outputs: the last timed step starts from the seeded state the W + K steps started from, RNGs included. The steps
+            # before it leave a state that differs in the last bits from run to run (the hash-grid backward adds its partial sums into
+            # the fp16 table gradient with atomics, in no fixed order) and Adam (eps 1e-15) magnifies such differences step by step.
+            # The restore is off the clock: the queue is drained, the state restored, and the step timed from an event of its own.
+            barrier()
+            t_pause = time.perf_counter()
+            restore_training_state(state0, model, opt, sched, scaler, device)
+            del state0
+            barrier()
+            resumed = (torch.cuda.Event(enable_timing=True), time.perf_counter())
+            resumed[0].record()
+            paused = resumed[1] - t_pause
+        train_step(model, opt, scaler, *batches[(args.warmup + i) % len(batches)], fused=fused, sched=sched,
+                   outputs=last_step if i == args.steps - 1 else None)
         step_marks[i + 1].record()
         host_marks[i + 1] = time.perf_counter()
     barrier()
-    el = max_over_ranks(time.perf_counter() - t0)
+    el = max_over_ranks(time.perf_counter() - t0 - paused)
     timer.enabled = False
     ksum = timer.summary()
     count_share = timer.count_share_ms()
     raw_steps = [step_marks[i].elapsed_time(step_marks[i + 1]) for i in range(args.steps)]
     host_steps = [1e3 * (host_marks[i + 1] - host_marks[i]) for i in range(args.steps)]
+    if resumed is not None:                                  # the last step from its own start, not from the end of the one before the restore
+        raw_steps[-1] = resumed[0].elapsed_time(step_marks[-1])
+        host_steps[-1] = 1e3 * (host_marks[-1] - resumed[1])
     per_step = sorted(raw_steps)
     step_stats = {"min": per_step[0], "median": per_step[len(per_step) // 2], "max": per_step[-1],
                   "slowest_step": max(range(args.steps), key=lambda i: raw_steps[i]) if args.steps else None,
@@ -815,35 +921,38 @@ def main():
     samples_per_step = NUM_RAYS * NUM_STEPS
     value = world * samples_per_step * args.steps / el
     progress(f"headline: {1000.0 * el / args.steps:.3f} ms/step")
-    # kernel-only step time (the optimizer is excluded or reported separately): a few more steps with an event pair around
-    # EVERY C-ABI call of the library — what the step costs in this library's kernels, the rest being torch's own (fused Adam, GradScaler
-    # unscale / inf check, fp16 <-> fp32 casts of parameters and gradients, fills, the loss)
     ks_all, n_k = {}, 5
-    try:
-        from focnerf_amd import _lib
-        names = [n for n, (_, a) in _lib.SIGNATURES.items() if a and a[-1] is _lib.c_vp and not n.endswith("_bytes") and not n.endswith("_option")]
-        with LibTimer(names) as lt:
-            m0 = torch.cuda.Event(enable_timing=True)
-            m1 = torch.cuda.Event(enable_timing=True)
-            m0.record()
-            for i in range(n_k):
-                train_step(model, opt, scaler, *batches[i % len(batches)], fused=fused, sched=sched)
-            m1.record()
-            ks_all = lt.summary()
-        lib_ms = sum(n * avg for n, avg in ks_all.values()) / n_k
-        step_stats["library_kernels_ms_per_step"] = lib_ms
-        step_stats["torch_native_ms_per_step"] = max(0.0, m0.elapsed_time(m1) / n_k - lib_ms)
-        step_stats["kernel_only_samples_per_sec"] = samples_per_step / (lib_ms * 1e-3)
-        step_stats["kernel_only_note"] = ("library_kernels = sum of event-timed C-ABI calls per step (every kernel of this library: sample, encoder fwd + "
-                                          "count, both MLPs fwd/bwd, tail fwd/bwd, grid backward); torch_native = the step's remaining GPU time "
-                                          "(Adam, GradScaler, casts, fills, loss), measured over 5 extra steps after the timed region")
-    except Exception as e:
-        step_stats["kernel_only_error"] = repr(e)
-    # the same figure from the committed rocprofv3 kernel trace of this command (profiles/rNN_bench_kernel_stats.csv): sum over this library's
-    # kernels of total duration / steps — no event pairs, no gaps between launches (the event-timed sum above moves by 10 % from run to run)
-    prof = profile_kernel_ms_per_step()
-    if prof is not None:
-        step_stats["from_committed_profile"] = prof       # numbers parsed from a file of an EARLIER run of this command, not measured by this run
+    if args.dump_outputs and rank == 0:        # before anything below trains the model further
+        dump_outputs(args.dump_outputs, last_step, model)
+    if args.full:
+        # kernel-only step time (the optimizer is excluded or reported separately): a few more steps with an event pair around
+        # EVERY C-ABI call of the library — what the step costs in this library's kernels, the rest being torch's own (fused Adam, GradScaler
+        # unscale / inf check, fp16 <-> fp32 casts of parameters and gradients, fills, the loss)
+        try:
+            from focnerf_amd import _lib
+            names = [n for n, (_, a) in _lib.SIGNATURES.items() if a and a[-1] is _lib.c_vp and not n.endswith("_bytes") and not n.endswith("_option")]
+            with LibTimer(names) as lt:
+                m0 = torch.cuda.Event(enable_timing=True)
+                m1 = torch.cuda.Event(enable_timing=True)
+                m0.record()
+                for i in range(n_k):
+                    train_step(model, opt, scaler, *batches[i % len(batches)], fused=fused, sched=sched)
+                m1.record()
+                ks_all = lt.summary()
+            lib_ms = sum(n * avg for n, avg in ks_all.values()) / n_k
+            step_stats["library_kernels_ms_per_step"] = lib_ms
+            step_stats["torch_native_ms_per_step"] = max(0.0, m0.elapsed_time(m1) / n_k - lib_ms)
+            step_stats["kernel_only_samples_per_sec"] = samples_per_step / (lib_ms * 1e-3)
+            step_stats["kernel_only_note"] = ("library_kernels = sum of event-timed C-ABI calls per step (every kernel of this library: sample, encoder fwd + "
+                                              "count, both MLPs fwd/bwd, tail fwd/bwd, grid backward); torch_native = the step's remaining GPU time "
+                                              "(Adam, GradScaler, casts, fills, loss), measured over 5 extra steps after the timed region")
+        except Exception as e:
+            step_stats["kernel_only_error"] = repr(e)
+        # the same figure from the committed rocprofv3 kernel trace of this command (profiles/rNN_bench_kernel_stats.csv): sum over this library's
+        # kernels of total duration / steps — no event pairs, no gaps between launches (the event-timed sum above moves by 10 % from run to run)
+        prof = profile_kernel_ms_per_step()
+        if prof is not None:
+            step_stats["from_committed_profile"] = prof       # numbers parsed from a file of an EARLIER run of this command, not measured by this run
     result = {
         "metric": "train_samples_per_sec", "value": value, "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": 1000.0 * el / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f16",
@@ -951,7 +1060,7 @@ def main():
     rays_o, rays_d = synthetic.get_rays(poses[:1], intr, VIEW, VIEW)
     # single-GPU properties (other paths of the same object) are reported at N = 1 only; the multi-rank runs keep to the headline
     # step plus the one exchange step the path has (combine), so that no rank-local failure can leave the others in a collective
-    if not args.no_extras and world == 1:
+    if args.full and not args.no_extras and world == 1:
         progress("single-GPU extras (torch-glue step, renders, occupancy path)")
         try:
             # ---- the same step through the reference caller's torch glue (NeRFRenderer.run) instead of the fused kernels
@@ -1283,7 +1392,7 @@ def main():
         except Exception as e:   # an extra must never take the headline number down with it
             result["extras_error"] = repr(e)
 
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         # ---- configs[3]/[4]: K = N objects, one per rank, a full 800x800 view end to end (field evaluation + exchange + composite + gather)
         progress("combined-render leg")
         model.eval()
@@ -1352,7 +1461,7 @@ def main():
             result["combined_render"] = {"error": repr(e), "trace": traceback.format_exc()[-800:]}
         guard.cancel()
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # The baseline north_star names: the reference's pure-PyTorch network (--ff off, --tcnn off: nerf/network.py) through the fixed-step
         # renderer on the node's host cores — configs[0] by the protocol of BASELINE.md section 2, IN FULL (one whole 400 x 400 view, median of
         # five full 4096-ray steps: ~2 min on 16 cores). oracle/torch_cpu_nerf.py is the torch-CPU restatement of that configuration, pinned to

@@ -37,8 +37,14 @@ def test_trunc_exp_matches_reference(golden_dir):
     x = torch.from_numpy(g["x"]).requires_grad_(True)
     y = trunc_exp(x)
     y.backward(torch.from_numpy(g["gy"]))
-    np.testing.assert_array_equal(y.detach().numpy(), g["y"])
-    np.testing.assert_array_equal(x.grad.numpy(), g["gx"])
+    # bit for bit the reference's expressions as torch evaluates them on this host ...
+    xt = torch.from_numpy(g["x"])
+    np.testing.assert_array_equal(y.detach().numpy(), xt.exp().numpy())
+    np.testing.assert_array_equal(x.grad.numpy(), (torch.from_numpy(g["gy"]) * xt.clamp(min=-15, max=15).exp()).numpy())
+    # ... and the reference's stored numbers to within 1 ulp: torch's CPU exp kernel is not the same on every host CPU (one element of the 256
+    # has come out 1 ulp apart on another host)
+    np.testing.assert_array_max_ulp(y.detach().numpy(), g["y"], maxulp=1)
+    np.testing.assert_array_max_ulp(x.grad.numpy(), g["gx"], maxulp=1)
 
 
 # ---------------------------------------------------------------- known answers from the source text

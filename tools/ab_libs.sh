@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 REPS=${REPS:-2}
 for rep in $(seq $REPS); do
   for lib in "$@"; do
-    FOCNERF_LIB_PATH=$(realpath "$lib") python3 "$R/bench.py" --steps 40 --warmup 10 --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "
+    FOCNERF_LIB_PATH=$(realpath "$lib") python3 "$R/bench.py" --full --steps 40 --warmup 10 --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d['kernels']

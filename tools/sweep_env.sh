@@ -3,7 +3,7 @@
 VAR=$1; shift
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 for v in "$@"; do
-  env $VAR=$v python3 "$R/bench.py" --steps 30 --warmup 10 --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "
+  env $VAR=$v python3 "$R/bench.py" --full --steps 30 --warmup 10 --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d['kernels']
