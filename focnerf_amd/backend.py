@@ -217,17 +217,46 @@ class _gridencoder:
         st["key"] = None
 
     @staticmethod
+    def binned_workspace_bytes(offsets, B, D, C, L, S, H, gridtype, dt, count_ahead=False):
+        """Bytes of the binned backward's workspace when that backward serves this grid at B points, else 0 (then the scattered-atomic
+        kernel runs; FOCNERF_GRID_ATOMIC=1 forces it). count_ahead: and its count pass may run ahead of it, in or next to the forward
+        (FOC_GRID_PRECOUNT=0: never)."""
+        import os
+        if os.environ.get("FOCNERF_GRID_ATOMIC", "0") == "1" or (count_ahead and (B == 0 or os.environ.get("FOC_GRID_PRECOUNT", "1") == "0")):
+            return 0
+        ws_bytes = lib.foc_grid_encode_backward_workspace_bytes(B, D, C, L, dt)
+        if not ws_bytes or B * 8 * L >= 2 ** 32 or not _gridencoder._binned_ok(offsets, S, H, L, gridtype):
+            return 0
+        return ws_bytes
+
+    @staticmethod
+    def precount_standalone():
+        """FOC_GRID_PRECOUNT=2: the count pass as its own launch (foc_grid_encode_backward_count) instead of riding in the forward's."""
+        import os
+        return os.environ.get("FOC_GRID_PRECOUNT", "1") == "2"
+
+    @staticmethod
+    def _precount_key(inputs, B, L, dt, ws):
+        return (inputs.data_ptr(), B, L, dt, ws.data_ptr())
+
+    @staticmethod
+    def issue_precount_ticket(inputs, B, L, dt, ws):
+        """The ticket of a count pass just enqueued for `inputs` (B points, L levels, table dtype dt) into the header of workspace `ws`,
+        for `grid_encode_backward(..., precount=ticket)`; it supersedes every earlier ticket of the device."""
+        idx, st = _gridencoder._pre_state(inputs.device)
+        st["ticket"] += 1
+        st["key"] = _gridencoder._precount_key(inputs, B, L, dt, ws)
+        return (idx, st["ticket"], st["key"])
+
+    @staticmethod
     def grid_encode_forward_counted(inputs, embeddings, offsets, outputs, B, D, C, L, S, H, gridtype, align_corners, interp, standalone=False):
         """[L,B,C] forward + the backward's count pass. Returns a ticket for `grid_encode_backward(..., precount=ticket)`, or None when
         the binned path does not apply (then nothing was computed: call grid_encode_forward)."""
-        import os
-        if os.environ.get("FOC_GRID_PRECOUNT", "1") == "0" or os.environ.get("FOCNERF_GRID_ATOMIC", "0") == "1":
-            return None
         _gridencoder._common(inputs, embeddings, offsets)
         require_cuda(outputs); _contig(outputs)
         dt = dtype_code(embeddings)
-        ws_bytes = lib.foc_grid_encode_backward_workspace_bytes(B, D, C, L, dt)
-        if not ws_bytes or B * 8 * L >= 2 ** 32 or B == 0 or not _gridencoder._binned_ok(offsets, S, H, L, gridtype):
+        ws_bytes = _gridencoder.binned_workspace_bytes(offsets, B, D, C, L, S, H, gridtype, dt, count_ahead=True)
+        if not ws_bytes:
             return None
         if outputs.dtype != embeddings.dtype or outputs.numel() != L * B * C:
             raise RuntimeError("grid_encode_forward_counted: outputs must be [L,B,C] of the embeddings' dtype")
@@ -242,10 +271,7 @@ class _gridencoder:
             check(lib.foc_grid_encode_forward_counted(ptr(inputs), ptr(embeddings), ptr(offsets), ptr(outputs), B, D, C, L, float(S), H, gridtype,
                                                       int(bool(align_corners)), interp, dt, host, ptr(ws), ws_bytes, stream_of(inputs)),
                   "grid_encode_forward_counted")
-        idx, st = _gridencoder._pre_state(inputs.device)
-        st["ticket"] += 1
-        st["key"] = (inputs.data_ptr(), B, L, dt, ws.data_ptr())
-        return (idx, st["ticket"], st["key"])
+        return _gridencoder.issue_precount_ticket(inputs, B, L, dt, ws)
 
     @staticmethod
     def _precount_valid(ticket, inputs, B, L, dt, ws):
@@ -253,7 +279,7 @@ class _gridencoder:
             return False
         idx, number, key = ticket
         st = _gridencoder._pre.get(idx)
-        return st is not None and st["ticket"] == number and st["key"] == key == (inputs.data_ptr(), B, L, dt, ws.data_ptr())
+        return st is not None and st["ticket"] == number and st["key"] == key == _gridencoder._precount_key(inputs, B, L, dt, ws)
 
     @staticmethod
     def grid_encode_backward(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs, gridtype, align_corners, interp, grad_bl=False,
@@ -264,9 +290,8 @@ class _gridencoder:
         if grad_embeddings.dtype != grad.dtype:
             raise RuntimeError("grid_encode_backward: grad_embeddings must share grad's dtype")
         # D=3, C=2 tables: partition + LDS accumulation instead of scattered atomics (FOCNERF_GRID_ATOMIC=1 forces the atomic kernel)
-        import os
-        ws_bytes = 0 if os.environ.get("FOCNERF_GRID_ATOMIC", "0") == "1" else lib.foc_grid_encode_backward_workspace_bytes(B, D, C, L, dt)
-        if ws_bytes and B * 8 * L < 2 ** 32 and _gridencoder._binned_ok(offsets, S, H, L, gridtype):
+        ws_bytes = _gridencoder.binned_workspace_bytes(offsets, B, D, C, L, S, H, gridtype, dt)
+        if ws_bytes:
             # persistent grow-only scratch (2 GB at B = 2M): a fresh torch.empty per call makes the caching allocator
             # re-malloc it whenever the freed block was split in between (measured: 28 ms hiccups per step)
             ws = _scratch.get("grid_bwd", ws_bytes, grad.device)

@@ -44,9 +44,6 @@ def _fused_backward_switch():
     return get_option("FOC_MLP_BWD_FUSED") != 0
 
 
-_fused_backward_ok = single_pass_backward       # name used by focnerf_amd.field
-
-
 def _keeps_activations(input_dim, hidden_dim, num_layers, activation=0):
     return not (single_pass_backward(input_dim, hidden_dim, num_layers, activation) and os.environ.get("FOC_MLP_RECOMPUTE", "1") != "0")
 

@@ -9,23 +9,103 @@ write them (`foc_ffmlp_forward_planar`, `foc_ffmlp_backward_planar`), so neither
     h = hashgrid_mlp(encoder, mlp, x)        # == mlp.forward_padded(encoder(x, bound))   (same values, same gradients)
 
 Used by NeRFNetwork (fused head) and render_fixed_steps; FOC_FUSED_FIELD=0 restores the two separate nodes.
+
+`field_plan(model)` decides, per call, which fused kernels serve a network — this node, the fixed-step tail, the whole-field inference
+kernel, the occupancy-grid training node, the native occupancy render loop, the head kernels — and carries the shapes they take.
 """
 import os
+from dataclasses import dataclass
+from typing import Optional
 
-import numpy as np
 import torch
 from torch.autograd import Function
 from torch.amp import custom_bwd, custom_fwd
 
 from .backend import _gridencoder, _ffmlp
-from .ffmlp import FFMLP, _fused_backward_ok
-from .gridencoder import GridEncoder
+from .ffmlp import FFMLP, single_pass_backward
+from .gridencoder import GridEncoder, GridSpec
 
 
-def field_fusable(encoder, mlp):
-    return (isinstance(encoder, GridEncoder) and isinstance(mlp, FFMLP) and encoder.input_dim == 3 and encoder.level_dim == 2
-            and mlp.input_dim == encoder.output_dim and _fused_backward_ok(mlp.input_dim, mlp.hidden_dim, mlp.num_layers, mlp.activation)
-            and mlp.padded_output_dim == 16 and os.environ.get("FOC_FUSED_FIELD", "1") != "0")
+@dataclass(frozen=True)
+class MlpShape:
+    """What the MLP kernels take besides the tensors: an FFMLP's shape (its blob layout, ffmlp.py)."""
+    input_dim: int
+    hidden_dim: int
+    num_layers: int
+    activation: int
+    output_activation: int
+    padded_output_dim: int
+
+    @staticmethod
+    def of(mlp):
+        if not isinstance(mlp, FFMLP):
+            return None
+        return MlpShape(mlp.input_dim, mlp.hidden_dim, mlp.num_layers, mlp.activation, mlp.output_activation, mlp.padded_output_dim)
+
+    def blob_numel(self):
+        return self.hidden_dim * (self.input_dim + self.hidden_dim * (self.num_layers - 1) + self.padded_output_dim)
+
+
+@dataclass(frozen=True)
+class FieldPlan:
+    """Which fused kernels serve a network, and the shapes they take. Built per call by `field_plan` (the switches are live); the
+    per-call conditions (GPU tensors, autocast, autograd, training) stay with the callers."""
+    grid: Optional[GridSpec]            # the hash grid's GridSpec (None: the encoder is no GridEncoder)
+    levels: int
+    sigma: Optional[MlpShape]           # None: not an FFMLP
+    colour: Optional[MlpShape]
+    uses_object_feature: bool           # FOC's network: a 16-wide encoded object feature in the colour input (48 wide)
+    field: bool                         # hash grid -> sigma network as one node (_hashgrid_mlp)
+    train_forward: bool                 # the fixed-step training forward of both networks in one kernel (foc_field_forward_train)
+    tail: bool                          # density head -> colour network -> composite as one node (fixedstep._render_tail)
+    infer: bool                         # the whole field without autograd in one kernel after the encoder (field_infer)
+    occ: bool                           # the occupancy-grid training forward as one node (occtrain._occ_train)
+    native_loop: bool                   # the occupancy-grid inference loop as one call per iteration (NeRFRenderer._native_inference_loop)
+    head: bool                          # the glue between the two networks as kernels (head.sample_head / rgb_head)
+
+
+def _on(switch):
+    return os.environ.get(switch, "1") != "0"
+
+
+def field_plan(model):
+    """The FieldPlan of `model` (a network of network.py / network_foc.py, or anything with some of their attributes) under the current
+    switches. Every shape rule of the fused kernels is stated once here; each verdict is a conjunction of these facts and its switch."""
+    from ._lib import get_option
+    from .shencoder import SHEncoder
+    enc, enc_dir = getattr(model, "encoder", None), getattr(model, "encoder_dir", None)
+    sigma, colour = MlpShape.of(getattr(model, "sigma_net", None)), MlpShape.of(getattr(model, "color_net", None))
+    obj = bool(getattr(model, "uses_object_feature", False))
+    grid = enc.spec() if isinstance(enc, GridEncoder) else None
+
+    # the hash grid the [L,B,C] kernels read: D 3, C 2, feeding the sigma network directly; the native loop's encoder is the plain one
+    hash_grid = grid is not None and enc.input_dim == 3 and enc.level_dim == 2 and sigma is not None and sigma.input_dim == enc.output_dim
+    plain_grid = grid is not None and grid.gridtype == 0 and not grid.align_corners and grid.interpolation == 0
+    # sigma network: the single-pass backward serves it (FOC_MLP_BWD_FUSED), a 16-wide output (sigma + 15 geometry features)
+    sigma_one_pass = sigma is not None and single_pass_backward(sigma.input_dim, sigma.hidden_dim, sigma.num_layers, sigma.activation)
+    sigma_16 = sigma is not None and sigma.padded_output_dim == 16
+    sigma_32_64 = sigma is not None and sigma.input_dim == 32 and sigma.hidden_dim == 64
+    # colour network: fed [SH16 | geo 15 | (object feature 16) | 0], 64 wide, a 16-wide output
+    colour_in = 48 if obj else 32
+    colour_64 = colour is not None and colour.input_dim == colour_in and colour.hidden_dim == 64 and colour.padded_output_dim == 16
+    colour_rows = (isinstance(enc_dir, SHEncoder) and enc_dir.degree == 4 and getattr(model, "geo_feat_dim", 0) == 15
+                   and (not obj or getattr(model, "yolo_encoding_dim", 0) == 16))
+    colour_relu_or_none = colour is not None and colour.activation in (0, 6)
+    both = sigma is not None and colour is not None
+    same_activation = both and sigma.activation == colour.activation
+    layer_pair = both and (sigma.num_layers, colour.num_layers) in ((2, 2), (2, 3), (3, 3))
+    whole_field = sigma_32_64 and colour_64 and colour_rows and layer_pair and same_activation   # both networks in one kernel
+
+    field = hash_grid and sigma_one_pass and sigma_16 and _on("FOC_FUSED_FIELD")
+    tail = colour_64 and colour.num_layers in (2, 3) and colour_relu_or_none and colour_rows and _on("FOC_FUSED_TAIL")
+    infer = field and whole_field and (not obj or sigma.activation == 0) and _on("FOC_FUSED_INFER")
+    return FieldPlan(
+        grid=grid, levels=enc.offsets.numel() - 1 if grid is not None else 0, sigma=sigma, colour=colour, uses_object_feature=obj,
+        field=field, tail=tail, infer=infer,
+        train_forward=(field and tail and whole_field and sigma.output_activation == 6 and get_option("FOC_FIELD_FWD_FUSED") != 0),
+        occ=field and tail and not obj and getattr(model, "bg_radius", 0) <= 0 and same_activation and _on("FOC_FUSED_OCC"),
+        native_loop=(infer and not obj and getattr(model, "density_scale", 1) == 1 and plain_grid and _on("FOC_RENDER_NATIVE")),
+        head=both and colour.input_dim == colour_in and colour_rows and _on("FOC_FUSED_HEAD"))
 
 
 def _raw_stream_of(device):
@@ -99,52 +179,63 @@ def scope_cached(key, owner, make):
     return v
 
 
-def colour_forward_fusable(sigma_net, color_net, obj=False):
-    """Shapes `foc_field_forward_train` serves (csrc/field_fwd.hip): both networks' training forward in one kernel — bit for bit
-    `foc_ffmlp_forward_planar` + `foc_color_head_forward`. FOC_FUSED_FWD=0: the two calls (parity aid)."""
-    return (isinstance(sigma_net, FFMLP) and isinstance(color_net, FFMLP) and sigma_net.input_dim == 32 and sigma_net.hidden_dim == 64
-            and color_net.hidden_dim == 64 and color_net.input_dim == (48 if obj else 32) and sigma_net.padded_output_dim == 16
-            and (sigma_net.num_layers, color_net.num_layers) in ((2, 2), (2, 3), (3, 3)) and sigma_net.activation == color_net.activation
-            and sigma_net.activation in (0, 6) and sigma_net.output_activation == 6 and os.environ.get("FOC_FUSED_FWD", "1") != "0")
+def _check_colour_branch(colour, B):
+    """The colour branch of `_hashgrid_mlp`, checked before its first launch: foc_field_forward_train trusts these sizes."""
+    cweights, shape, ray_sh, T, c_width, obj_feat = colour
+    T = int(T)
+    if not (ray_sh.dtype == torch.half and ray_sh.dim() == 2 and ray_sh.shape[1] == 16 and ray_sh.is_contiguous() and T > 0
+            and B == ray_sh.shape[0] * T):
+        raise RuntimeError(f"hashgrid_mlp colour branch: ray_sh must be a contiguous half [B / T, 16] tensor with B = {B}, T = {T}; got "
+                           f"{tuple(ray_sh.shape)} {ray_sh.dtype}{'' if ray_sh.is_contiguous() else ' (strided)'}")
+    if c_width not in (4, 16):
+        raise RuntimeError(f"hashgrid_mlp colour branch: c_width must be 4 or 16, got {c_width}")
+    if shape.input_dim not in (32, 48) or (obj_feat is not None) != (shape.input_dim == 48) or (obj_feat is not None and obj_feat.numel() != 16):
+        raise RuntimeError(f"hashgrid_mlp colour branch: a {shape.input_dim}-wide colour input takes "
+                           f"{'a 16-element object feature' if shape.input_dim == 48 else 'no object feature'}, got "
+                           f"{'none' if obj_feat is None else f'{obj_feat.numel()} elements'}")
+    if cweights.numel() != 64 * (shape.input_dim + 64 * (shape.num_layers - 1) + 16):
+        raise RuntimeError(f"hashgrid_mlp colour branch: the colour weights hold {cweights.numel()} elements, a {shape.input_dim}-wide "
+                           f"{shape.num_layers}-layer network has {64 * (shape.input_dim + 64 * (shape.num_layers - 1) + 16)}")
 
 
 class _hashgrid_mlp(Function):
     @staticmethod
     @custom_fwd(device_type="cuda")
-    def forward(ctx, x, embeddings, weights, offsets, enc_cfg, mlp_cfg, training, colour=None):
-        # x [B,3] fp32 in [0,1]; embeddings [rows,2]; weights: FFMLP blob
-        # colour = (colour weights, ray_sh [B / T, 16] half, T, colour layers, c_width, obj_feat or None): the colour network's forward runs in the
-        # SAME kernel as the sigma network's (foc_field_forward_train) and its logits come back as a second, non-differentiable output — the
+    def forward(ctx, x, embeddings, weights, offsets, grid, sigma, training, colour=None):
+        # x [B,3] fp32 in [0,1]; embeddings [rows,2]; weights: FFMLP blob; grid: GridSpec; sigma: MlpShape of the blob
+        # colour = (colour weights, colour MlpShape, ray_sh [B / T, 16] half, T, c_width, obj_feat or None): the colour network's forward runs in
+        # the SAME kernel as the sigma network's (foc_field_forward_train) and its logits come back as a second, non-differentiable output — the
         # node that owns the colour network (fixedstep._render_tail) takes them instead of launching foc_color_head_forward, and computes every
         # gradient of the colour network in its own backward as before
-        S, H, gridtype, align_corners, interp = enc_cfg
-        input_dim, hidden_dim, num_layers, activation, output_activation = mlp_cfg
         x = x.contiguous().float()
         B = x.shape[0]
+        if colour is not None:
+            _check_colour_branch(colour, B)
+        S, H, (gridtype, align_corners, interp) = grid.log2_scale, grid.base_resolution, grid.tail()
         L = offsets.shape[0] - 1
         emb = _half_of(embeddings)                              # grid.py:41-44: half table under autocast (C even)
         w = _half_of(weights)                                   # ffmlp.py:23: custom_fwd(cast_inputs=half)
         enc = torch.empty(L, B, 2, device=x.device, dtype=torch.half)
         # training: the backward's count pass rides along in the forward launch (backend.grid_encode_forward_counted)
         ticket = _gridencoder.grid_encode_forward_counted(x, emb, offsets, enc, B, 3, 2, L, S, H, gridtype, align_corners, interp,
-                                                          standalone=os.environ.get("FOC_GRID_PRECOUNT", "1") == "2") if training else None
+                                                          standalone=_gridencoder.precount_standalone()) if training else None
         if ticket is None:
             _gridencoder.grid_encode_forward(x, emb, offsets, enc, B, 3, 2, L, S, H, None, gridtype, align_corners, interp)
         h = torch.empty(B, 16, device=x.device, dtype=torch.half)
         c = None
         if colour is not None:
             from ._lib import lib, ptr, stream_of, check
-            cweights, ray_sh, T, c_layers, c_width, obj_feat = colour
+            cweights, cshape, ray_sh, T, c_width, obj_feat = colour
             wc = _half_of(cweights)
             obj16 = obj_feat.detach().reshape(-1).half().contiguous() if obj_feat is not None else None
             c = torch.empty(B, c_width, device=x.device, dtype=torch.half)
-            check(lib.foc_field_forward_train(ptr(enc), ptr(w), num_layers, ptr(ray_sh), int(T), ptr(wc), int(c_layers), 64, int(activation), B, ptr(h), ptr(c),
-                                              int(c_width), ptr(obj16), stream_of(enc)), "field_forward_train")
+            check(lib.foc_field_forward_train(ptr(enc), ptr(w), sigma.num_layers, ptr(ray_sh), int(T), ptr(wc), int(cshape.num_layers), 64,
+                                              int(sigma.activation), B, ptr(h), ptr(c), int(c_width), ptr(obj16), stream_of(enc)), "field_forward_train")
         else:
-            _ffmlp.ffmlp_forward_planar(enc, w, B, input_dim, 16, hidden_dim, num_layers, activation, output_activation, h)
+            _ffmlp.ffmlp_forward_planar(enc, w, B, sigma.input_dim, 16, sigma.hidden_dim, sigma.num_layers, sigma.activation, sigma.output_activation, h)
         if training:
             ctx.save_for_backward(x, emb, w, offsets, enc)
-            ctx.cfg = (enc_cfg, mlp_cfg, B, L)
+            ctx.cfg = (grid, sigma, B, L)
             ctx.ticket = ticket
         if c is None:
             return h
@@ -156,30 +247,18 @@ class _hashgrid_mlp(Function):
     @custom_bwd(device_type="cuda")
     def backward(ctx, grad_h, _grad_c=None):
         x, emb, w, offsets, enc = ctx.saved_tensors
-        (S, H, gridtype, align_corners, interp), (input_dim, hidden_dim, num_layers, activation, output_activation), B, L = ctx.cfg
+        grid, sigma, B, L = ctx.cfg
         if grad_h is None:                        # (set_materialize_grads(False): h took no part in the loss)
             return (None,) * 8
         grad_h = grad_h.contiguous().half()
         g_enc = torch.empty_like(enc)                           # [L,B,2]
         g_w = torch.empty_like(w)
-        _ffmlp.ffmlp_backward_planar(grad_h, enc, w, B, input_dim, 16, hidden_dim, num_layers, activation, output_activation, True, g_enc, g_w)
+        _ffmlp.ffmlp_backward_planar(grad_h, enc, w, B, sigma.input_dim, 16, sigma.hidden_dim, sigma.num_layers, sigma.activation,
+                                     sigma.output_activation, True, g_enc, g_w)
         g_emb = torch.zeros_like(emb)
-        _gridencoder.grid_encode_backward(g_enc, x, emb, offsets, g_emb, B, 3, 2, L, S, H, None, None, gridtype, align_corners, interp, grad_bl=False,
-                                          precount=ctx.ticket)
+        _gridencoder.grid_encode_backward(g_enc, x, emb, offsets, g_emb, B, 3, 2, L, grid.log2_scale, grid.base_resolution, None, None, *grid.tail(),
+                                          grad_bl=False, precount=ctx.ticket)
         return None, g_emb, g_w, None, None, None, None, None
-
-
-def infer_fusable(model):
-    """Whole-field inference kernel (csrc/ffmlp.hip, k_nerf_infer): hash grid (D=3, C=2, 16 levels) -> 64-wide sigma net -> degree-4 SH
-    + 15 geometry features (+ FOC's 16-wide encoded object feature, network_tcnn.py:611-640: 48-wide colour input) -> 64-wide colour net."""
-    from .shencoder import SHEncoder
-    enc, sn, cn = getattr(model, "encoder", None), getattr(model, "sigma_net", None), getattr(model, "color_net", None)
-    obj = getattr(model, "uses_object_feature", False)
-    return (field_fusable(enc, sn) and isinstance(cn, FFMLP) and isinstance(getattr(model, "encoder_dir", None), SHEncoder)
-            and sn.input_dim == 32 and sn.hidden_dim == 64 and cn.hidden_dim == 64 and cn.input_dim == (48 if obj else 32) and cn.padded_output_dim == 16
-            and getattr(model, "geo_feat_dim", 0) == 15 and (sn.num_layers, cn.num_layers) in ((2, 2), (2, 3), (3, 3))
-            and (not obj or (getattr(model, "yolo_encoding_dim", 0) == 16 and sn.activation == 0))
-            and sn.activation == cn.activation and os.environ.get("FOC_FUSED_INFER", "1") != "0")
 
 
 @torch.no_grad()
@@ -189,14 +268,14 @@ def field_infer(model, xn, dirs, dir_div=1, dir_block=0, obj_feat=None):
     obj_feat [16]: the encoded object feature of an object-conditioned network (required iff `model.uses_object_feature`)."""
     from ._lib import lib, ptr, stream_of, check
     enc, sn, cn = model.encoder, model.sigma_net, model.color_net
+    grid = enc.spec()
     xn = xn.contiguous().float()
     dirs = dirs.contiguous().float()
     M = xn.shape[0]
     L = enc.offsets.shape[0] - 1
     emb, ws, wc = _half_of(enc.embeddings), _half_of(sn.weights), _half_of(cn.weights)
     planes = torch.empty(L, M, 2, device=xn.device, dtype=torch.half)
-    _gridencoder.grid_encode_forward(xn, emb, enc.offsets, planes, M, 3, 2, L, float(np.log2(enc.per_level_scale)), enc.base_resolution, None,
-                                     enc.gridtype_id, enc.align_corners, enc.interp_id)
+    _gridencoder.grid_encode_forward(xn, emb, enc.offsets, planes, M, 3, 2, L, grid.log2_scale, grid.base_resolution, None, *grid.tail())
     sigma = torch.empty(M, dtype=torch.float32, device=xn.device)
     rgb = torch.empty(M, 3, dtype=torch.float32, device=xn.device)
     obj16 = None
@@ -210,11 +289,14 @@ def field_infer(model, xn, dirs, dir_div=1, dir_block=0, obj_feat=None):
     return sigma, rgb
 
 
-def hashgrid_mlp(encoder, mlp, x, bound=1):
-    """x [...,3] in [-bound, bound] -> [..., 16] half: mlp.forward_padded(encoder(x, bound))."""
+def hashgrid_mlp(encoder, mlp, x, bound=1, colour=None):
+    """x [...,3] in [-bound, bound] (bound None: already in [0,1]) -> [..., 16] half: mlp.forward_padded(encoder(x, bound)).
+    colour: the colour branch of `_hashgrid_mlp` (the fixed-step training forward) -> (h [B,16], colour logits [B, c_width])."""
     prefix = list(x.shape[:-1])
-    xn = ((x + bound) / (2 * bound)).view(-1, 3)
-    enc_cfg = (float(np.log2(encoder.per_level_scale)), encoder.base_resolution, encoder.gridtype_id, encoder.align_corners, encoder.interp_id)
-    mlp_cfg = (mlp.input_dim, mlp.hidden_dim, mlp.num_layers, mlp.activation, mlp.output_activation)
-    h = _hashgrid_mlp.apply(xn, encoder.embeddings, mlp.weights, encoder.offsets, enc_cfg, mlp_cfg, mlp.training and torch.is_grad_enabled())
+    xn = (x if bound is None else (x + bound) / (2 * bound)).view(-1, 3)
+    h = _hashgrid_mlp.apply(xn, encoder.embeddings, mlp.weights, encoder.offsets, encoder.spec(), MlpShape.of(mlp), mlp.training and torch.is_grad_enabled(),
+                            colour)
+    if colour is not None:
+        h, c = h
+        return h.view(prefix + [16]), c
     return h.view(prefix + [16])

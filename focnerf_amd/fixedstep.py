@@ -134,20 +134,6 @@ class _fixed_composite(Function):
         return grad_c, grad_w, None, None, None, None, None
 
 
-def tail_fusable(model):
-    """Shapes `_render_tail` serves: 16-wide sigma head, degree-4 SH, 64-wide colour network of 2 or 3 layers, its input the 32-wide
-    [SH16 | geo15 | 0] of network_ff.py or FOC's 48-wide [SH16 | geo15 | object feature 16 | 0] (network_tcnn.py:611-640)."""
-    import os
-    from .ffmlp import FFMLP
-    from .shencoder import SHEncoder
-    cn = getattr(model, "color_net", None)
-    want_in = 48 if getattr(model, "uses_object_feature", False) else 32
-    return (isinstance(cn, FFMLP) and cn.input_dim == want_in and cn.hidden_dim == 64 and cn.num_layers in (2, 3) and cn.padded_output_dim == 16
-            and cn.activation in (0, 6)
-            and isinstance(getattr(model, "encoder_dir", None), SHEncoder) and getattr(model, "geo_feat_dim", 0) == 15
-            and (want_in == 32 or getattr(model, "yolo_encoding_dim", 0) == 16) and os.environ.get("FOC_FUSED_TAIL", "1") != "0")
-
-
 _C_WIDTH = 4        # columns of the colour network's output that exist in memory on the fused tail (rgb logits + one pad)
 
 
@@ -285,9 +271,10 @@ def render_fixed_steps(model, rays_o, rays_d, yolo_details=None, num_steps=512, 
     aabb = model.aabb_train if model.training else model.aabb_infer
     nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, aabb, model.min_near)
     noise = torch.rand(N * T, dtype=torch.float32, device=dev) if perturb else None
-    want_tail = (tail_fusable(model) and model.training and torch.is_grad_enabled())
-    from .field import infer_fusable, field_infer
-    fused_infer = not torch.is_grad_enabled() and infer_fusable(model)
+    from .field import field_plan, field_infer
+    plan = field_plan(model)
+    want_tail = plan.tail and model.training and torch.is_grad_enabled()
+    fused_infer = not torch.is_grad_enabled() and plan.infer
     rb = ray_block_default() if fused_infer else 0
     enc_in, _, ray_sh = fixed_sample(rays_o, rays_d, nears, fars, aabb, noise, T, model.bound, want_ray_sh=True) if want_tail else \
         fixed_sample(rays_o, rays_d, nears, fars, aabb, noise, T, model.bound, ray_block=rb) + (None,)
@@ -295,7 +282,7 @@ def render_fixed_steps(model, rays_o, rays_d, yolo_details=None, num_steps=512, 
     if fused_infer:
         # inference: sample -> encoder planes -> whole-field kernel -> weights + mask + composite kernel; between the kernels the samples
         # stand in 64-ray blocks (neighbouring rays at one depth on the lanes of a wave: the encoder's gathers share cache lines)
-        obj_feat = model.encode_object_feature(yolo_details, dev) if getattr(model, "uses_object_feature", False) else None
+        obj_feat = model.encode_object_feature(yolo_details, dev) if plan.uses_object_feature else None
         sigma, rgb = field_infer(model, enc_in, rays_d, dir_div=T, dir_block=rb, obj_feat=obj_feat)
         bg_ray, bg_scalar = _background(bg_color, N, dev)
         # `_out` = (depth [N], image [N,3]) fp32 contiguous views of the caller's whole-view buffers (NeRFRenderer.render, staged)
@@ -325,25 +312,19 @@ def render_fixed_steps(model, rays_o, rays_d, yolo_details=None, num_steps=512, 
         return results
 
     enc = model.encoder
-    from .field import field_fusable, _hashgrid_mlp, colour_forward_fusable
+    from .field import hashgrid_mlp
     c_pre = obj_feat = None
-    uses_obj = getattr(model, "uses_object_feature", False)
     with torch.autocast("cuda", dtype=torch.float16):
-        if uses_obj:                                                      # FOC network (network_foc.py): encoded YOLO feature in the colour input
+        if plan.uses_object_feature:                                      # FOC network (network_foc.py): encoded YOLO feature in the colour input
             obj_feat = model.encode_object_feature(yolo_details, dev)
-        if field_fusable(enc, model.sigma_net):
-            import numpy as np
-            mlp = model.sigma_net
+        if plan.field:
             # with the fused tail the colour network's forward rides in the sigma network's kernel (its logits reach _render_tail as `c_pre`)
             colour = wc16 = None
-            if want_tail and colour_forward_fusable(mlp, model.color_net, uses_obj):
+            if want_tail and plan.train_forward:
                 from .field import _half_of
                 wc16 = _half_of(model.color_net.weights)                  # ONE half copy per step for both nodes that read the colour weights
-                colour = (wc16, ray_sh, T, model.color_net.num_layers, _C_WIDTH, obj_feat)
-            h = _hashgrid_mlp.apply(enc_in, enc.embeddings, mlp.weights, enc.offsets,
-                                    (float(np.log2(enc.per_level_scale)), enc.base_resolution, enc.gridtype_id, enc.align_corners, enc.interp_id),
-                                    (mlp.input_dim, mlp.hidden_dim, mlp.num_layers, mlp.activation, mlp.output_activation),
-                                    mlp.training and torch.is_grad_enabled(), colour)
+                colour = (wc16, plan.colour, ray_sh, T, _C_WIDTH, obj_feat)
+            h = hashgrid_mlp(enc, model.sigma_net, enc_in, None, colour)
             if colour is not None:
                 h, c_pre = h
         else:
@@ -400,7 +381,7 @@ def render_field4(model, rays_o, rays_d, num_steps=512, weight_thresh=1e-10, yol
     `densities` [N,T] and `rgbs` [N,T,3] (zero where the object's own compositing weight is <= 1e-10) — PACKED as field4 [N,T,4] fp32
     (sigma, r, g, b), written into `out` when given. Fused path: sample -> encoder -> whole-field kernel -> weights + mask + pack
     (foc_fixed_field_pack); other networks go through `model.run(..., return_fields=True)` and are packed with torch ops."""
-    from .field import infer_fusable, field_infer
+    from .field import field_plan, field_infer
     rays_o = rays_o.contiguous().view(-1, 3).float()
     rays_d = rays_d.contiguous().view(-1, 3).float()
     N, T = rays_o.shape[0], int(num_steps)
@@ -408,12 +389,13 @@ def render_field4(model, rays_o, rays_d, num_steps=512, weight_thresh=1e-10, yol
     if out is None:
         out = torch.empty(N, T, 4, dtype=torch.float32, device=dev)
     assert out.shape == (N, T, 4) and out.dtype == torch.float32 and out.is_contiguous()
-    if infer_fusable(model) and model.bg_radius <= 0:
+    plan = field_plan(model)
+    if plan.infer and model.bg_radius <= 0:
         aabb = model.aabb_train if model.training else model.aabb_infer
         nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, aabb, model.min_near)
         rb = ray_block_default()
         enc_in, _ = fixed_sample(rays_o, rays_d, nears, fars, aabb, None, T, model.bound, ray_block=rb)
-        obj_feat = model.encode_object_feature(yolo_details, dev) if getattr(model, "uses_object_feature", False) else None
+        obj_feat = model.encode_object_feature(yolo_details, dev) if plan.uses_object_feature else None
         sigma, rgb = field_infer(model, enc_in, rays_d, dir_div=T, dir_block=rb, obj_feat=obj_feat)
         check(lib.foc_fixed_field_pack(ptr(sigma), ptr(rgb), ptr(nears), ptr(fars), None, None, 1.0, N, T, float(model.density_scale),
                                        float(weight_thresh), None, None, None, ptr(out), rb, stream_of(sigma)), "fixed_field_pack")

@@ -164,6 +164,11 @@ class GridEncoder(nn.Module):
                 f"(x{self.per_level_scale:.4f}), table={tuple(self.embeddings.shape)}, {self.gridtype}/{self.interpolation}, "
                 f"align_corners={self.align_corners}")
 
+    def spec(self):
+        """The GridSpec the kernels take for this encoder."""
+        return GridSpec(float(np.log2(self.per_level_scale)), int(self.base_resolution), int(self.gridtype_id), bool(self.align_corners),
+                        int(self.interp_id))
+
     def _unit_cube(self, x, bound):
         return (x + bound) / (2 * bound)
 

@@ -9,11 +9,9 @@ The reference file itself cannot be constructed from its own tree (it imports an
 focnerf_amd/dropin on PYTHONPATH it can (tests/test_dropin.py).
 
 Under fp16 autocast on flat [M,3] GPU inputs the glue between the kernels (trunc_exp, SH, concatenation + padding, sigmoid) runs as
-fused kernels too (csrc/head.hip; FOC_FUSED_HEAD=0 keeps the torch expressions), and without autograd the whole field is one kernel
+fused kernels too (csrc/head.hip; FOC_FUSED_HEAD=0 keeps the torch expressions; `field.field_plan` says which apply), and without autograd the whole field is one kernel
 after the encoder (csrc/ffmlp.hip, k_nerf_infer).
 """
-import os
-
 import torch
 
 from .activation import trunc_exp
@@ -43,38 +41,33 @@ class NeRFNetwork(NeRFRenderer):
     def _shade(self, d, geo_feat):
         return torch.sigmoid(self.color_net(self._colour_input(d, geo_feat)))
 
-    # ---- fused kernels
-    def _fused_head_ok(self, x):
-        """csrc/head.hip serves FOC's shapes: degree-4 SH, 15 geometry features, both networks FFMLPs with 16-wide padded outputs, fp16
-        autocast, flat [M,3] GPU inputs."""
-        from .shencoder import SHEncoder
-        return (x.is_cuda and x.dim() == 2 and torch.is_autocast_enabled() and self.geo_feat_dim == 15 and self.in_dim_color == 32
-                and isinstance(self.encoder_dir, SHEncoder) and getattr(self.encoder_dir, "degree", 0) == 4
-                and isinstance(self.sigma_net, FFMLP) and isinstance(self.color_net, FFMLP) and os.environ.get("FOC_FUSED_HEAD", "1") != "0")
-
-    def _geometry_rows(self, x):
+    # ---- fused kernels (field.field_plan: which ones serve this network)
+    def _geometry_rows(self, x, plan):
         """[M,3] -> [M,16] half: the density network's padded output, the encoding kept in the encoder's [L,B,C] planes when possible."""
-        from .field import field_fusable, hashgrid_mlp
-        if field_fusable(self.encoder, self.sigma_net):
+        from .field import hashgrid_mlp
+        if plan.field:
             return hashgrid_mlp(self.encoder, self.sigma_net, x, self.bound)
         return self.sigma_net.forward_padded(self.encoder(x, bound=self.bound))
 
     def forward(self, x, d):
         """positions x in [-bound, bound]^3 and unit directions d -> (sigma [...], rgb [..., 3])."""
-        if not self._fused_head_ok(x):
+        from .field import field_plan
+        plan = field_plan(self)
+        if not (x.is_cuda and x.dim() == 2 and torch.is_autocast_enabled() and plan.head):
             field = self.density(x)
             return field['sigma'], self._shade(d, field['geo_feat'])
-        from .field import field_infer, infer_fusable
+        from .field import field_infer
         from .head import rgb_head, sample_head
-        if not torch.is_grad_enabled() and infer_fusable(self):
+        if not torch.is_grad_enabled() and plan.infer:
             return field_infer(self, (x + self.bound) / (2 * self.bound), d)
-        sigma, colour_rows = sample_head(self._geometry_rows(x), d)
+        sigma, colour_rows = sample_head(self._geometry_rows(x, plan), d)
         return sigma, rgb_head(self.color_net.forward_padded(colour_rows))
 
     def density(self, x):
-        from .field import field_fusable
-        if x.is_cuda and x.dim() == 2 and torch.is_autocast_enabled() and field_fusable(self.encoder, self.sigma_net):
-            h = self._geometry_rows(x)
+        from .field import field_plan
+        plan = field_plan(self)
+        if x.is_cuda and x.dim() == 2 and torch.is_autocast_enabled() and plan.field:
+            h = self._geometry_rows(x, plan)
         else:
             h = self.sigma_net(self.encoder(x, bound=self.bound))
         return {'sigma': trunc_exp(h[..., 0]), 'geo_feat': h[..., 1:]}

@@ -19,8 +19,6 @@ W0[:, 31:47] . obj, is a constant per neuron. The fused training tail (`fixedste
 and otherwise run the 32-wide kernels of `network.NeRFNetwork`; the gradient of the encoded feature (for `yolo_feat_encoder`) and of
 W0[:, 31:47] follow from the column sum of the first layer's delta (csrc/ffmlp.hip, MlpHead).
 """
-import os
-
 import torch
 import torch.nn as nn
 
@@ -103,35 +101,33 @@ class NeRFNetwork(NeRFRenderer):
         return scope_cached(("object_feature", id(self), id(yolo_details[2])), yolo_details[2], encode)
 
     # ------------------------------------------------------------------ field
-    def _fused_ok(self, x):
-        from .shencoder import SHEncoder
-        return (x.is_cuda and x.dim() == 2 and torch.is_autocast_enabled() and self.geo_feat_dim == 15 and self.yolo_encoding_dim == 16
-                and isinstance(self.encoder_dir, SHEncoder) and os.environ.get("FOC_FUSED_HEAD", "1") != "0")
-
-    def _sigma_features(self, x):
-        from .field import field_fusable, hashgrid_mlp
-        if x.is_cuda and x.dim() == 2 and torch.is_autocast_enabled() and field_fusable(self.encoder, self.sigma_net):
+    def _sigma_features(self, x, plan):
+        from .field import hashgrid_mlp
+        if x.is_cuda and x.dim() == 2 and torch.is_autocast_enabled() and plan.field:
             return hashgrid_mlp(self.encoder, self.sigma_net, x, self.bound)
         return self.sigma_net(self.encoder(x, bound=self.bound))
 
     def forward(self, x, d, yolo_details=None):
         """:555-586. The reference concatenates `yolo_details[2]` as a per-sample feature here; a [16] vector is broadcast."""
+        from .field import field_plan
+        plan = field_plan(self)
         obj = yolo_details[2] if yolo_details is not None else torch.zeros(self.yolo_encoding_dim, device=x.device)
         obj = torch.as_tensor(obj, device=x.device)
-        if self._fused_ok(x) and obj.numel() == self.yolo_encoding_dim:
-            from .field import field_infer, infer_fusable
+        if x.is_cuda and x.dim() == 2 and torch.is_autocast_enabled() and plan.head and obj.numel() == self.yolo_encoding_dim:
+            from .field import field_infer
             from .head import sample_head, rgb_head
-            if not torch.is_grad_enabled() and infer_fusable(self):
+            if not torch.is_grad_enabled() and plan.infer:
                 return field_infer(self, (x + self.bound) / (2 * self.bound), d, obj_feat=obj)
-            sigma, cin = sample_head(self._sigma_features(x), d, obj)
+            sigma, cin = sample_head(self._sigma_features(x, plan), d, obj)
             return sigma, rgb_head(self.color_net.forward_padded(cin))
-        h = self._sigma_features(x)
+        h = self._sigma_features(x, plan)
         sigma = trunc_exp(h[..., 0])
         geo_feat = h[..., 1:]
         return sigma, self._color_torch(d, geo_feat, obj)
 
     def density(self, x, yolo_details=None):
-        h = self._sigma_features(x)
+        from .field import field_plan
+        h = self._sigma_features(x, field_plan(self))
         return {'sigma': trunc_exp(h[..., 0]), 'geo_feat': h[..., 1:]}
 
     def _color_torch(self, d, geo_feat, obj_feat):

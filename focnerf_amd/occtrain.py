@@ -10,11 +10,10 @@ its first k-chunk is one SH row per sample written by the march's emit pass, its
 MlpHead; sigma, rgb and their gradients stay on the lane in csrc/occtrain.hip), same gradients up to fp32 summation order.
 
 The step it replaces was bound by its launches: ~85 kernels, 0.9 ms of GPU time, 1.2 ms of host time to enqueue them from Python.
-FOC_FUSED_OCC=0 keeps the chain (tests compare the two).
+FOC_FUSED_OCC=0 keeps the chain (tests compare the two); `field.field_plan` decides which networks it serves (`plan.occ`).
 """
 import os
 
-import numpy as np
 import torch
 from torch.autograd import Function
 
@@ -24,16 +23,6 @@ from ._lib import lib, ptr, stream_of, check, FocOccTrainNode, FOC_F16
 from .backend import _gridencoder, _ffmlp, _scratch
 
 _C_WIDTH = 4
-
-
-def occ_train_fusable(model):
-    """Shapes the node serves: hash grid (D 3, C 2) -> FFMLP density network with a 16-wide output -> degree-4 SH + 15 geometry features
-    -> 64-wide FFMLP colour network of 2 or 3 layers, no background model, no object feature."""
-    from .field import field_fusable
-    from .fixedstep import tail_fusable
-    return (field_fusable(model.encoder, model.sigma_net) and tail_fusable(model) and not getattr(model, "uses_object_feature", False)
-            and model.bg_radius <= 0 and model.sigma_net.activation == model.color_net.activation
-            and os.environ.get("FOC_FUSED_OCC", "1") != "0")
 
 
 def _round_up(count, align):
@@ -51,25 +40,25 @@ def _no_jitter(n, dev):
     return z[:n]
 
 
-_plan_bytes = {}
+_mlp_bytes = {}
 
 
-def _native_plan(offsets, S, H, L, gridtype, M, sig_cfg, col_cfg):
+def _native_plan(offsets, grid, L, M, sigma, colour):
     """(grid workspace bytes, MLP workspace bytes) when the node can run as ONE library call each way (include/focnerf.h FocOccTrainNode:
     the encoder's counted forward and binned backward must apply, the switches that take other paths must be at their defaults), else None.
     FOC_OCC_NATIVE_NODE=0: always the call-by-call chain below (the tests compare the two)."""
-    if (os.environ.get("FOC_OCC_NATIVE_NODE", "1") == "0" or os.environ.get("FOC_GRID_PRECOUNT", "1") != "1"
-            or os.environ.get("FOCNERF_GRID_ATOMIC", "0") == "1"):
+    if os.environ.get("FOC_OCC_NATIVE_NODE", "1") == "0" or _gridencoder.precount_standalone():
         return None
-    key = (M, L, sig_cfg[:3], col_cfg[0])
-    sizes = _plan_bytes.get(key)
-    if sizes is None:
-        sizes = _plan_bytes[key] = (int(lib.foc_grid_encode_backward_workspace_bytes(M, 3, 2, L, FOC_F16)),
-                                    max(int(lib.foc_ffmlp_backward_workspace_bytes(32, 64, int(col_cfg[0]))),
-                                        int(lib.foc_ffmlp_backward_workspace_bytes(int(sig_cfg[0]), int(sig_cfg[1]), int(sig_cfg[2])))))
-    if not sizes[0] or M * 8 * L >= 2 ** 32 or not _gridencoder._binned_ok(offsets, S, H, L, gridtype):
+    grid_bytes = _gridencoder.binned_workspace_bytes(offsets, M, 3, 2, L, grid.log2_scale, grid.base_resolution, grid.gridtype, FOC_F16,
+                                                     count_ahead=True)
+    if not grid_bytes:
         return None
-    return sizes
+    key = (sigma.input_dim, sigma.hidden_dim, sigma.num_layers, colour.num_layers)
+    mlp_bytes = _mlp_bytes.get(key)
+    if mlp_bytes is None:
+        mlp_bytes = _mlp_bytes[key] = max(int(lib.foc_ffmlp_backward_workspace_bytes(32, 64, colour.num_layers)),
+                                          int(lib.foc_ffmlp_backward_workspace_bytes(sigma.input_dim, sigma.hidden_dim, sigma.num_layers)))
+    return int(grid_bytes), mlp_bytes
 
 
 def _a(t):
@@ -81,8 +70,8 @@ class _occ_train(Function):
     def forward(ctx, emb, w_sigma, w_color, o, d, aabb, bitfield, counter, bg_ray, cfg):
         from .field import _half_of
         (bound, cascade, grid_size, mean_count, perturb, align, force_all_rays, dt_gamma, max_steps, T_thresh, density_scale, bg_scalar,
-         offsets, enc_cfg, sig_cfg, col_cfg, min_near) = cfg
-        S, H, gridtype, align_corners, interp = enc_cfg
+         offsets, grid, sigma, colour, min_near) = cfg
+        S, H, (gridtype, align_corners, interp) = grid.log2_scale, grid.base_resolution, grid.tail()
         n, dev = o.shape[0], o.device
         st = stream_of(o)
         budgeted = mean_count > 0 and not force_all_rays
@@ -97,7 +86,7 @@ class _occ_train(Function):
         jitter = torch.rand(n, dtype=torch.float32, device=dev) if perturb else _no_jitter(n, dev)
         scratch = _scratch.get("march", lib.foc_march_rays_train_scratch_bytes(n, max_steps), dev)
         L = offsets.shape[0] - 1
-        plan = _native_plan(offsets, S, H, L, gridtype, cap, sig_cfg, col_cfg) if (budgeted and cap > 0 and n > 0) else None
+        plan = _native_plan(offsets, grid, L, cap, sigma, colour) if (budgeted and cap > 0 and n > 0) else None
         if plan is not None:
             # the whole forward as one library call (csrc/occtrain.hip foc_occ_train_forward): the same five entry points in the same order,
             # enqueued from C — the step's host time no longer depends on nine trips through the binding
@@ -121,21 +110,18 @@ class _occ_train(Function):
             nd.embeddings, nd.offsets, nd.offsets_host = _a(emb16), _a(offsets), _gridencoder._host_offsets(offsets)
             nd.planes, nd.grid_workspace, nd.grid_workspace_bytes = _a(planes), _a(gws), plan[0]
             nd.sigma_input_dim, nd.sigma_hidden, nd.sigma_layers, nd.sigma_activation, nd.sigma_output_activation = (
-                int(sig_cfg[0]), int(sig_cfg[1]), int(sig_cfg[2]), int(sig_cfg[3]), 6)
-            nd.color_hidden, nd.color_layers, nd.color_activation, nd.c_width = 64, int(col_cfg[0]), int(col_cfg[1]), _C_WIDTH
+                sigma.input_dim, sigma.hidden_dim, sigma.num_layers, sigma.activation, 6)
+            nd.color_hidden, nd.color_layers, nd.color_activation, nd.c_width = 64, colour.num_layers, colour.activation, _C_WIDTH
             nd.w_sigma, nd.w_color, nd.h, nd.c = _a(ws16), _a(wc16), _a(h), _a(c)
             nd.T_thresh, nd.density_scale, nd.bg_scalar, nd.bg_ray = float(T_thresh), float(density_scale), float(bg_scalar), _a(bg_ray)
             nd.weights_sum, nd.image_raw, nd.image, nd.depth = _a(ws), _a(image_raw), _a(image), _a(depth)
             check(lib.foc_occ_train_forward(ctypes.byref(nd), st), "occ_train_forward")
             # the count pass rode in the encoder's forward: the ticket the backward checks, as backend.grid_encode_forward_counted issues it
-            idx, pre = _gridencoder._pre_state(dev)
-            pre["ticket"] += 1
-            pre["key"] = (enc_in.data_ptr(), M, L, FOC_F16, gws.data_ptr())
+            ctx.ticket = _gridencoder.issue_precount_ticket(enc_in, M, L, FOC_F16, gws)
             ctx.save_for_backward(enc_in, emb16, ws16, wc16, offsets, planes, h, c, sh, deltas, rays, counter, ws, image_raw,
                                   bg_ray if bg_ray is not None else torch.empty(0, device=dev))
             ctx.nears_fars = nf
-            ctx.cfg = (M, n, float(T_thresh), float(density_scale), float(bg_scalar), bg_ray is not None, enc_cfg, sig_cfg, col_cfg)
-            ctx.ticket = (idx, pre["ticket"], pre["key"])
+            ctx.cfg = (M, n, float(T_thresh), float(density_scale), float(bg_scalar), bg_ray is not None, grid, sigma, colour)
             ctx.node, ctx.plan = nd, plan
             ctx.mark_non_differentiable(depth)
             ctx.set_materialize_grads(False)
@@ -156,10 +142,11 @@ class _occ_train(Function):
             _gridencoder.grid_encode_forward(enc_in, emb16, offsets, planes, M, 3, 2, L, S, H, None, gridtype, align_corners, interp)
         h = torch.empty(M, 16, dtype=torch.float16, device=dev)
         if M:
-            _ffmlp.ffmlp_forward_planar(planes, ws16, M, sig_cfg[0], 16, sig_cfg[1], sig_cfg[2], sig_cfg[3], 6, h)
+            _ffmlp.ffmlp_forward_planar(planes, ws16, M, sigma.input_dim, 16, sigma.hidden_dim, sigma.num_layers, sigma.activation, 6, h)
         c = torch.empty(M, _C_WIDTH, dtype=torch.float16, device=dev)
         if M:
-            check(lib.foc_color_head_forward(ptr(h), ptr(sh), 1, ptr(wc16), M, 64, int(col_cfg[0]), int(col_cfg[1]), ptr(c), _C_WIDTH, None, st), "color_head_forward")
+            check(lib.foc_color_head_forward(ptr(h), ptr(sh), 1, ptr(wc16), M, 64, colour.num_layers, colour.activation, ptr(c), _C_WIDTH, None, st),
+                  "color_head_forward")
         out = torch.empty(n * 8, dtype=torch.float32, device=dev)
         ws, depth, image_raw, image = out[:n], out[n: 2 * n], out[2 * n: 5 * n].view(n, 3), out[5 * n:].view(n, 3)
         check(lib.foc_occ_tail_forward(ptr(h), ptr(c), _C_WIDTH, ptr(deltas), ptr(rays), M, n, float(T_thresh), float(density_scale), ptr(bg_ray), float(bg_scalar),
@@ -167,7 +154,7 @@ class _occ_train(Function):
         ctx.save_for_backward(enc_in, emb16, ws16, wc16, offsets, planes, h, c, sh, deltas, rays, counter, ws, image_raw,
                               bg_ray if bg_ray is not None else torch.empty(0, device=dev))
         ctx.nears_fars = nf
-        ctx.cfg = (M, n, float(T_thresh), float(density_scale), float(bg_scalar), bg_ray is not None, enc_cfg, sig_cfg, col_cfg)
+        ctx.cfg = (M, n, float(T_thresh), float(density_scale), float(bg_scalar), bg_ray is not None, grid, sigma, colour)
         ctx.ticket = ticket
         ctx.mark_non_differentiable(depth)
         ctx.set_materialize_grads(False)
@@ -176,8 +163,8 @@ class _occ_train(Function):
     @staticmethod
     def backward(ctx, g_image, g_ws, _g_depth):
         enc_in, emb16, ws16, wc16, offsets, planes, h, c, sh, deltas, rays, counter, ws, image_raw, bg_ray = ctx.saved_tensors
-        M, n, T_thresh, density_scale, bg_scalar, has_bg, enc_cfg, sig_cfg, col_cfg = ctx.cfg
-        S, H, gridtype, align_corners, interp = enc_cfg
+        M, n, T_thresh, density_scale, bg_scalar, has_bg, grid, sigma, colour = ctx.cfg
+        S, H, (gridtype, align_corners, interp) = grid.log2_scale, grid.base_resolution, grid.tail()
         dev = h.device
         st = stream_of(h)
         L = offsets.shape[0] - 1
@@ -208,25 +195,26 @@ class _occ_train(Function):
         check(lib.foc_occ_tail_backward(ptr(g_image), ptr(g_ws), ptr(h), ptr(c), _C_WIDTH, ptr(deltas), ptr(rays), ptr(counter), ptr(ws), ptr(image_raw), M, n,
                                         T_thresh, density_scale, ptr(bg_ray if has_bg else None), bg_scalar, ptr(grad_c), ptr(grad_h0), st), "occ_tail_backward")
         grad_h = torch.empty_like(h)
-        wsb = _scratch.get("ffmlp_ws", lib.foc_ffmlp_backward_workspace_bytes(32, 64, int(col_cfg[0])), dev)
-        check(lib.foc_color_head_backward(ptr(grad_c), ptr(h), ptr(sh), 1, ptr(grad_h0), ptr(wc16), M, 64, int(col_cfg[0]), int(col_cfg[1]), ptr(grad_h), ptr(g_wcol),
+        wsb = _scratch.get("ffmlp_ws", lib.foc_ffmlp_backward_workspace_bytes(32, 64, colour.num_layers), dev)
+        check(lib.foc_color_head_backward(ptr(grad_c), ptr(h), ptr(sh), 1, ptr(grad_h0), ptr(wc16), M, 64, colour.num_layers, colour.activation, ptr(grad_h), ptr(g_wcol),
                                           ptr(wsb), wsb.numel(), _C_WIDTH, None, None, st), "color_head_backward")
         g_planes = torch.empty_like(planes)
-        _ffmlp.ffmlp_backward_planar(grad_h, planes, ws16, M, sig_cfg[0], 16, sig_cfg[1], sig_cfg[2], sig_cfg[3], 6, True, g_planes, g_wsig)
+        _ffmlp.ffmlp_backward_planar(grad_h, planes, ws16, M, sigma.input_dim, 16, sigma.hidden_dim, sigma.num_layers, sigma.activation, 6, True,
+                                     g_planes, g_wsig)
         _gridencoder.grid_encode_backward(g_planes, enc_in, emb16, offsets, g_emb, M, 3, 2, L, S, H, None, None, gridtype, align_corners, interp, grad_bl=False,
                                           precount=ctx.ticket)
         return g_emb, g_wsig, g_wcol, None, None, None, None, None, None, None, None
 
 
-def render_occupancy_train(model, o, d, counter, bg_color, perturb, force_all_rays, dt_gamma, max_steps, T_thresh, align):
-    """o, d [n,3] fp32 contiguous, counter int32[2] (zeroed by the caller) -> (image [n,3], weights_sum [n], depth [n]); the rays' box test
-    against the model's training box (near_far_from_aabb, min_near) happens inside the march."""
+def render_occupancy_train(model, plan, o, d, counter, bg_color, perturb, force_all_rays, dt_gamma, max_steps, T_thresh, align):
+    """o, d [n,3] fp32 contiguous, counter int32[2] (zeroed by the caller) -> (image [n,3], weights_sum [n], depth [n]) for a network whose
+    `field.field_plan` is `plan` (plan.occ); the rays' box test against the model's training box (near_far_from_aabb, min_near) happens
+    inside the march."""
     from .fixedstep import _background
-    enc, sn, cn = model.encoder, model.sigma_net, model.color_net
+    enc = model.encoder
     n, dev = o.shape[0], o.device
     bg_ray, bg_scalar = _background(bg_color, n, dev)
     cfg = (float(model.bound), int(model.cascade), int(model.grid_size), int(model.mean_count), bool(perturb), int(align), bool(force_all_rays), float(dt_gamma),
-           int(max_steps), float(T_thresh), float(model.density_scale), float(bg_scalar), enc.offsets,
-           (float(np.log2(enc.per_level_scale)), enc.base_resolution, enc.gridtype_id, enc.align_corners, enc.interp_id),
-           (sn.input_dim, sn.hidden_dim, sn.num_layers, sn.activation), (cn.num_layers, cn.activation), float(model.min_near))
-    return _occ_train.apply(enc.embeddings, sn.weights, cn.weights, o, d, model._aabb().contiguous().float(), model.density_bitfield, counter, bg_ray, cfg)
+           int(max_steps), float(T_thresh), float(model.density_scale), float(bg_scalar), enc.offsets, plan.grid, plan.sigma, plan.colour, float(model.min_near))
+    return _occ_train.apply(enc.embeddings, model.sigma_net.weights, model.color_net.weights, o, d, model._aabb().contiguous().float(), model.density_bitfield,
+                            counter, bg_ray, cfg)

@@ -214,15 +214,17 @@ class NeRFRenderer(nn.Module):
         o, d, lead = _flat_rays(rays_o, rays_d)
         n, dev = o.shape[0], o.device
         out = {}
+        from .field import field_plan
+        plan = field_plan(self)
         if self.training:
-            from .occtrain import occ_train_fusable, render_occupancy_train
-            if o.is_cuda and torch.is_grad_enabled() and torch.is_autocast_enabled() and occ_train_fusable(self):
+            from .occtrain import render_occupancy_train
+            if o.is_cuda and torch.is_grad_enabled() and torch.is_autocast_enabled() and plan.occ:
                 # the whole training forward as one autograd node (focnerf_amd/occtrain.py): same samples, same image; the box test of
                 # near_far_from_aabb rides in the march's count pass
                 slot = self.step_counter[self.local_step % 16]
                 slot.zero_()
                 self.local_step += 1
-                image, opacity, depth = render_occupancy_train(self, o.float(), d.float(), slot, bg_color, perturb, force_all_rays, dt_gamma, max_steps, T_thresh,
+                image, opacity, depth = render_occupancy_train(self, plan, o.float(), d.float(), slot, bg_color, perturb, force_all_rays, dt_gamma, max_steps, T_thresh,
                                                                _MARCH_ALIGN)
                 out['weights_sum'] = opacity
                 out['image'], out['depth'] = image.view(*lead, 3), depth.view(*lead)
@@ -247,8 +249,10 @@ class NeRFRenderer(nn.Module):
             # device_compaction: None (default) = the native loop where it serves the network (same image and depth as the reference's loop,
             # bit for bit: tests/test_gpu_network.py), else the reference's loop as it is; True = the native loop, else the Python loop with the
             # list compacted on the device and its length read late; False = the reference's loop (boolean mask, a host round trip per iteration)
-            if (device_compaction is None or device_compaction) and self._native_loop_ok(o):
-                self._native_inference_loop(o, d, near, far, alive, t_now, opacity, depth, image, perturb, dt_gamma, max_steps, T_thresh)
+            # the native loop serves the networks of the whole-field kernel on the GPU, under autocast (fp16 table and weights): plan.native_loop
+            if ((device_compaction is None or device_compaction) and o.is_cuda and torch.is_autocast_enabled() and not torch.is_grad_enabled()
+                    and plan.native_loop):
+                self._native_inference_loop(plan, o, d, near, far, alive, t_now, opacity, depth, image, perturb, dt_gamma, max_steps, T_thresh)
                 marched = max_steps                                   # the Python loop below has nothing left to do
             device_compaction = bool(device_compaction)
             import contextlib
@@ -299,27 +303,18 @@ class NeRFRenderer(nn.Module):
         return out
 
     # ------------------------------------------------------------------ the inference loop, one native call per iteration
-    def _native_loop_ok(self, o):
-        """`foc_occ_render_step` serves the networks of the whole-field kernel (hash grid D = 3, C = 2 -> 64-wide sigma net -> SH + 64-wide
-        colour net) at density_scale 1, on the GPU, under autocast (fp16 table and weights)."""
-        from .field import infer_fusable
-        return (o.is_cuda and torch.is_autocast_enabled() and not torch.is_grad_enabled() and infer_fusable(self) and self.density_scale == 1
-                and not getattr(self, "uses_object_feature", False) and self.encoder.gridtype_id == 0 and not self.encoder.align_corners
-                and self.encoder.interp_id == 0 and os.environ.get("FOC_RENDER_NATIVE", "1") != "0")
-
-    def _native_inference_loop(self, o, d, near, far, alive, t_now, opacity, depth, image, perturb, dt_gamma, max_steps, T_thresh):
+    def _native_inference_loop(self, plan, o, d, near, far, alive, t_now, opacity, depth, image, perturb, dt_gamma, max_steps, T_thresh):
         """The loop of legacy/nerf/renderer.py:323-372 with every iteration ONE call into the library (csrc/occrender.hip: march, encode,
         whole-field kernel, composite, compaction) on buffers allocated once per view; bursts of FOC_RENDER_BURST samples per ray, the live
         count read `FOC_RENDER_COUNT_LAG` iterations late, the reference's stopping point reproduced. Same samples, same per-ray
         accumulation order: the same image and depth bit for bit on every configuration the tests run (jittered first samples with the
         same noise included), with one caveat spelled out at the burst rule below — a re-derivation of t that can differ by an ulp where a
         single advance more than doubles t while fewer than half of the rays are alive."""
-        import numpy as np
         from ._lib import lib, ptr, stream_of, check
         from .field import _half_of, half_cache_scope
         n, dev = o.shape[0], o.device
         enc, sn, cn = self.encoder, self.sigma_net, self.color_net
-        L = enc.offsets.shape[0] - 1
+        L = plan.levels
         lag = max(1, int(os.environ.get("FOC_RENDER_COUNT_LAG", "2")))
         # Samples per ray and iteration. The reference sizes a burst so that live x burst stays within the view's ray count (max(min(n // live,
         # 8), 1), renderer.py:337: ONE sample per ray for the ~130 iterations in which most rays are alive) — a memory bound of its time. What
@@ -349,7 +344,6 @@ class NeRFRenderer(nn.Module):
         n_deaths = int(max_steps) + 32
         deaths = torch.zeros(n_deaths, 64, dtype=torch.int32, device=dev)       # [sample index][slice]: see RM_DEATH_SLICES
         trace = bool(os.environ.get("FOC_RENDER_TRACE"))
-        S = float(np.log2(enc.per_level_scale))
 
         def rule(n_alive):                                      # renderer.py:337
             return max(min(n // n_alive, 8), 1)
@@ -367,7 +361,8 @@ class NeRFRenderer(nn.Module):
                 check(lib.foc_occ_render_step(live, burst, ptr(src), ptr(dst), ptr(count), ptr(t_now), ptr(o), ptr(d), float(self.bound), float(dt_gamma),
                                               int(max_steps), self.cascade, self.grid_size, ptr(self.density_bitfield), ptr(near), ptr(far),
                                               ptr(jitter if marched == 0 else still), ptr(samples), ptr(planes), ptr(sigma), ptr(rgb), ptr(emb),
-                                              ptr(enc.offsets), None, L, S, enc.base_resolution, ptr(ws), sn.num_layers, ptr(wc), cn.num_layers, sn.activation,
+                                              ptr(enc.offsets), None, L, plan.grid.log2_scale, plan.grid.base_resolution, ptr(ws), plan.sigma.num_layers, ptr(wc),
+                                              plan.colour.num_layers, plan.sigma.activation,
                                               None, float(T_thresh), ptr(opacity), ptr(depth), ptr(image), ptr(scratch), flags, ptr(deaths), marched, n_deaths,
                                               st), "occ_render_step")
                 state["it"], state["marched"] = it + 1, marched + burst
@@ -559,8 +554,8 @@ class NeRFRenderer(nn.Module):
             # 40.9 ms per 800 x 800 view (8192: 41.6, 32768: 42.5, 65536: 45.2; FOC_RENDER_MIN_CHUNK=0: the caller's chunks as they are)
             piece = max_ray_batch
             if not torch.is_grad_enabled() and dev.type == "cuda" and kwargs.get("fused"):
-                from .field import infer_fusable
-                if infer_fusable(self):
+                from .field import field_plan
+                if field_plan(self).infer:
                     piece = max(max_ray_batch, int(os.environ.get("FOC_RENDER_MIN_CHUNK", "16384")))
             try:
                 for b in range(B):

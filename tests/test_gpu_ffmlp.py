@@ -390,13 +390,14 @@ def test_other_activations_through_the_module_and_autograd():
     """FFMLP(activation='sigmoid' | ...) trains through autograd: non-ReLU activations keep the reference's data flow (stored activations +
     gradient buffer) instead of the single-pass backward, and the fused paths that assume ReLU stay away from them."""
     from focnerf_amd.ffmlp import FFMLP, single_pass_backward
-    from focnerf_amd.field import field_fusable
+    from types import SimpleNamespace
+    from focnerf_amd.field import field_plan
     from focnerf_amd.gridencoder import GridEncoder
     assert single_pass_backward(32, 64, 2, 0) and not single_pass_backward(32, 64, 2, 3)
     enc = GridEncoder(input_dim=3, num_levels=16, level_dim=2).cuda()
     for name in ("sigmoid", "softplus", "squareplus", "exponential", "sine"):
         net = FFMLP(32, 3, 64, 2, activation=name).cuda().train()
-        assert net.activation in ACT_NAMES and not field_fusable(enc, net)
+        assert net.activation in ACT_NAMES and not field_plan(SimpleNamespace(encoder=enc, sigma_net=net)).field
         x = (torch.randn(500, 32, device="cuda") * 0.5).half().requires_grad_(True)
         with torch.autocast("cuda", dtype=torch.float16):
             y = net(x)

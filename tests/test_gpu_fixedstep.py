@@ -367,9 +367,10 @@ def test_render_tail_node_is_bitwise_the_three_node_chain(N, T, layers, perturb,
 
 def test_render_tail_is_the_path_render_fixed_steps_trains_through(monkeypatch):
     """render_fixed_steps with and without the fused tail (FOC_FUSED_TAIL=0): same image bits; gradients equal up to atomics order."""
-    from focnerf_amd.fixedstep import render_fixed_steps, tail_fusable
+    from focnerf_amd.field import field_plan
+    from focnerf_amd.fixedstep import render_fixed_steps
     m = _model(1, 5).train()
-    assert tail_fusable(m)
+    assert field_plan(m).tail
     o, d = _rays(1, 16, 2)
     target = torch.rand(1, o.shape[1], 3, device="cuda")
     outs = {}

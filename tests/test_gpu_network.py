@@ -184,7 +184,8 @@ def test_inference_loop_matches_training_composite(monkeypatch):
         a = m.render(o, d, staged=False, perturb=False, force_all_rays=True, dt_gamma=1 / 128, max_steps=1024, bg_color=1.0)
         m.eval()
         b = m.render(o, d, device_compaction=False, **kw)                 # the reference's loop
-        assert m._native_loop_ok(o.view(-1, 3))
+        from focnerf_amd.field import field_plan
+        assert o.is_cuda and torch.is_autocast_enabled() and not torch.is_grad_enabled() and field_plan(m).native_loop
         dflt = m.render(o, d, **kw)                                       # default: the native loop where it serves the network
         c = m.render(o, d, device_compaction=True, **kw)                  # native loop
         monkeypatch.setenv("FOC_RENDER_NATIVE", "0")
@@ -255,9 +256,9 @@ def test_fused_head_matches_torch_glue(monkeypatch):
 def test_fused_field_matches_separate_nodes(B, monkeypatch):
     """hashgrid_mlp (encoder output kept as [L,B,C] planes, planar-input MLP kernels) == sigma_net.forward_padded(encoder(x)):
     identical h bits, same parameter gradients (fp32 atomics / fixed-point sums: tolerance)."""
-    from focnerf_amd.field import hashgrid_mlp, field_fusable
+    from focnerf_amd.field import hashgrid_mlp, field_plan
     m = _model(1, False).train()
-    assert field_fusable(m.encoder, m.sigma_net)
+    assert field_plan(m).field
     gen = torch.Generator(device="cuda").manual_seed(11)
     x = torch.rand(B, 3, device="cuda", generator=gen) * 2 - 1
     gh = (torch.randn(B, 16, device="cuda", generator=gen) * 0.1).half()

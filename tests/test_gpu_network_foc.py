@@ -59,9 +59,9 @@ def test_foc_network_shapes_and_params():
     names = {n for n, _ in m.named_parameters()}
     assert {"encoder.embeddings", "sigma_net.weights", "color_net.weights", "yolo_feat_encoder.l0.weight", "yolo_feat_encoder.l1.weight"} <= names
     assert len(m.get_params(1e-2)) == 5
-    from focnerf_amd.field import infer_fusable
-    from focnerf_amd.fixedstep import tail_fusable
-    assert tail_fusable(m) and infer_fusable(m), "the object-conditioned network must be on the fused paths"
+    from focnerf_amd.field import field_plan
+    plan = field_plan(m)
+    assert plan.tail and plan.infer, "the object-conditioned network must be on the fused paths"
 
 
 @pytest.mark.parametrize("layers,out_width,T,N", [(2, 4, 64, 37), (3, 16, 128, 16), (2, 16, 1, 700), (2, 4, 512, 9)])
