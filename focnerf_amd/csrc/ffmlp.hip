@@ -1280,7 +1280,11 @@ static int mlp_check(const char *who, uint32_t B, uint32_t input_dim, uint32_t o
     // checked per launch)
     FOC_REQUIRE(input_dim > 0 && input_dim % 16 == 0 && input_dim <= 256u, FOC_E_INVALID, "%s: input_dim must be a multiple of 16 up to 256 (got %u)", who, input_dim);
     FOC_REQUIRE(output_dim <= 16, FOC_E_INVALID, "%s: output_dim must be <= 16 (got %u)", who, output_dim);
-    FOC_REQUIRE(num_layers >= 2 && num_layers <= 16, FOC_E_INVALID, "%s: num_layers must be in [2,16] (got %u)", who, num_layers);
+    // num_layers counts the hidden layers: 1 = input -> hidden -> output (two matmuls, tcnn's FullyFusedMLP with n_hidden_layers 1); the
+    // reference's FFMLP module asks for >= 2 (ffmlp.py:115) and still does (focnerf_amd/ffmlp.py), the C ABI takes both
+    FOC_REQUIRE(num_layers >= 1 && num_layers <= 16, FOC_E_INVALID, "%s: num_layers must be in [1,16] (got %u)", who, num_layers);
+    FOC_REQUIRE(hidden_dim != 256 || num_layers >= 2, FOC_E_INVALID,
+                "%s: hidden_dim 256 needs num_layers >= 2 (the layer-by-layer path is not built for one hidden layer; tcnn's FullyFusedMLP stops at 128 neurons)", who);
     FOC_REQUIRE(activation <= 6, FOC_E_INVALID, "%s: hidden activation must be one of relu(0) exponential(1) sine(2) sigmoid(3) squareplus(4) softplus(5) none(6) (got %u)", who, activation);
     FOC_REQUIRE(output_activation == 6, FOC_E_INVALID, "%s: output activation must be none(6) (got %u)", who, output_activation);
     return FOC_OK;
@@ -1373,7 +1377,7 @@ static int mlp_bwd_fused_launch(const void *grad, const void *inputs, const void
             else kern = planar ? k_mlp_bwd_fused<HIDDEN, NL, NB, true, 1, true, true> : k_mlp_bwd_fused<HIDDEN, NL, NB, true, 0, true, true>;
         }
     }
-    if constexpr (HIDDEN == 64 && NL <= 3) {
+    if constexpr (HIDDEN == 64 && NL >= 2 && NL <= 3) {
         if (head) kern = head->out_width == 4u ? (relu ? (lean ? k_mlp_bwd_fused<HIDDEN, NL, NB, true, 3, true, false, true> : k_mlp_bwd_fused<HIDDEN, NL, NB, true, 3, true>)
                                                        : k_mlp_bwd_fused<HIDDEN, NL, NB, true, 3, false>)
                                                : (relu ? (lean ? k_mlp_bwd_fused<HIDDEN, NL, NB, true, 2, true, false, true> : k_mlp_bwd_fused<HIDDEN, NL, NB, true, 2, true>)
@@ -1435,6 +1439,7 @@ static int mlp_bwd_launch(const void *grad, const void *inputs, const void *weig
     if constexpr (HIDDEN <= 64) {
         if (use_fused && in_dim <= 64 && !gen) {
             switch (num_layers) {
+                case 1: return mlp_bwd_fused_launch<HIDDEN, 1>(grad, inputs, weights, fwd_buf, B, in_dim, relu, bwd_buf, grad_inputs, grad_weights, ws, planar, st);
                 case 2: return mlp_bwd_fused_launch<HIDDEN, 2>(grad, inputs, weights, fwd_buf, B, in_dim, relu, bwd_buf, grad_inputs, grad_weights, ws, planar, st);
                 case 3: return mlp_bwd_fused_launch<HIDDEN, 3>(grad, inputs, weights, fwd_buf, B, in_dim, relu, bwd_buf, grad_inputs, grad_weights, ws, planar, st);
                 case 4: return mlp_bwd_fused_launch<HIDDEN, 4>(grad, inputs, weights, fwd_buf, B, in_dim, relu, bwd_buf, grad_inputs, grad_weights, ws, planar, st);
@@ -1443,7 +1448,7 @@ static int mlp_bwd_launch(const void *grad, const void *inputs, const void *weig
         }
     }
     FOC_REQUIRE(bwd_buf && fwd_buf, FOC_E_INVALID, "ffmlp_backward: forward_buffer and backward_buffer are required for this shape / activation (two-kernel path)");
-    FOC_REQUIRE(!planar, FOC_E_INVALID, "ffmlp_backward: planar inputs are served by the fused kernel only (hidden_dim <= 64, input_dim <= 64, 2..4 layers)");
+    FOC_REQUIRE(!planar, FOC_E_INVALID, "ffmlp_backward: planar inputs are served by the fused kernel only (hidden_dim <= 64, input_dim <= 64, 1..4 layers)");
     constexpr int NB = 2;
     const bool dx = grad_inputs != nullptr;
     const size_t lds = mlp_bwd_lds<HIDDEN>(in_dim, num_layers, dx);
@@ -1503,7 +1508,7 @@ uint64_t foc_ffmlp_backward_workspace_bytes(uint32_t input_dim, uint32_t hidden_
     // the fp32 image of the weight blob (split-K sums of k_mlp_dw; the object-conditioned head's finalize) and, for the shapes
     // k_mlp_bwd_fused serves, one slot of partial tiles per workgroup of its launch
     uint64_t floats = mlp_dw_blob_floats(input_dim, hidden_dim, num_layers);
-    if (hidden_dim <= 64 && input_dim <= 64 && num_layers >= 2 && num_layers <= 4) floats += (uint64_t)MLP_DW_MAX_SLOTS * (num_layers + 1) * MLP_DW_SLOT_STAGE;
+    if (hidden_dim <= 64 && input_dim <= 64 && num_layers >= 1 && num_layers <= 4) floats += (uint64_t)MLP_DW_MAX_SLOTS * (num_layers + 1) * MLP_DW_SLOT_STAGE;
     return floats * sizeof(float);
 }
 
@@ -1597,6 +1602,7 @@ int foc_color_head_forward(const void *h, const void *ray_sh, uint32_t samples_p
     FocDeviceGuard foc_guard_(stream, h);
     int rc = mlp_check("color_head_forward", B, 32, 16, hidden_dim, num_layers, activation, 6);
     if (rc) return rc;
+    FOC_REQUIRE(num_layers >= 2, FOC_E_INVALID, "color_head_forward: num_layers must be in [2,16] (got %u)", num_layers);
     if (B == 0) return FOC_OK;
     FOC_REQUIRE(h && ray_sh && weights && outputs, FOC_E_INVALID, "color_head_forward: null pointer");
     FOC_REQUIRE(hidden_dim == 64 && samples_per_ray >= 1, FOC_E_INVALID, "color_head_forward: hidden_dim must be 64 (got %u), samples_per_ray >= 1", hidden_dim);

@@ -35,7 +35,7 @@ def single_pass_backward(input_dim, hidden_dim, num_layers, activation=0):
     """Shapes served by k_mlp_bwd_fused (activation gradients, weight gradients and input gradients in one pass): ReLU / no activation —
     every NeRF network; the reference's other hidden activations (exponential, sine, sigmoid, squareplus, softplus, utils.h:424-589) take
     its own data flow, stored activations and a [layers, B, hidden] gradient buffer."""
-    return (activation in (ACTIVATIONS['relu'], NO_ACTIVATION) and hidden_dim <= 64 and input_dim <= 64 and 2 <= num_layers <= 4
+    return (activation in (ACTIVATIONS['relu'], NO_ACTIVATION) and hidden_dim <= 64 and input_dim <= 64 and 1 <= num_layers <= 4
             and _fused_backward_switch())
 
 

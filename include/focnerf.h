@@ -332,7 +332,9 @@ int foc_freq_encode_backward(const float *grad, const float *outputs, uint32_t B
  * inputs [B,input_dim], outputs [B,16] (output_dim is the padded 16), row-major.
  * Any B >= 1 is accepted (the reference kernels need a multiple of 128 and its wrapper pads with a copy,
  * ffmlp/ffmlp.py:157-159; here the ragged last tile is handled in the kernels, so no padded copy is needed);
- * hidden_dim in {16,32,64,128,256}; input_dim % 16 == 0; output_dim <= 16; num_layers >= 2.
+ * hidden_dim in {16,32,64,128,256}; input_dim % 16 == 0; output_dim <= 16; num_layers (hidden layers) 1..16, at hidden_dim 256
+ * 2..16. num_layers 1 is input -> hidden -> output, two matmuls (tcnn's FullyFusedMLP with one hidden layer; the reference's FFMLP
+ * module asks for >= 2, ffmlp.py:115). The colour-head and whole-field entry points below keep their own layer counts.
  * activation codes follow ffmlp.py:86-93: 0 relu, 1 exponential, 2 sine, 3 sigmoid, 4 squareplus, 5 softplus, 6 none — the hidden
  * activations of ffmlp/src/utils.h:424-589, evaluated as there (fp32 function of the half-rounded sum; the backward factor from the stored
  * post-activation in half arithmetic; Sine's backward a pass-through, as the reference leaves it). Codes 1..5 take the reference's data
@@ -344,7 +346,7 @@ int foc_freq_encode_backward(const float *grad, const float *outputs, uint32_t B
  *       activation, output_activation, forward_buffer [num_layers,B,hidden], outputs)
  * forward_buffer may be NULL: no activations are kept (outputs are the same bits); pass NULL
  * to foc_ffmlp_backward as well and it re-evaluates them from `inputs` on chip (hidden_dim <= 64,
- * input_dim <= 64, num_layers 2..4 — the shapes of the fused backward kernel). */
+ * input_dim <= 64, num_layers 1..4 — the shapes of the fused backward kernel). */
 int foc_ffmlp_forward(const void *inputs, const void *weights, uint32_t B, uint32_t input_dim,
                       uint32_t output_dim, uint32_t hidden_dim, uint32_t num_layers,
                       uint32_t activation, uint32_t output_activation,
@@ -363,7 +365,7 @@ int foc_ffmlp_inference(const void *inputs, const void *weights, uint32_t B, uin
  * activation gradients then never leave the chip); other shapes need both (FOC_E_INVALID otherwise).
  * workspace: device memory, foc_ffmlp_backward_workspace_bytes(input_dim, hidden_dim, num_layers) bytes, caller-owned, needs NO zero fill:
  * [fp32 image of the weight blob: the split-K sums of the two-kernel form, the object-conditioned head's finalize] followed, for the shapes
- * the single-pass kernel serves (hidden_dim <= 64, input_dim <= 64, 2..4 layers), by up to 1024 per-workgroup slots of
+ * the single-pass kernel serves (hidden_dim <= 64, input_dim <= 64, 1..4 layers), by up to 1024 per-workgroup slots of
  * (num_layers + 1) x 4096 fp32 partial weight-gradient tiles that a second kernel sums in a fixed order (33 - 80 MB; the reference's CUTLASS
  * split-K workspace, cutlass_matmul.h:335-363, is a process-global map instead). `workspace_bytes` = the size of the caller's buffer: a
  * buffer smaller than foc_ffmlp_backward_workspace_bytes() is refused (FOC_E_INVALID) instead of being written past its end; for the colour
@@ -381,7 +383,7 @@ uint64_t foc_ffmlp_backward_workspace_bytes(uint32_t input_dim, uint32_t hidden_
  * permute + copy to [B, L*C] the reference wrapper makes (grid.py:57); `grad_inputs_planar` has the same layout,
  * i.e. the [L, B, C] gradient foc_grid_encode_backward(_binned) reads (grid.py:75 builds it with another permute).
  * Semantics otherwise as foc_ffmlp_forward / foc_ffmlp_backward with forward_buffer and backward_buffer NULL
- * (same shape limits: hidden_dim <= 64, input_dim <= 64, num_layers 2..4 for the backward). */
+ * (same shape limits: hidden_dim <= 64, input_dim <= 64, num_layers 1..4 for the backward). */
 int foc_ffmlp_forward_planar(const void *inputs_planar, const void *weights, uint32_t B, uint32_t input_dim,
                              uint32_t output_dim, uint32_t hidden_dim, uint32_t num_layers,
                              uint32_t activation, uint32_t output_activation, void *outputs, void *stream);
