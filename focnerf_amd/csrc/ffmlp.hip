@@ -46,7 +46,7 @@ __global__ void __launch_bounds__(MLP_BLOCK, 2) k_mlp_fwd(const _Float16 *__rest
     const float *obj_bias = reinterpret_cast<const float *>(lds + (size_t)(f_out + KC) * 512);      // head mode with an object feature only
     if constexpr (IMODE == 2) {
         stage_weights_fwd<HIDDEN>(weights, lds, in_dim, num_layers, true, head_ld0(hd));
-        if (hd.obj) stage_obj_bias(weights, hd.obj, const_cast<float *>(obj_bias), HIDDEN);
+        if (hd.obj) stage_obj_bias(weights, hd.obj, const_cast<float *>(obj_bias), HIDDEN, hd.pad);
     } else stage_weights_fwd<HIDDEN>(weights, lds, in_dim, num_layers);
     __syncthreads();
 
@@ -463,7 +463,7 @@ __global__ void __launch_bounds__(MLP_BLOCK, 2) k_mlp_bwd_fused(const _Float16 *
     const float *obj_bias = reinterpret_cast<const float *>(ldsF + (size_t)(((HIDDEN + 31) / 32) * (in_dim / 16) + (NL - 1) * ((HIDDEN + 31) / 32) * (HIDDEN / 16)) * 512);
     if constexpr (RECOMP) {
         stage_weights_fwd<HIDDEN>(weights, ldsF, in_dim, NL, false, ld0);
-        if constexpr (HEAD) { if (has_obj) stage_obj_bias(weights, hd.obj, const_cast<float *>(obj_bias), HIDDEN); }
+        if constexpr (HEAD) { if (has_obj) stage_obj_bias(weights, hd.obj, const_cast<float *>(obj_bias), HIDDEN, hd.pad); }
     }
     __syncthreads();
 
@@ -962,15 +962,17 @@ __global__ void __launch_bounds__(1024) k_mlp_dw_reduce(const float *__restrict_
 
 // Finalize of the colour head with an object feature (MlpHead): the workspace's W0 block has 48-wide rows of which the MFMAs filled
 // columns 0..30 and column 31 = cs[o] = sum_b delta_0[b][o]. dW0[o][31 + j] = cs[o] * obj[j] (the input columns 31..46 hold the same
-// obj[j] for every sample), dW0[o][47] = 0 (zero pad input), and grad_obj[j] = sum_o W0[o][31 + j] * cs[o] (fp32, [16]).
+// obj[j] for every sample), dW0[o][47] = cs[o] * pad (the constant input column: 0 for a zero pad, MlpHead::pad), and
+// grad_obj[j] = sum_o W0[o][31 + j] * cs[o] (fp32, [16]).
 __global__ void __launch_bounds__(256) k_mlp_dw_finalize_obj(const float *__restrict__ ws, _Float16 *__restrict__ gw, uint32_t n, uint32_t hidden,
-                                                             const _Float16 *__restrict__ W, const _Float16 *__restrict__ obj, float *__restrict__ grad_obj) {
+                                                             const _Float16 *__restrict__ W, const _Float16 *__restrict__ obj, float *__restrict__ grad_obj,
+                                                             float pad) {
     const uint32_t n0 = hidden * HEAD_OBJ_LD;
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
         float v = ws[i];
         if (i < n0) {
             const uint32_t o = i / HEAD_OBJ_LD, col = i % HEAD_OBJ_LD;
-            if (col >= 31) v = col < 47 ? ws[o * HEAD_OBJ_LD + 31] * (float)obj[col - 31] : 0.0f;
+            if (col >= 31) v = col < 47 ? ws[o * HEAD_OBJ_LD + 31] * (float)obj[col - 31] : (pad != 0.0f ? ws[o * HEAD_OBJ_LD + 31] * pad : 0.0f);
         }
         gw[i] = (_Float16)v;
     }
@@ -1017,7 +1019,8 @@ __device__ __forceinline__ void nf_sh16_half(float x, float y, float z, int h, h
 template <int NLS, int NLC, bool PLANAR, bool RELU_CT, bool BLK, bool OBJ>
 __global__ void __launch_bounds__(MLP_BLOCK, 2) k_nerf_infer(const _Float16 *__restrict__ enc, const float *__restrict__ dirs, uint32_t dir_div,
                                                           uint32_t dir_block, uint32_t n_dirs, const _Float16 *__restrict__ w_sigma, const _Float16 *__restrict__ w_color, uint32_t B,
-                                                          int relu_rt, float *__restrict__ sigma_out, float *__restrict__ rgb_out, const _Float16 *__restrict__ obj) {
+                                                          int relu_rt, float *__restrict__ sigma_out, float *__restrict__ rgb_out, const _Float16 *__restrict__ obj,
+                                                          float pad) {
     const int relu = RELU_CT ? 1 : relu_rt;            // ReLU as a compile-time fact (see k_mlp_bwd_fused); `false` keeps the runtime flag
     f16v FZ;                                           // constant zero C operand: the first MFMA of every chain takes the inline constant 0
 #pragma unroll
@@ -1062,7 +1065,7 @@ __global__ void __launch_bounds__(MLP_BLOCK, 2) k_nerf_infer(const _Float16 *__r
         }
     }
     const float *obj_bias = reinterpret_cast<const float *>(ldsC + (size_t)(MT * KS0 + (NLC - 1) * MT * KC + KC) * 512);
-    if constexpr (OBJ) stage_obj_bias(w_color, obj, const_cast<float *>(obj_bias), HIDDEN);
+    if constexpr (OBJ) stage_obj_bias(w_color, obj, const_cast<float *>(obj_bias), HIDDEN, pad);
     __syncthreads();
 
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1320,7 +1323,7 @@ static int mlp_fwd_launch(const void *inputs, const void *weights, uint32_t B, u
     const uint32_t cap = mlp_num_cus() * mlp_resident_blocks(reinterpret_cast<const void *>(kern), lds);
     if (grid > cap) grid = cap;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(MLP_BLOCK), lds, st, (const _Float16 *)inputs, (const _Float16 *)weights, (_Float16 *)fwd_buf,
-                       (_Float16 *)outputs, B, in_dim, num_layers, act, head ? *head : MlpHead{nullptr, nullptr, 1u, 16u, nullptr});
+                       (_Float16 *)outputs, B, in_dim, num_layers, act, head ? *head : MlpHead{nullptr, nullptr, 1u, 16u, nullptr, 0.0f});
     FOC_CHECK_LAUNCH(TRAIN ? "ffmlp_forward" : "ffmlp_inference");
     return FOC_OK;
 }
@@ -1393,14 +1396,14 @@ static int mlp_bwd_fused_launch(const void *grad, const void *inputs, const void
     float *slots = ws + mlp_dw_blob_floats(has_obj ? HEAD_OBJ_LD : in_dim, HIDDEN, NL);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(MLP_BLOCK), lds_launch, st, (const _Float16 *)grad, (const _Float16 *)inputs, (const _Float16 *)weights,
                        (const _Float16 *)fwd_buf, (_Float16 *)bwd_buf, (_Float16 *)grad_inputs, slots, B, in_dim, relu, (uint32_t)(lds_w / sizeof(_Float16)),
-                       head ? *head : MlpHead{nullptr, nullptr, 1u, 16u, nullptr});
+                       head ? *head : MlpHead{nullptr, nullptr, 1u, 16u, nullptr, 0.0f});
     FOC_CHECK_LAUNCH("ffmlp_backward(fused)");
     hipLaunchKernelGGL((k_mlp_dw_reduce<HIDDEN>), dim3((NL + 1) * 64), dim3(1024), 0, st, (const float *)slots, grid, (uint32_t)NL, in_dim,
                        has_obj ? (uint32_t)HEAD_OBJ_LD : in_dim, (_Float16 *)grad_weights, has_obj ? ws : (float *)nullptr);
     FOC_CHECK_LAUNCH("ffmlp_backward(reduce)");
     if (has_obj) {
         hipLaunchKernelGGL(k_mlp_dw_finalize_obj, dim3(foc_grid_1d(n_w, 256)), dim3(256), 0, st, ws, (_Float16 *)grad_weights, n_w, (uint32_t)HIDDEN,
-                           (const _Float16 *)weights, head->obj, grad_obj);
+                           (const _Float16 *)weights, head->obj, grad_obj, head->pad);
         FOC_CHECK_LAUNCH("ffmlp_backward(finalize)");
     }
     return FOC_OK;
@@ -1467,7 +1470,7 @@ static int mlp_bwd_launch(const void *grad, const void *inputs, const void *weig
 
 template <int NLS, int NLC>
 static int nerf_infer_launch(const void *enc, const float *dirs, uint32_t dir_div, uint32_t dir_block, uint32_t n_dirs, const void *w_sigma, const void *w_color, uint32_t B, int relu, int planar,
-                             float *sigma, float *rgb, const void *obj, hipStream_t st) {
+                             float *sigma, float *rgb, const void *obj, float pad, hipStream_t st) {
     const size_t lds = (size_t)((2 * 2 + (NLS - 1) * 8 + 4) + (2 * 2 + (NLC - 1) * 8 + 4)) * 1024 + (obj ? 256 : 0);
     const bool blk = planar && dir_block == 64u;     // the staged render's sample order (fixedstep.hip FS_RAY_BLOCK)
     auto kern = planar ? (blk ? (relu ? k_nerf_infer<NLS, NLC, true, true, true, false> : k_nerf_infer<NLS, NLC, true, false, true, false>)
@@ -1483,7 +1486,7 @@ static int nerf_infer_launch(const void *enc, const float *dirs, uint32_t dir_di
     const uint32_t cap = mlp_num_cus() * mlp_resident_blocks(reinterpret_cast<const void *>(kern), lds);
     if (grid > cap) grid = cap;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(MLP_BLOCK), lds, st, (const _Float16 *)enc, dirs, dir_div, dir_block, n_dirs, (const _Float16 *)w_sigma,
-                       (const _Float16 *)w_color, B, relu, sigma, rgb, (const _Float16 *)obj);
+                       (const _Float16 *)w_color, B, relu, sigma, rgb, (const _Float16 *)obj, pad);
     FOC_CHECK_LAUNCH("nerf_field_inference");
     return FOC_OK;
 }
@@ -1574,10 +1577,9 @@ int foc_ffmlp_backward_planar(const void *grad, const void *inputs_planar, const
                          calc_grad_inputs, nullptr, grad_inputs_planar, grad_weights, workspace, workspace_bytes, 1, stream);
 }
 
-int foc_nerf_field_inference(const void *enc, int enc_planar, const float *dirs, uint32_t dir_div, uint32_t dir_block, uint32_t n_dirs,
-                             const void *sigma_weights, uint32_t sigma_layers,
-                             const void *color_weights, uint32_t color_layers, uint32_t hidden_dim, uint32_t activation, uint32_t B, float *sigma,
-                             float *rgb, const void *obj_feat, void *stream) {
+static int nerf_field_inference(const void *enc, int enc_planar, const float *dirs, uint32_t dir_div, uint32_t dir_block, uint32_t n_dirs,
+                                const void *sigma_weights, uint32_t sigma_layers, const void *color_weights, uint32_t color_layers, uint32_t hidden_dim,
+                                uint32_t activation, uint32_t B, float *sigma, float *rgb, const void *obj_feat, float input_pad, void *stream) {
     FocDeviceGuard foc_guard_(stream, enc);
     if (B == 0) return FOC_OK;
     FOC_REQUIRE(enc && dirs && sigma_weights && color_weights && rgb, FOC_E_INVALID, "nerf_field_inference: null pointer");
@@ -1585,20 +1587,40 @@ int foc_nerf_field_inference(const void *enc, int enc_planar, const float *dirs,
     FOC_REQUIRE(dir_block == 0 || n_dirs >= 1, FOC_E_INVALID, "nerf_field_inference: the block-interleaved row order needs the number of directions");
     FOC_REQUIRE((uint64_t)dir_block * dir_div < (1ull << 32), FOC_E_INVALID, "nerf_field_inference: dir_block * dir_div must fit 32 bits");
     FOC_REQUIRE(activation == 0 || activation == 6, FOC_E_INVALID, "nerf_field_inference: hidden activation must be relu(0) or none(6)");
+    FOC_REQUIRE(input_pad == 0.0f || obj_feat, FOC_E_INVALID, "nerf_field_inference: input_pad is column 47 of the 48-wide colour input and needs obj_feat");
     const int relu = activation == 0;
     hipStream_t st = (hipStream_t)stream;
     const uint32_t key = sigma_layers * 10 + color_layers;
+    const float pad = input_pad;
     switch (key) {
-        case 22: return nerf_infer_launch<2, 2>(enc, dirs, dir_div, dir_block, n_dirs, sigma_weights, color_weights, B, relu, enc_planar, sigma, rgb, obj_feat, st);
-        case 23: return nerf_infer_launch<2, 3>(enc, dirs, dir_div, dir_block, n_dirs, sigma_weights, color_weights, B, relu, enc_planar, sigma, rgb, obj_feat, st);
-        case 33: return nerf_infer_launch<3, 3>(enc, dirs, dir_div, dir_block, n_dirs, sigma_weights, color_weights, B, relu, enc_planar, sigma, rgb, obj_feat, st);
-        default: foc_set_error("nerf_field_inference: layer counts (%u, %u) are not built (2/2, 2/3, 3/3)", sigma_layers, color_layers); return FOC_E_INVALID;
+        case 12: return nerf_infer_launch<1, 2>(enc, dirs, dir_div, dir_block, n_dirs, sigma_weights, color_weights, B, relu, enc_planar, sigma, rgb, obj_feat, pad, st);
+        case 13: return nerf_infer_launch<1, 3>(enc, dirs, dir_div, dir_block, n_dirs, sigma_weights, color_weights, B, relu, enc_planar, sigma, rgb, obj_feat, pad, st);
+        case 22: return nerf_infer_launch<2, 2>(enc, dirs, dir_div, dir_block, n_dirs, sigma_weights, color_weights, B, relu, enc_planar, sigma, rgb, obj_feat, pad, st);
+        case 23: return nerf_infer_launch<2, 3>(enc, dirs, dir_div, dir_block, n_dirs, sigma_weights, color_weights, B, relu, enc_planar, sigma, rgb, obj_feat, pad, st);
+        case 33: return nerf_infer_launch<3, 3>(enc, dirs, dir_div, dir_block, n_dirs, sigma_weights, color_weights, B, relu, enc_planar, sigma, rgb, obj_feat, pad, st);
+        default: foc_set_error("nerf_field_inference: layer counts (%u, %u) are not built (1/2, 1/3, 2/2, 2/3, 3/3)", sigma_layers, color_layers); return FOC_E_INVALID;
     }
 }
 
+int foc_nerf_field_inference(const void *enc, int enc_planar, const float *dirs, uint32_t dir_div, uint32_t dir_block, uint32_t n_dirs,
+                             const void *sigma_weights, uint32_t sigma_layers,
+                             const void *color_weights, uint32_t color_layers, uint32_t hidden_dim, uint32_t activation, uint32_t B, float *sigma,
+                             float *rgb, const void *obj_feat, void *stream) {
+    return nerf_field_inference(enc, enc_planar, dirs, dir_div, dir_block, n_dirs, sigma_weights, sigma_layers, color_weights, color_layers, hidden_dim,
+                                activation, B, sigma, rgb, obj_feat, 0.0f, stream);
+}
+
+int foc_nerf_field_inference_pad(const void *enc, int enc_planar, const float *dirs, uint32_t dir_div, uint32_t dir_block, uint32_t n_dirs,
+                                 const void *sigma_weights, uint32_t sigma_layers,
+                                 const void *color_weights, uint32_t color_layers, uint32_t hidden_dim, uint32_t activation, uint32_t B, float *sigma,
+                                 float *rgb, const void *obj_feat, float input_pad, void *stream) {
+    return nerf_field_inference(enc, enc_planar, dirs, dir_div, dir_block, n_dirs, sigma_weights, sigma_layers, color_weights, color_layers, hidden_dim,
+                                activation, B, sigma, rgb, obj_feat, input_pad, stream);
+}
+
 // The colour network of the fixed-step training path, fed from the sigma network's output rows and a per-ray SH table (input mode 2).
-int foc_color_head_forward(const void *h, const void *ray_sh, uint32_t samples_per_ray, const void *weights, uint32_t B, uint32_t hidden_dim,
-                           uint32_t num_layers, uint32_t activation, void *outputs, uint32_t out_width, const void *obj_feat, void *stream) {
+static int color_head_forward(const void *h, const void *ray_sh, uint32_t samples_per_ray, const void *weights, uint32_t B, uint32_t hidden_dim,
+                              uint32_t num_layers, uint32_t activation, void *outputs, uint32_t out_width, const void *obj_feat, float input_pad, void *stream) {
     FocDeviceGuard foc_guard_(stream, h);
     int rc = mlp_check("color_head_forward", B, 32, 16, hidden_dim, num_layers, activation, 6);
     if (rc) return rc;
@@ -1607,14 +1629,26 @@ int foc_color_head_forward(const void *h, const void *ray_sh, uint32_t samples_p
     FOC_REQUIRE(h && ray_sh && weights && outputs, FOC_E_INVALID, "color_head_forward: null pointer");
     FOC_REQUIRE(hidden_dim == 64 && samples_per_ray >= 1, FOC_E_INVALID, "color_head_forward: hidden_dim must be 64 (got %u), samples_per_ray >= 1", hidden_dim);
     FOC_REQUIRE(out_width == 16 || out_width == 4, FOC_E_INVALID, "color_head_forward: out_width must be 16 or 4 (got %u)", out_width);
-    const MlpHead hd{(const _Float16 *)ray_sh, nullptr, samples_per_ray, out_width, (const _Float16 *)obj_feat};
+    FOC_REQUIRE(input_pad == 0.0f || obj_feat, FOC_E_INVALID, "color_head_forward: input_pad is column 47 of the 48-wide colour input and needs obj_feat");
+    const MlpHead hd{(const _Float16 *)ray_sh, nullptr, samples_per_ray, out_width, (const _Float16 *)obj_feat, input_pad};
     FOC_REQUIRE(activation == FOC_ACT_RELU || activation == FOC_ACT_NONE, FOC_E_INVALID, "color_head_forward: hidden activation must be relu(0) or none(6)");
     return mlp_fwd_launch<64, false>(h, weights, B, 32, num_layers, (int)activation, nullptr, outputs, 0, (hipStream_t)stream, &hd);
 }
 
-int foc_color_head_backward(const void *grad, const void *h, const void *ray_sh, uint32_t samples_per_ray, const void *grad_h0, const void *weights,
-                            uint32_t B, uint32_t hidden_dim, uint32_t num_layers, uint32_t activation, void *grad_h, void *grad_weights, void *workspace,
-                            uint64_t workspace_bytes, uint32_t out_width, const void *obj_feat, float *grad_obj, void *stream) {
+int foc_color_head_forward(const void *h, const void *ray_sh, uint32_t samples_per_ray, const void *weights, uint32_t B, uint32_t hidden_dim,
+                           uint32_t num_layers, uint32_t activation, void *outputs, uint32_t out_width, const void *obj_feat, void *stream) {
+    return color_head_forward(h, ray_sh, samples_per_ray, weights, B, hidden_dim, num_layers, activation, outputs, out_width, obj_feat, 0.0f, stream);
+}
+
+int foc_color_head_forward_pad(const void *h, const void *ray_sh, uint32_t samples_per_ray, const void *weights, uint32_t B, uint32_t hidden_dim,
+                               uint32_t num_layers, uint32_t activation, void *outputs, uint32_t out_width, const void *obj_feat, float input_pad,
+                               void *stream) {
+    return color_head_forward(h, ray_sh, samples_per_ray, weights, B, hidden_dim, num_layers, activation, outputs, out_width, obj_feat, input_pad, stream);
+}
+
+static int color_head_backward(const void *grad, const void *h, const void *ray_sh, uint32_t samples_per_ray, const void *grad_h0, const void *weights,
+                               uint32_t B, uint32_t hidden_dim, uint32_t num_layers, uint32_t activation, void *grad_h, void *grad_weights, void *workspace,
+                               uint64_t workspace_bytes, uint32_t out_width, const void *obj_feat, float *grad_obj, float input_pad, void *stream) {
     FocDeviceGuard foc_guard_(stream, grad);
     int rc = mlp_check("color_head_backward", B, 32, 16, hidden_dim, num_layers, activation, 6);
     if (rc) return rc;
@@ -1634,10 +1668,25 @@ int foc_color_head_backward(const void *grad, const void *h, const void *ray_sh,
                 obj_feat ? HEAD_OBJ_LD : 32u, num_layers, (unsigned long long)foc_ffmlp_backward_workspace_bytes(obj_feat ? HEAD_OBJ_LD : 32u, 64, num_layers));
     FOC_REQUIRE(out_width == 16 || out_width == 4, FOC_E_INVALID, "color_head_backward: out_width must be 16 or 4 (got %u)", out_width);
     FOC_REQUIRE(activation == FOC_ACT_RELU || activation == FOC_ACT_NONE, FOC_E_INVALID, "color_head_backward: hidden activation must be relu(0) or none(6)");
-    const MlpHead hd{(const _Float16 *)ray_sh, (const _Float16 *)grad_h0, samples_per_ray, out_width, (const _Float16 *)obj_feat};
+    FOC_REQUIRE(input_pad == 0.0f || obj_feat, FOC_E_INVALID, "color_head_backward: input_pad is column 47 of the 48-wide colour input and needs obj_feat");
+    const MlpHead hd{(const _Float16 *)ray_sh, (const _Float16 *)grad_h0, samples_per_ray, out_width, (const _Float16 *)obj_feat, input_pad};
     const int relu = activation == 0;
     if (num_layers == 2) return mlp_bwd_fused_launch<64, 2>(grad, h, weights, nullptr, B, 32, relu, nullptr, grad_h, grad_weights, (float *)workspace, 0, (hipStream_t)stream, &hd, grad_obj);
     return mlp_bwd_fused_launch<64, 3>(grad, h, weights, nullptr, B, 32, relu, nullptr, grad_h, grad_weights, (float *)workspace, 0, (hipStream_t)stream, &hd, grad_obj);
+}
+
+int foc_color_head_backward(const void *grad, const void *h, const void *ray_sh, uint32_t samples_per_ray, const void *grad_h0, const void *weights,
+                            uint32_t B, uint32_t hidden_dim, uint32_t num_layers, uint32_t activation, void *grad_h, void *grad_weights, void *workspace,
+                            uint64_t workspace_bytes, uint32_t out_width, const void *obj_feat, float *grad_obj, void *stream) {
+    return color_head_backward(grad, h, ray_sh, samples_per_ray, grad_h0, weights, B, hidden_dim, num_layers, activation, grad_h, grad_weights, workspace,
+                               workspace_bytes, out_width, obj_feat, grad_obj, 0.0f, stream);
+}
+
+int foc_color_head_backward_pad(const void *grad, const void *h, const void *ray_sh, uint32_t samples_per_ray, const void *grad_h0, const void *weights,
+                                uint32_t B, uint32_t hidden_dim, uint32_t num_layers, uint32_t activation, void *grad_h, void *grad_weights, void *workspace,
+                                uint64_t workspace_bytes, uint32_t out_width, const void *obj_feat, float *grad_obj, float input_pad, void *stream) {
+    return color_head_backward(grad, h, ray_sh, samples_per_ray, grad_h0, weights, B, hidden_dim, num_layers, activation, grad_h, grad_weights, workspace,
+                               workspace_bytes, out_width, obj_feat, grad_obj, input_pad, stream);
 }
 
 int foc_allocate_splitk(uint64_t size) { (void)size; return FOC_OK; }

@@ -35,7 +35,7 @@ __global__ void __launch_bounds__(MLP_BLOCK, FF_MIN_WAVES) k_field_fwd_train(con
     const float *obj_bias = reinterpret_cast<const float *>(ldsC + FC * 512);
     stage_weights_fwd<HIDDEN>(w_sigma, ldsS, 32, NLS);
     stage_weights_fwd<HIDDEN>(w_color, ldsC, 32, NLC, true, head_ld0(hd));
-    if (hd.obj) stage_obj_bias(w_color, hd.obj, const_cast<float *>(obj_bias), HIDDEN);
+    if (hd.obj) stage_obj_bias(w_color, hd.obj, const_cast<float *>(obj_bias), HIDDEN, hd.pad);
     __syncthreads();
 
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -194,26 +194,43 @@ static int ff_launch_act(const void *planes, const void *w_sigma, const void *w_
     return relu ? ff_launch<NLS, NLC, true>(planes, w_sigma, w_color, h, c, B, hd, st) : ff_launch<NLS, NLC, false>(planes, w_sigma, w_color, h, c, B, hd, st);
 }
 
-extern "C" {
-
-int foc_field_forward_train(const void *planes, const void *sigma_weights, uint32_t sigma_layers, const void *ray_sh, uint32_t samples_per_ray,
-                            const void *color_weights, uint32_t color_layers, uint32_t hidden_dim, uint32_t activation, uint32_t B, void *h, void *c,
-                            uint32_t out_width, const void *obj_feat, void *stream) {
+static int field_forward_train(const void *planes, const void *sigma_weights, uint32_t sigma_layers, const void *ray_sh, uint32_t samples_per_ray,
+                               const void *color_weights, uint32_t color_layers, uint32_t hidden_dim, uint32_t activation, uint32_t B, void *h, void *c,
+                               uint32_t out_width, const void *obj_feat, float input_pad, void *stream) {
     FocDeviceGuard foc_guard_(stream, planes);
     if (B == 0) return FOC_OK;
     FOC_REQUIRE(planes && sigma_weights && ray_sh && color_weights && h && c, FOC_E_INVALID, "field_forward_train: null pointer");
     FOC_REQUIRE(hidden_dim == 64 && samples_per_ray >= 1, FOC_E_INVALID, "field_forward_train: hidden_dim must be 64 (got %u), samples_per_ray >= 1", hidden_dim);
     FOC_REQUIRE(activation == FOC_ACT_RELU || activation == FOC_ACT_NONE, FOC_E_INVALID, "field_forward_train: hidden activation must be relu(0) or none(6)");
     FOC_REQUIRE(out_width == 16 || out_width == 4, FOC_E_INVALID, "field_forward_train: out_width must be 16 or 4 (got %u)", out_width);
-    const MlpHead hd{(const _Float16 *)ray_sh, nullptr, samples_per_ray, out_width, (const _Float16 *)obj_feat};
+    FOC_REQUIRE(input_pad == 0.0f || obj_feat, FOC_E_INVALID, "field_forward_train: input_pad is column 47 of the 48-wide colour input and needs obj_feat");
+    const MlpHead hd{(const _Float16 *)ray_sh, nullptr, samples_per_ray, out_width, (const _Float16 *)obj_feat, input_pad};
     const int relu = activation == FOC_ACT_RELU;
     hipStream_t st = (hipStream_t)stream;
     switch (sigma_layers * 10 + color_layers) {
+        case 12: return ff_launch_act<1, 2>(planes, sigma_weights, color_weights, h, c, B, relu, hd, st);
+        case 13: return ff_launch_act<1, 3>(planes, sigma_weights, color_weights, h, c, B, relu, hd, st);
         case 22: return ff_launch_act<2, 2>(planes, sigma_weights, color_weights, h, c, B, relu, hd, st);
         case 23: return ff_launch_act<2, 3>(planes, sigma_weights, color_weights, h, c, B, relu, hd, st);
         case 33: return ff_launch_act<3, 3>(planes, sigma_weights, color_weights, h, c, B, relu, hd, st);
-        default: foc_set_error("field_forward_train: layer counts (%u, %u) are not built (2/2, 2/3, 3/3)", sigma_layers, color_layers); return FOC_E_INVALID;
+        default: foc_set_error("field_forward_train: layer counts (%u, %u) are not built (1/2, 1/3, 2/2, 2/3, 3/3)", sigma_layers, color_layers); return FOC_E_INVALID;
     }
+}
+
+extern "C" {
+
+int foc_field_forward_train(const void *planes, const void *sigma_weights, uint32_t sigma_layers, const void *ray_sh, uint32_t samples_per_ray,
+                            const void *color_weights, uint32_t color_layers, uint32_t hidden_dim, uint32_t activation, uint32_t B, void *h, void *c,
+                            uint32_t out_width, const void *obj_feat, void *stream) {
+    return field_forward_train(planes, sigma_weights, sigma_layers, ray_sh, samples_per_ray, color_weights, color_layers, hidden_dim, activation, B, h, c,
+                               out_width, obj_feat, 0.0f, stream);
+}
+
+int foc_field_forward_train_pad(const void *planes, const void *sigma_weights, uint32_t sigma_layers, const void *ray_sh, uint32_t samples_per_ray,
+                                const void *color_weights, uint32_t color_layers, uint32_t hidden_dim, uint32_t activation, uint32_t B, void *h, void *c,
+                                uint32_t out_width, const void *obj_feat, float input_pad, void *stream) {
+    return field_forward_train(planes, sigma_weights, sigma_layers, ray_sh, samples_per_ray, color_weights, color_layers, hidden_dim, activation, B, h, c,
+                               out_width, obj_feat, input_pad, stream);
 }
 
 } // extern "C"

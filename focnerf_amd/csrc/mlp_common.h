@@ -99,19 +99,23 @@ struct MlpHead {
     // form. Backward: column 31 of the layer-0 input tile is set to 1, so the weight-gradient MFMAs deliver the column sum of delta_0 in
     // dW0[:, 31]; dW0[:, 31:47] = colsum (x) obj and grad_obj = W0[:, 31:47]^T colsum follow in the finalize kernel. W0 rows are 48 wide.
     const _Float16 *obj;           // [16] or null
+    // value of input column 47 of the 48-wide row (with `obj` only): 0 as above; 1.0 for the tinycudann layout (network_tcnn.py), where the
+    // padded input column acts as a free bias. Forward: W0[:, 47] * pad joins the per-neuron constant; backward: dW0[:, 47] = colsum * pad.
+    float pad;
 };
 #define HEAD_OBJ_LD 48u
 __device__ __forceinline__ uint32_t head_ld0(const MlpHead &hd) { return hd.obj ? HEAD_OBJ_LD : 32u; }
 
-// obj_bias[mt][h][reg] (fp32, accumulator-register order of acc_row) = sum_j W0[n][31 + j] * obj[j], n = 32 mt + acc_row(reg, h):
-// 64 threads, sequential fmaf in j order. `W0` has HEAD_OBJ_LD-wide rows.
-__device__ __forceinline__ void stage_obj_bias(const _Float16 *__restrict__ W0, const _Float16 *__restrict__ obj, float *bias, uint32_t hidden) {
+// obj_bias[mt][h][reg] (fp32, accumulator-register order of acc_row) = sum_j W0[n][31 + j] * obj[j] (+ W0[n][47] * pad), n = 32 mt + acc_row(reg, h):
+// 64 threads, sequential fmaf in j order, the pad term last. `W0` has HEAD_OBJ_LD-wide rows. pad = 0 adds nothing (not even a signed zero).
+__device__ __forceinline__ void stage_obj_bias(const _Float16 *__restrict__ W0, const _Float16 *__restrict__ obj, float *bias, uint32_t hidden, float pad) {
     if (threadIdx.x < hidden) {
         const uint32_t n = threadIdx.x, r = n & 31u, mt = n >> 5;
         const uint32_t h = (r >> 2) & 1u, reg = (r & 3u) + 4u * (r >> 3);
         float a = 0.0f;
 #pragma unroll
         for (int j = 0; j < 16; j++) a = fmaf((float)W0[(size_t)n * HEAD_OBJ_LD + 31 + j], (float)obj[j], a);
+        if (pad != 0.0f) a = fmaf((float)W0[(size_t)n * HEAD_OBJ_LD + 47], pad, a);
         bias[(mt * 2 + h) * 16 + reg] = a;
     }
 }

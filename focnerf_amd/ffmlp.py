@@ -90,6 +90,8 @@ def ffmlp_forward(inputs, weights, input_dim, output_dim, hidden_dim, num_layers
 
 
 class FFMLP(nn.Module):
+    min_layers = 2          # the reference's rule; a subclass that serves tinycudann's one-hidden-layer networks lowers it (network_tcnn.py)
+
     def __init__(self, input_dim, output_dim, hidden_dim, num_layers, activation='relu'):
         super().__init__()
         if hidden_dim not in SUPPORTED_HIDDEN:
@@ -98,7 +100,7 @@ class FFMLP(nn.Module):
             raise AssertionError(f"FFMLP input_dim should be 16 * m (m  > 0), but got {input_dim}")
         if output_dim > 16:
             raise AssertionError(f"FFMLP current only supports output dim <= 16, but got {output_dim}")
-        if num_layers < 2:
+        if num_layers < self.min_layers:
             raise AssertionError(f"FFMLP num_layers should be larger than 2 (3 matmuls), but got {num_layers}")
         self.input_dim, self.output_dim, self.hidden_dim, self.num_layers = input_dim, output_dim, hidden_dim, num_layers
         self.activation, self.output_activation = convert_activation(activation), convert_activation('none')

@@ -62,6 +62,7 @@ class FieldPlan:
     occ: bool                           # the occupancy-grid training forward as one node (occtrain._occ_train)
     native_loop: bool                   # the occupancy-grid inference loop as one call per iteration (NeRFRenderer._native_inference_loop)
     head: bool                          # the glue between the two networks as kernels (head.sample_head / rgb_head)
+    colour_input_pad: float = 0.0       # column 47 of the 48-wide object-conditioned colour input (1.0: tinycudann layout, network_tcnn.py)
 
 
 def _on(switch):
@@ -76,6 +77,7 @@ def field_plan(model):
     enc, enc_dir = getattr(model, "encoder", None), getattr(model, "encoder_dir", None)
     sigma, colour = MlpShape.of(getattr(model, "sigma_net", None)), MlpShape.of(getattr(model, "color_net", None))
     obj = bool(getattr(model, "uses_object_feature", False))
+    pad = float(getattr(model, "colour_input_pad", 0.0)) if obj else 0.0     # the *_pad kernels take it; sample_head writes a zero there
     grid = enc.spec() if isinstance(enc, GridEncoder) else None
 
     # the hash grid the [L,B,C] kernels read: D 3, C 2, feeding the sigma network directly; the native loop's encoder is the plain one
@@ -93,7 +95,7 @@ def field_plan(model):
     colour_relu_or_none = colour is not None and colour.activation in (0, 6)
     both = sigma is not None and colour is not None
     same_activation = both and sigma.activation == colour.activation
-    layer_pair = both and (sigma.num_layers, colour.num_layers) in ((2, 2), (2, 3), (3, 3))
+    layer_pair = both and (sigma.num_layers, colour.num_layers) in ((1, 2), (1, 3), (2, 2), (2, 3), (3, 3))
     whole_field = sigma_32_64 and colour_64 and colour_rows and layer_pair and same_activation   # both networks in one kernel
 
     field = hash_grid and sigma_one_pass and sigma_16 and _on("FOC_FUSED_FIELD")
@@ -105,7 +107,7 @@ def field_plan(model):
         train_forward=(field and tail and whole_field and sigma.output_activation == 6 and get_option("FOC_FIELD_FWD_FUSED") != 0),
         occ=field and tail and not obj and getattr(model, "bg_radius", 0) <= 0 and same_activation and _on("FOC_FUSED_OCC"),
         native_loop=(infer and not obj and getattr(model, "density_scale", 1) == 1 and plain_grid and _on("FOC_RENDER_NATIVE")),
-        head=both and colour.input_dim == colour_in and colour_rows and _on("FOC_FUSED_HEAD"))
+        head=both and colour.input_dim == colour_in and colour_rows and pad == 0 and _on("FOC_FUSED_HEAD"), colour_input_pad=pad)
 
 
 def _raw_stream_of(device):
@@ -181,7 +183,7 @@ def scope_cached(key, owner, make):
 
 def _check_colour_branch(colour, B):
     """The colour branch of `_hashgrid_mlp`, checked before its first launch: foc_field_forward_train trusts these sizes."""
-    cweights, shape, ray_sh, T, c_width, obj_feat = colour
+    cweights, shape, ray_sh, T, c_width, obj_feat = colour[:6]
     T = int(T)
     if not (ray_sh.dtype == torch.half and ray_sh.dim() == 2 and ray_sh.shape[1] == 16 and ray_sh.is_contiguous() and T > 0
             and B == ray_sh.shape[0] * T):
@@ -193,6 +195,8 @@ def _check_colour_branch(colour, B):
         raise RuntimeError(f"hashgrid_mlp colour branch: a {shape.input_dim}-wide colour input takes "
                            f"{'a 16-element object feature' if shape.input_dim == 48 else 'no object feature'}, got "
                            f"{'none' if obj_feat is None else f'{obj_feat.numel()} elements'}")
+    if len(colour) > 6 and colour[6] != 0 and obj_feat is None:
+        raise RuntimeError("hashgrid_mlp colour branch: an input pad is column 47 of the 48-wide colour input and needs an object feature")
     if cweights.numel() != 64 * (shape.input_dim + 64 * (shape.num_layers - 1) + 16):
         raise RuntimeError(f"hashgrid_mlp colour branch: the colour weights hold {cweights.numel()} elements, a {shape.input_dim}-wide "
                            f"{shape.num_layers}-layer network has {64 * (shape.input_dim + 64 * (shape.num_layers - 1) + 16)}")
@@ -203,7 +207,8 @@ class _hashgrid_mlp(Function):
     @custom_fwd(device_type="cuda")
     def forward(ctx, x, embeddings, weights, offsets, grid, sigma, training, colour=None):
         # x [B,3] fp32 in [0,1]; embeddings [rows,2]; weights: FFMLP blob; grid: GridSpec; sigma: MlpShape of the blob
-        # colour = (colour weights, colour MlpShape, ray_sh [B / T, 16] half, T, c_width, obj_feat or None): the colour network's forward runs in
+        # colour = (colour weights, colour MlpShape, ray_sh [B / T, 16] half, T, c_width, obj_feat or None[, input pad = column 47 of the
+        # 48-wide colour input, 0 when absent]): the colour network's forward runs in
         # the SAME kernel as the sigma network's (foc_field_forward_train) and its logits come back as a second, non-differentiable output — the
         # node that owns the colour network (fixedstep._render_tail) takes them instead of launching foc_color_head_forward, and computes every
         # gradient of the colour network in its own backward as before
@@ -225,12 +230,17 @@ class _hashgrid_mlp(Function):
         c = None
         if colour is not None:
             from ._lib import lib, ptr, stream_of, check
-            cweights, cshape, ray_sh, T, c_width, obj_feat = colour
+            cweights, cshape, ray_sh, T, c_width, obj_feat = colour[:6]
+            pad = float(colour[6]) if len(colour) > 6 else 0.0
             wc = _half_of(cweights)
             obj16 = obj_feat.detach().reshape(-1).half().contiguous() if obj_feat is not None else None
             c = torch.empty(B, c_width, device=x.device, dtype=torch.half)
-            check(lib.foc_field_forward_train(ptr(enc), ptr(w), sigma.num_layers, ptr(ray_sh), int(T), ptr(wc), int(cshape.num_layers), 64,
-                                              int(sigma.activation), B, ptr(h), ptr(c), int(c_width), ptr(obj16), stream_of(enc)), "field_forward_train")
+            args = (ptr(enc), ptr(w), sigma.num_layers, ptr(ray_sh), int(T), ptr(wc), int(cshape.num_layers), 64, int(sigma.activation), B, ptr(h),
+                    ptr(c), int(c_width), ptr(obj16))
+            if pad != 0:
+                check(lib.foc_field_forward_train_pad(*args, pad, stream_of(enc)), "field_forward_train_pad")
+            else:
+                check(lib.foc_field_forward_train(*args, stream_of(enc)), "field_forward_train")
         else:
             _ffmlp.ffmlp_forward_planar(enc, w, B, sigma.input_dim, 16, sigma.hidden_dim, sigma.num_layers, sigma.activation, sigma.output_activation, h)
         if training:
@@ -284,8 +294,13 @@ def field_infer(model, xn, dirs, dir_div=1, dir_block=0, obj_feat=None):
             raise RuntimeError("field_infer: an object-conditioned network needs its encoded object feature")
         obj16 = obj_feat.detach().reshape(-1).half().contiguous()
         assert obj16.numel() == 16
-    check(lib.foc_nerf_field_inference(ptr(planes), 1, ptr(dirs), int(dir_div), int(dir_block), dirs.shape[0], ptr(ws), sn.num_layers, ptr(wc), cn.num_layers, 64, sn.activation, M,
-                                       ptr(sigma), ptr(rgb), ptr(obj16), stream_of(xn)), "nerf_field_inference")
+    args = (ptr(planes), 1, ptr(dirs), int(dir_div), int(dir_block), dirs.shape[0], ptr(ws), sn.num_layers, ptr(wc), cn.num_layers, 64, sn.activation, M,
+            ptr(sigma), ptr(rgb), ptr(obj16))
+    pad = float(getattr(model, "colour_input_pad", 0.0)) if obj16 is not None else 0.0
+    if pad != 0:                              # the tinycudann layout (network_tcnn.py): column 47 of the colour input is a constant
+        check(lib.foc_nerf_field_inference_pad(*args, pad, stream_of(xn)), "nerf_field_inference_pad")
+    else:
+        check(lib.foc_nerf_field_inference(*args, stream_of(xn)), "nerf_field_inference")
     return sigma, rgb
 
 

@@ -149,11 +149,13 @@ class _render_tail(Function):
 
     obj_feat [16] (or None): FOC's encoded object feature — the colour network then has 48-wide W0 rows; the feature's share of layer 0
     is a constant per neuron inside the kernels, its gradient (for the object-feature encoder) comes back as one [16] vector.
-    want_sumsq: a seventh, differentiable output sumsq [N] = sum_t sigma^2 per ray (the samples' share of the outside-mask criterion)."""
+    want_sumsq: a seventh, differentiable output sumsq [N] = sum_t sigma^2 per ray (the samples' share of the outside-mask criterion).
+    input_pad: column 47 of the 48-wide colour input (with obj_feat only): 0, or 1.0 for the tinycudann layout (network_tcnn.py) — then the
+    *_pad twins of the colour-head kernels run."""
 
     @staticmethod
     def forward(ctx, h, cweights, ray_sh, nears, fars, noise, bg_ray, bg_scalar, N, T, density_scale, thresh, num_layers, activation, obj_feat=None,
-                want_sumsq=False, c_pre=None, w16_pre=None):
+                want_sumsq=False, c_pre=None, w16_pre=None, input_pad=0.0):
         # c_pre [M,4] half: the colour logits already computed from this h, these weights and this ray_sh by the encoder -> sigma node's fused
         # forward (field._hashgrid_mlp with `colour`, foc_field_forward_train: the bits foc_color_head_forward would give) — then no launch here
         from .field import _half_of
@@ -173,8 +175,11 @@ class _render_tail(Function):
             c = c_pre
         else:
             c = torch.empty(M, _C_WIDTH, dtype=torch.float16, device=dev)
-            check(lib.foc_color_head_forward(ptr(h), ptr(ray_sh), T, ptr(w16), M, 64, int(num_layers), int(activation), ptr(c), _C_WIDTH, ptr(obj16), st),
-                  "color_head_forward")
+            args = (ptr(h), ptr(ray_sh), T, ptr(w16), M, 64, int(num_layers), int(activation), ptr(c), _C_WIDTH, ptr(obj16))
+            if input_pad != 0:
+                check(lib.foc_color_head_forward_pad(*args, float(input_pad), st), "color_head_forward_pad")
+            else:
+                check(lib.foc_color_head_forward(*args, st), "color_head_forward")
         sigma = torch.empty(M, dtype=torch.float32, device=dev)
         trans = torch.empty(M, dtype=torch.float32, device=dev)
         weights = torch.empty(M, dtype=torch.float32, device=dev)
@@ -190,7 +195,7 @@ class _render_tail(Function):
                               bg_ray if bg_ray is not None else empty, obj16 if obj16 is not None else empty)
         ctx.flags = (noise is not None, bg_ray is not None, obj16 is not None, obj_feat.dtype if obj_feat is not None else None,
                      tuple(obj_feat.shape) if obj_feat is not None else None)
-        ctx.dims = (N, T, float(density_scale), float(thresh), float(bg_scalar), int(num_layers), int(activation))
+        ctx.dims = (N, T, float(density_scale), float(thresh), float(bg_scalar), int(num_layers), int(activation), float(input_pad))
         ctx.mark_non_differentiable(sigma, weights, c)
         ctx.set_materialize_grads(False)          # unused outputs arrive as None in backward, not as five freshly zero-filled tensors (25 us)
         if want_sumsq:
@@ -203,7 +208,7 @@ class _render_tail(Function):
         h, w16, sigma, trans, weights, c, ray_sh, nears, fars, noise, bg_ray, obj16 = ctx.saved_tensors
         has_noise, has_bg, has_obj, obj_dtype, obj_shape = ctx.flags
         obj16 = obj16 if has_obj else None
-        N, T, ds, thresh, bg_scalar, num_layers, activation = ctx.dims
+        N, T, ds, thresh, bg_scalar, num_layers, activation, input_pad = ctx.dims
         noise = noise if has_noise else None
         bg_ray = bg_ray if has_bg else None
         dev, M = h.device, N * T
@@ -221,10 +226,14 @@ class _render_tail(Function):
         g_w = torch.empty_like(w16)
         wsb = _scratch.get("ffmlp_ws", lib.foc_ffmlp_backward_workspace_bytes(48 if has_obj else 32, 64, num_layers), dev)
         g_obj32 = torch.empty(16, dtype=torch.float32, device=dev) if has_obj and ctx.needs_input_grad[14] else None
-        check(lib.foc_color_head_backward(ptr(grad_c), ptr(h), ptr(ray_sh), T, ptr(grad_h0), ptr(w16), M, 64, num_layers, activation, ptr(grad_h),
-                                          ptr(g_w), ptr(wsb), wsb.numel(), _C_WIDTH, ptr(obj16), ptr(g_obj32), st), "color_head_backward")
+        args = (ptr(grad_c), ptr(h), ptr(ray_sh), T, ptr(grad_h0), ptr(w16), M, 64, num_layers, activation, ptr(grad_h), ptr(g_w), ptr(wsb),
+                wsb.numel(), _C_WIDTH, ptr(obj16), ptr(g_obj32))
+        if input_pad != 0:
+            check(lib.foc_color_head_backward_pad(*args, input_pad, st), "color_head_backward_pad")
+        else:
+            check(lib.foc_color_head_backward(*args, st), "color_head_backward")
         g_obj = g_obj32.to(obj_dtype).view(obj_shape) if g_obj32 is not None else None
-        return (grad_h, g_w) + (None,) * 12 + (g_obj, None, None, None)
+        return (grad_h, g_w) + (None,) * 12 + (g_obj, None, None, None, None)
 
 
 class _masked_norm(Function):
@@ -323,7 +332,7 @@ def render_fixed_steps(model, rays_o, rays_d, yolo_details=None, num_steps=512, 
             if want_tail and plan.train_forward:
                 from .field import _half_of
                 wc16 = _half_of(model.color_net.weights)                  # ONE half copy per step for both nodes that read the colour weights
-                colour = (wc16, plan.colour, ray_sh, T, _C_WIDTH, obj_feat)
+                colour = (wc16, plan.colour, ray_sh, T, _C_WIDTH, obj_feat, plan.colour_input_pad)
             h = hashgrid_mlp(enc, model.sigma_net, enc_in, None, colour)
             if colour is not None:
                 h, c_pre = h
@@ -342,7 +351,7 @@ def render_fixed_steps(model, rays_o, rays_d, yolo_details=None, num_steps=512, 
             bg_ray, bg_scalar = _background(bg_color, N, dev)
             outs = _render_tail.apply(h, cn.weights, ray_sh, nears, fars, noise, bg_ray, bg_scalar, N, T, model.density_scale, weight_thresh,
                                       cn.num_layers, cn.activation, obj_feat, want_crit and yolo_details[0].numel() == N, c_pre,
-                                      wc16 if c_pre is not None else None)
+                                      wc16 if c_pre is not None else None, plan.colour_input_pad)
             image, weights_sum, depth, sigma, weights, c = outs[:6]
             if len(outs) == 7:
                 # a per-ray mask: the samples' sum of sigma^2 comes out of the tail kernel (no [M]-sized torch expression, no boolean-mask
@@ -351,6 +360,8 @@ def render_fixed_steps(model, rays_o, rays_d, yolo_details=None, num_steps=512, 
                 criterion_outside_mask = _masked_norm.apply(outs[6], (~yolo_details[0].reshape(N)).to(torch.float32))
         else:
             weights, weights_sum, depth, sigma, cin = _density_head.apply(h, rays_d, nears, fars, noise, N, T, model.density_scale, obj_feat)
+            if plan.colour_input_pad != 0:                                # the head kernel writes 0 in column 47 (tinycudann layout: the pad)
+                cin = torch.cat([cin[:, :47], cin.new_full((cin.shape[0], 1), plan.colour_input_pad)], dim=1)
         if want_crit and criterion_outside_mask is None:
             from .activation import trunc_exp
             criterion_outside_mask = torch.norm(trunc_exp(h[:, 0]).view(N, T)[~yolo_details[0].squeeze(0)] - 0)

@@ -409,6 +409,14 @@ int foc_nerf_field_inference(const void *enc, int enc_planar, const float *dirs,
                              uint32_t dir_block, uint32_t n_dirs, const void *sigma_weights, uint32_t sigma_layers, const void *color_weights,
                              uint32_t color_layers, uint32_t hidden_dim, uint32_t activation, uint32_t B,
                              float *sigma, float *rgb, const void *obj_feat, void *stream);
+/* foc_nerf_field_inference with the value of input column 47 of the 48-wide object-conditioned colour row (replaces
+ * foc_nerf_field_inference for the tinycudann parameter layout, focnerf_amd/network_tcnn.py, whose padded input column holds 1.0 and so acts
+ * as a bias): W0[:,47] * input_pad joins the per-neuron constant W0[:,31:47] . obj_feat. input_pad = 0 gives the bits of
+ * foc_nerf_field_inference; input_pad != 0 needs obj_feat. (sigma_layers, color_layers) here and there: (1,2), (1,3), (2,2), (2,3), (3,3). */
+int foc_nerf_field_inference_pad(const void *enc, int enc_planar, const float *dirs, uint32_t dir_div,
+                                 uint32_t dir_block, uint32_t n_dirs, const void *sigma_weights, uint32_t sigma_layers, const void *color_weights,
+                                 uint32_t color_layers, uint32_t hidden_dim, uint32_t activation, uint32_t B,
+                                 float *sigma, float *rgb, const void *obj_feat, float input_pad, void *stream);
 
 /* The colour network of a ray-ordered sample list without its materialised input (network_ff.py:104-108 builds
  * cin = [SH16(dir) | h[:,1:16] | 0] per sample, 64 B written and read twice): the kernels take the sigma network's output
@@ -432,17 +440,34 @@ int foc_color_head_backward(const void *grad, const void *h, const void *ray_sh,
                             const void *grad_h0, const void *weights, uint32_t B, uint32_t hidden_dim,
                             uint32_t num_layers, uint32_t activation, void *grad_h, void *grad_weights,
                             void *workspace, uint64_t workspace_bytes, uint32_t out_width, const void *obj_feat, float *grad_obj, void *stream);
+/* The two above with the value of input column 47 of the 48-wide row (replace foc_color_head_forward / _backward for the tinycudann
+ * layout, as foc_nerf_field_inference_pad): cin = [SH16 | h[:,1:16] | obj_feat | input_pad]. Forward: W0[:,47] * input_pad is added to
+ * the per-neuron constant after the object columns' products. Backward: grad_weights[:,47] = (sum_b delta_0[b,:]) * input_pad; grad_h and
+ * grad_obj do not change. input_pad = 0 gives the bits of the entry points above; input_pad != 0 needs obj_feat. */
+int foc_color_head_forward_pad(const void *h, const void *ray_sh, uint32_t samples_per_ray, const void *weights,
+                               uint32_t B, uint32_t hidden_dim, uint32_t num_layers, uint32_t activation,
+                               void *outputs, uint32_t out_width, const void *obj_feat, float input_pad, void *stream);
+int foc_color_head_backward_pad(const void *grad, const void *h, const void *ray_sh, uint32_t samples_per_ray,
+                                const void *grad_h0, const void *weights, uint32_t B, uint32_t hidden_dim,
+                                uint32_t num_layers, uint32_t activation, void *grad_h, void *grad_weights,
+                                void *workspace, uint64_t workspace_bytes, uint32_t out_width, const void *obj_feat, float *grad_obj,
+                                float input_pad, void *stream);
 
 /* The TRAINING forward of the whole field in ONE kernel (csrc/field_fwd.hip): foc_ffmlp_forward_planar on the encoder's planes ->
  * h [B,16] fp16 (written: the compositing tail and the backward read it) -> foc_color_head_forward fed from h and ray_sh, back to back in
  * registers — nerf/network_ff.py:51-75 as ffmlp.cu:331-407 evaluates it twice. Results are BIT FOR BIT those of the two separate calls
  * (same operands in the same k positions and order for every MFMA); h is not read back for the colour network (-32 B per sample, one
- * launch). planes [16][B] half2 (input width 32), hidden_dim 64, (sigma_layers, color_layers) in {(2,2), (2,3), (3,3)}, activation relu(0) /
+ * launch). planes [16][B] half2 (input width 32), hidden_dim 64, (sigma_layers, color_layers) in {(1,2), (1,3), (2,2), (2,3), (3,3)}, activation relu(0) /
  * none(6); ray_sh / samples_per_ray / out_width / obj_feat as foc_color_head_forward. The backward stays the two calls
  * foc_color_head_backward -> foc_ffmlp_backward_planar (they re-evaluate the activations from h and the planes). */
 int foc_field_forward_train(const void *planes, const void *sigma_weights, uint32_t sigma_layers, const void *ray_sh, uint32_t samples_per_ray,
                             const void *color_weights, uint32_t color_layers, uint32_t hidden_dim, uint32_t activation, uint32_t B,
                             void *h, void *c, uint32_t out_width, const void *obj_feat, void *stream);
+/* foc_field_forward_train with input column 47 of the 48-wide colour row = input_pad (replaces foc_field_forward_train for the tinycudann
+ * layout; the bits of foc_ffmlp_forward_planar + foc_color_head_forward_pad). input_pad = 0: the bits of foc_field_forward_train. */
+int foc_field_forward_train_pad(const void *planes, const void *sigma_weights, uint32_t sigma_layers, const void *ray_sh, uint32_t samples_per_ray,
+                                const void *color_weights, uint32_t color_layers, uint32_t hidden_dim, uint32_t activation, uint32_t B,
+                                void *h, void *c, uint32_t out_width, const void *obj_feat, float input_pad, void *stream);
 
 /* ffmlp.cu:721-740  allocate_splitk(size) / free_splitk(): the reference creates side
  * streams for its CUTLASS split-K GEMMs. Weight gradients here are produced inside the

@@ -8,7 +8,9 @@ Prints one JSON line:
     backward products, the re-evaluated forward not counted);
   * foc_tcnn_step: one training step at configs[1] size (4096 rays x 512 samples, fixed-step NeRFRenderer.run, fp16 autocast, Adam over
     the five parameter groups) of a network in FOC's tcnn topology built from tcnn.Encoding / tcnn.Network and called in the order of the
-    reference's network_tcnn.py; samples/s beside `dropin_ops_path` of BENCH_r05 (4.7e8: nerf/network_ff.py on the same public ops)."""
+    reference's network_tcnn.py; samples/s beside `dropin_ops_path` of BENCH_r05 (4.7e8: nerf/network_ff.py on the same public ops);
+  * fused_step: the same step of network_tcnn.NeRFNetwork (that topology with the drop-in's parameter layout) and of network_foc.NeRFNetwork
+    through run(fused=True) (fixed-step fused path, upsample_steps 0), the three legs timed alternately in one process."""
 import json
 import os
 import statistics
@@ -63,8 +65,9 @@ def time_mlp(reps):
     return out
 
 
-def time_foc_step(steps):
-    from focnerf_amd import synthetic, tcnn
+def _dropin_network():
+    """FOC's tcnn topology on tcnn.Encoding / tcnn.Network, called op by op in the order of the reference's network_tcnn.py"""
+    from focnerf_amd import tcnn
     from focnerf_amd.activation import trunc_exp
     from focnerf_amd.renderer import NeRFRenderer
 
@@ -95,9 +98,13 @@ def time_foc_step(steps):
             rgbs[mask] = torch.sigmoid(self.color_net(h)).to(rgbs.dtype)
             return rgbs
 
-    dev, bound, T = torch.device("cuda"), 2, 512
-    torch.manual_seed(0)
-    net = Net(bound).to(dev)
+    return Net
+
+
+def _training_step(net, fused, bound=2, T=512):
+    """one Adam step at configs[1] size (4096 rays x 512 samples) of `net`, through run(fused=True) or NeRFRenderer.run"""
+    from focnerf_amd import synthetic
+    dev = torch.device("cuda")
     rays_o, rays_d = synthetic.make_view_rays(64, 64, bound, 1, seed=0, device=dev)
     rays_o, rays_d = rays_o[0].contiguous(), rays_d[0].contiguous()
     yolo = (torch.ones(1, rays_o.shape[0], T, dtype=torch.bool, device=dev), None, torch.rand(144, device=dev))
@@ -105,29 +112,51 @@ def time_foc_step(steps):
     opt = torch.optim.Adam([{'params': m.parameters(), 'lr': 1e-2} for m in (net.encoder, net.sigma_net, net.encoder_dir, net.color_net,
                                                                               net.yolo_feat_encoder)], betas=(0.9, 0.99), eps=1e-15)
     scaler = torch.amp.GradScaler("cuda")
+    kw = dict(fused=True, upsample_steps=0) if fused else {}
 
     def step():
         opt.zero_grad(set_to_none=True)
         with torch.autocast("cuda", dtype=torch.float16):
-            out = net.run(rays_o, rays_d, yolo_details=yolo, num_steps=T, perturb=True)
+            out = net.run(rays_o, rays_d, yolo_details=yolo, num_steps=T, perturb=True, **kw)
             loss = torch.nn.functional.mse_loss(out["image"].float(), target)
         scaler.scale(loss).backward()
         scaler.step(opt)
         scaler.update()
-    for _ in range(3):
-        step()
+    return step, rays_o.shape[0] * T
+
+
+def time_steps(steps):
+    """foc_tcnn_step (drop-in, op by op) and fused_step (network_tcnn / network_foc under run(fused=True)), in alternating bursts"""
+    from focnerf_amd import network_foc, network_tcnn
+    dev, bound = torch.device("cuda"), 2
+    torch.manual_seed(0)
+    legs = {"dropin_ops": _training_step(_dropin_network()(bound).to(dev), False),
+            "network_tcnn_fused": _training_step(network_tcnn.NeRFNetwork(bound=bound, cuda_ray=False, density_scale=1, min_near=0.05).to(dev), True),
+            "network_foc_fused": _training_step(network_foc.NeRFNetwork(bound=bound, cuda_ray=False, density_scale=1, min_near=0.05).to(dev), True)}
+    for step, _ in legs.values():
+        for _ in range(3):
+            step()
     torch.cuda.synchronize()
-    ms = statistics.median(_events(step, steps) for _ in range(3)) * 1e-3
-    sps = rays_o.shape[0] * T / (ms * 1e-3)
-    return {"ms_per_step": round(ms, 3), "samples_per_sec": sps, "vs_dropin_ops_path_r05": round(sps / DROPIN_OPS_PATH_R05, 3),
-            "rays": rays_o.shape[0], "samples_per_ray": T, "bound": bound}
+    ts = {k: [] for k in legs}
+    for _ in range(3):
+        for k, (step, _) in legs.items():
+            ts[k].append(_events(step, steps))
+    out = {}
+    for k, (_, n) in legs.items():
+        ms = statistics.median(ts[k]) * 1e-3
+        sps = n / (ms * 1e-3)
+        out[k] = {"ms_per_step": round(ms, 3), "samples_per_sec": sps, "vs_dropin_ops_path_r05": round(sps / DROPIN_OPS_PATH_R05, 3)}
+    out["network_tcnn_fused"]["vs_dropin_ops"] = round(out["network_tcnn_fused"]["samples_per_sec"] / out["dropin_ops"]["samples_per_sec"], 3)
+    out["network_tcnn_fused"]["vs_network_foc_fused"] = round(out["network_tcnn_fused"]["samples_per_sec"] / out["network_foc_fused"]["samples_per_sec"], 3)
+    out.update(rays=4096, samples_per_ray=512, bound=bound)
+    return out
 
 
 def main():
     if not torch.cuda.is_available():
         raise SystemExit("time_tcnn.py needs a GPU")
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
-    print(json.dumps({"tool": "time_tcnn", "rows": 4096 * 512, "mlp": time_mlp(reps), "foc_tcnn_step": time_foc_step(max(5, reps // 2))}))
+    print(json.dumps({"tool": "time_tcnn", "rows": 4096 * 512, "mlp": time_mlp(reps), "steps": time_steps(max(5, reps // 2))}))
 
 
 if __name__ == "__main__":
