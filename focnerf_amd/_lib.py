@@ -80,6 +80,8 @@ SIGNATURES = {
     "foc_view_tile_order": (i32, [c_vp, u32, u32, u32, c_vp, c_vp, c_vp]),
     "foc_occ_train_forward": (i32, [ctypes.POINTER(FocOccTrainNode), c_vp]),
     "foc_occ_train_backward": (i32, [ctypes.POINTER(FocOccTrainNode), c_vp]),
+    "foc_occ_train_forward_pad31": (i32, [ctypes.POINTER(FocOccTrainNode), f32, c_vp]),
+    "foc_occ_train_backward_pad31": (i32, [ctypes.POINTER(FocOccTrainNode), f32, c_vp]),
     "foc_occ_tail_forward": (i32, [c_vp, c_vp, u32, c_vp, c_vp, u32, u32, f32, f32, c_vp, f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "foc_occ_tail_backward": (i32, [c_vp, c_vp, c_vp, c_vp, u32, c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, f32, f32, c_vp, f32, c_vp, c_vp, c_vp]),
     "foc_march_rays_train_scratch_bytes": (u64, [u32, u32]),
@@ -97,6 +99,9 @@ SIGNATURES = {
     "foc_occ_render_step_scratch_bytes": (u64, [u32]),
     "foc_occ_render_step": (i32, [u32, u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, f32, f32, u32, u32, u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                   c_vp, c_vp, c_vp, u32, f32, u32, c_vp, u32, c_vp, u32, u32, c_vp, f32, c_vp, c_vp, c_vp, c_vp, u32, c_vp, u32, u32, c_vp]),
+    "foc_occ_render_step_pad31": (i32, [u32, u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, f32, f32, u32, u32, u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                        c_vp, c_vp, c_vp, u32, f32, u32, c_vp, u32, c_vp, u32, u32, c_vp, f32, c_vp, c_vp, c_vp, c_vp, u32, c_vp, u32, u32, f32,
+                                        c_vp]),
     "foc_grid_encode_forward": (i32, [c_vp, c_vp, c_vp, c_vp, u32, u32, u32, u32, f32, u32, c_vp, u32, i32, u32,
                                       i32, c_vp, c_vp]),
     "foc_grid_encode_forward_bl": (i32, [c_vp, c_vp, c_vp, c_vp, u32, u32, u32, u32, f32, u32, c_vp, u32, i32, u32,
@@ -143,6 +148,9 @@ SIGNATURES = {
     "foc_color_head_forward_pad": (i32, [c_vp, c_vp, u32, c_vp, u32, u32, u32, u32, c_vp, u32, c_vp, f32, c_vp]),
     "foc_color_head_backward_pad": (i32, [c_vp, c_vp, c_vp, u32, c_vp, c_vp, u32, u32, u32, u32, c_vp, c_vp, c_vp, u64, u32, c_vp, c_vp, f32, c_vp]),
     "foc_field_forward_train_pad": (i32, [c_vp, c_vp, u32, c_vp, u32, c_vp, u32, u32, u32, u32, c_vp, c_vp, u32, c_vp, f32, c_vp]),
+    "foc_color_head_forward_pad31": (i32, [c_vp, c_vp, u32, c_vp, u32, u32, u32, u32, c_vp, u32, c_vp, f32, c_vp]),
+    "foc_color_head_backward_pad31": (i32, [c_vp, c_vp, c_vp, u32, c_vp, c_vp, u32, u32, u32, u32, c_vp, c_vp, c_vp, u64, u32, c_vp, c_vp, f32, c_vp]),
+    "foc_field_forward_train_pad31": (i32, [c_vp, c_vp, u32, c_vp, u32, c_vp, u32, u32, u32, u32, c_vp, c_vp, u32, c_vp, f32, c_vp]),
     "foc_fixed_composite_forward": (i32, [c_vp, c_vp, c_vp, f32, u32, u32, f32, c_vp, c_vp]),
     "foc_fixed_composite_backward": (i32, [c_vp, c_vp, c_vp, c_vp, f32, u32, u32, f32, c_vp, c_vp, c_vp]),
     "foc_sample_head_forward": (i32, [c_vp, c_vp, u64, c_vp, c_vp, c_vp, u32, c_vp]),
@@ -153,6 +161,7 @@ SIGNATURES = {
     "foc_fixed_render_inference": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, f32, u32, u32, f32, f32, c_vp, c_vp, c_vp, c_vp, u32, c_vp, c_vp]),
     "foc_nerf_field_inference": (i32, [c_vp, i32, c_vp, u32, u32, u32, c_vp, u32, c_vp, u32, u32, u32, u32, c_vp, c_vp, c_vp, c_vp]),
     "foc_nerf_field_inference_pad": (i32, [c_vp, i32, c_vp, u32, u32, u32, c_vp, u32, c_vp, u32, u32, u32, u32, c_vp, c_vp, c_vp, f32, c_vp]),
+    "foc_nerf_field_inference_pad31": (i32, [c_vp, i32, c_vp, u32, u32, u32, c_vp, u32, c_vp, u32, u32, u32, u32, c_vp, c_vp, c_vp, f32, c_vp]),
     "foc_mark_untrained_grid": (i32, [c_vp, u32, f32, f32, f32, f32, f32, u32, u32, c_vp, c_vp, c_vp]),
     "foc_grid_cells_xyz": (i32, [u32, u32, f32, c_vp, c_vp, c_vp]),
     "foc_grid_update_sample_workspace_bytes": (u64, [u32, u32]),

@@ -43,10 +43,10 @@ __global__ void __launch_bounds__(MLP_BLOCK, 2) k_mlp_fwd(const _Float16 *__rest
     extern __shared__ __attribute__((aligned(16))) _Float16 lds[];
     const uint32_t KS0 = IMODE == 2 ? 2u : in_dim / 16;
     const uint32_t f_hidden = MT * KS0, f_out = f_hidden + (num_layers - 1) * MT * KC;
-    const float *obj_bias = reinterpret_cast<const float *>(lds + (size_t)(f_out + KC) * 512);      // head mode with an object feature only
+    const float *obj_bias = reinterpret_cast<const float *>(lds + (size_t)(f_out + KC) * 512);      // head mode with a layer-0 constant only
     if constexpr (IMODE == 2) {
         stage_weights_fwd<HIDDEN>(weights, lds, in_dim, num_layers, true, head_ld0(hd));
-        if (hd.obj) stage_obj_bias(weights, hd.obj, const_cast<float *>(obj_bias), HIDDEN, hd.pad);
+        if (head_bias(hd)) stage_head_bias(weights, hd, const_cast<float *>(obj_bias), HIDDEN);
     } else stage_weights_fwd<HIDDEN>(weights, lds, in_dim, num_layers);
     __syncthreads();
 
@@ -67,7 +67,7 @@ __global__ void __launch_bounds__(MLP_BLOCK, 2) k_mlp_fwd(const _Float16 *__rest
 
         // ---- layer 0: B operand straight from global inputs (natural k order)
         if constexpr (IMODE == 2) {
-            if (hd.obj) {                                  // the object feature's share of layer 0: a constant per neuron (MlpHead)
+            if (head_bias(hd)) {                           // the object feature's share of layer 0 / the column-31 pad: a constant per neuron (MlpHead)
 #pragma unroll
                 for (int mt = 0; mt < MT; mt++) {
                     const f16v b0 = ld_obj_bias(obj_bias, mt, h);
@@ -455,6 +455,10 @@ __global__ void __launch_bounds__(MLP_BLOCK, 2) k_mlp_bwd_fused(const _Float16 *
     uint32_t ld0 = in_dim;
     bool has_obj = false;
     if constexpr (HEAD) { ld0 = head_ld0(hd); has_obj = hd.obj != nullptr; }
+    // column 31 of the layer-0 input tile as the weight-gradient MFMAs see it (see the A_0 tile below): 1 with an object feature, the pad without
+    bool col31_set = false;
+    _Float16 col31 = (_Float16)0.0f;
+    if constexpr (HEAD) { col31_set = head_bias(hd); col31 = has_obj ? (_Float16)1.0f : (_Float16)hd.pad; }
     stage_weights_bwd<HIDDEN>(weights, lds, in_dim, NL, with_dx, HEAD, ld0);
     const uint32_t WA = (in_dim > (uint32_t)HIDDEN ? in_dim : (uint32_t)(HIDDEN < 32 ? 32 : HIDDEN)) + 8;
     _Float16 *sD = lds + lds_w_halfs;                    // [4][RW][WD]
@@ -463,7 +467,7 @@ __global__ void __launch_bounds__(MLP_BLOCK, 2) k_mlp_bwd_fused(const _Float16 *
     const float *obj_bias = reinterpret_cast<const float *>(ldsF + (size_t)(((HIDDEN + 31) / 32) * (in_dim / 16) + (NL - 1) * ((HIDDEN + 31) / 32) * (HIDDEN / 16)) * 512);
     if constexpr (RECOMP) {
         stage_weights_fwd<HIDDEN>(weights, ldsF, in_dim, NL, false, ld0);
-        if constexpr (HEAD) { if (has_obj) stage_obj_bias(weights, hd.obj, const_cast<float *>(obj_bias), HIDDEN, hd.pad); }
+        if constexpr (HEAD) { if (head_bias(hd)) stage_head_bias(weights, hd, const_cast<float *>(obj_bias), HIDDEN); }
     }
     __syncthreads();
 
@@ -585,7 +589,7 @@ __global__ void __launch_bounds__(MLP_BLOCK, 2) k_mlp_bwd_fused(const _Float16 *
                 }
             };
             bool from_bias = false;
-            if constexpr (HEAD) from_bias = has_obj;
+            if constexpr (HEAD) from_bias = head_bias(hd);
             if (from_bias) {
 #pragma unroll
                 for (int mt = 0; mt < MT; mt++) {
@@ -722,8 +726,9 @@ __global__ void __launch_bounds__(MLP_BLOCK, 2) k_mlp_bwd_fused(const _Float16 *
                         for (int nb = 0; nb < NB; nb++)
                             if ((uint32_t)kc < KS0) {
                                 h8 v = x_cur[kc][nb];
-                                // object feature: column 31 of the input tile (a zero of the shifted h row) becomes 1, so that dW0[:, 31] = sum_b delta_0
-                                if constexpr (HEAD) { if (kc == 1 && has_obj && h == 1) v[7] = (_Float16)1.0f; }
+                                // object feature: column 31 of the input tile (a zero of the shifted h row) becomes 1, so that dW0[:, 31] = sum_b delta_0;
+                                // the 32-wide row's pad (MlpHead::pad without obj): it becomes pad, dW0[:, 31] = sum_b delta_0 * pad
+                                if constexpr (HEAD) { if (kc == 1 && col31_set && h == 1) v[7] = col31; }
                                 *reinterpret_cast<h8 *>(myA + (nb * 32 + c) * WA + 16 * kc + 8 * h) = v;
                             }
                 }
@@ -1016,7 +1021,8 @@ __device__ __forceinline__ void nf_sh16_half(float x, float y, float z, int h, h
 // of the directions and the division that finds them).
 // OBJ: FOC's object-conditioned colour network (nerf/network_tcnn.py:611-640, MlpHead above): 48-wide W0 rows, the encoded object feature's
 // share W0[:, 31:47] . obj as the initial value of the colour layer-0 accumulators.
-template <int NLS, int NLC, bool PLANAR, bool RELU_CT, bool BLK, bool OBJ>
+// P31: the 32-wide colour row of the legacy tinycudann layout (network_tcnn_legacy.py), column 31 = pad: W0[:, 31] * pad as that initial value.
+template <int NLS, int NLC, bool PLANAR, bool RELU_CT, bool BLK, bool OBJ, bool P31 = false>
 __global__ void __launch_bounds__(MLP_BLOCK, 2) k_nerf_infer(const _Float16 *__restrict__ enc, const float *__restrict__ dirs, uint32_t dir_div,
                                                           uint32_t dir_block, uint32_t n_dirs, const _Float16 *__restrict__ w_sigma, const _Float16 *__restrict__ w_color, uint32_t B,
                                                           int relu_rt, float *__restrict__ sigma_out, float *__restrict__ rgb_out, const _Float16 *__restrict__ obj,
@@ -1066,6 +1072,7 @@ __global__ void __launch_bounds__(MLP_BLOCK, 2) k_nerf_infer(const _Float16 *__r
     }
     const float *obj_bias = reinterpret_cast<const float *>(ldsC + (size_t)(MT * KS0 + (NLC - 1) * MT * KC + KC) * 512);
     if constexpr (OBJ) stage_obj_bias(w_color, obj, const_cast<float *>(obj_bias), HIDDEN, pad);
+    else if constexpr (P31) stage_pad31_bias(w_color, pad, const_cast<float *>(obj_bias), HIDDEN);
     __syncthreads();
 
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1166,7 +1173,7 @@ __global__ void __launch_bounds__(MLP_BLOCK, 2) k_nerf_infer(const _Float16 *__r
 #pragma unroll
         for (int mt = 0; mt < MT; mt++) {
             const h8 a0 = ld_frag(ldsC, mt * KS0 + 0, lane);
-            if constexpr (OBJ) {
+            if constexpr (OBJ || P31) {
                 // read per tile (pointer laundered): hoisted out of the tile loop the 32 values stay live across it and the kernel spills
                 const float *bp = obj_bias;
                 asm volatile("" : "+v"(bp));
@@ -1310,7 +1317,7 @@ static int mlp_fwd_launch(const void *inputs, const void *weights, uint32_t B, u
     const bool gen = act != FOC_ACT_RELU && act != FOC_ACT_NONE;
     FOC_REQUIRE(!gen || (!planar && !head), FOC_E_INVALID, "ffmlp_forward: activation %d is served on row-major inputs only", act);
     constexpr int NB = 1;                          // one 32-row tile per wave: 92 registers, 5 waves per SIMD (two tiles: 157 registers, 3 waves; 57 -> 54 us per 2 M rows)
-    const size_t lds = mlp_fwd_lds<HIDDEN>(in_dim, num_layers) + (head && head->obj ? 256 : 0);       // + obj_bias [2][2][16] fp32
+    const size_t lds = mlp_fwd_lds<HIDDEN>(in_dim, num_layers) + (head && head_bias(*head) ? 256 : 0);       // + obj_bias [2][2][16] fp32
     FOC_REQUIRE(lds <= 160 * 1024, FOC_E_INVALID, "ffmlp_forward: weights (%zu B) do not fit the 160 KiB LDS", lds);
     FOC_REQUIRE(!(planar && TRAIN), FOC_E_INVALID, "ffmlp_forward: planar inputs go with the activation-free forward");
     auto kern = planar ? k_mlp_fwd<HIDDEN, NB, false, 1> : k_mlp_fwd<HIDDEN, NB, TRAIN, 0>;
@@ -1362,7 +1369,8 @@ static int mlp_bwd_fused_launch(const void *grad, const void *inputs, const void
     const bool recomp = fwd_buf == nullptr;
     constexpr int MT = (HIDDEN + 31) / 32, KC = HIDDEN / 16;
     const bool has_obj = head && head->obj;
-    const size_t lds = lds_w + (size_t)4 * RW * (WD + WA) * sizeof(_Float16) + (recomp ? (size_t)(MT * (in_dim / 16) + (NL - 1) * MT * KC) * 1024 : 0) + (has_obj ? 256 : 0);
+    const size_t lds = lds_w + (size_t)4 * RW * (WD + WA) * sizeof(_Float16) + (recomp ? (size_t)(MT * (in_dim / 16) + (NL - 1) * MT * KC) * 1024 : 0) +
+                       (head && head_bias(*head) ? 256 : 0);
     FOC_REQUIRE(lds <= 160 * 1024, FOC_E_INVALID, "ffmlp_backward: fused kernel needs %zu B of LDS", lds);
 #ifdef FOC_TIMING_ONE_WG
     const size_t lds_launch = lds < 84 * 1024 ? 84 * 1024 : lds;      // timing build: one workgroup (one wave per SIMD) per CU
@@ -1471,7 +1479,7 @@ static int mlp_bwd_launch(const void *grad, const void *inputs, const void *weig
 template <int NLS, int NLC>
 static int nerf_infer_launch(const void *enc, const float *dirs, uint32_t dir_div, uint32_t dir_block, uint32_t n_dirs, const void *w_sigma, const void *w_color, uint32_t B, int relu, int planar,
                              float *sigma, float *rgb, const void *obj, float pad, hipStream_t st) {
-    const size_t lds = (size_t)((2 * 2 + (NLS - 1) * 8 + 4) + (2 * 2 + (NLC - 1) * 8 + 4)) * 1024 + (obj ? 256 : 0);
+    const size_t lds = (size_t)((2 * 2 + (NLS - 1) * 8 + 4) + (2 * 2 + (NLC - 1) * 8 + 4)) * 1024 + (obj || pad != 0.0f ? 256 : 0);
     const bool blk = planar && dir_block == 64u;     // the staged render's sample order (fixedstep.hip FS_RAY_BLOCK)
     auto kern = planar ? (blk ? (relu ? k_nerf_infer<NLS, NLC, true, true, true, false> : k_nerf_infer<NLS, NLC, true, false, true, false>)
                               : (relu ? k_nerf_infer<NLS, NLC, true, true, false, false> : k_nerf_infer<NLS, NLC, true, false, false, false>))
@@ -1480,6 +1488,10 @@ static int nerf_infer_launch(const void *enc, const float *dirs, uint32_t dir_di
         // the object-conditioned form is built for what FOC runs: ReLU networks on the encoder's planes
         FOC_REQUIRE(planar && relu, FOC_E_INVALID, "nerf_field_inference: an object feature needs planar encodings and ReLU networks");
         kern = blk ? k_nerf_infer<NLS, NLC, true, true, true, true> : k_nerf_infer<NLS, NLC, true, true, false, true>;
+    } else if (pad != 0.0f) {
+        // the column-31 pad (foc_nerf_field_inference_pad31), built for what the legacy tinycudann network runs: ReLU on the planes
+        FOC_REQUIRE(planar && relu, FOC_E_INVALID, "nerf_field_inference_pad31: a pad needs planar encodings and ReLU networks");
+        kern = blk ? k_nerf_infer<NLS, NLC, true, true, true, false, true> : k_nerf_infer<NLS, NLC, true, true, false, false, true>;
     }
     if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     uint32_t grid = foc_div_up(foc_div_up(B, 64), MLP_WAVES);
@@ -1579,7 +1591,8 @@ int foc_ffmlp_backward_planar(const void *grad, const void *inputs_planar, const
 
 static int nerf_field_inference(const void *enc, int enc_planar, const float *dirs, uint32_t dir_div, uint32_t dir_block, uint32_t n_dirs,
                                 const void *sigma_weights, uint32_t sigma_layers, const void *color_weights, uint32_t color_layers, uint32_t hidden_dim,
-                                uint32_t activation, uint32_t B, float *sigma, float *rgb, const void *obj_feat, float input_pad, void *stream) {
+                                uint32_t activation, uint32_t B, float *sigma, float *rgb, const void *obj_feat, float input_pad, bool pad31,
+                                void *stream) {
     FocDeviceGuard foc_guard_(stream, enc);
     if (B == 0) return FOC_OK;
     FOC_REQUIRE(enc && dirs && sigma_weights && color_weights && rgb, FOC_E_INVALID, "nerf_field_inference: null pointer");
@@ -1587,7 +1600,8 @@ static int nerf_field_inference(const void *enc, int enc_planar, const float *di
     FOC_REQUIRE(dir_block == 0 || n_dirs >= 1, FOC_E_INVALID, "nerf_field_inference: the block-interleaved row order needs the number of directions");
     FOC_REQUIRE((uint64_t)dir_block * dir_div < (1ull << 32), FOC_E_INVALID, "nerf_field_inference: dir_block * dir_div must fit 32 bits");
     FOC_REQUIRE(activation == 0 || activation == 6, FOC_E_INVALID, "nerf_field_inference: hidden activation must be relu(0) or none(6)");
-    FOC_REQUIRE(input_pad == 0.0f || obj_feat, FOC_E_INVALID, "nerf_field_inference: input_pad is column 47 of the 48-wide colour input and needs obj_feat");
+    int rc = head_pad_check("nerf_field_inference", pad31, obj_feat, input_pad);
+    if (rc) return rc;
     const int relu = activation == 0;
     hipStream_t st = (hipStream_t)stream;
     const uint32_t key = sigma_layers * 10 + color_layers;
@@ -1607,7 +1621,7 @@ int foc_nerf_field_inference(const void *enc, int enc_planar, const float *dirs,
                              const void *color_weights, uint32_t color_layers, uint32_t hidden_dim, uint32_t activation, uint32_t B, float *sigma,
                              float *rgb, const void *obj_feat, void *stream) {
     return nerf_field_inference(enc, enc_planar, dirs, dir_div, dir_block, n_dirs, sigma_weights, sigma_layers, color_weights, color_layers, hidden_dim,
-                                activation, B, sigma, rgb, obj_feat, 0.0f, stream);
+                                activation, B, sigma, rgb, obj_feat, 0.0f, false, stream);
 }
 
 int foc_nerf_field_inference_pad(const void *enc, int enc_planar, const float *dirs, uint32_t dir_div, uint32_t dir_block, uint32_t n_dirs,
@@ -1615,12 +1629,21 @@ int foc_nerf_field_inference_pad(const void *enc, int enc_planar, const float *d
                                  const void *color_weights, uint32_t color_layers, uint32_t hidden_dim, uint32_t activation, uint32_t B, float *sigma,
                                  float *rgb, const void *obj_feat, float input_pad, void *stream) {
     return nerf_field_inference(enc, enc_planar, dirs, dir_div, dir_block, n_dirs, sigma_weights, sigma_layers, color_weights, color_layers, hidden_dim,
-                                activation, B, sigma, rgb, obj_feat, input_pad, stream);
+                                activation, B, sigma, rgb, obj_feat, input_pad, false, stream);
+}
+
+int foc_nerf_field_inference_pad31(const void *enc, int enc_planar, const float *dirs, uint32_t dir_div, uint32_t dir_block, uint32_t n_dirs,
+                                   const void *sigma_weights, uint32_t sigma_layers,
+                                   const void *color_weights, uint32_t color_layers, uint32_t hidden_dim, uint32_t activation, uint32_t B, float *sigma,
+                                   float *rgb, const void *obj_feat, float input_pad, void *stream) {
+    return nerf_field_inference(enc, enc_planar, dirs, dir_div, dir_block, n_dirs, sigma_weights, sigma_layers, color_weights, color_layers, hidden_dim,
+                                activation, B, sigma, rgb, obj_feat, input_pad, true, stream);
 }
 
 // The colour network of the fixed-step training path, fed from the sigma network's output rows and a per-ray SH table (input mode 2).
 static int color_head_forward(const void *h, const void *ray_sh, uint32_t samples_per_ray, const void *weights, uint32_t B, uint32_t hidden_dim,
-                              uint32_t num_layers, uint32_t activation, void *outputs, uint32_t out_width, const void *obj_feat, float input_pad, void *stream) {
+                              uint32_t num_layers, uint32_t activation, void *outputs, uint32_t out_width, const void *obj_feat, float input_pad, bool pad31,
+                              void *stream) {
     FocDeviceGuard foc_guard_(stream, h);
     int rc = mlp_check("color_head_forward", B, 32, 16, hidden_dim, num_layers, activation, 6);
     if (rc) return rc;
@@ -1629,7 +1652,8 @@ static int color_head_forward(const void *h, const void *ray_sh, uint32_t sample
     FOC_REQUIRE(h && ray_sh && weights && outputs, FOC_E_INVALID, "color_head_forward: null pointer");
     FOC_REQUIRE(hidden_dim == 64 && samples_per_ray >= 1, FOC_E_INVALID, "color_head_forward: hidden_dim must be 64 (got %u), samples_per_ray >= 1", hidden_dim);
     FOC_REQUIRE(out_width == 16 || out_width == 4, FOC_E_INVALID, "color_head_forward: out_width must be 16 or 4 (got %u)", out_width);
-    FOC_REQUIRE(input_pad == 0.0f || obj_feat, FOC_E_INVALID, "color_head_forward: input_pad is column 47 of the 48-wide colour input and needs obj_feat");
+    rc = head_pad_check("color_head_forward", pad31, obj_feat, input_pad);
+    if (rc) return rc;
     const MlpHead hd{(const _Float16 *)ray_sh, nullptr, samples_per_ray, out_width, (const _Float16 *)obj_feat, input_pad};
     FOC_REQUIRE(activation == FOC_ACT_RELU || activation == FOC_ACT_NONE, FOC_E_INVALID, "color_head_forward: hidden activation must be relu(0) or none(6)");
     return mlp_fwd_launch<64, false>(h, weights, B, 32, num_layers, (int)activation, nullptr, outputs, 0, (hipStream_t)stream, &hd);
@@ -1637,18 +1661,27 @@ static int color_head_forward(const void *h, const void *ray_sh, uint32_t sample
 
 int foc_color_head_forward(const void *h, const void *ray_sh, uint32_t samples_per_ray, const void *weights, uint32_t B, uint32_t hidden_dim,
                            uint32_t num_layers, uint32_t activation, void *outputs, uint32_t out_width, const void *obj_feat, void *stream) {
-    return color_head_forward(h, ray_sh, samples_per_ray, weights, B, hidden_dim, num_layers, activation, outputs, out_width, obj_feat, 0.0f, stream);
+    return color_head_forward(h, ray_sh, samples_per_ray, weights, B, hidden_dim, num_layers, activation, outputs, out_width, obj_feat, 0.0f, false, stream);
 }
 
 int foc_color_head_forward_pad(const void *h, const void *ray_sh, uint32_t samples_per_ray, const void *weights, uint32_t B, uint32_t hidden_dim,
                                uint32_t num_layers, uint32_t activation, void *outputs, uint32_t out_width, const void *obj_feat, float input_pad,
                                void *stream) {
-    return color_head_forward(h, ray_sh, samples_per_ray, weights, B, hidden_dim, num_layers, activation, outputs, out_width, obj_feat, input_pad, stream);
+    return color_head_forward(h, ray_sh, samples_per_ray, weights, B, hidden_dim, num_layers, activation, outputs, out_width, obj_feat, input_pad, false,
+                              stream);
+}
+
+int foc_color_head_forward_pad31(const void *h, const void *ray_sh, uint32_t samples_per_ray, const void *weights, uint32_t B, uint32_t hidden_dim,
+                                 uint32_t num_layers, uint32_t activation, void *outputs, uint32_t out_width, const void *obj_feat, float input_pad,
+                                 void *stream) {
+    return color_head_forward(h, ray_sh, samples_per_ray, weights, B, hidden_dim, num_layers, activation, outputs, out_width, obj_feat, input_pad, true,
+                              stream);
 }
 
 static int color_head_backward(const void *grad, const void *h, const void *ray_sh, uint32_t samples_per_ray, const void *grad_h0, const void *weights,
                                uint32_t B, uint32_t hidden_dim, uint32_t num_layers, uint32_t activation, void *grad_h, void *grad_weights, void *workspace,
-                               uint64_t workspace_bytes, uint32_t out_width, const void *obj_feat, float *grad_obj, float input_pad, void *stream) {
+                               uint64_t workspace_bytes, uint32_t out_width, const void *obj_feat, float *grad_obj, float input_pad, bool pad31,
+                               void *stream) {
     FocDeviceGuard foc_guard_(stream, grad);
     int rc = mlp_check("color_head_backward", B, 32, 16, hidden_dim, num_layers, activation, 6);
     if (rc) return rc;
@@ -1668,7 +1701,8 @@ static int color_head_backward(const void *grad, const void *h, const void *ray_
                 obj_feat ? HEAD_OBJ_LD : 32u, num_layers, (unsigned long long)foc_ffmlp_backward_workspace_bytes(obj_feat ? HEAD_OBJ_LD : 32u, 64, num_layers));
     FOC_REQUIRE(out_width == 16 || out_width == 4, FOC_E_INVALID, "color_head_backward: out_width must be 16 or 4 (got %u)", out_width);
     FOC_REQUIRE(activation == FOC_ACT_RELU || activation == FOC_ACT_NONE, FOC_E_INVALID, "color_head_backward: hidden activation must be relu(0) or none(6)");
-    FOC_REQUIRE(input_pad == 0.0f || obj_feat, FOC_E_INVALID, "color_head_backward: input_pad is column 47 of the 48-wide colour input and needs obj_feat");
+    rc = head_pad_check("color_head_backward", pad31, obj_feat, input_pad);
+    if (rc) return rc;
     const MlpHead hd{(const _Float16 *)ray_sh, (const _Float16 *)grad_h0, samples_per_ray, out_width, (const _Float16 *)obj_feat, input_pad};
     const int relu = activation == 0;
     if (num_layers == 2) return mlp_bwd_fused_launch<64, 2>(grad, h, weights, nullptr, B, 32, relu, nullptr, grad_h, grad_weights, (float *)workspace, 0, (hipStream_t)stream, &hd, grad_obj);
@@ -1679,14 +1713,21 @@ int foc_color_head_backward(const void *grad, const void *h, const void *ray_sh,
                             uint32_t B, uint32_t hidden_dim, uint32_t num_layers, uint32_t activation, void *grad_h, void *grad_weights, void *workspace,
                             uint64_t workspace_bytes, uint32_t out_width, const void *obj_feat, float *grad_obj, void *stream) {
     return color_head_backward(grad, h, ray_sh, samples_per_ray, grad_h0, weights, B, hidden_dim, num_layers, activation, grad_h, grad_weights, workspace,
-                               workspace_bytes, out_width, obj_feat, grad_obj, 0.0f, stream);
+                               workspace_bytes, out_width, obj_feat, grad_obj, 0.0f, false, stream);
 }
 
 int foc_color_head_backward_pad(const void *grad, const void *h, const void *ray_sh, uint32_t samples_per_ray, const void *grad_h0, const void *weights,
                                 uint32_t B, uint32_t hidden_dim, uint32_t num_layers, uint32_t activation, void *grad_h, void *grad_weights, void *workspace,
                                 uint64_t workspace_bytes, uint32_t out_width, const void *obj_feat, float *grad_obj, float input_pad, void *stream) {
     return color_head_backward(grad, h, ray_sh, samples_per_ray, grad_h0, weights, B, hidden_dim, num_layers, activation, grad_h, grad_weights, workspace,
-                               workspace_bytes, out_width, obj_feat, grad_obj, input_pad, stream);
+                               workspace_bytes, out_width, obj_feat, grad_obj, input_pad, false, stream);
+}
+
+int foc_color_head_backward_pad31(const void *grad, const void *h, const void *ray_sh, uint32_t samples_per_ray, const void *grad_h0, const void *weights,
+                                  uint32_t B, uint32_t hidden_dim, uint32_t num_layers, uint32_t activation, void *grad_h, void *grad_weights, void *workspace,
+                                  uint64_t workspace_bytes, uint32_t out_width, const void *obj_feat, float *grad_obj, float input_pad, void *stream) {
+    return color_head_backward(grad, h, ray_sh, samples_per_ray, grad_h0, weights, B, hidden_dim, num_layers, activation, grad_h, grad_weights, workspace,
+                               workspace_bytes, out_width, obj_feat, grad_obj, input_pad, true, stream);
 }
 
 int foc_allocate_splitk(uint64_t size) { (void)size; return FOC_OK; }

@@ -35,7 +35,7 @@ __global__ void __launch_bounds__(MLP_BLOCK, FF_MIN_WAVES) k_field_fwd_train(con
     const float *obj_bias = reinterpret_cast<const float *>(ldsC + FC * 512);
     stage_weights_fwd<HIDDEN>(w_sigma, ldsS, 32, NLS);
     stage_weights_fwd<HIDDEN>(w_color, ldsC, 32, NLC, true, head_ld0(hd));
-    if (hd.obj) stage_obj_bias(w_color, hd.obj, const_cast<float *>(obj_bias), HIDDEN, hd.pad);
+    if (head_bias(hd)) stage_head_bias(w_color, hd, const_cast<float *>(obj_bias), HIDDEN);
     __syncthreads();
 
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -119,10 +119,10 @@ __global__ void __launch_bounds__(MLP_BLOCK, FF_MIN_WAVES) k_field_fwd_train(con
         const ff_u2 s02 = __builtin_amdgcn_permlane32_swap(P0, P2, false, false);      // P0[32:63] <-> P2[0:31]
         const ff_u2 s13 = __builtin_amdgcn_permlane32_swap(P1, P3, false, false);
         const h8 hk = head_shift(u32x4{s02.x, s13.x, s02.y, s13.y}, nxt);
-        // ---- colour network: layer 0 = [SH16 | h[1:16] | 0] (+ the object feature's share as the accumulators' start), k_mlp_fwd's head form
+        // ---- colour network: layer 0 = [SH16 | h[1:16] | 0] (+ the object feature's share / the column-31 pad as the accumulators' start), k_mlp_fwd's head form
 #pragma unroll
         for (int mt = 0; mt < MT; mt++) {
-            if (hd.obj) acc[mt] = ld_obj_bias(obj_bias, mt, h);
+            if (head_bias(hd)) acc[mt] = ld_obj_bias(obj_bias, mt, h);
             else {
 #pragma unroll
                 for (int e = 0; e < 16; e++) acc[mt][e] = 0.0f;
@@ -196,14 +196,15 @@ static int ff_launch_act(const void *planes, const void *w_sigma, const void *w_
 
 static int field_forward_train(const void *planes, const void *sigma_weights, uint32_t sigma_layers, const void *ray_sh, uint32_t samples_per_ray,
                                const void *color_weights, uint32_t color_layers, uint32_t hidden_dim, uint32_t activation, uint32_t B, void *h, void *c,
-                               uint32_t out_width, const void *obj_feat, float input_pad, void *stream) {
+                               uint32_t out_width, const void *obj_feat, float input_pad, bool pad31, void *stream) {
     FocDeviceGuard foc_guard_(stream, planes);
     if (B == 0) return FOC_OK;
     FOC_REQUIRE(planes && sigma_weights && ray_sh && color_weights && h && c, FOC_E_INVALID, "field_forward_train: null pointer");
     FOC_REQUIRE(hidden_dim == 64 && samples_per_ray >= 1, FOC_E_INVALID, "field_forward_train: hidden_dim must be 64 (got %u), samples_per_ray >= 1", hidden_dim);
     FOC_REQUIRE(activation == FOC_ACT_RELU || activation == FOC_ACT_NONE, FOC_E_INVALID, "field_forward_train: hidden activation must be relu(0) or none(6)");
     FOC_REQUIRE(out_width == 16 || out_width == 4, FOC_E_INVALID, "field_forward_train: out_width must be 16 or 4 (got %u)", out_width);
-    FOC_REQUIRE(input_pad == 0.0f || obj_feat, FOC_E_INVALID, "field_forward_train: input_pad is column 47 of the 48-wide colour input and needs obj_feat");
+    const int prc = head_pad_check("field_forward_train", pad31, obj_feat, input_pad);
+    if (prc) return prc;
     const MlpHead hd{(const _Float16 *)ray_sh, nullptr, samples_per_ray, out_width, (const _Float16 *)obj_feat, input_pad};
     const int relu = activation == FOC_ACT_RELU;
     hipStream_t st = (hipStream_t)stream;
@@ -223,14 +224,21 @@ int foc_field_forward_train(const void *planes, const void *sigma_weights, uint3
                             const void *color_weights, uint32_t color_layers, uint32_t hidden_dim, uint32_t activation, uint32_t B, void *h, void *c,
                             uint32_t out_width, const void *obj_feat, void *stream) {
     return field_forward_train(planes, sigma_weights, sigma_layers, ray_sh, samples_per_ray, color_weights, color_layers, hidden_dim, activation, B, h, c,
-                               out_width, obj_feat, 0.0f, stream);
+                               out_width, obj_feat, 0.0f, false, stream);
 }
 
 int foc_field_forward_train_pad(const void *planes, const void *sigma_weights, uint32_t sigma_layers, const void *ray_sh, uint32_t samples_per_ray,
                                 const void *color_weights, uint32_t color_layers, uint32_t hidden_dim, uint32_t activation, uint32_t B, void *h, void *c,
                                 uint32_t out_width, const void *obj_feat, float input_pad, void *stream) {
     return field_forward_train(planes, sigma_weights, sigma_layers, ray_sh, samples_per_ray, color_weights, color_layers, hidden_dim, activation, B, h, c,
-                               out_width, obj_feat, input_pad, stream);
+                               out_width, obj_feat, input_pad, false, stream);
+}
+
+int foc_field_forward_train_pad31(const void *planes, const void *sigma_weights, uint32_t sigma_layers, const void *ray_sh, uint32_t samples_per_ray,
+                                  const void *color_weights, uint32_t color_layers, uint32_t hidden_dim, uint32_t activation, uint32_t B, void *h, void *c,
+                                  uint32_t out_width, const void *obj_feat, float input_pad, void *stream) {
+    return field_forward_train(planes, sigma_weights, sigma_layers, ray_sh, samples_per_ray, color_weights, color_layers, hidden_dim, activation, B, h, c,
+                               out_width, obj_feat, input_pad, true, stream);
 }
 
 } // extern "C"

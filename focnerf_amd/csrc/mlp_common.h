@@ -99,12 +99,17 @@ struct MlpHead {
     // form. Backward: column 31 of the layer-0 input tile is set to 1, so the weight-gradient MFMAs deliver the column sum of delta_0 in
     // dW0[:, 31]; dW0[:, 31:47] = colsum (x) obj and grad_obj = W0[:, 31:47]^T colsum follow in the finalize kernel. W0 rows are 48 wide.
     const _Float16 *obj;           // [16] or null
-    // value of input column 47 of the 48-wide row (with `obj` only): 0 as above; 1.0 for the tinycudann layout (network_tcnn.py), where the
-    // padded input column acts as a free bias. Forward: W0[:, 47] * pad joins the per-neuron constant; backward: dW0[:, 47] = colsum * pad.
+    // value of the constant last input column, 0 or 1.0 for the tinycudann layouts, where the padded input column acts as a free bias.
+    // With `obj`: column 47 of the 48-wide row (network_tcnn.py). Forward: W0[:, 47] * pad joins the per-neuron constant; backward:
+    // dW0[:, 47] = colsum * pad. Without `obj`: column 31 of the 32-wide row [SH16 | h[1:16] | pad] (network_tcnn_legacy.py, the *_pad31
+    // entry points). Forward: W0[:, 31] * pad is the per-neuron start of the layer-0 accumulators; backward: column 31 of the layer-0 input
+    // tile (the zero shifted into the h row) holds pad, so the weight-gradient MFMAs give dW0[:, 31] = sum_b delta_0 * pad. pad = 0: as above.
     float pad;
 };
 #define HEAD_OBJ_LD 48u
 __device__ __forceinline__ uint32_t head_ld0(const MlpHead &hd) { return hd.obj ? HEAD_OBJ_LD : 32u; }
+// the colour head's layer 0 starts from a per-neuron constant (staged by stage_head_bias): the object feature's share, or the column-31 pad
+__host__ __device__ __forceinline__ bool head_bias(const MlpHead &hd) { return hd.obj != nullptr || hd.pad != 0.0f; }
 
 // obj_bias[mt][h][reg] (fp32, accumulator-register order of acc_row) = sum_j W0[n][31 + j] * obj[j] (+ W0[n][47] * pad), n = 32 mt + acc_row(reg, h):
 // 64 threads, sequential fmaf in j order, the pad term last. `W0` has HEAD_OBJ_LD-wide rows. pad = 0 adds nothing (not even a signed zero).
@@ -118,6 +123,26 @@ __device__ __forceinline__ void stage_obj_bias(const _Float16 *__restrict__ W0, 
         if (pad != 0.0f) a = fmaf((float)W0[(size_t)n * HEAD_OBJ_LD + 47], pad, a);
         bias[(mt * 2 + h) * 16 + reg] = a;
     }
+}
+// Host: which column an entry point's input_pad stands in. The *_pad31 twins: column 31 of the 32-wide row, which has no object feature;
+// the others: column 47 of the 48-wide row, which needs one (input_pad = 0 needs nothing).
+static inline int head_pad_check(const char *who, bool pad31, const void *obj_feat, float input_pad) {
+    if (pad31) FOC_REQUIRE(!obj_feat, FOC_E_INVALID, "%s_pad31: input_pad is column 31 of the 32-wide colour input, obj_feat must be NULL "
+                                                     "(a 48-wide row takes its pad through foc_%s_pad)", who, who);
+    else FOC_REQUIRE(input_pad == 0.0f || obj_feat, FOC_E_INVALID, "%s: input_pad is column 47 of the 48-wide colour input and needs obj_feat", who);
+    return FOC_OK;
+}
+// The same layout for the 32-wide row without an object feature: bias = W0[n][31] * pad (one product, exact for pad = 1). `W0` has 32-wide rows.
+__device__ __forceinline__ void stage_pad31_bias(const _Float16 *__restrict__ W0, float pad, float *bias, uint32_t hidden) {
+    if (threadIdx.x < hidden) {
+        const uint32_t n = threadIdx.x, r = n & 31u, mt = n >> 5;
+        const uint32_t h = (r >> 2) & 1u, reg = (r & 3u) + 4u * (r >> 3);
+        bias[(mt * 2 + h) * 16 + reg] = (float)W0[(size_t)n * 32 + 31] * pad;
+    }
+}
+__device__ __forceinline__ void stage_head_bias(const _Float16 *__restrict__ W0, const MlpHead &hd, float *bias, uint32_t hidden) {
+    if (hd.obj) stage_obj_bias(W0, hd.obj, bias, hidden, hd.pad);
+    else stage_pad31_bias(W0, hd.pad, bias, hidden);
 }
 __device__ __forceinline__ f16v ld_obj_bias(const float *bias, int mt, int h) {
     typedef float f4 __attribute__((ext_vector_type(4)));

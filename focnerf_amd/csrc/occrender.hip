@@ -42,17 +42,23 @@ uint64_t foc_occ_render_step_scratch_bytes(uint32_t n_rays) {
     return wl + cc;
 }
 
-int foc_occ_render_step(uint32_t n_alive, uint32_t n_step, const int32_t *rays_alive, int32_t *rays_alive_out, int32_t *count,
-                        float *rays_t, const float *rays_o, const float *rays_d, float bound, float dt_gamma, uint32_t max_steps,
-                        uint32_t C, uint32_t H, const uint8_t *grid, const float *nears, const float *fars, const float *noises,
-                        float *samples /* [n_alive*n_step*8]: normalised xyzs | dirs | deltas */,
-                        void *planes /* fp16 [L, n_alive*n_step, 2] */, float *sigma, float *rgb,
-                        const void *embeddings, const int32_t *offsets, const int32_t *offsets_host, uint32_t L, float S, uint32_t base_res,
-                        const void *sigma_weights, uint32_t sigma_layers, const void *color_weights, uint32_t color_layers, uint32_t activation,
-                        const void *obj_feat, float T_thresh, float *weights_sum, float *depth, float *image, void *scratch, uint32_t flags, int32_t *deaths, uint32_t deaths_base,
-                        uint32_t deaths_len, void *stream) {
+// pad31 (foc_occ_render_step_pad31): the field through foc_nerf_field_inference_pad31, column 31 of the colour input = input_pad
+static int occ_render_step(uint32_t n_alive, uint32_t n_step, const int32_t *rays_alive, int32_t *rays_alive_out, int32_t *count,
+                           float *rays_t, const float *rays_o, const float *rays_d, float bound, float dt_gamma, uint32_t max_steps,
+                           uint32_t C, uint32_t H, const uint8_t *grid, const float *nears, const float *fars, const float *noises,
+                           float *samples, void *planes, float *sigma, float *rgb,
+                           const void *embeddings, const int32_t *offsets, const int32_t *offsets_host, uint32_t L, float S, uint32_t base_res,
+                           const void *sigma_weights, uint32_t sigma_layers, const void *color_weights, uint32_t color_layers, uint32_t activation,
+                           const void *obj_feat, float T_thresh, float *weights_sum, float *depth, float *image, void *scratch, uint32_t flags, int32_t *deaths,
+                           uint32_t deaths_base, uint32_t deaths_len, float input_pad, bool pad31, void *stream) {
     FocDeviceGuard foc_guard_(stream, rays_alive);
     FOC_REQUIRE(count, FOC_E_INVALID, "occ_render_step: null pointer");
+    if (pad31) {                                            // refused before anything is enqueued
+        const uint32_t lk = sigma_layers * 10 + color_layers;
+        FOC_REQUIRE(!obj_feat, FOC_E_INVALID, "occ_render_step_pad31: input_pad is column 31 of the 32-wide colour input, obj_feat must be NULL");
+        FOC_REQUIRE(input_pad == 0.0f || lk == 12 || lk == 13 || lk == 22 || lk == 23 || lk == 33, FOC_E_INVALID,
+                    "occ_render_step_pad31: a pad needs (sigma_layers, color_layers) in (1,2), (1,3), (2,2), (2,3), (3,3) (got %u, %u)", sigma_layers, color_layers);
+    }
     hipStream_t st = (hipStream_t)stream;
     if (n_alive == 0) return foc_zero_async(count, sizeof(int32_t), st) == hipSuccess ? FOC_OK : FOC_E_LAUNCH;
     FOC_REQUIRE(rays_alive && rays_alive_out && rays_t && rays_o && rays_d && grid && fars && noises && samples && planes && sigma && rgb && embeddings &&
@@ -85,13 +91,42 @@ int foc_occ_render_step(uint32_t n_alive, uint32_t n_step, const int32_t *rays_a
         const uint32_t mc = (uint32_t)(M - m0 < piece ? M - m0 : piece);
         rc = foc_grid_encode_forward(xyzs + 3 * m0, embeddings, offsets, planes, mc, 3, 2, L, S, base_res, nullptr, 0, 0, 0, FOC_F16, offsets_host, stream);
         if (rc) return rc;
-        rc = foc_nerf_field_inference(planes, 1, dirs + 3 * m0, 1, 0, mc, sigma_weights, sigma_layers, color_weights, color_layers, 64, activation, mc, sigma + m0,
-                                      rgb + 3 * m0, obj_feat, stream);
+        rc = pad31 ? foc_nerf_field_inference_pad31(planes, 1, dirs + 3 * m0, 1, 0, mc, sigma_weights, sigma_layers, color_weights, color_layers, 64, activation,
+                                                    mc, sigma + m0, rgb + 3 * m0, obj_feat, input_pad, stream)
+                   : foc_nerf_field_inference(planes, 1, dirs + 3 * m0, 1, 0, mc, sigma_weights, sigma_layers, color_weights, color_layers, 64, activation, mc,
+                                              sigma + m0, rgb + 3 * m0, obj_feat, stream);
         if (rc) return rc;
     }
     // composite marks finished rays in the INPUT list; the compaction then writes the survivors to the output list
     return foc_composite_compact(n_alive, n_step, T_thresh, const_cast<int32_t *>(rays_alive), rays_t, sigma, rgb, deltas, weights_sum, depth, image, rays_alive_out,
                                  count, compact_scratch, deaths, deaths_base, deaths_len, sample_major, stream);
+}
+
+int foc_occ_render_step(uint32_t n_alive, uint32_t n_step, const int32_t *rays_alive, int32_t *rays_alive_out, int32_t *count,
+                        float *rays_t, const float *rays_o, const float *rays_d, float bound, float dt_gamma, uint32_t max_steps,
+                        uint32_t C, uint32_t H, const uint8_t *grid, const float *nears, const float *fars, const float *noises,
+                        float *samples /* [n_alive*n_step*8]: normalised xyzs | dirs | deltas */,
+                        void *planes /* fp16 [L, n_alive*n_step, 2] */, float *sigma, float *rgb,
+                        const void *embeddings, const int32_t *offsets, const int32_t *offsets_host, uint32_t L, float S, uint32_t base_res,
+                        const void *sigma_weights, uint32_t sigma_layers, const void *color_weights, uint32_t color_layers, uint32_t activation,
+                        const void *obj_feat, float T_thresh, float *weights_sum, float *depth, float *image, void *scratch, uint32_t flags, int32_t *deaths, uint32_t deaths_base,
+                        uint32_t deaths_len, void *stream) {
+    return occ_render_step(n_alive, n_step, rays_alive, rays_alive_out, count, rays_t, rays_o, rays_d, bound, dt_gamma, max_steps, C, H, grid, nears, fars, noises,
+                           samples, planes, sigma, rgb, embeddings, offsets, offsets_host, L, S, base_res, sigma_weights, sigma_layers, color_weights, color_layers,
+                           activation, obj_feat, T_thresh, weights_sum, depth, image, scratch, flags, deaths, deaths_base, deaths_len, 0.0f, false, stream);
+}
+
+int foc_occ_render_step_pad31(uint32_t n_alive, uint32_t n_step, const int32_t *rays_alive, int32_t *rays_alive_out, int32_t *count,
+                              float *rays_t, const float *rays_o, const float *rays_d, float bound, float dt_gamma, uint32_t max_steps,
+                              uint32_t C, uint32_t H, const uint8_t *grid, const float *nears, const float *fars, const float *noises,
+                              float *samples, void *planes, float *sigma, float *rgb,
+                              const void *embeddings, const int32_t *offsets, const int32_t *offsets_host, uint32_t L, float S, uint32_t base_res,
+                              const void *sigma_weights, uint32_t sigma_layers, const void *color_weights, uint32_t color_layers, uint32_t activation,
+                              const void *obj_feat, float T_thresh, float *weights_sum, float *depth, float *image, void *scratch, uint32_t flags, int32_t *deaths,
+                              uint32_t deaths_base, uint32_t deaths_len, float input_pad, void *stream) {
+    return occ_render_step(n_alive, n_step, rays_alive, rays_alive_out, count, rays_t, rays_o, rays_d, bound, dt_gamma, max_steps, C, H, grid, nears, fars, noises,
+                           samples, planes, sigma, rgb, embeddings, offsets, offsets_host, L, S, base_res, sigma_weights, sigma_layers, color_weights, color_layers,
+                           activation, obj_feat, T_thresh, weights_sum, depth, image, scratch, flags, deaths, deaths_base, deaths_len, input_pad, true, stream);
 }
 
 } // extern "C"

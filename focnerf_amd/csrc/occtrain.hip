@@ -226,9 +226,20 @@ static int ot_check_node(const FocOccTrainNode *n, const char *who) {
     return FOC_OK;
 }
 
-int foc_occ_train_forward(const FocOccTrainNode *n, void *stream) {
-    int rc = ot_check_node(n, "occ_train_forward");
+// The *_pad31 twins (pad31): column 31 of the colour input holds input_pad (the legacy tinycudann layout, network_tcnn_legacy.py), through
+// foc_field_forward_train_pad31 / foc_color_head_forward_pad31 / foc_color_head_backward_pad31, and the one-kernel forward of both networks
+// also serves one sigma hidden layer ((1, 2), (1, 3): bit for bit the two calls, as at the other pairs).
+static int ot_check_pad31(const FocOccTrainNode *n, float input_pad, const char *who) {
+    const uint32_t lk = n->sigma_layers * 10 + n->color_layers;
+    FOC_REQUIRE(input_pad == 0.0f || lk == 12 || lk == 13 || lk == 22 || lk == 23 || lk == 33, FOC_E_INVALID,
+                "%s: a pad needs (sigma_layers, color_layers) in (1,2), (1,3), (2,2), (2,3), (3,3) (got %u, %u)", who, n->sigma_layers, n->color_layers);
+    return FOC_OK;
+}
+
+static int occ_train_forward(const FocOccTrainNode *n, float input_pad, bool pad31, void *stream) {
+    int rc = ot_check_node(n, pad31 ? "occ_train_forward_pad31" : "occ_train_forward");
     if (rc != FOC_OK) return rc;
+    if (pad31 && (rc = ot_check_pad31(n, input_pad, "occ_train_forward_pad31")) != FOC_OK) return rc;
     const uint32_t M = n->cap;
     rc = foc_march_rays_train_field(n->rays_o, n->rays_d, n->bitfield, n->bound, n->dt_gamma, n->max_steps, n->n_rays, n->cascade, n->grid_size, M, n->nears, n->fars,
                                     n->enc_in, n->sh_rows, n->deltas, n->rays, n->counter, n->jitter, n->march_scratch, n->pad_align, n->aabb, n->min_near, stream);
@@ -238,32 +249,40 @@ int foc_occ_train_forward(const FocOccTrainNode *n, void *stream) {
     if (rc != FOC_OK) return rc;
     // both networks in one kernel when the shapes are FOC's (csrc/field_fwd.hip: bit for bit the two calls below)
     const uint32_t lk = n->sigma_layers * 10 + n->color_layers;
-    if (n->sigma_input_dim == 32 && n->sigma_hidden == 64 && n->color_hidden == 64 && (lk == 22 || lk == 23 || lk == 33) &&
+    if (n->sigma_input_dim == 32 && n->sigma_hidden == 64 && n->color_hidden == 64 && (lk == 22 || lk == 23 || lk == 33 || (pad31 && (lk == 12 || lk == 13))) &&
         n->sigma_activation == n->color_activation && (n->sigma_activation == 0 || n->sigma_activation == 6) && n->sigma_output_activation == 6 &&
         foc_opt(FOC_OPT_FIELD_FWD_FUSED)) {
-        rc = foc_field_forward_train(n->planes, n->w_sigma, n->sigma_layers, n->sh_rows, 1, n->w_color, n->color_layers, 64, n->sigma_activation, M, n->h, n->c,
-                                     n->c_width, nullptr, stream);
+        rc = pad31 ? foc_field_forward_train_pad31(n->planes, n->w_sigma, n->sigma_layers, n->sh_rows, 1, n->w_color, n->color_layers, 64, n->sigma_activation,
+                                                   M, n->h, n->c, n->c_width, nullptr, input_pad, stream)
+                   : foc_field_forward_train(n->planes, n->w_sigma, n->sigma_layers, n->sh_rows, 1, n->w_color, n->color_layers, 64, n->sigma_activation, M, n->h,
+                                             n->c, n->c_width, nullptr, stream);
         if (rc != FOC_OK) return rc;
     } else {
         rc = foc_ffmlp_forward_planar(n->planes, n->w_sigma, M, n->sigma_input_dim, 16, n->sigma_hidden, n->sigma_layers, n->sigma_activation, n->sigma_output_activation,
                                       n->h, stream);
         if (rc != FOC_OK) return rc;
-        rc = foc_color_head_forward(n->h, n->sh_rows, 1, n->w_color, M, n->color_hidden, n->color_layers, n->color_activation, n->c, n->c_width, nullptr, stream);
+        rc = pad31 ? foc_color_head_forward_pad31(n->h, n->sh_rows, 1, n->w_color, M, n->color_hidden, n->color_layers, n->color_activation, n->c, n->c_width,
+                                                  nullptr, input_pad, stream)
+                   : foc_color_head_forward(n->h, n->sh_rows, 1, n->w_color, M, n->color_hidden, n->color_layers, n->color_activation, n->c, n->c_width, nullptr,
+                                            stream);
         if (rc != FOC_OK) return rc;
     }
     return foc_occ_tail_forward(n->h, n->c, n->c_width, n->deltas, n->rays, M, n->n_rays, n->T_thresh, n->density_scale, n->bg_ray, n->bg_scalar, n->nears, n->fars,
                                 n->weights_sum, n->image_raw, n->image, n->depth, stream);
 }
 
-int foc_occ_train_backward(const FocOccTrainNode *n, void *stream) {
-    int rc = ot_check_node(n, "occ_train_backward");
+static int occ_train_backward(const FocOccTrainNode *n, float input_pad, bool pad31, void *stream) {
+    int rc = ot_check_node(n, pad31 ? "occ_train_backward_pad31" : "occ_train_backward");
     if (rc != FOC_OK) return rc;
+    if (pad31 && (rc = ot_check_pad31(n, input_pad, "occ_train_backward_pad31")) != FOC_OK) return rc;
     const uint32_t M = n->cap;
     rc = foc_occ_tail_backward(n->grad_image, n->grad_ws, n->h, n->c, n->c_width, n->deltas, n->rays, n->counter, n->weights_sum, n->image_raw, M, n->n_rays, n->T_thresh,
                                n->density_scale, n->bg_ray, n->bg_scalar, n->grad_c, n->grad_h0, stream);
     if (rc != FOC_OK) return rc;
-    rc = foc_color_head_backward(n->grad_c, n->h, n->sh_rows, 1, n->grad_h0, n->w_color, M, n->color_hidden, n->color_layers, n->color_activation, n->grad_h,
-                                 n->grad_w_color, n->mlp_workspace, n->mlp_workspace_bytes, n->c_width, nullptr, nullptr, stream);
+    rc = pad31 ? foc_color_head_backward_pad31(n->grad_c, n->h, n->sh_rows, 1, n->grad_h0, n->w_color, M, n->color_hidden, n->color_layers, n->color_activation,
+                                               n->grad_h, n->grad_w_color, n->mlp_workspace, n->mlp_workspace_bytes, n->c_width, nullptr, nullptr, input_pad, stream)
+               : foc_color_head_backward(n->grad_c, n->h, n->sh_rows, 1, n->grad_h0, n->w_color, M, n->color_hidden, n->color_layers, n->color_activation, n->grad_h,
+                                         n->grad_w_color, n->mlp_workspace, n->mlp_workspace_bytes, n->c_width, nullptr, nullptr, stream);
     if (rc != FOC_OK) return rc;
     rc = foc_ffmlp_backward_planar(n->grad_h, n->planes, n->w_sigma, M, n->sigma_input_dim, 16, n->sigma_hidden, n->sigma_layers, n->sigma_activation,
                                    n->sigma_output_activation, 1, n->grad_planes, n->grad_w_sigma, n->mlp_workspace, n->mlp_workspace_bytes, stream);
@@ -272,5 +291,10 @@ int foc_occ_train_backward(const FocOccTrainNode *n, void *stream) {
         n->grad_planes, n->enc_in, n->embeddings, n->offsets, n->grad_embeddings, M, 3, 2, n->levels, n->per_level_scale_log2, n->base_resolution, nullptr, nullptr,
         n->gridtype, n->align_corners, n->interp, n->table_dtype, 0, n->offsets_host, n->grid_workspace, n->grid_workspace_bytes, stream);
 }
+
+int foc_occ_train_forward(const FocOccTrainNode *n, void *stream) { return occ_train_forward(n, 0.0f, false, stream); }
+int foc_occ_train_backward(const FocOccTrainNode *n, void *stream) { return occ_train_backward(n, 0.0f, false, stream); }
+int foc_occ_train_forward_pad31(const FocOccTrainNode *n, float input_pad, void *stream) { return occ_train_forward(n, input_pad, true, stream); }
+int foc_occ_train_backward_pad31(const FocOccTrainNode *n, float input_pad, void *stream) { return occ_train_backward(n, input_pad, true, stream); }
 
 } // extern "C"

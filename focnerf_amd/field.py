@@ -62,7 +62,18 @@ class FieldPlan:
     occ: bool                           # the occupancy-grid training forward as one node (occtrain._occ_train)
     native_loop: bool                   # the occupancy-grid inference loop as one call per iteration (NeRFRenderer._native_inference_loop)
     head: bool                          # the glue between the two networks as kernels (head.sample_head / rgb_head)
-    colour_input_pad: float = 0.0       # column 47 of the 48-wide object-conditioned colour input (1.0: tinycudann layout, network_tcnn.py)
+    colour_input_pad: float = 0.0       # the colour input's last column: 47 of the 48-wide object-conditioned row (1.0: tinycudann layout,
+                                        # network_tcnn.py), 31 of the 32-wide row (1.0: legacy tinycudann layout, network_tcnn_legacy.py)
+
+
+def pad_twin(name, pad, obj):
+    """(entry point, extra arguments) for the library call `name` with the colour input's pad: `name` itself for pad 0 (the old call,
+    unchanged), else its twin that takes the pad before the stream — `name`_pad for the 48-wide object-conditioned row (column 47),
+    `name`_pad31 for the 32-wide row (column 31)."""
+    from ._lib import lib
+    if pad == 0:
+        return getattr(lib, name), ()
+    return getattr(lib, name + ("_pad" if obj else "_pad31")), (float(pad),)
 
 
 def _on(switch):
@@ -77,7 +88,7 @@ def field_plan(model):
     enc, enc_dir = getattr(model, "encoder", None), getattr(model, "encoder_dir", None)
     sigma, colour = MlpShape.of(getattr(model, "sigma_net", None)), MlpShape.of(getattr(model, "color_net", None))
     obj = bool(getattr(model, "uses_object_feature", False))
-    pad = float(getattr(model, "colour_input_pad", 0.0)) if obj else 0.0     # the *_pad kernels take it; sample_head writes a zero there
+    pad = float(getattr(model, "colour_input_pad", 0.0))     # the *_pad / *_pad31 kernels take it; sample_head writes a zero there
     grid = enc.spec() if isinstance(enc, GridEncoder) else None
 
     # the hash grid the [L,B,C] kernels read: D 3, C 2, feeding the sigma network directly; the native loop's encoder is the plain one
@@ -195,8 +206,6 @@ def _check_colour_branch(colour, B):
         raise RuntimeError(f"hashgrid_mlp colour branch: a {shape.input_dim}-wide colour input takes "
                            f"{'a 16-element object feature' if shape.input_dim == 48 else 'no object feature'}, got "
                            f"{'none' if obj_feat is None else f'{obj_feat.numel()} elements'}")
-    if len(colour) > 6 and colour[6] != 0 and obj_feat is None:
-        raise RuntimeError("hashgrid_mlp colour branch: an input pad is column 47 of the 48-wide colour input and needs an object feature")
     if cweights.numel() != 64 * (shape.input_dim + 64 * (shape.num_layers - 1) + 16):
         raise RuntimeError(f"hashgrid_mlp colour branch: the colour weights hold {cweights.numel()} elements, a {shape.input_dim}-wide "
                            f"{shape.num_layers}-layer network has {64 * (shape.input_dim + 64 * (shape.num_layers - 1) + 16)}")
@@ -207,8 +216,8 @@ class _hashgrid_mlp(Function):
     @custom_fwd(device_type="cuda")
     def forward(ctx, x, embeddings, weights, offsets, grid, sigma, training, colour=None):
         # x [B,3] fp32 in [0,1]; embeddings [rows,2]; weights: FFMLP blob; grid: GridSpec; sigma: MlpShape of the blob
-        # colour = (colour weights, colour MlpShape, ray_sh [B / T, 16] half, T, c_width, obj_feat or None[, input pad = column 47 of the
-        # 48-wide colour input, 0 when absent]): the colour network's forward runs in
+        # colour = (colour weights, colour MlpShape, ray_sh [B / T, 16] half, T, c_width, obj_feat or None[, input pad = the last column of
+        # the colour input (47 of the 48-wide row, 31 of the 32-wide one), 0 when absent]): the colour network's forward runs in
         # the SAME kernel as the sigma network's (foc_field_forward_train) and its logits come back as a second, non-differentiable output — the
         # node that owns the colour network (fixedstep._render_tail) takes them instead of launching foc_color_head_forward, and computes every
         # gradient of the colour network in its own backward as before
@@ -229,7 +238,7 @@ class _hashgrid_mlp(Function):
         h = torch.empty(B, 16, device=x.device, dtype=torch.half)
         c = None
         if colour is not None:
-            from ._lib import lib, ptr, stream_of, check
+            from ._lib import ptr, stream_of, check
             cweights, cshape, ray_sh, T, c_width, obj_feat = colour[:6]
             pad = float(colour[6]) if len(colour) > 6 else 0.0
             wc = _half_of(cweights)
@@ -237,10 +246,8 @@ class _hashgrid_mlp(Function):
             c = torch.empty(B, c_width, device=x.device, dtype=torch.half)
             args = (ptr(enc), ptr(w), sigma.num_layers, ptr(ray_sh), int(T), ptr(wc), int(cshape.num_layers), 64, int(sigma.activation), B, ptr(h),
                     ptr(c), int(c_width), ptr(obj16))
-            if pad != 0:
-                check(lib.foc_field_forward_train_pad(*args, pad, stream_of(enc)), "field_forward_train_pad")
-            else:
-                check(lib.foc_field_forward_train(*args, stream_of(enc)), "field_forward_train")
+            fn, extra = pad_twin("foc_field_forward_train", pad, obj16 is not None)
+            check(fn(*args, *extra, stream_of(enc)), "field_forward_train")
         else:
             _ffmlp.ffmlp_forward_planar(enc, w, B, sigma.input_dim, 16, sigma.hidden_dim, sigma.num_layers, sigma.activation, sigma.output_activation, h)
         if training:
@@ -276,7 +283,7 @@ def field_infer(model, xn, dirs, dir_div=1, dir_block=0, obj_feat=None):
     """xn [M,3] fp32 in [0,1] (already normalised), dirs [M / dir_div, 3] -> sigma [M] fp32, rgb [M,3] fp32 (no autograd).
     dir_block = 64: the rows stand in the block-interleaved order of `fixedstep.fixed_sample(..., ray_block=64)`.
     obj_feat [16]: the encoded object feature of an object-conditioned network (required iff `model.uses_object_feature`)."""
-    from ._lib import lib, ptr, stream_of, check
+    from ._lib import ptr, stream_of, check
     enc, sn, cn = model.encoder, model.sigma_net, model.color_net
     grid = enc.spec()
     xn = xn.contiguous().float()
@@ -296,11 +303,9 @@ def field_infer(model, xn, dirs, dir_div=1, dir_block=0, obj_feat=None):
         assert obj16.numel() == 16
     args = (ptr(planes), 1, ptr(dirs), int(dir_div), int(dir_block), dirs.shape[0], ptr(ws), sn.num_layers, ptr(wc), cn.num_layers, 64, sn.activation, M,
             ptr(sigma), ptr(rgb), ptr(obj16))
-    pad = float(getattr(model, "colour_input_pad", 0.0)) if obj16 is not None else 0.0
-    if pad != 0:                              # the tinycudann layout (network_tcnn.py): column 47 of the colour input is a constant
-        check(lib.foc_nerf_field_inference_pad(*args, pad, stream_of(xn)), "nerf_field_inference_pad")
-    else:
-        check(lib.foc_nerf_field_inference(*args, stream_of(xn)), "nerf_field_inference")
+    # the tinycudann layouts (network_tcnn.py, network_tcnn_legacy.py): the last column of the colour input is a constant
+    fn, extra = pad_twin("foc_nerf_field_inference", float(getattr(model, "colour_input_pad", 0.0)), obj16 is not None)
+    check(fn(*args, *extra, stream_of(xn)), "nerf_field_inference")
     return sigma, rgb
 
 

@@ -150,15 +150,16 @@ class _render_tail(Function):
     obj_feat [16] (or None): FOC's encoded object feature — the colour network then has 48-wide W0 rows; the feature's share of layer 0
     is a constant per neuron inside the kernels, its gradient (for the object-feature encoder) comes back as one [16] vector.
     want_sumsq: a seventh, differentiable output sumsq [N] = sum_t sigma^2 per ray (the samples' share of the outside-mask criterion).
-    input_pad: column 47 of the 48-wide colour input (with obj_feat only): 0, or 1.0 for the tinycudann layout (network_tcnn.py) — then the
-    *_pad twins of the colour-head kernels run."""
+    input_pad: the last column of the colour input: 0, or 1.0 for the tinycudann layouts — column 47 of the 48-wide row with obj_feat
+    (network_tcnn.py), column 31 of the 32-wide row without (network_tcnn_legacy.py); then the *_pad / *_pad31 twins of the colour-head
+    kernels run."""
 
     @staticmethod
     def forward(ctx, h, cweights, ray_sh, nears, fars, noise, bg_ray, bg_scalar, N, T, density_scale, thresh, num_layers, activation, obj_feat=None,
                 want_sumsq=False, c_pre=None, w16_pre=None, input_pad=0.0):
         # c_pre [M,4] half: the colour logits already computed from this h, these weights and this ray_sh by the encoder -> sigma node's fused
         # forward (field._hashgrid_mlp with `colour`, foc_field_forward_train: the bits foc_color_head_forward would give) — then no launch here
-        from .field import _half_of
+        from .field import _half_of, pad_twin
         h = h.contiguous()
         assert h.dtype == torch.float16 and h.shape == (N * T, 16)
         assert ray_sh.dtype == torch.float16 and ray_sh.shape == (N, 16) and ray_sh.is_contiguous()
@@ -176,10 +177,8 @@ class _render_tail(Function):
         else:
             c = torch.empty(M, _C_WIDTH, dtype=torch.float16, device=dev)
             args = (ptr(h), ptr(ray_sh), T, ptr(w16), M, 64, int(num_layers), int(activation), ptr(c), _C_WIDTH, ptr(obj16))
-            if input_pad != 0:
-                check(lib.foc_color_head_forward_pad(*args, float(input_pad), st), "color_head_forward_pad")
-            else:
-                check(lib.foc_color_head_forward(*args, st), "color_head_forward")
+            fn, extra = pad_twin("foc_color_head_forward", input_pad, obj16 is not None)
+            check(fn(*args, *extra, st), "color_head_forward")
         sigma = torch.empty(M, dtype=torch.float32, device=dev)
         trans = torch.empty(M, dtype=torch.float32, device=dev)
         weights = torch.empty(M, dtype=torch.float32, device=dev)
@@ -205,6 +204,7 @@ class _render_tail(Function):
     @staticmethod
     def backward(ctx, g_image, g_ws, g_depth, _g_sigma, _g_weights, _g_c, g_sumsq=None):
         from .backend import _scratch
+        from .field import pad_twin
         h, w16, sigma, trans, weights, c, ray_sh, nears, fars, noise, bg_ray, obj16 = ctx.saved_tensors
         has_noise, has_bg, has_obj, obj_dtype, obj_shape = ctx.flags
         obj16 = obj16 if has_obj else None
@@ -228,10 +228,8 @@ class _render_tail(Function):
         g_obj32 = torch.empty(16, dtype=torch.float32, device=dev) if has_obj and ctx.needs_input_grad[14] else None
         args = (ptr(grad_c), ptr(h), ptr(ray_sh), T, ptr(grad_h0), ptr(w16), M, 64, num_layers, activation, ptr(grad_h), ptr(g_w), ptr(wsb),
                 wsb.numel(), _C_WIDTH, ptr(obj16), ptr(g_obj32))
-        if input_pad != 0:
-            check(lib.foc_color_head_backward_pad(*args, input_pad, st), "color_head_backward_pad")
-        else:
-            check(lib.foc_color_head_backward(*args, st), "color_head_backward")
+        fn, extra = pad_twin("foc_color_head_backward", input_pad, has_obj)
+        check(fn(*args, *extra, st), "color_head_backward")
         g_obj = g_obj32.to(obj_dtype).view(obj_shape) if g_obj32 is not None else None
         return (grad_h, g_w) + (None,) * 12 + (g_obj, None, None, None, None)
 
@@ -360,8 +358,8 @@ def render_fixed_steps(model, rays_o, rays_d, yolo_details=None, num_steps=512, 
                 criterion_outside_mask = _masked_norm.apply(outs[6], (~yolo_details[0].reshape(N)).to(torch.float32))
         else:
             weights, weights_sum, depth, sigma, cin = _density_head.apply(h, rays_d, nears, fars, noise, N, T, model.density_scale, obj_feat)
-            if plan.colour_input_pad != 0:                                # the head kernel writes 0 in column 47 (tinycudann layout: the pad)
-                cin = torch.cat([cin[:, :47], cin.new_full((cin.shape[0], 1), plan.colour_input_pad)], dim=1)
+            if plan.colour_input_pad != 0:                                # the head kernel writes 0 in the last column (tinycudann layouts: the pad)
+                cin = torch.cat([cin[:, :-1], cin.new_full((cin.shape[0], 1), plan.colour_input_pad)], dim=1)
         if want_crit and criterion_outside_mask is None:
             from .activation import trunc_exp
             criterion_outside_mask = torch.norm(trunc_exp(h[:, 0]).view(N, T)[~yolo_details[0].squeeze(0)] - 0)

@@ -10,7 +10,9 @@ its first k-chunk is one SH row per sample written by the march's emit pass, its
 MlpHead; sigma, rgb and their gradients stay on the lane in csrc/occtrain.hip), same gradients up to fp32 summation order.
 
 The step it replaces was bound by its launches: ~85 kernels, 0.9 ms of GPU time, 1.2 ms of host time to enqueue them from Python.
-FOC_FUSED_OCC=0 keeps the chain (tests compare the two); `field.field_plan` decides which networks it serves (`plan.occ`).
+FOC_FUSED_OCC=0 keeps the chain (tests compare the two); `field.field_plan` decides which networks it serves (`plan.occ`). A network whose
+colour input ends in a constant column (`plan.colour_input_pad`: network_tcnn_legacy.py, column 31 = 1.0) runs the *_pad31 entry points;
+with pad 0 the calls are the old ones.
 """
 import os
 
@@ -69,8 +71,9 @@ class _occ_train(Function):
     @staticmethod
     def forward(ctx, emb, w_sigma, w_color, o, d, aabb, bitfield, counter, bg_ray, cfg):
         from .field import _half_of
+        from .field import pad_twin
         (bound, cascade, grid_size, mean_count, perturb, align, force_all_rays, dt_gamma, max_steps, T_thresh, density_scale, bg_scalar,
-         offsets, grid, sigma, colour, min_near) = cfg
+         offsets, grid, sigma, colour, min_near, pad) = cfg
         S, H, (gridtype, align_corners, interp) = grid.log2_scale, grid.base_resolution, grid.tail()
         n, dev = o.shape[0], o.device
         st = stream_of(o)
@@ -115,13 +118,16 @@ class _occ_train(Function):
             nd.w_sigma, nd.w_color, nd.h, nd.c = _a(ws16), _a(wc16), _a(h), _a(c)
             nd.T_thresh, nd.density_scale, nd.bg_scalar, nd.bg_ray = float(T_thresh), float(density_scale), float(bg_scalar), _a(bg_ray)
             nd.weights_sum, nd.image_raw, nd.image, nd.depth = _a(ws), _a(image_raw), _a(image), _a(depth)
-            check(lib.foc_occ_train_forward(ctypes.byref(nd), st), "occ_train_forward")
+            if pad != 0:                                    # column 31 of the colour input = pad: the node's twin, the pad beside the node
+                check(lib.foc_occ_train_forward_pad31(ctypes.byref(nd), pad, st), "occ_train_forward_pad31")
+            else:
+                check(lib.foc_occ_train_forward(ctypes.byref(nd), st), "occ_train_forward")
             # the count pass rode in the encoder's forward: the ticket the backward checks, as backend.grid_encode_forward_counted issues it
             ctx.ticket = _gridencoder.issue_precount_ticket(enc_in, M, L, FOC_F16, gws)
             ctx.save_for_backward(enc_in, emb16, ws16, wc16, offsets, planes, h, c, sh, deltas, rays, counter, ws, image_raw,
                                   bg_ray if bg_ray is not None else torch.empty(0, device=dev))
             ctx.nears_fars = nf
-            ctx.cfg = (M, n, float(T_thresh), float(density_scale), float(bg_scalar), bg_ray is not None, grid, sigma, colour)
+            ctx.cfg = (M, n, float(T_thresh), float(density_scale), float(bg_scalar), bg_ray is not None, grid, sigma, colour, pad)
             ctx.node, ctx.plan = nd, plan
             ctx.mark_non_differentiable(depth)
             ctx.set_materialize_grads(False)
@@ -145,8 +151,8 @@ class _occ_train(Function):
             _ffmlp.ffmlp_forward_planar(planes, ws16, M, sigma.input_dim, 16, sigma.hidden_dim, sigma.num_layers, sigma.activation, 6, h)
         c = torch.empty(M, _C_WIDTH, dtype=torch.float16, device=dev)
         if M:
-            check(lib.foc_color_head_forward(ptr(h), ptr(sh), 1, ptr(wc16), M, 64, colour.num_layers, colour.activation, ptr(c), _C_WIDTH, None, st),
-                  "color_head_forward")
+            fn, extra = pad_twin("foc_color_head_forward", pad, False)
+            check(fn(ptr(h), ptr(sh), 1, ptr(wc16), M, 64, colour.num_layers, colour.activation, ptr(c), _C_WIDTH, None, *extra, st), "color_head_forward")
         out = torch.empty(n * 8, dtype=torch.float32, device=dev)
         ws, depth, image_raw, image = out[:n], out[n: 2 * n], out[2 * n: 5 * n].view(n, 3), out[5 * n:].view(n, 3)
         check(lib.foc_occ_tail_forward(ptr(h), ptr(c), _C_WIDTH, ptr(deltas), ptr(rays), M, n, float(T_thresh), float(density_scale), ptr(bg_ray), float(bg_scalar),
@@ -154,7 +160,7 @@ class _occ_train(Function):
         ctx.save_for_backward(enc_in, emb16, ws16, wc16, offsets, planes, h, c, sh, deltas, rays, counter, ws, image_raw,
                               bg_ray if bg_ray is not None else torch.empty(0, device=dev))
         ctx.nears_fars = nf
-        ctx.cfg = (M, n, float(T_thresh), float(density_scale), float(bg_scalar), bg_ray is not None, grid, sigma, colour)
+        ctx.cfg = (M, n, float(T_thresh), float(density_scale), float(bg_scalar), bg_ray is not None, grid, sigma, colour, pad)
         ctx.ticket = ticket
         ctx.mark_non_differentiable(depth)
         ctx.set_materialize_grads(False)
@@ -163,7 +169,8 @@ class _occ_train(Function):
     @staticmethod
     def backward(ctx, g_image, g_ws, _g_depth):
         enc_in, emb16, ws16, wc16, offsets, planes, h, c, sh, deltas, rays, counter, ws, image_raw, bg_ray = ctx.saved_tensors
-        M, n, T_thresh, density_scale, bg_scalar, has_bg, grid, sigma, colour = ctx.cfg
+        from .field import pad_twin
+        M, n, T_thresh, density_scale, bg_scalar, has_bg, grid, sigma, colour, pad = ctx.cfg
         S, H, (gridtype, align_corners, interp) = grid.log2_scale, grid.base_resolution, grid.tail()
         dev = h.device
         st = stream_of(h)
@@ -186,7 +193,10 @@ class _occ_train(Function):
             nd.grad_planes, nd.grad_w_color, nd.grad_w_sigma, nd.grad_embeddings = _a(g_planes), _a(g_wcol), _a(g_wsig), _a(g_emb)
             nd.mlp_workspace, nd.mlp_workspace_bytes, nd.grid_workspace, nd.grid_workspace_bytes = _a(mws), mws.numel(), _a(gws), ctx.plan[0]
             nd.precounted = int(_gridencoder._precount_valid(ctx.ticket, enc_in, M, L, FOC_F16, gws))
-            check(lib.foc_occ_train_backward(ctypes.byref(nd), st), "occ_train_backward")
+            if pad != 0:
+                check(lib.foc_occ_train_backward_pad31(ctypes.byref(nd), pad, st), "occ_train_backward_pad31")
+            else:
+                check(lib.foc_occ_train_backward(ctypes.byref(nd), st), "occ_train_backward")
             _gridencoder._invalidate_precount(dev)          # the header now belongs to this pass (and a used ticket is spent)
             ctx.node = None
             return g_emb, g_wsig, g_wcol, None, None, None, None, None, None, None, None
@@ -196,8 +206,9 @@ class _occ_train(Function):
                                         T_thresh, density_scale, ptr(bg_ray if has_bg else None), bg_scalar, ptr(grad_c), ptr(grad_h0), st), "occ_tail_backward")
         grad_h = torch.empty_like(h)
         wsb = _scratch.get("ffmlp_ws", lib.foc_ffmlp_backward_workspace_bytes(32, 64, colour.num_layers), dev)
-        check(lib.foc_color_head_backward(ptr(grad_c), ptr(h), ptr(sh), 1, ptr(grad_h0), ptr(wc16), M, 64, colour.num_layers, colour.activation, ptr(grad_h), ptr(g_wcol),
-                                          ptr(wsb), wsb.numel(), _C_WIDTH, None, None, st), "color_head_backward")
+        fn, extra = pad_twin("foc_color_head_backward", pad, False)
+        check(fn(ptr(grad_c), ptr(h), ptr(sh), 1, ptr(grad_h0), ptr(wc16), M, 64, colour.num_layers, colour.activation, ptr(grad_h), ptr(g_wcol),
+                 ptr(wsb), wsb.numel(), _C_WIDTH, None, None, *extra, st), "color_head_backward")
         g_planes = torch.empty_like(planes)
         _ffmlp.ffmlp_backward_planar(grad_h, planes, ws16, M, sigma.input_dim, 16, sigma.hidden_dim, sigma.num_layers, sigma.activation, 6, True,
                                      g_planes, g_wsig)
@@ -215,6 +226,7 @@ def render_occupancy_train(model, plan, o, d, counter, bg_color, perturb, force_
     n, dev = o.shape[0], o.device
     bg_ray, bg_scalar = _background(bg_color, n, dev)
     cfg = (float(model.bound), int(model.cascade), int(model.grid_size), int(model.mean_count), bool(perturb), int(align), bool(force_all_rays), float(dt_gamma),
-           int(max_steps), float(T_thresh), float(model.density_scale), float(bg_scalar), enc.offsets, plan.grid, plan.sigma, plan.colour, float(model.min_near))
+           int(max_steps), float(T_thresh), float(model.density_scale), float(bg_scalar), enc.offsets, plan.grid, plan.sigma, plan.colour, float(model.min_near),
+           float(plan.colour_input_pad))
     return _occ_train.apply(enc.embeddings, model.sigma_net.weights, model.color_net.weights, o, d, model._aabb().contiguous().float(), model.density_bitfield,
                             counter, bg_ray, cfg)

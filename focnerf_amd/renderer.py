@@ -311,7 +311,7 @@ class NeRFRenderer(nn.Module):
         same noise included), with one caveat spelled out at the burst rule below — a re-derivation of t that can differ by an ulp where a
         single advance more than doubles t while fewer than half of the rays are alive."""
         from ._lib import lib, ptr, stream_of, check
-        from .field import _half_of, half_cache_scope
+        from .field import _half_of, half_cache_scope, pad_twin
         n, dev = o.shape[0], o.device
         enc, sn, cn = self.encoder, self.sigma_net, self.color_net
         L = plan.levels
@@ -348,6 +348,8 @@ class NeRFRenderer(nn.Module):
         def rule(n_alive):                                      # renderer.py:337
             return max(min(n // n_alive, 8), 1)
 
+        # a constant last column of the colour input (network_tcnn_legacy.py: column 31 = 1.0): the step's twin, the pad before the stream
+        render_step, pad_args = pad_twin("foc_occ_render_step", plan.colour_input_pad, plan.uses_object_feature)
         with half_cache_scope():
             emb, ws, wc = _half_of(enc.embeddings), _half_of(sn.weights), _half_of(cn.weights)
             st = stream_of(o)
@@ -358,13 +360,13 @@ class NeRFRenderer(nn.Module):
                 if trace:
                     print(f"[occ loop] it {it} live<= {live} burst {burst} flags {flags} marched {marched}", flush=True)
                 src, dst = lists[it & 1], lists[(it & 1) ^ 1]
-                check(lib.foc_occ_render_step(live, burst, ptr(src), ptr(dst), ptr(count), ptr(t_now), ptr(o), ptr(d), float(self.bound), float(dt_gamma),
+                check(render_step(live, burst, ptr(src), ptr(dst), ptr(count), ptr(t_now), ptr(o), ptr(d), float(self.bound), float(dt_gamma),
                                               int(max_steps), self.cascade, self.grid_size, ptr(self.density_bitfield), ptr(near), ptr(far),
                                               ptr(jitter if marched == 0 else still), ptr(samples), ptr(planes), ptr(sigma), ptr(rgb), ptr(emb),
                                               ptr(enc.offsets), None, L, plan.grid.log2_scale, plan.grid.base_resolution, ptr(ws), plan.sigma.num_layers, ptr(wc),
                                               plan.colour.num_layers, plan.sigma.activation,
                                               None, float(T_thresh), ptr(opacity), ptr(depth), ptr(image), ptr(scratch), flags, ptr(deaths), marched, n_deaths,
-                                              st), "occ_render_step")
+                                              *pad_args, st), "occ_render_step")
                 state["it"], state["marched"] = it + 1, marched + burst
 
             # ---- the wide bursts, the live count read `lag` iterations late (an upper bound: rays only die)

@@ -212,6 +212,18 @@ int foc_occ_render_step(uint32_t n_alive, uint32_t n_step, const int32_t *rays_a
                         const void *sigma_weights, uint32_t sigma_layers, const void *color_weights, uint32_t color_layers, uint32_t activation,
                         const void *obj_feat, float T_thresh, float *weights_sum, float *depth, float *image, void *scratch, uint32_t flags,
                         int32_t *deaths, uint32_t deaths_base, uint32_t deaths_len, void *stream);
+/* foc_occ_render_step with input column 31 of the 32-wide colour row [SH16 | h[1:16] | input_pad] = input_pad: the field through
+ * foc_nerf_field_inference_pad31 (the legacy tinycudann layout, focnerf_amd/network_tcnn_legacy.py, pad 1.0). obj_feat must be NULL;
+ * input_pad != 0 needs (sigma_layers, color_layers) in (1,2), (1,3), (2,2), (2,3), (3,3); both are refused before anything is enqueued.
+ * input_pad = 0: the bits of foc_occ_render_step. */
+int foc_occ_render_step_pad31(uint32_t n_alive, uint32_t n_step, const int32_t *rays_alive, int32_t *rays_alive_out, int32_t *count,
+                              float *rays_t, const float *rays_o, const float *rays_d, float bound, float dt_gamma, uint32_t max_steps,
+                              uint32_t C, uint32_t H, const uint8_t *grid, const float *nears, const float *fars, const float *noises,
+                              float *samples, void *planes, float *sigma, float *rgb,
+                              const void *embeddings, const int32_t *offsets, const int32_t *offsets_host, uint32_t L, float S, uint32_t base_res,
+                              const void *sigma_weights, uint32_t sigma_layers, const void *color_weights, uint32_t color_layers, uint32_t activation,
+                              const void *obj_feat, float T_thresh, float *weights_sum, float *depth, float *image, void *scratch, uint32_t flags,
+                              int32_t *deaths, uint32_t deaths_base, uint32_t deaths_len, float input_pad, void *stream);
 
 int foc_compact_alive(const int32_t *rays_alive, uint32_t n_alive, int32_t *out, int32_t *n_out,
                       int32_t *scratch, void *stream);
@@ -417,6 +429,15 @@ int foc_nerf_field_inference_pad(const void *enc, int enc_planar, const float *d
                                  uint32_t dir_block, uint32_t n_dirs, const void *sigma_weights, uint32_t sigma_layers, const void *color_weights,
                                  uint32_t color_layers, uint32_t hidden_dim, uint32_t activation, uint32_t B,
                                  float *sigma, float *rgb, const void *obj_feat, float input_pad, void *stream);
+/* foc_nerf_field_inference with the value of input column 31 of the 32-wide colour row [SH16 | h[1:16] | input_pad] (replaces
+ * foc_nerf_field_inference for the legacy tinycudann layout, focnerf_amd/network_tcnn_legacy.py: tcnn pads the 31-wide input with 1.0, a
+ * bias): W0[:,31] * input_pad is the initial value of the colour layer-0 accumulators. 32-wide W0 rows; obj_feat must be NULL (a 48-wide
+ * row takes its pad through foc_nerf_field_inference_pad); input_pad != 0 needs enc_planar = 1 and ReLU. input_pad = 0 gives the bits of
+ * foc_nerf_field_inference. (sigma_layers, color_layers): (1,2), (1,3), (2,2), (2,3), (3,3). */
+int foc_nerf_field_inference_pad31(const void *enc, int enc_planar, const float *dirs, uint32_t dir_div,
+                                   uint32_t dir_block, uint32_t n_dirs, const void *sigma_weights, uint32_t sigma_layers, const void *color_weights,
+                                   uint32_t color_layers, uint32_t hidden_dim, uint32_t activation, uint32_t B,
+                                   float *sigma, float *rgb, const void *obj_feat, float input_pad, void *stream);
 
 /* The colour network of a ray-ordered sample list without its materialised input (network_ff.py:104-108 builds
  * cin = [SH16(dir) | h[:,1:16] | 0] per sample, 64 B written and read twice): the kernels take the sigma network's output
@@ -452,6 +473,20 @@ int foc_color_head_backward_pad(const void *grad, const void *h, const void *ray
                                 uint32_t num_layers, uint32_t activation, void *grad_h, void *grad_weights,
                                 void *workspace, uint64_t workspace_bytes, uint32_t out_width, const void *obj_feat, float *grad_obj,
                                 float input_pad, void *stream);
+/* foc_color_head_forward / _backward with input column 31 of the 32-wide row = input_pad (replace them for the legacy tinycudann layout,
+ * as foc_nerf_field_inference_pad31): cin = [SH16 | h[:,1:16] | input_pad], 32-wide W0 rows; obj_feat must be NULL (grad_obj is not
+ * written). Forward: W0[:,31] * input_pad is the initial value of the layer-0 accumulators (the object feature's slot). Backward: column 31
+ * of the layer-0 input tile holds input_pad, so grad_weights[:,31] = sum_b delta_0[b,:] * input_pad — the products of the materialised
+ * input; grad_h does not change. Same values as foc_ffmlp_forward / _backward on that cin up to fp32 summation order; input_pad = 0
+ * gives the bits of the entry points above. num_layers 2 or 3. */
+int foc_color_head_forward_pad31(const void *h, const void *ray_sh, uint32_t samples_per_ray, const void *weights,
+                                 uint32_t B, uint32_t hidden_dim, uint32_t num_layers, uint32_t activation,
+                                 void *outputs, uint32_t out_width, const void *obj_feat, float input_pad, void *stream);
+int foc_color_head_backward_pad31(const void *grad, const void *h, const void *ray_sh, uint32_t samples_per_ray,
+                                  const void *grad_h0, const void *weights, uint32_t B, uint32_t hidden_dim,
+                                  uint32_t num_layers, uint32_t activation, void *grad_h, void *grad_weights,
+                                  void *workspace, uint64_t workspace_bytes, uint32_t out_width, const void *obj_feat, float *grad_obj,
+                                  float input_pad, void *stream);
 
 /* The TRAINING forward of the whole field in ONE kernel (csrc/field_fwd.hip): foc_ffmlp_forward_planar on the encoder's planes ->
  * h [B,16] fp16 (written: the compositing tail and the backward read it) -> foc_color_head_forward fed from h and ray_sh, back to back in
@@ -468,6 +503,12 @@ int foc_field_forward_train(const void *planes, const void *sigma_weights, uint3
 int foc_field_forward_train_pad(const void *planes, const void *sigma_weights, uint32_t sigma_layers, const void *ray_sh, uint32_t samples_per_ray,
                                 const void *color_weights, uint32_t color_layers, uint32_t hidden_dim, uint32_t activation, uint32_t B,
                                 void *h, void *c, uint32_t out_width, const void *obj_feat, float input_pad, void *stream);
+/* foc_field_forward_train with input column 31 of the 32-wide colour row = input_pad (replaces it for the legacy tinycudann layout; the
+ * bits of foc_ffmlp_forward_planar + foc_color_head_forward_pad31). obj_feat must be NULL. input_pad = 0: the bits of
+ * foc_field_forward_train. Layer pairs as there. */
+int foc_field_forward_train_pad31(const void *planes, const void *sigma_weights, uint32_t sigma_layers, const void *ray_sh, uint32_t samples_per_ray,
+                                  const void *color_weights, uint32_t color_layers, uint32_t hidden_dim, uint32_t activation, uint32_t B,
+                                  void *h, void *c, uint32_t out_width, const void *obj_feat, float input_pad, void *stream);
 
 /* ffmlp.cu:721-740  allocate_splitk(size) / free_splitk(): the reference creates side
  * streams for its CUTLASS split-K GEMMs. Weight gradients here are produced inside the
@@ -639,6 +680,13 @@ typedef struct FocOccTrainNode {
 } FocOccTrainNode;
 int foc_occ_train_forward(const FocOccTrainNode *node, void *stream);
 int foc_occ_train_backward(const FocOccTrainNode *node, void *stream);
+/* The node with input column 31 of the 32-wide colour row = input_pad (the legacy tinycudann layout, focnerf_amd/network_tcnn_legacy.py):
+ * the same sequence through foc_field_forward_train_pad31 / foc_color_head_forward_pad31 / foc_color_head_backward_pad31; the one-kernel
+ * forward of both networks also serves (sigma_layers, color_layers) = (1,2), (1,3). The node's layout is FocOccTrainNode's; input_pad
+ * travels beside it, and the backward must get the forward's value. input_pad != 0 needs (1,2), (1,3), (2,2), (2,3) or (3,3), refused
+ * before anything is enqueued. input_pad = 0: the bits of the two entry points above. */
+int foc_occ_train_forward_pad31(const FocOccTrainNode *node, float input_pad, void *stream);
+int foc_occ_train_backward_pad31(const FocOccTrainNode *node, float input_pad, void *stream);
 
 /* Extension (no reference binding; focnerf_amd/rayorder.py): perm [N] int64 = the order in which a staged render walks a view's rays —
  * tile_h x tile_w pixel tiles when rays_d [N,3] fp32 is a row-major H x W pixel grid (recognised from the directions: W >= 16, H >= 8),
