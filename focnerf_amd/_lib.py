@@ -168,6 +168,9 @@ SIGNATURES = {
     "foc_grid_update_sample": (i32, [c_vp, u32, u32, f32, u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, u64, c_vp]),
     "foc_grid_update_apply_workspace_bytes": (u64, [u32, u32]),
     "foc_grid_update_apply": (i32, [c_vp, u32, u32, c_vp, c_vp, u32, f32, f32, f32, c_vp, c_vp, c_vp, u64, c_vp]),
+    "foc_background_forward": (i32, [c_vp, c_vp, c_vp, f32, u32, c_vp, c_vp, f32, u32, c_vp, c_vp, c_vp]),
+    "foc_background_backward_workspace_bytes": (u64, [u32]),
+    "foc_background_backward": (i32, [c_vp, c_vp, c_vp, c_vp, f32, u32, c_vp, c_vp, f32, u32, c_vp, c_vp, c_vp, c_vp, u64, c_vp]),
 }
 
 

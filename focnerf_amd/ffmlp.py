@@ -132,3 +132,46 @@ class FFMLP(nn.Module):
     def forward(self, inputs):
         y = self.forward_padded(inputs)
         return y if self.padded_output_dim == self.output_dim else y[:, :self.output_dim]
+
+
+class PackedMLP:
+    """An FFMLP-shaped view of a stack of bias-free `nn.Linear` layers with ReLU between them (network_linear.py): the attributes the
+    fused kernels' callers read (field.MlpShape, `training`, `forward_padded`), and `weights` = the FFMLP blob packed from the layers'
+    weights — [hidden x input_dim] with zero columns past the layer's own input | hidden layers | [16 x hidden] with zero rows past its
+    outputs. The blob is built on every read with torch ops that autograd follows, so its gradient comes back as each layer's gradient
+    and the padding entries are dropped. Inside a `field.half_cache_scope` one packing serves the scope; nothing is kept across scopes
+    (torch_ema writes the parameters through `.data`). Not a module: the layers stay where the reference has them."""
+
+    def __init__(self, layers, input_dim):
+        self.layers = layers
+        self.in_features = layers[0].in_features
+        self.input_dim = input_dim                         # the kernels' width: a multiple of 16
+        self.hidden_dim = layers[0].out_features
+        self.num_layers = len(layers) - 1                  # FFMLP's count: matrices - 1
+        self.output_dim = layers[-1].out_features
+        self.padded_output_dim = -(-self.output_dim // 16) * 16
+        self.activation, self.output_activation = ACTIVATIONS['relu'], NO_ACTIVATION
+        self.num_parameters = self.hidden_dim * (input_dim + self.hidden_dim * (self.num_layers - 1) + self.padded_output_dim)
+
+    @property
+    def training(self):
+        return self.layers.training
+
+    def _pack(self):
+        w = [layer.weight for layer in self.layers]
+        first = nn.functional.pad(w[0], (0, self.input_dim - self.in_features))
+        last = nn.functional.pad(w[-1], (0, 0, 0, self.padded_output_dim - self.output_dim))
+        return torch.cat([first.reshape(-1)] + [m.reshape(-1) for m in w[1:-1]] + [last.reshape(-1)])
+
+    @property
+    def weights(self):
+        from .field import scope_cached
+        return scope_cached(("packed_mlp", id(self.layers)), self.layers, self._pack)
+
+    def forward_padded(self, inputs):
+        """inputs [B, input_dim] (the padding columns zero) -> the kernel's [B, 16] result, as FFMLP.forward_padded."""
+        return ffmlp_forward(inputs, self.weights, self.input_dim, self.padded_output_dim, self.hidden_dim, self.num_layers, self.activation,
+                             self.output_activation, not self.training, inputs.requires_grad)
+
+    def __call__(self, inputs):
+        return self.forward_padded(inputs)[:, :self.output_dim]

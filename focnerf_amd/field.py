@@ -22,8 +22,16 @@ from torch.autograd import Function
 from torch.amp import custom_bwd, custom_fwd
 
 from .backend import _gridencoder, _ffmlp
-from .ffmlp import FFMLP, single_pass_backward
+from .ffmlp import FFMLP, PackedMLP, single_pass_backward
 from .gridencoder import GridEncoder, GridSpec
+
+
+def fused_mlp(model, name):
+    """What the fused kernels read as `model.<name>` ('sigma_net', 'color_net', 'bg_net'): the FFMLP itself, or — for a network whose
+    layers are bias-free nn.Linear modules (network_linear.py, `model.fused_mlp`) — its ffmlp.PackedMLP, whose `weights` is the packed
+    blob. None when the model has no such network."""
+    get = getattr(model, "fused_mlp", None)
+    return get(name) if get is not None else getattr(model, name, None)
 
 
 @dataclass(frozen=True)
@@ -38,7 +46,7 @@ class MlpShape:
 
     @staticmethod
     def of(mlp):
-        if not isinstance(mlp, FFMLP):
+        if not isinstance(mlp, (FFMLP, PackedMLP)):
             return None
         return MlpShape(mlp.input_dim, mlp.hidden_dim, mlp.num_layers, mlp.activation, mlp.output_activation, mlp.padded_output_dim)
 
@@ -64,6 +72,7 @@ class FieldPlan:
     head: bool                          # the glue between the two networks as kernels (head.sample_head / rgb_head)
     colour_input_pad: float = 0.0       # the colour input's last column: 47 of the 48-wide object-conditioned row (1.0: tinycudann layout,
                                         # network_tcnn.py), 31 of the 32-wide row (1.0: legacy tinycudann layout, network_tcnn_legacy.py)
+    background: bool = False            # the background model (encoder_bg -> bg_net) as one kernel each way (background.py, csrc/background.hip)
 
 
 def pad_twin(name, pad, obj):
@@ -86,7 +95,7 @@ def field_plan(model):
     from ._lib import get_option
     from .shencoder import SHEncoder
     enc, enc_dir = getattr(model, "encoder", None), getattr(model, "encoder_dir", None)
-    sigma, colour = MlpShape.of(getattr(model, "sigma_net", None)), MlpShape.of(getattr(model, "color_net", None))
+    sigma, colour = MlpShape.of(fused_mlp(model, "sigma_net")), MlpShape.of(fused_mlp(model, "color_net"))
     obj = bool(getattr(model, "uses_object_feature", False))
     pad = float(getattr(model, "colour_input_pad", 0.0))     # the *_pad / *_pad31 kernels take it; sample_head writes a zero there
     grid = enc.spec() if isinstance(enc, GridEncoder) else None
@@ -112,13 +121,22 @@ def field_plan(model):
     field = hash_grid and sigma_one_pass and sigma_16 and _on("FOC_FUSED_FIELD")
     tail = colour_64 and colour.num_layers in (2, 3) and colour_relu_or_none and colour_rows and _on("FOC_FUSED_TAIL")
     infer = field and whole_field and (not obj or sigma.activation == 0) and _on("FOC_FUSED_INFER")
+    # the background model csrc/background.hip computes: a plain 4-level hash grid over D 2 with C 2, then [SH16(d) | grid 8 | 0] -> 64 ->
+    # ReLU -> 3 without biases (legacy/nerf/network.py:71-92, 145-160)
+    enc_bg, bg_mlp = getattr(model, "encoder_bg", None), fused_mlp(model, "bg_net")
+    bg_grid = enc_bg.spec() if isinstance(enc_bg, GridEncoder) else None
+    background = (bg_grid is not None and enc_bg.input_dim == 2 and enc_bg.level_dim == 2 and enc_bg.offsets.numel() == 5
+                  and bg_grid.gridtype == 0 and not bg_grid.align_corners and bg_grid.interpolation == 0
+                  and isinstance(bg_mlp, PackedMLP) and bg_mlp.in_features == 24 and MlpShape.of(bg_mlp) == MlpShape(32, 64, 1, 0, 6, 16)
+                  and bg_mlp.output_dim == 3 and isinstance(enc_dir, SHEncoder) and enc_dir.degree == 4 and _on("FOC_FUSED_BG"))
     return FieldPlan(
         grid=grid, levels=enc.offsets.numel() - 1 if grid is not None else 0, sigma=sigma, colour=colour, uses_object_feature=obj,
         field=field, tail=tail, infer=infer,
         train_forward=(field and tail and whole_field and sigma.output_activation == 6 and get_option("FOC_FIELD_FWD_FUSED") != 0),
-        occ=field and tail and not obj and getattr(model, "bg_radius", 0) <= 0 and same_activation and _on("FOC_FUSED_OCC"),
+        occ=field and tail and not obj and (getattr(model, "bg_radius", 0) <= 0 or background) and same_activation and _on("FOC_FUSED_OCC"),
         native_loop=(infer and not obj and getattr(model, "density_scale", 1) == 1 and plain_grid and _on("FOC_RENDER_NATIVE")),
-        head=both and colour.input_dim == colour_in and colour_rows and pad == 0 and _on("FOC_FUSED_HEAD"), colour_input_pad=pad)
+        head=both and colour.input_dim == colour_in and colour_rows and pad == 0 and _on("FOC_FUSED_HEAD"), colour_input_pad=pad,
+        background=background)
 
 
 def _raw_stream_of(device):
@@ -284,7 +302,7 @@ def field_infer(model, xn, dirs, dir_div=1, dir_block=0, obj_feat=None):
     dir_block = 64: the rows stand in the block-interleaved order of `fixedstep.fixed_sample(..., ray_block=64)`.
     obj_feat [16]: the encoded object feature of an object-conditioned network (required iff `model.uses_object_feature`)."""
     from ._lib import ptr, stream_of, check
-    enc, sn, cn = model.encoder, model.sigma_net, model.color_net
+    enc, sn, cn = model.encoder, fused_mlp(model, "sigma_net"), fused_mlp(model, "color_net")
     grid = enc.spec()
     xn = xn.contiguous().float()
     dirs = dirs.contiguous().float()

@@ -106,24 +106,30 @@ class _density_head(Function):
 
 
 class _fixed_composite(Function):
-    """c [M,16] half (colour-net output), weights [M] -> image [N,3] = sum w*sigmoid(c)*[w>thresh] + (1 - sum w)*bg."""
+    """c [M,16] half (colour-net output), weights [M] -> image [N,3] = sum w*sigmoid(c)*[w>thresh] + (1 - sum w)*bg.
+    A per-ray bg_ray that needs a gradient (a learned background, network_linear.py) gets g_image * (1 - weights_sum): `weights_sum` [N]
+    is then required."""
 
     @staticmethod
-    def forward(ctx, c, weights, bg_ray, bg_scalar, N, T, thresh):
+    def forward(ctx, c, weights, bg_ray, bg_scalar, N, T, thresh, weights_sum=None):
         c = c.contiguous()
         weights = weights.contiguous()
         assert c.dtype == torch.float16 and c.shape == (N * T, 16) and weights.dtype == torch.float32
         image = torch.empty(N, 3, dtype=torch.float32, device=c.device)
         check(lib.foc_fixed_composite_forward(ptr(c), ptr(weights), ptr(bg_ray), float(bg_scalar), N, T, float(thresh), ptr(image), stream_of(c)),
               "fixed_composite_forward")
-        ctx.save_for_backward(c, weights, bg_ray if bg_ray is not None else torch.empty(0, device=c.device))
+        ctx.bg_grad = bg_ray is not None and ctx.needs_input_grad[2]
+        if ctx.bg_grad and weights_sum is None:
+            raise RuntimeError("_fixed_composite: a background that needs a gradient needs weights_sum")
+        empty = torch.empty(0, device=c.device)
+        ctx.save_for_backward(c, weights, bg_ray if bg_ray is not None else empty, weights_sum.detach() if ctx.bg_grad else empty)
         ctx.has_bg = bg_ray is not None
         ctx.dims = (N, T, float(thresh), float(bg_scalar))
         return image
 
     @staticmethod
     def backward(ctx, g_image):
-        c, weights, bg_ray = ctx.saved_tensors
+        c, weights, bg_ray, weights_sum = ctx.saved_tensors
         N, T, thresh, bg_scalar = ctx.dims
         bg_ray = bg_ray if ctx.has_bg else None
         g_image = g_image.contiguous().float()
@@ -131,7 +137,8 @@ class _fixed_composite(Function):
         grad_w = torch.empty_like(weights)
         check(lib.foc_fixed_composite_backward(ptr(g_image), ptr(c), ptr(weights), ptr(bg_ray), bg_scalar, N, T, thresh, ptr(grad_c), ptr(grad_w),
                                                stream_of(c)), "fixed_composite_backward")
-        return grad_c, grad_w, None, None, None, None, None
+        g_bg = g_image * (1 - weights_sum).unsqueeze(-1) if ctx.bg_grad else None
+        return grad_c, grad_w, g_bg, None, None, None, None, None
 
 
 _C_WIDTH = 4        # columns of the colour network's output that exist in memory on the fused tail (rgb logits + one pad)
@@ -190,8 +197,9 @@ class _render_tail(Function):
                                          float(thresh), ptr(sigma), ptr(trans), ptr(weights), ptr(ws), ptr(depth), ptr(image), _C_WIDTH, ptr(sumsq), st),
               "fixed_tail_forward")
         empty = torch.empty(0, device=dev)
+        ctx.bg_grad = bg_ray is not None and ctx.needs_input_grad[6]         # a learned background (network_linear.py): g_image * (1 - ws)
         ctx.save_for_backward(h, w16, sigma, trans, weights, c, ray_sh, nears, fars, noise if noise is not None else empty,
-                              bg_ray if bg_ray is not None else empty, obj16 if obj16 is not None else empty)
+                              bg_ray if bg_ray is not None else empty, obj16 if obj16 is not None else empty, ws if ctx.bg_grad else empty)
         ctx.flags = (noise is not None, bg_ray is not None, obj16 is not None, obj_feat.dtype if obj_feat is not None else None,
                      tuple(obj_feat.shape) if obj_feat is not None else None)
         ctx.dims = (N, T, float(density_scale), float(thresh), float(bg_scalar), int(num_layers), int(activation), float(input_pad))
@@ -205,7 +213,7 @@ class _render_tail(Function):
     def backward(ctx, g_image, g_ws, g_depth, _g_sigma, _g_weights, _g_c, g_sumsq=None):
         from .backend import _scratch
         from .field import pad_twin
-        h, w16, sigma, trans, weights, c, ray_sh, nears, fars, noise, bg_ray, obj16 = ctx.saved_tensors
+        h, w16, sigma, trans, weights, c, ray_sh, nears, fars, noise, bg_ray, obj16, ws = ctx.saved_tensors
         has_noise, has_bg, has_obj, obj_dtype, obj_shape = ctx.flags
         obj16 = obj16 if has_obj else None
         N, T, ds, thresh, bg_scalar, num_layers, activation, input_pad = ctx.dims
@@ -231,7 +239,8 @@ class _render_tail(Function):
         fn, extra = pad_twin("foc_color_head_backward", input_pad, has_obj)
         check(fn(*args, *extra, st), "color_head_backward")
         g_obj = g_obj32.to(obj_dtype).view(obj_shape) if g_obj32 is not None else None
-        return (grad_h, g_w) + (None,) * 12 + (g_obj, None, None, None, None)
+        g_bg = g_image * (1 - ws).unsqueeze(-1) if ctx.bg_grad else None
+        return (grad_h, g_w, None, None, None, None, g_bg) + (None,) * 7 + (g_obj, None, None, None, None)
 
 
 class _masked_norm(Function):
@@ -280,6 +289,9 @@ def render_fixed_steps(model, rays_o, rays_d, yolo_details=None, num_steps=512, 
     noise = torch.rand(N * T, dtype=torch.float32, device=dev) if perturb else None
     from .field import field_plan, field_infer
     plan = field_plan(model)
+    if getattr(model, "bg_radius", 0) > 0:
+        # the background model replaces bg_color (legacy/nerf/renderer.py:232-234); a learned one gets its gradient from the nodes below
+        bg_color = model._background_colour(rays_o, rays_d, bg_color)
     want_tail = plan.tail and model.training and torch.is_grad_enabled()
     fused_infer = not torch.is_grad_enabled() and plan.infer
     rb = ray_block_default() if fused_infer else 0
@@ -319,8 +331,10 @@ def render_fixed_steps(model, rays_o, rays_d, yolo_details=None, num_steps=512, 
         return results
 
     enc = model.encoder
-    from .field import hashgrid_mlp
+    from .field import hashgrid_mlp, fused_mlp
     c_pre = obj_feat = None
+    # the colour weight blob, read once per step (a packed blob, network_linear.py, is built on each read)
+    cweights = fused_mlp(model, "color_net").weights if want_tail else None
     with torch.autocast("cuda", dtype=torch.float16):
         if plan.uses_object_feature:                                      # FOC network (network_foc.py): encoded YOLO feature in the colour input
             obj_feat = model.encode_object_feature(yolo_details, dev)
@@ -329,15 +343,15 @@ def render_fixed_steps(model, rays_o, rays_d, yolo_details=None, num_steps=512, 
             colour = wc16 = None
             if want_tail and plan.train_forward:
                 from .field import _half_of
-                wc16 = _half_of(model.color_net.weights)                  # ONE half copy per step for both nodes that read the colour weights
+                wc16 = _half_of(cweights)                                 # ONE half copy per step for both nodes that read the colour weights
                 colour = (wc16, plan.colour, ray_sh, T, _C_WIDTH, obj_feat, plan.colour_input_pad)
-            h = hashgrid_mlp(enc, model.sigma_net, enc_in, None, colour)
+            h = hashgrid_mlp(enc, fused_mlp(model, "sigma_net"), enc_in, None, colour)
             if colour is not None:
                 h, c_pre = h
         else:
             feats = grid_encode(enc_in, enc.embeddings, enc.offsets, enc.per_level_scale, enc.base_resolution, False, enc.gridtype_id,
                                 enc.align_corners, enc.interp_id)
-            h = model.sigma_net(feats)                                    # [M,16] half
+            h = fused_mlp(model, "sigma_net")(feats)                      # [M,16] half
         if h.shape[1] != 16:                                              # FFMLP slices to output_dim (= 16 here: 1 + geo_feat_dim 15)
             raise RuntimeError("render_fixed_steps expects a 16-wide sigma head (1 + geo_feat_dim = 16)")
         fused_tail = want_tail
@@ -345,9 +359,9 @@ def render_fixed_steps(model, rays_o, rays_d, yolo_details=None, num_steps=512, 
         want_crit = model.training and yolo_details is not None and yolo_details[0] is not None
         criterion_outside_mask = None
         if fused_tail:
-            cn = model.color_net
+            cn = fused_mlp(model, "color_net")
             bg_ray, bg_scalar = _background(bg_color, N, dev)
-            outs = _render_tail.apply(h, cn.weights, ray_sh, nears, fars, noise, bg_ray, bg_scalar, N, T, model.density_scale, weight_thresh,
+            outs = _render_tail.apply(h, cweights, ray_sh, nears, fars, noise, bg_ray, bg_scalar, N, T, model.density_scale, weight_thresh,
                                       cn.num_layers, cn.activation, obj_feat, want_crit and yolo_details[0].numel() == N, c_pre,
                                       wc16 if c_pre is not None else None, plan.colour_input_pad)
             image, weights_sum, depth, sigma, weights, c = outs[:6]
@@ -364,12 +378,12 @@ def render_fixed_steps(model, rays_o, rays_d, yolo_details=None, num_steps=512, 
             from .activation import trunc_exp
             criterion_outside_mask = torch.norm(trunc_exp(h[:, 0]).view(N, T)[~yolo_details[0].squeeze(0)] - 0)
         if not fused_tail:
-            c = model.color_net.forward_padded(cin)                        # [M,16] half, columns 0..2 = rgb logits
+            c = fused_mlp(model, "color_net").forward_padded(cin)          # [M,16] half, columns 0..2 = rgb logits
     t_mid = time.time()
 
     if not fused_tail:
         bg_ray, bg_scalar = _background(bg_color, N, dev)
-        image = _fixed_composite.apply(c, weights, bg_ray, bg_scalar, N, T, weight_thresh)
+        image = _fixed_composite.apply(c, weights, bg_ray, bg_scalar, N, T, weight_thresh, weights_sum)
 
     results = {'depth': depth.view(*prefix), 'image': image.view(*prefix, 3), 'weights_sum': weights_sum,
                'criterion_outside_mask': criterion_outside_mask, 'timing': [t_mid - t_start, time.time() - t_mid]}

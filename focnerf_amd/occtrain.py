@@ -126,6 +126,7 @@ class _occ_train(Function):
             ctx.ticket = _gridencoder.issue_precount_ticket(enc_in, M, L, FOC_F16, gws)
             ctx.save_for_backward(enc_in, emb16, ws16, wc16, offsets, planes, h, c, sh, deltas, rays, counter, ws, image_raw,
                                   bg_ray if bg_ray is not None else torch.empty(0, device=dev))
+            ctx.bg_grad = bg_ray is not None and ctx.needs_input_grad[8]
             ctx.nears_fars = nf
             ctx.cfg = (M, n, float(T_thresh), float(density_scale), float(bg_scalar), bg_ray is not None, grid, sigma, colour, pad)
             ctx.node, ctx.plan = nd, plan
@@ -159,6 +160,7 @@ class _occ_train(Function):
                                        ptr(nears), ptr(fars), ptr(ws), ptr(image_raw), ptr(image), ptr(depth), st), "occ_tail_forward")
         ctx.save_for_backward(enc_in, emb16, ws16, wc16, offsets, planes, h, c, sh, deltas, rays, counter, ws, image_raw,
                               bg_ray if bg_ray is not None else torch.empty(0, device=dev))
+        ctx.bg_grad = bg_ray is not None and ctx.needs_input_grad[8]
         ctx.nears_fars = nf
         ctx.cfg = (M, n, float(T_thresh), float(density_scale), float(bg_scalar), bg_ray is not None, grid, sigma, colour, pad)
         ctx.ticket = ticket
@@ -178,9 +180,12 @@ class _occ_train(Function):
         g_emb = torch.zeros_like(emb16)
         g_wsig, g_wcol = torch.empty_like(ws16), torch.empty_like(wc16)
         if M == 0 or (g_image is None and g_ws is None):
-            return g_emb, g_wsig.zero_(), g_wcol.zero_(), None, None, None, None, None, None, None, None
+            g_bg = g_image * (1 - ws).unsqueeze(-1) if ctx.bg_grad and g_image is not None else None
+            return g_emb, g_wsig.zero_(), g_wcol.zero_(), None, None, None, None, None, g_bg, None
         g_image = g_image.contiguous().float() if g_image is not None else torch.zeros(n, 3, dtype=torch.float32, device=dev)
         g_ws = g_ws.contiguous().float() if g_ws is not None else None
+        # a learned background (network_linear.py): image = raw + (1 - ws) bg
+        g_bg = g_image * (1 - ws).unsqueeze(-1) if ctx.bg_grad else None
         nd = getattr(ctx, "node", None)
         if nd is not None:                                  # the whole backward as one library call (foc_occ_train_backward)
             gws = _scratch.get("grid_bwd", ctx.plan[0], dev)
@@ -199,7 +204,7 @@ class _occ_train(Function):
                 check(lib.foc_occ_train_backward(ctypes.byref(nd), st), "occ_train_backward")
             _gridencoder._invalidate_precount(dev)          # the header now belongs to this pass (and a used ticket is spent)
             ctx.node = None
-            return g_emb, g_wsig, g_wcol, None, None, None, None, None, None, None, None
+            return g_emb, g_wsig, g_wcol, None, None, None, None, None, g_bg, None
         gblock = torch.empty(M * (_C_WIDTH + 1), dtype=torch.float16, device=dev)      # grad_c [M,4] | grad_h0 [M]: every row written by the kernel
         grad_c, grad_h0 = gblock[: M * _C_WIDTH].view(M, _C_WIDTH), gblock[M * _C_WIDTH:]
         check(lib.foc_occ_tail_backward(ptr(g_image), ptr(g_ws), ptr(h), ptr(c), _C_WIDTH, ptr(deltas), ptr(rays), ptr(counter), ptr(ws), ptr(image_raw), M, n,
@@ -214,7 +219,7 @@ class _occ_train(Function):
                                      g_planes, g_wsig)
         _gridencoder.grid_encode_backward(g_planes, enc_in, emb16, offsets, g_emb, M, 3, 2, L, S, H, None, None, gridtype, align_corners, interp, grad_bl=False,
                                           precount=ctx.ticket)
-        return g_emb, g_wsig, g_wcol, None, None, None, None, None, None, None, None
+        return g_emb, g_wsig, g_wcol, None, None, None, None, None, g_bg, None
 
 
 def render_occupancy_train(model, plan, o, d, counter, bg_color, perturb, force_all_rays, dt_gamma, max_steps, T_thresh, align):
@@ -228,5 +233,6 @@ def render_occupancy_train(model, plan, o, d, counter, bg_color, perturb, force_
     cfg = (float(model.bound), int(model.cascade), int(model.grid_size), int(model.mean_count), bool(perturb), int(align), bool(force_all_rays), float(dt_gamma),
            int(max_steps), float(T_thresh), float(model.density_scale), float(bg_scalar), enc.offsets, plan.grid, plan.sigma, plan.colour, float(model.min_near),
            float(plan.colour_input_pad))
-    return _occ_train.apply(enc.embeddings, model.sigma_net.weights, model.color_net.weights, o, d, model._aabb().contiguous().float(), model.density_bitfield,
+    from .field import fused_mlp
+    return _occ_train.apply(enc.embeddings, fused_mlp(model, "sigma_net").weights, fused_mlp(model, "color_net").weights, o, d, model._aabb().contiguous().float(), model.density_bitfield,
                             counter, bg_ray, cfg)

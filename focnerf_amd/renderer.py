@@ -224,6 +224,8 @@ class NeRFRenderer(nn.Module):
                 slot = self.step_counter[self.local_step % 16]
                 slot.zero_()
                 self.local_step += 1
+                if self.bg_radius > 0:                            # the background model (plan.occ: network_linear.py, plan.background)
+                    bg_color = self._background_colour(o, d, bg_color)
                 image, opacity, depth = render_occupancy_train(self, plan, o.float(), d.float(), slot, bg_color, perturb, force_all_rays, dt_gamma, max_steps, T_thresh,
                                                                _MARCH_ALIGN)
                 out['weights_sum'] = opacity
@@ -311,9 +313,9 @@ class NeRFRenderer(nn.Module):
         same noise included), with one caveat spelled out at the burst rule below — a re-derivation of t that can differ by an ulp where a
         single advance more than doubles t while fewer than half of the rays are alive."""
         from ._lib import lib, ptr, stream_of, check
-        from .field import _half_of, half_cache_scope, pad_twin
+        from .field import _half_of, half_cache_scope, pad_twin, fused_mlp
         n, dev = o.shape[0], o.device
-        enc, sn, cn = self.encoder, self.sigma_net, self.color_net
+        enc, sn, cn = self.encoder, fused_mlp(self, "sigma_net"), fused_mlp(self, "color_net")
         L = plan.levels
         lag = max(1, int(os.environ.get("FOC_RENDER_COUNT_LAG", "2")))
         # Samples per ray and iteration. The reference sizes a burst so that live x burst stays within the view's ray count (max(min(n // live,

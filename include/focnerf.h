@@ -777,6 +777,30 @@ int foc_grid_update_apply(float *density_grid, uint32_t cascade, uint32_t H, con
                           uint32_t Mc, float density_scale, float decay, float density_thresh, uint8_t *bitfield,
                           float *mean_out, void *workspace, uint64_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Background model of torch-ngp's default network (focnerf_amd/network_linear.py, csrc/background.hip): per ray
+ *     rgb = sigmoid(W1 . relu(W0 . [SH16(d) | grid8((sph_from_ray(o, d, radius) + 1) / 2)]))
+ * replacing the op chain of legacy/nerf/network.py:145-160 (NeRFNetwork.background) with sph_from_ray in front of it
+ * (legacy/nerf/renderer.py:232-234, 271-274), fp16 autocast semantics.
+ * coords [N,2] fp32 in [-1,1] (the sphere coordinates), or NULL: then they are computed from rays_o [N,3] with `radius` (> 0);
+ * rays_d [N,3] fp32. embeddings [rows,2] fp32: a 4-level hash grid over D = 2 (offsets int32 [5] on the device, per-level scale
+ * log2 and base resolution as foc_grid_encode_forward takes them; linear interpolation, align_corners off), read as fp16.
+ * weights fp16: the FFMLP blob of the 32 -> 64 -> 16 network, W0 [64,32] (columns 24..31 zero) | W1 [16,64] (rows 3..15 zero).
+ * rgb [N,3] fp16.
+ * ------------------------------------------------------------------------- */
+int foc_background_forward(const float *rays_o, const float *rays_d, const float *coords, float radius, uint32_t N, const float *embeddings,
+                           const int32_t *offsets, float per_level_scale_log2, uint32_t base_resolution, const void *weights, void *rgb,
+                           void *stream);
+/* grad_rgb [N,3] fp16 -> grad_embeddings [rows,2] fp32 (ADDED to: the caller zero-fills; fp32 atomics, so a row's sum depends on the
+ * order of arrival) and grad_weights fp32 [64*32 + 16*64] (written whole; padding entries 0; a fixed-order reduction: the same bits on
+ * every run). workspace: foc_background_backward_workspace_bytes(N) bytes, no zero fill; `workspace_bytes` = its size, a smaller
+ * buffer is refused. The rays take no gradient. */
+uint64_t foc_background_backward_workspace_bytes(uint32_t N);
+int foc_background_backward(const void *grad_rgb, const float *rays_o, const float *rays_d, const float *coords, float radius, uint32_t N,
+                            const float *embeddings, const int32_t *offsets, float per_level_scale_log2, uint32_t base_resolution,
+                            const void *weights, float *grad_embeddings, float *grad_weights, void *workspace, uint64_t workspace_bytes,
+                            void *stream);
+
 #ifdef __cplusplus
 }
 #endif
