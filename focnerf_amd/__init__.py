@@ -3,6 +3,7 @@ raymarching, gridencoder, freqencoder, ffmlp (+ the multi-object combine), behin
 reference's Python operator API. The compute lives in libfocnerf_hip.so (C ABI in
 include/focnerf.h); importing this package fails loudly if that library is missing."""
 from . import _lib  # noqa: F401  (raises ImportError when libfocnerf_hip.so is absent)
+from .determinism import use_deterministic, is_deterministic, deterministic  # noqa: F401  (FOC_DETERMINISTIC: bit-reproducible training steps)
 
 __all__ = ["raymarching", "gridencoder", "freqencoder", "ffmlp", "activation", "encoding", "shencoder",
-           "renderer", "network", "combine"]
+           "renderer", "network", "combine", "use_deterministic", "is_deterministic", "deterministic"]

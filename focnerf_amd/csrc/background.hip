@@ -19,7 +19,9 @@
 // Backward (rays carry no gradient, so there is no input gradient): the forward is recomputed per ray, then
 //   * the table gradient: per ray 4 levels x 4 corners x 2 channels, w * g added with fp32 atomics into the fp32 gradient — each table
 //     row's sum depends on the order in which rays arrive (rows shared by several rays: every row of the dense levels 0-2, hash
-//     collisions on level 3); nothing else does;
+//     collisions on level 3); nothing else does. FOC_DETERMINISTIC: the addends go, as 2^-40-scaled 64-bit integers, into a hash table
+//     keyed by table row that lives in the workspace (BgDetEntry; integer atomics: which entry a row claims depends on arrival, its
+//     sums do not), and k_bg_det_finish adds each row's total to the gradient once;
 //   * dW0 (64 x 24 used entries) and dW1 (3 x 64): each workgroup (one wave) stages 64 rays' inputs, activations and output gradients
 //     in LDS and sums every weight's products over its rays in ray order, chunk after chunk; k_bg_dw_reduce adds the workgroups'
 //     partials in workgroup order. The assignment of rays to workgroups depends only on N: the same bits on every run.
@@ -181,11 +183,48 @@ __global__ void __launch_bounds__(256) k_bg_forward(const float *__restrict__ ra
     }
 }
 
+// FOC_DETERMINISTIC: one entry per touched table row, open addressing with linear probing in a zeroed table of 2^k >= 32 N entries (a ray
+// touches at most 16 rows: the table is at most half full, a probe always ends). |w g| < 2^16 (g a half, w <= 1), so an addend is below
+// 2^56 and is exact from 2^-16 up; smaller ones are rounded to 2^-40. The sums wrap at 2^23, far above what a half gradient can carry.
+struct BgDetEntry { uint32_t key, bad; unsigned long long sum[2]; };      // key = row + 1 (0: free); bad bit c: channel c got an inf / NaN addend
+static_assert(sizeof(BgDetEntry) == 24, "bg_det_table_bytes");
+__device__ __forceinline__ void bg_det_add(BgDetEntry *__restrict__ tab, uint32_t mask, uint32_t row, float v0, float v1) {
+    const uint32_t key = row + 1u;
+    uint32_t h = (row * 2654435761u) & mask;
+    bool mine = false;
+    for (uint32_t probe = 0; probe <= mask && !mine; probe++) {
+        const uint32_t prev = atomicCAS(&tab[h].key, 0u, key);
+        mine = prev == 0u || prev == key;
+        if (!mine) h = (h + 1u) & mask;
+    }
+    if (!mine) return;                                      // cannot happen: the table has more entries than the launch has rows
+    const float v[2] = {v0, v1};
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+        if (v[c] == 0.0f) continue;
+        if (!(fabsf(v[c]) < 8388608.0f)) { (void)__hip_atomic_fetch_or(&tab[h].bad, 1u << c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); continue; }
+        const long long q = __double2ll_rn((double)v[c] * 1099511627776.0);
+        (void)__hip_atomic_fetch_add(&tab[h].sum[c], (unsigned long long)q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+__global__ void __launch_bounds__(256) k_bg_det_finish(const BgDetEntry *__restrict__ tab, uint32_t entries, float *__restrict__ grad_emb) {
+    for (uint32_t e = blockIdx.x * 256 + threadIdx.x; e < entries; e += gridDim.x * 256) {
+        const BgDetEntry t = tab[e];
+        if (!t.key) continue;
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+            const float a = (t.bad >> c) & 1u ? __builtin_nanf("") : (float)((double)(long long)t.sum[c] * (1.0 / 1099511627776.0));
+            if (a != 0.0f) grad_emb[(uint64_t)(t.key - 1u) * 2 + c] += a;        // the one entry of this row: nothing else adds to it
+        }
+    }
+}
+
 // One wave per workgroup; workgroup b takes the 64-ray chunks b, b + G, b + 2G, ... (G = gridDim.x, a function of N only).
 __global__ void __launch_bounds__(BG_RAYS) k_bg_backward(const _Float16 *__restrict__ grad_rgb, const float *__restrict__ rays_o,
                                                          const float *__restrict__ rays_d, const float *__restrict__ coords, float radius, uint32_t N,
                                                          const float *__restrict__ emb, const int32_t *__restrict__ offsets, BgLevels lv,
-                                                         const _Float16 *__restrict__ W, float *__restrict__ grad_emb, float *__restrict__ partials) {
+                                                         const _Float16 *__restrict__ W, float *__restrict__ grad_emb, float *__restrict__ partials,
+                                                         BgDetEntry *__restrict__ det_tab, uint32_t det_mask) {
     __shared__ float w[BG_DW];
     __shared__ _Float16 xs[BG_IN * BG_LDS_LD], as[BG_HIDDEN * BG_LDS_LD], gzs[BG_HIDDEN * BG_LDS_LD], g2s[BG_OUT * BG_LDS_LD];
     bg_stage_weights(W, w);
@@ -225,7 +264,17 @@ __global__ void __launch_bounds__(BG_RAYS) k_bg_backward(const _Float16 *__restr
 #pragma unroll
                 for (int i = 0; i < 8; i++) gx[i] = fmaf(gz, w[m * BG_IN + 16 + i], gx[i]);
             }
-            if (inside) {                                       // the grid columns of the input gradient (fp16, as the GEMM's) -> the table
+            if (inside && det_tab) {                            // FOC_DETERMINISTIC: the same addends, as integers (bg_det_add)
+#pragma unroll
+                for (int l = 0; l < BG_LEVELS; l++) {
+                    const float g0 = bg_h(gx[2 * l]), g1 = bg_h(gx[2 * l + 1]);
+#pragma unroll
+                    for (int idx = 0; idx < 4; idx++) {
+                        const float v0 = wts[l][idx] * g0, v1 = wts[l][idx] * g1;
+                        if (v0 != 0.0f || v1 != 0.0f) bg_det_add(det_tab, det_mask, rows[l][idx], v0, v1);
+                    }
+                }
+            } else if (inside) {                                // the grid columns of the input gradient (fp16, as the GEMM's) -> the table
 #pragma unroll
                 for (int l = 0; l < BG_LEVELS; l++) {
 #pragma unroll
@@ -307,7 +356,18 @@ static int bg_check(const char *who, const float *rays_o, const float *rays_d, c
 
 extern "C" {
 
-uint64_t foc_background_backward_workspace_bytes(uint32_t N) { return (uint64_t)bg_workgroups(N) * BG_DW * sizeof(float); }
+// FOC_DETERMINISTIC: entries of the row table behind the partials (a power of two, at least twice the 16 N rows a launch can touch)
+static uint32_t bg_det_entries(uint32_t N) {
+    uint32_t e = 1024u;
+    while (e < (1u << 31) && (uint64_t)e < 32ull * N) e <<= 1;
+    return e;
+}
+static uint64_t bg_partials_bytes(uint32_t N) { return ((uint64_t)bg_workgroups(N) * BG_DW * sizeof(float) + 255) & ~(uint64_t)255; }
+static uint64_t bg_workspace_bytes(uint32_t N, bool det) {
+    if (!det) return (uint64_t)bg_workgroups(N) * BG_DW * sizeof(float);
+    return bg_partials_bytes(N) + (uint64_t)bg_det_entries(N) * sizeof(BgDetEntry);
+}
+uint64_t foc_background_backward_workspace_bytes(uint32_t N) { return bg_workspace_bytes(N, foc_opt(FOC_OPT_DETERMINISTIC) != 0); }
 
 int foc_background_forward(const float *rays_o, const float *rays_d, const float *coords, float radius, uint32_t N, const float *embeddings,
                            const int32_t *offsets, float per_level_scale_log2, uint32_t base_resolution, const void *weights, void *rgb,
@@ -334,14 +394,27 @@ int foc_background_backward(const void *grad_rgb, const float *rays_o, const flo
     if (N) {
         if (int rc = bg_check("background_backward", rays_o, rays_d, coords, radius, embeddings, offsets, weights)) return rc;
         FOC_REQUIRE(grad_rgb && grad_embeddings && workspace, FOC_E_INVALID, "background_backward: null pointer");
-        const uint64_t need = foc_background_backward_workspace_bytes(N);
+        const bool det = foc_opt(FOC_OPT_DETERMINISTIC) != 0;      // read once: the size asked for and the launches agree
+        const uint64_t need = bg_workspace_bytes(N, det);
         FOC_REQUIRE(workspace_bytes >= need, FOC_E_INVALID, "background_backward: workspace of %llu bytes, %u rays need %llu "
-                    "(foc_background_backward_workspace_bytes)", (unsigned long long)workspace_bytes, N, (unsigned long long)need);
+                    "(foc_background_backward_workspace_bytes%s)", (unsigned long long)workspace_bytes, N, (unsigned long long)need,
+                    det ? "; FOC_DETERMINISTIC adds the row table" : "");
+        FOC_REQUIRE(!det || N <= (1u << 26), FOC_E_INVALID, "background_backward: FOC_DETERMINISTIC serves up to 2^26 rays per call (got %u)", N);
+        BgDetEntry *det_tab = det ? reinterpret_cast<BgDetEntry *>(reinterpret_cast<char *>(workspace) + bg_partials_bytes(N)) : nullptr;
+        const uint32_t det_entries = det ? bg_det_entries(N) : 0u;
+        if (det && foc_zero_async(det_tab, (size_t)det_entries * sizeof(BgDetEntry), (hipStream_t)stream) != hipSuccess) {
+            foc_set_error("background_backward: zero fill of the row table failed");
+            return FOC_E_LAUNCH;
+        }
         BgLevels lv;
         bg_levels(per_level_scale_log2, base_resolution, lv);
         hipLaunchKernelGGL(k_bg_backward, dim3(G), dim3(BG_RAYS), 0, (hipStream_t)stream, (const _Float16 *)grad_rgb, rays_o, rays_d, coords, radius,
-                           N, embeddings, offsets, lv, (const _Float16 *)weights, grad_embeddings, (float *)workspace);
+                           N, embeddings, offsets, lv, (const _Float16 *)weights, grad_embeddings, (float *)workspace, det_tab, det_entries - 1u);
         FOC_CHECK_LAUNCH("background_backward");
+        if (det) {
+            hipLaunchKernelGGL(k_bg_det_finish, dim3(foc_grid_1d(det_entries, 256)), dim3(256), 0, (hipStream_t)stream, (const BgDetEntry *)det_tab, det_entries, grad_embeddings);
+            FOC_CHECK_LAUNCH("background_backward(deterministic finish)");
+        }
     }
     hipLaunchKernelGGL(k_bg_dw_reduce, dim3(foc_div_up(BG_BLOB, 256)), dim3(256), 0, (hipStream_t)stream, (const float *)workspace, G, grad_weights);
     FOC_CHECK_LAUNCH("background_dw_reduce");

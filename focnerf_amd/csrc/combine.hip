@@ -226,7 +226,7 @@ struct FocOptionRow { const char *name; std::atomic<int> value; };
 static FocOptionRow foc_option_table[FOC_OPT_COUNT] = {
     {"FOC_MLP_BWD_FUSED", 1}, {"FOC_FIELD_FWD_FUSED", 1}, {"FOC_GB_MERGE_MAX_RES", 480}, {"FOC_GB_FACTORED", 1}, {"FOC_GB_TAIL_SPLIT", 16}, {"FOC_GRID_FUSE_SMALL", 1},
     {"FOC_GRID_PAIRS", 1}, {"FOC_GRID_FAST", 1}, {"FOC_MARCH_SERIAL", -1}, {"FOC_MARCH_RAYS_ROW_MAX", 131072}, {"FOC_OCC_MARCH_FORM", -1},
-    {"FOC_OCC_SAMPLE_MAJOR", 1}, {"FOC_OCC_FIELD_PIECE", 1 << 23},
+    {"FOC_OCC_SAMPLE_MAJOR", 1}, {"FOC_OCC_FIELD_PIECE", 1 << 23}, {"FOC_DETERMINISTIC", 0},
 };
 static int foc_option_parse(int which, const char *text) {
     if (which == FOC_OPT_OCC_MARCH_FORM) {                  // the forms have names: two | row | lane | staged (or 0..3, -1 = by burst length)

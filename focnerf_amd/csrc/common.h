@@ -29,6 +29,7 @@ enum FocOpt {
     FOC_OPT_OCC_MARCH_FORM,       // native occupancy loop's march: -1 by burst length, 0 two phases, 1 row, 2 lane, 3 staged
     FOC_OPT_OCC_SAMPLE_MAJOR,     // 1: sample-major sample arrays inside the native occupancy step
     FOC_OPT_OCC_FIELD_PIECE,      // samples per field evaluation inside the native occupancy step (2^23)
+    FOC_OPT_DETERMINISTIC,        // 0: default; 1: bit-reproducible training steps (include/focnerf.h "Deterministic mode"); 2: as 1, the grid backward's chunks meet through per-chunk planes (measurement aid)
     FOC_OPT_COUNT
 };
 int foc_opt(FocOpt which);

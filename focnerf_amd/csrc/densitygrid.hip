@@ -190,7 +190,9 @@ __global__ void __launch_bounds__(256) k_dg_scatter(const float *__restrict__ si
 }
 
 // valid = (grid >= 0) & (tmp >= 0); grid[valid] = max(grid*decay, tmp); sum of clamp(grid, min=0)   (:494-497)
-__global__ void __launch_bounds__(256) k_dg_ema(float *__restrict__ grid, const float *__restrict__ tmp, uint32_t n, float decay, double *__restrict__ sum) {
+// partials (FOC_DETERMINISTIC): each workgroup stores its sum instead of adding it to *sum in arrival order; k_dg_sum_partials adds them in workgroup order
+__global__ void __launch_bounds__(256) k_dg_ema(float *__restrict__ grid, const float *__restrict__ tmp, uint32_t n, float decay, double *__restrict__ sum,
+                                                double *__restrict__ partials) {
     __shared__ double s_part[4];
     double local = 0.0;
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
@@ -203,7 +205,24 @@ __global__ void __launch_bounds__(256) k_dg_ema(float *__restrict__ grid, const 
     for (int o = 32; o >= 1; o >>= 1) local += __shfl_down(local, o, 64);
     if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = local;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(sum, s_part[0] + s_part[1] + s_part[2] + s_part[3]);
+    if (threadIdx.x == 0) {
+        const double s = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+        if (partials) partials[blockIdx.x] = s; else atomicAdd(sum, s);
+    }
+}
+
+// *sum = the workgroups' partial sums added in workgroup order: thread t takes partials t, t + 256, ... in turn, then a fixed tree over the 256 threads
+__global__ void __launch_bounds__(256) k_dg_sum_partials(const double *__restrict__ partials, uint32_t G, double *__restrict__ sum) {
+    __shared__ double s[256];
+    double local = 0.0;
+    for (uint32_t b = threadIdx.x; b < G; b += 256) local += partials[b];
+    s[threadIdx.x] = local;
+    __syncthreads();
+    for (uint32_t o = 128; o >= 1; o >>= 1) {
+        if (threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *sum = s[0];
 }
 
 // mean = sum / n (fp32 result like torch.mean); bitfield = packbits(grid, min(mean, density_thresh))   (:497-503)
@@ -289,7 +308,11 @@ int foc_grid_update_sample(const float *density_grid, uint32_t C, uint32_t H, fl
     return FOC_OK;
 }
 
-uint64_t foc_grid_update_apply_workspace_bytes(uint32_t C, uint32_t H) { return (uint64_t)C * H * H * H * 4 + 256; }
+#define DG_EMA_MAX_WG 2048u            // foc_grid_1d's cap: workgroups of k_dg_ema, and doubles of its partials under FOC_DETERMINISTIC
+static uint64_t dg_apply_base_bytes(uint32_t C, uint32_t H) { return (uint64_t)C * H * H * H * 4 + 256; }
+uint64_t foc_grid_update_apply_workspace_bytes(uint32_t C, uint32_t H) {
+    return dg_apply_base_bytes(C, H) + (foc_opt(FOC_OPT_DETERMINISTIC) ? DG_EMA_MAX_WG * sizeof(double) : 0);
+}
 
 int foc_grid_update_apply(float *density_grid, uint32_t C, uint32_t H, const float *sigmas, const int32_t *indices, uint32_t Mc, float density_scale,
                           float decay, float density_thresh, uint8_t *bitfield, float *mean_out, void *workspace, uint64_t workspace_bytes, void *stream) {
@@ -297,7 +320,9 @@ int foc_grid_update_apply(float *density_grid, uint32_t C, uint32_t H, const flo
     int rc = dg_check("grid_update_apply", C, H);
     if (rc) return rc;
     FOC_REQUIRE(density_grid && sigmas && bitfield && workspace, FOC_E_INVALID, "grid_update_apply: null pointer");
-    FOC_REQUIRE(workspace_bytes >= foc_grid_update_apply_workspace_bytes(C, H), FOC_E_INVALID, "grid_update_apply: workspace too small");
+    const bool det = foc_opt(FOC_OPT_DETERMINISTIC) != 0;             // read once: the size asked for and the launches agree
+    FOC_REQUIRE(workspace_bytes >= dg_apply_base_bytes(C, H) + (det ? DG_EMA_MAX_WG * sizeof(double) : 0), FOC_E_INVALID, det ? "grid_update_apply: workspace too small "
+                "(FOC_DETERMINISTIC adds the per-workgroup partial sums: foc_grid_update_apply_workspace_bytes)" : "grid_update_apply: workspace too small");
     const uint32_t H3 = H * H * H, n = C * H3;
     FOC_REQUIRE(indices || Mc == H3, FOC_E_INVALID, "grid_update_apply: without indices, sigmas must cover every cell (Mc == H^3)");
     FOC_REQUIRE((((uintptr_t)density_grid) & 15u) == 0, FOC_E_INVALID, "grid_update_apply: density_grid must be 16-byte aligned");
@@ -310,8 +335,14 @@ int foc_grid_update_apply(float *density_grid, uint32_t C, uint32_t H, const flo
         hipLaunchKernelGGL(k_dg_scatter, dim3(foc_grid_1d((uint64_t)C * Mc, 256)), dim3(256), 0, st, sigmas, indices, C, Mc, H3, density_scale, tmp);
         FOC_CHECK_LAUNCH("grid_update_apply(scatter)");
     }
-    hipLaunchKernelGGL(k_dg_ema, dim3(foc_grid_1d(n, 256)), dim3(256), 0, st, density_grid, tmp, n, decay, sum);
+    const uint32_t ema_wg = foc_grid_1d(n, 256, DG_EMA_MAX_WG);
+    double *partials = det ? reinterpret_cast<double *>(reinterpret_cast<char *>(workspace) + dg_apply_base_bytes(C, H)) : nullptr;      // 8-byte aligned: n is a multiple of 64
+    hipLaunchKernelGGL(k_dg_ema, dim3(ema_wg), dim3(256), 0, st, density_grid, tmp, n, decay, sum, partials);
     FOC_CHECK_LAUNCH("grid_update_apply(ema)");
+    if (det) {
+        hipLaunchKernelGGL(k_dg_sum_partials, dim3(1), dim3(256), 0, st, (const double *)partials, ema_wg, sum);
+        FOC_CHECK_LAUNCH("grid_update_apply(sum)");
+    }
     hipLaunchKernelGGL(k_dg_pack, dim3(foc_grid_1d(n / 8, 256)), dim3(256), 0, st, density_grid, n / 8, sum, 1.0 / (double)n, density_thresh, bitfield, mean_out);
     FOC_CHECK_LAUNCH("grid_update_apply(pack)");
     return FOC_OK;

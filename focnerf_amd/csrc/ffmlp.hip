@@ -311,14 +311,18 @@ __global__ void __launch_bounds__(MLP_BLOCK) k_mlp_bwd(const _Float16 *__restric
 //   dW[o][i] = sum_b D[b][o] * A[b][i]   with D = delta (or grad for the output layer), A = layer input.
 // A workgroup streams 64-sample chunks of D and A through LDS (coalesced 16-byte loads), each wave owns
 // 32x32 output tiles and reads its MFMA operands transposed out of LDS; partial sums go to the fp32
-// workspace with float atomics shaped as whole 128-byte row segments.
+// workspace with float atomics shaped as whole 128-byte row segments — the sum of a weight depends on the order in which the
+// workgroups along x arrive. FOC_DETERMINISTIC: slot_stride != 0, workgroup x adds into its OWN zeroed image ws + x * slot_stride (one
+// add per element: nothing to order) and k_mlp_dw_finalize_slots sums the at most MLP_DW_DET_SLOTS images in workgroup order.
 #define DW_CHUNK 64
+#define MLP_DW_DET_SLOTS 32u
 // AW: widest layer input the LDS tile holds — 128 (hidden <= 128, inputs up to 128), 256 (hidden 256, or the reference's dynamic input layer with
 // up to 256 inputs at a narrower hidden width, ffmlp.cu:151-239: any 16 m that fits shared memory)
 template <int HIDDEN, int AW = (HIDDEN > 128 ? HIDDEN : 128)>
 __global__ void __launch_bounds__(MLP_BLOCK) k_mlp_dw(const _Float16 *__restrict__ grad, const _Float16 *__restrict__ inputs,
                                                       const _Float16 *__restrict__ fwd_buf, const _Float16 *__restrict__ bwd_buf,
-                                                      float *__restrict__ ws, uint32_t B, uint32_t in_dim, uint32_t num_layers) {
+                                                      float *__restrict__ ws_base, uint32_t B, uint32_t in_dim, uint32_t num_layers, uint64_t slot_stride) {
+    float *__restrict__ ws = ws_base + (uint64_t)blockIdx.x * slot_stride;
     constexpr int LDP = 8;   // row padding (halfs) to spread the strided 2-byte reads over banks
     __shared__ __attribute__((aligned(16))) _Float16 sD[DW_CHUNK][(HIDDEN < 32 ? 32 : HIDDEN) + LDP];   // >= 32 columns: transposed reads span a whole 32-row tile
     __shared__ __attribute__((aligned(16))) _Float16 sA[DW_CHUNK][AW + LDP];
@@ -410,6 +414,14 @@ __global__ void __launch_bounds__(MLP_BLOCK) k_mlp_dw(const _Float16 *__restrict
 // fp32 workspace -> fp16 grad_weights (one rounding, like a full-K fp32 accumulation)
 __global__ void __launch_bounds__(256) k_mlp_dw_finalize(const float *__restrict__ ws, _Float16 *__restrict__ gw, uint32_t n) {
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) gw[i] = (_Float16)ws[i];
+}
+// FOC_DETERMINISTIC: the same over `slots` images `stride` floats apart, added in slot order
+__global__ void __launch_bounds__(256) k_mlp_dw_finalize_slots(const float *__restrict__ ws, uint32_t slots, uint64_t stride, _Float16 *__restrict__ gw, uint32_t n) {
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        float v = 0.0f;
+        for (uint32_t k = 0; k < slots; k++) v += ws[k * stride + i];
+        gw[i] = (_Float16)v;
+    }
 }
 
 // ---------------------------------------------------------------- M2+M3 fused: activation gradients AND weight gradients in one pass
@@ -1420,10 +1432,12 @@ static int mlp_bwd_fused_launch(const void *grad, const void *inputs, const void
 // weight gradients of every layer from the stored activations and activation gradients: split-K over the batch into the fp32 workspace, one rounding
 template <int HIDDEN>
 static int mlp_dw_launch(const void *grad, const void *inputs, const void *fwd_buf, const void *bwd_buf, uint32_t B, uint32_t in_dim, uint32_t num_layers,
-                         void *grad_weights, float *ws, hipStream_t st) {
+                         void *grad_weights, float *ws, bool det, hipStream_t st) {
     const uint32_t n_w = HIDDEN * (in_dim + HIDDEN * (num_layers - 1) + 16);
-    if (foc_zero_async(ws, (size_t)n_w * sizeof(float), st) != hipSuccess) { foc_set_error("ffmlp_backward: memset of workspace failed"); return FOC_E_LAUNCH; }
+    const uint64_t det_stride = det ? mlp_dw_blob_floats(in_dim, HIDDEN, num_layers) : 0;       // floats between the per-workgroup images (0: one image, atomics)
     uint32_t gx = foc_div_up(B, DW_CHUNK);
+    if (det && gx > MLP_DW_DET_SLOTS) gx = MLP_DW_DET_SLOTS;
+    if (foc_zero_async(ws, det ? (size_t)gx * det_stride * sizeof(float) : (size_t)n_w * sizeof(float), st) != hipSuccess) { foc_set_error("ffmlp_backward: memset of workspace failed"); return FOC_E_LAUNCH; }
     const int wgs_per_cu = 8;                    // split-K workgroups per CU over all layers
     // 16 output tiles per workgroup: hidden x hidden, or hidden x in_dim for an input layer wider than the hidden layers
     const uint32_t tiles = ((HIDDEN + 31) / 32) * ((max((uint32_t)HIDDEN, in_dim) + 31) / 32), GZ = (tiles + 15) / 16;
@@ -1433,16 +1447,17 @@ static int mlp_dw_launch(const void *grad, const void *inputs, const void *fwd_b
     auto kern = k_mlp_dw<HIDDEN>;
     if constexpr (HIDDEN <= 128) { if (in_dim > 128) kern = k_mlp_dw<HIDDEN, 256>; }
     hipLaunchKernelGGL(kern, dim3(gx, num_layers + 1, GZ), dim3(MLP_BLOCK), 0, st, (const _Float16 *)grad, (const _Float16 *)inputs,
-                       (const _Float16 *)fwd_buf, (const _Float16 *)bwd_buf, ws, B, in_dim, num_layers);
+                       (const _Float16 *)fwd_buf, (const _Float16 *)bwd_buf, ws, B, in_dim, num_layers, det_stride);
     FOC_CHECK_LAUNCH("ffmlp_backward(weights)");
-    hipLaunchKernelGGL(k_mlp_dw_finalize, dim3(foc_grid_1d(n_w, 256)), dim3(256), 0, st, ws, (_Float16 *)grad_weights, n_w);
+    if (det) hipLaunchKernelGGL(k_mlp_dw_finalize_slots, dim3(foc_grid_1d(n_w, 256)), dim3(256), 0, st, ws, gx, det_stride, (_Float16 *)grad_weights, n_w);
+    else hipLaunchKernelGGL(k_mlp_dw_finalize, dim3(foc_grid_1d(n_w, 256)), dim3(256), 0, st, ws, (_Float16 *)grad_weights, n_w);
     FOC_CHECK_LAUNCH("ffmlp_backward(finalize)");
     return FOC_OK;
 }
 
 template <int HIDDEN>
 static int mlp_bwd_launch(const void *grad, const void *inputs, const void *weights, const void *fwd_buf, uint32_t B, uint32_t in_dim,
-                          uint32_t num_layers, int act, void *bwd_buf, void *grad_inputs, void *grad_weights, float *ws, int planar, hipStream_t st) {
+                          uint32_t num_layers, int act, void *bwd_buf, void *grad_inputs, void *grad_weights, float *ws, int planar, bool det, hipStream_t st) {
     const bool gen = act != FOC_ACT_RELU && act != FOC_ACT_NONE;      // the single-pass kernel is built for ReLU / None: the others take the reference's data flow
     const int relu = act == FOC_ACT_RELU;
     // fused single-pass kernel for the shapes the NeRF networks use; FOC_MLP_BWD_FUSED=0 forces the two-kernel form (tuning / tests)
@@ -1473,7 +1488,7 @@ static int mlp_bwd_launch(const void *grad, const void *inputs, const void *weig
     hipLaunchKernelGGL(kern, dim3(grid), dim3(MLP_BLOCK), lds, st, (const _Float16 *)grad, (const _Float16 *)weights, (const _Float16 *)fwd_buf,
                        (_Float16 *)bwd_buf, (_Float16 *)grad_inputs, B, in_dim, num_layers, act);
     FOC_CHECK_LAUNCH("ffmlp_backward(activations)");
-    return mlp_dw_launch<HIDDEN>(grad, inputs, fwd_buf, bwd_buf, B, in_dim, num_layers, grad_weights, ws, st);
+    return mlp_dw_launch<HIDDEN>(grad, inputs, fwd_buf, bwd_buf, B, in_dim, num_layers, grad_weights, ws, det, st);
 }
 
 template <int NLS, int NLC>
@@ -1519,12 +1534,21 @@ int foc_ffmlp_inference(const void *inputs, const void *weights, uint32_t B, uin
     return mlp_fwd<false>(inputs, weights, B, input_dim, output_dim, hidden_dim, num_layers, activation, output_activation, inference_buffer, outputs, stream);
 }
 
+static uint64_t mlp_bwd_workspace_bytes(uint32_t input_dim, uint32_t hidden_dim, uint32_t num_layers, bool det);
 uint64_t foc_ffmlp_backward_workspace_bytes(uint32_t input_dim, uint32_t hidden_dim, uint32_t num_layers) {
+    if (foc_opt(FOC_OPT_DETERMINISTIC)) return mlp_bwd_workspace_bytes(input_dim, hidden_dim, num_layers, true);      // sufficient under the current option value
     // the fp32 image of the weight blob (split-K sums of k_mlp_dw; the object-conditioned head's finalize) and, for the shapes
     // k_mlp_bwd_fused serves, one slot of partial tiles per workgroup of its launch
     uint64_t floats = mlp_dw_blob_floats(input_dim, hidden_dim, num_layers);
     if (hidden_dim <= 64 && input_dim <= 64 && num_layers >= 1 && num_layers <= 4) floats += (uint64_t)MLP_DW_MAX_SLOTS * (num_layers + 1) * MLP_DW_SLOT_STAGE;
     return floats * sizeof(float);
+}
+// with FOC_DETERMINISTIC set the split-K kernel keeps one blob image per workgroup along x (at most MLP_DW_DET_SLOTS)
+static uint64_t mlp_bwd_workspace_bytes(uint32_t input_dim, uint32_t hidden_dim, uint32_t num_layers, bool det) {
+    uint64_t floats = mlp_dw_blob_floats(input_dim, hidden_dim, num_layers);
+    const uint64_t det_floats = det ? floats * MLP_DW_DET_SLOTS : 0;
+    if (hidden_dim <= 64 && input_dim <= 64 && num_layers >= 1 && num_layers <= 4) floats += (uint64_t)MLP_DW_MAX_SLOTS * (num_layers + 1) * MLP_DW_SLOT_STAGE;
+    return (floats > det_floats ? floats : det_floats) * sizeof(float);
 }
 
 static int mlp_bwd_entry(const void *grad, const void *inputs, const void *weights, const void *forward_buffer, uint32_t B, uint32_t input_dim,
@@ -1543,24 +1567,25 @@ static int mlp_bwd_entry(const void *grad, const void *inputs, const void *weigh
     }
     FOC_REQUIRE(grad && inputs && weights && grad_weights && workspace, FOC_E_INVALID, "ffmlp_backward: null pointer");
     FOC_REQUIRE(!calc_grad_inputs || grad_inputs, FOC_E_INVALID, "ffmlp_backward: calc_grad_inputs set but grad_inputs is null");
-    FOC_REQUIRE(workspace_bytes >= foc_ffmlp_backward_workspace_bytes(input_dim, hidden_dim, num_layers), FOC_E_INVALID,
-                "ffmlp_backward: workspace of %llu bytes, foc_ffmlp_backward_workspace_bytes(%u, %u, %u) asks for %llu (ABI 2: blob image + per-workgroup slots)",
+    const bool det = foc_opt(FOC_OPT_DETERMINISTIC) != 0;             // read once: the size asked for and the launches agree
+    FOC_REQUIRE(workspace_bytes >= mlp_bwd_workspace_bytes(input_dim, hidden_dim, num_layers, det), FOC_E_INVALID,
+                "ffmlp_backward: workspace of %llu bytes, foc_ffmlp_backward_workspace_bytes(%u, %u, %u) asks for %llu (ABI 2: blob image + per-workgroup slots%s)",
                 (unsigned long long)workspace_bytes, input_dim, hidden_dim, num_layers,
-                (unsigned long long)foc_ffmlp_backward_workspace_bytes(input_dim, hidden_dim, num_layers));
+                (unsigned long long)mlp_bwd_workspace_bytes(input_dim, hidden_dim, num_layers, det), det ? "; FOC_DETERMINISTIC: one image per split-K workgroup" : "");
     const int relu = (int)activation;                     // the reference's activation code (0 = ReLU ... 6 = None), handed on as it is
     hipStream_t st = (hipStream_t)stream;
     void *gi = calc_grad_inputs ? grad_inputs : nullptr;
     switch (hidden_dim) {
-        case 16: return mlp_bwd_launch<16>(grad, inputs, weights, forward_buffer, B, input_dim, num_layers, relu, backward_buffer, gi, grad_weights, (float *)workspace, planar, st);
-        case 32: return mlp_bwd_launch<32>(grad, inputs, weights, forward_buffer, B, input_dim, num_layers, relu, backward_buffer, gi, grad_weights, (float *)workspace, planar, st);
-        case 64: return mlp_bwd_launch<64>(grad, inputs, weights, forward_buffer, B, input_dim, num_layers, relu, backward_buffer, gi, grad_weights, (float *)workspace, planar, st);
-        case 128: return mlp_bwd_launch<128>(grad, inputs, weights, forward_buffer, B, input_dim, num_layers, relu, backward_buffer, gi, grad_weights, (float *)workspace, planar, st);
+        case 16: return mlp_bwd_launch<16>(grad, inputs, weights, forward_buffer, B, input_dim, num_layers, relu, backward_buffer, gi, grad_weights, (float *)workspace, planar, det, st);
+        case 32: return mlp_bwd_launch<32>(grad, inputs, weights, forward_buffer, B, input_dim, num_layers, relu, backward_buffer, gi, grad_weights, (float *)workspace, planar, det, st);
+        case 64: return mlp_bwd_launch<64>(grad, inputs, weights, forward_buffer, B, input_dim, num_layers, relu, backward_buffer, gi, grad_weights, (float *)workspace, planar, det, st);
+        case 128: return mlp_bwd_launch<128>(grad, inputs, weights, forward_buffer, B, input_dim, num_layers, relu, backward_buffer, gi, grad_weights, (float *)workspace, planar, det, st);
         case 256: {
             FOC_REQUIRE(backward_buffer && forward_buffer, FOC_E_INVALID, "ffmlp_backward: hidden_dim 256 runs layer by layer and needs forward_buffer and backward_buffer");
             FOC_REQUIRE(!planar, FOC_E_INVALID, "ffmlp_backward: planar inputs are served up to hidden_dim 64");
             rc = mlp_wide_backward_activations(grad, weights, forward_buffer, B, input_dim, 256, num_layers, relu, backward_buffer, gi, st);
             if (rc) return rc;
-            return mlp_dw_launch<256>(grad, inputs, forward_buffer, backward_buffer, B, input_dim, num_layers, grad_weights, (float *)workspace, st);
+            return mlp_dw_launch<256>(grad, inputs, forward_buffer, backward_buffer, B, input_dim, num_layers, grad_weights, (float *)workspace, det, st);
         }
     }
     return FOC_E_INVALID;

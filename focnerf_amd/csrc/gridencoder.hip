@@ -1060,16 +1060,23 @@ __device__ __forceinline__ unsigned long long gb_half_to_fixed(uint32_t h) {
 }
 
 #define GB_RTHREADS 1024u
-template <typename T>
+// DET (FOC_DETERMINISTIC, fp16 tables only): how the chunks of one slot meet. 0: every chunk rounds its partial to half and adds it to
+// grad_grid with global_atomic_pk_add_f16, in arrival order. 1 and 2: a slot with ONE chunk does exactly that (one add per element: no
+// order to depend on); the chunks of a slot with several keep their exact 2^24-scaled int64 sums — 1: added with 64-bit integer
+// atomics into the slot's zeroed image det_sum[slot][2][GB_SEG] (integer addition is associative: arrival order cannot matter),
+// 2: stored as the chunk's own plane det_sum[chunk][2][GB_SEG] — and k_gbin_det_finish converts each element's total ONCE.
+// det_bad: the s_bad words of the slot (1: atomicOr) or of the chunk (2).
+template <typename T, int DET>
 __global__ void __launch_bounds__(GB_RTHREADS) k_gbin_reduce(const GbHeader *__restrict__ hdr, const void *__restrict__ recs, uint64_t max_recs,
-                                                             const int32_t *__restrict__ offsets, T *__restrict__ grad_grid, uint32_t L, uint32_t fact_mask) {
+                                                             const int32_t *__restrict__ offsets, T *__restrict__ grad_grid, uint32_t L, uint32_t fact_mask,
+                                                             unsigned long long *__restrict__ det_sum, uint32_t *__restrict__ det_bad) {
     // 128 KiB (fp32 tables: f64 sums; fp16 tables: the same bytes as 2^24-scaled int64), one PLANE per channel: with the two channels
     // of a row side by side a wave instruction (one channel of 64 random rows) could only ever touch every other pair of banks —
     // half of the LDS's banks idle, twice the conflict cycles; planes spread a channel's 64 addends over all 64 banks
     __shared__ double acc[GB_SEG * 2];
     unsigned long long *acci = reinterpret_cast<unsigned long long *>(acc);
     __shared__ uint32_t s_bad[GB_SEG / 32];        // fp16 tables: rows that received an inf/NaN addend (an overflowed AMP step) -> NaN out
-    __shared__ uint32_t s_slot, s_lo, s_hi;
+    __shared__ uint32_t s_slot, s_lo, s_hi, s_multi;
     const uint32_t n = L * GB_MAX_SEGS;
     const uint32_t total_chunks = hdr->chunk_prefix[n];
     // (one workgroup per chunk; a persistent form — one workgroup per CU walking the chunks with the grid's stride — measured 263 vs
@@ -1080,7 +1087,7 @@ __global__ void __launch_bounds__(GB_RTHREADS) k_gbin_reduce(const GbHeader *__r
     // Which (level, segment) slot and which chunk of it this workgroup owns: the slot with chunk_prefix[slot] <= blockIdx.x < chunk_prefix[slot + 1]
     // (empty slots have equal neighbours and match nothing). Every thread tests one or two slots: one round trip to the header instead of
     // thread 0's eleven dependent loads of a binary search (no measurable difference: the header sits in L2; kept for the shorter chain).
-    if (threadIdx.x == 0) { s_slot = 0u; s_lo = 0u; s_hi = 0u; }      // a header that matches nothing (not this launch's) reduces nothing
+    if (threadIdx.x == 0) { s_slot = 0u; s_lo = 0u; s_hi = 0u; s_multi = 0u; }      // a header that matches nothing (not this launch's) reduces nothing
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < n; i += GB_RTHREADS) {
         const uint32_t p0 = hdr->chunk_prefix[i], p1 = hdr->chunk_prefix[i + 1];
@@ -1089,6 +1096,7 @@ __global__ void __launch_bounds__(GB_RTHREADS) k_gbin_reduce(const GbHeader *__r
         if (p0 <= chunk_id && chunk_id < p1) {
             const uint32_t c = chunk_id - p0;
             s_slot = i;
+            if constexpr (DET != 0) s_multi = p1 - p0 > 1u ? 1u : 0u;
             // clamped to the record arrays: a header that does not belong to these records must not turn into an out-of-bounds read
             s_lo = (uint32_t)min(b0 + (uint64_t)c * GB_CHUNK, max_recs);
             s_hi = (uint32_t)min(b0 + min(cnt, (c + 1) * GB_CHUNK), max_recs);
@@ -1268,6 +1276,25 @@ __global__ void __launch_bounds__(GB_RTHREADS) k_gbin_reduce(const GbHeader *__r
     const uint32_t row0 = seg * GB_SEG;
     T *dst = grad_grid + ((uint64_t)off0 + row0) * 2;
     const uint32_t nrows = hashmap_size > row0 ? min(GB_SEG, hashmap_size - row0) : 0u;
+    if constexpr (sizeof(T) == 2 && DET != 0) {
+        if (s_multi) {                                     // workgroup-uniform
+            if constexpr (DET == 1) {
+                unsigned long long *img = det_sum + (uint64_t)slot * (GB_SEG * 2);
+                for (uint32_t r = threadIdx.x; r < nrows; r += GB_RTHREADS) {
+                    const unsigned long long a = acci[r], b = acci[GB_SEG + r];
+                    if (a) (void)__hip_atomic_fetch_add(img + r, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (b) (void)__hip_atomic_fetch_add(img + GB_SEG + r, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+                if (threadIdx.x < GB_SEG / 32 && s_bad[threadIdx.x])
+                    (void)__hip_atomic_fetch_or(det_bad + (uint64_t)slot * (GB_SEG / 32) + threadIdx.x, s_bad[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            } else {
+                unsigned long long *pl = det_sum + (uint64_t)chunk_id * (GB_SEG * 2);
+                for (uint32_t r = threadIdx.x; r < nrows; r += GB_RTHREADS) { pl[r] = acci[r]; pl[GB_SEG + r] = acci[GB_SEG + r]; }
+                if (threadIdx.x < GB_SEG / 32) det_bad[(uint64_t)chunk_id * (GB_SEG / 32) + threadIdx.x] = s_bad[threadIdx.x];
+            }
+            return;
+        }
+    }
     if constexpr (sizeof(T) == 2) {
         typedef _Float16 __attribute__((ext_vector_type(2))) v2h;
         for (uint32_t r = threadIdx.x; r < nrows; r += GB_RTHREADS) {
@@ -1284,6 +1311,59 @@ __global__ void __launch_bounds__(GB_RTHREADS) k_gbin_reduce(const GbHeader *__r
         }
     }
     }
+}
+
+// FOC_DETERMINISTIC, variant 1: zero the int64 image and the bad-row words of every slot that has more than one chunk (8 workgroups per slot).
+#define GB_DET_PARTS (GB_SEG / GB_RTHREADS)
+__global__ void __launch_bounds__(GB_RTHREADS) k_gbin_det_zero(const GbHeader *__restrict__ hdr, unsigned long long *__restrict__ det_sum,
+                                                               uint32_t *__restrict__ det_bad, uint32_t L) {
+    const uint32_t slot = blockIdx.x / GB_DET_PARTS, part = blockIdx.x % GB_DET_PARTS;
+    if (slot >= L * GB_MAX_SEGS || hdr->chunk_prefix[slot + 1] - hdr->chunk_prefix[slot] < 2u) return;
+    unsigned long long *img = det_sum + (uint64_t)slot * (GB_SEG * 2);
+    img[part * GB_RTHREADS + threadIdx.x] = 0ull;
+    img[GB_SEG + part * GB_RTHREADS + threadIdx.x] = 0ull;
+    if (part == 0 && threadIdx.x < GB_SEG / 32) det_bad[(uint64_t)slot * (GB_SEG / 32) + threadIdx.x] = 0u;
+}
+
+// FOC_DETERMINISTIC: the slots with more than one chunk, one thread per table row: the exact total S of the row's 2^24-scaled addends
+// (1: the image the chunks added into; 2: the chunks' planes, summed here) becomes (_Float16)(float)((double)S / 2^24) — k_gbin_reduce's
+// own expression for a chunk — and is added to grad_grid ONCE (NaN for a row that any chunk marked bad).
+template <int DET>
+__global__ void __launch_bounds__(GB_RTHREADS) k_gbin_det_finish(const GbHeader *__restrict__ hdr, const unsigned long long *__restrict__ det_sum,
+                                                                 const uint32_t *__restrict__ det_bad, uint32_t n_planes, const int32_t *__restrict__ offsets,
+                                                                 __half *__restrict__ grad_grid, uint32_t L) {
+    const uint32_t slot = blockIdx.x / GB_DET_PARTS, part = blockIdx.x % GB_DET_PARTS;
+    if (slot >= L * GB_MAX_SEGS) return;
+    const uint32_t p0 = hdr->chunk_prefix[slot], p1 = min(hdr->chunk_prefix[slot + 1], n_planes);
+    if (p1 < p0 + 2u) return;
+    const uint32_t level = slot / GB_MAX_SEGS, seg = slot % GB_MAX_SEGS;
+    const uint32_t off0 = (uint32_t)offsets[level];
+    const uint32_t hashmap_size = (uint32_t)offsets[level + 1] - off0;
+    const uint32_t row0 = seg * GB_SEG;
+    const uint32_t nrows = hashmap_size > row0 ? min(GB_SEG, hashmap_size - row0) : 0u;
+    const uint32_t r = part * GB_RTHREADS + threadIdx.x;
+    if (r >= nrows) return;
+    unsigned long long s0 = 0ull, s1 = 0ull;
+    uint32_t bad = 0u;
+    if constexpr (DET == 1) {
+        const unsigned long long *img = det_sum + (uint64_t)slot * (GB_SEG * 2);
+        s0 = img[r]; s1 = img[GB_SEG + r];
+        bad = det_bad[(uint64_t)slot * (GB_SEG / 32) + (r >> 5)];
+    } else {
+#pragma unroll 4
+        for (uint32_t c = p0; c < p1; c++) {
+            const unsigned long long *pl = det_sum + (uint64_t)c * (GB_SEG * 2);
+            s0 += pl[r]; s1 += pl[GB_SEG + r];
+            bad |= det_bad[(uint64_t)c * (GB_SEG / 32) + (r >> 5)];
+        }
+    }
+    float a = (float)((double)(long long)s0 * (1.0 / 16777216.0)), b = (float)((double)(long long)s1 * (1.0 / 16777216.0));
+    if ((bad >> (r & 31u)) & 1u) { a = __builtin_nanf(""); b = __builtin_nanf(""); }
+    if (a == 0.0f && b == 0.0f) return;
+    typedef _Float16 __attribute__((ext_vector_type(2))) v2h;
+    v2h hv; hv[0] = (_Float16)ge_opaque(a); hv[1] = (_Float16)ge_opaque(b);
+    __half *dst = grad_grid + ((uint64_t)off0 + row0) * 2;
+    (void)__builtin_amdgcn_global_atomic_fadd_v2f16((__attribute__((address_space(1))) v2h *)(dst + 2 * r), hv);
 }
 
 // gridencoder.cu:343-369: grad_inputs[b,d] = sum_{l,c} grad[l,b,c] * dy_dx[b,l,d,c]   (fp32 accumulate)
@@ -1553,10 +1633,25 @@ static int ge_tv_c(uint32_t C, const void *inputs, const void *emb, void *grad, 
 // records (pairs of corners along x) a pass can produce: 4 per (point, level), 5 when a pair straddles a segment boundary
 static uint64_t gb_max_recs(uint32_t B, uint32_t L) { return (uint64_t)B * 5u * L; }
 static uint64_t gb_rec_array_bytes(uint64_t m, int dtype) { return ((m + 3) & ~(uint64_t)3) * 4 + m * (dtype == FOC_F16 ? 8 : 16); }
-static uint64_t gb_workspace_bytes(uint32_t B, uint32_t L, int dtype) {
+// chunks of the reduce in the worst case (its grid)
+static uint32_t gb_max_chunks(uint32_t B, uint32_t L) { return (uint32_t)(((uint64_t)B * 5u * L + GB_CHUNK - 1) / GB_CHUNK) + L * GB_MAX_SEGS; }
+// FOC_DETERMINISTIC (fp16 tables): the int64 sums and bad-row words that follow the default layout — one image per slot (1) or per chunk (2)
+static int gb_det_mode(int dtype) {
+    const int det = foc_opt(FOC_OPT_DETERMINISTIC);
+    return dtype == FOC_F16 && det ? (det == 2 ? 2 : 1) : 0;
+}
+static uint64_t gb_det_images(uint32_t B, uint32_t L, int det) { return det == 2 ? gb_max_chunks(B, L) : det ? L * GB_MAX_SEGS : 0u; }
+static uint64_t gb_base_workspace_bytes(uint32_t B, uint32_t L, int dtype) {
     const uint64_t hdr = (sizeof(GbHeader) + 255) & ~(uint64_t)255;
     const uint64_t m = gb_max_recs(B, L);
     const uint64_t wg = (uint64_t)foc_div_up(B, GB_PM_TILE) * L * GB_MAX_SEGS * 4;      // per-workgroup counts / bases of the point-major passes
+    return (hdr + gb_rec_array_bytes(m, dtype) + 256 + wg + 256 + 255) & ~(uint64_t)255;
+}
+static uint64_t gb_workspace_bytes(uint32_t B, uint32_t L, int dtype, int det) {
+    const uint64_t hdr = (sizeof(GbHeader) + 255) & ~(uint64_t)255;
+    const uint64_t m = gb_max_recs(B, L);
+    const uint64_t wg = (uint64_t)foc_div_up(B, GB_PM_TILE) * L * GB_MAX_SEGS * 4;      // per-workgroup counts / bases of the point-major passes
+    if (det) return gb_base_workspace_bytes(B, L, dtype) + gb_det_images(B, L, det) * (GB_SEG * 2 * 8 + GB_SEG / 8);
     return hdr + gb_rec_array_bytes(m, dtype) + 256 + wg + 256;
 }
 static uint64_t gb_recs_bytes(uint32_t B, uint32_t L, int dtype) {
@@ -1638,7 +1733,7 @@ static uint32_t gb_scatter_resident(size_t elem) {
 
 template <typename T>
 static int gb_run(const void *grad, const float *inputs, const int32_t *offsets, void *grad_emb, uint32_t B, uint32_t L, const GeLevels &lv,
-                  uint32_t gridtype, bool ac, uint32_t interp, bool bl, void *workspace, bool counted, uint32_t fact_mask, const GbSizes &sz, hipStream_t st) {
+                  uint32_t gridtype, bool ac, uint32_t interp, bool bl, void *workspace, bool counted, uint32_t fact_mask, const GbSizes &sz, int det, hipStream_t st) {
     GbHeader *hdr = reinterpret_cast<GbHeader *>(workspace);
     void *recs = reinterpret_cast<char *>(workspace) + ((sizeof(GbHeader) + 255) & ~(uint64_t)255);
     const uint64_t max_recs = gb_max_recs(B, L);
@@ -1658,8 +1753,30 @@ static int gb_run(const void *grad, const float *inputs, const int32_t *offsets,
     hipLaunchKernelGGL((k_gbin_scatter_pms<T>), dim3(n_whole + n_tail * split), dim3(GB_PMS_WG), 0, st, (const T *)grad, inputs, offsets, hdr, wg_hist, recs, max_recs, B, L, lv,
                        gridtype, ac, interp, bl, fact_mask, sz, n_tiles, n_whole, split);
     FOC_CHECK_LAUNCH("grid_encode_backward(scatter)");
-    const uint32_t ub = (uint32_t)(((uint64_t)B * 5u * L + GB_CHUNK - 1) / GB_CHUNK) + L * GB_MAX_SEGS;      // chunks in the worst case
-    hipLaunchKernelGGL((k_gbin_reduce<T>), dim3(ub), dim3(GB_RTHREADS), 0, st, hdr, recs, max_recs, offsets, (T *)grad_emb, L, fact_mask);
+    const uint32_t ub = gb_max_chunks(B, L);
+    if constexpr (sizeof(T) == 2) {
+        if (det) {
+            const uint64_t images = gb_det_images(B, L, det);
+            unsigned long long *det_sum = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(workspace) + gb_base_workspace_bytes(B, L, FOC_F16));
+            uint32_t *det_bad = reinterpret_cast<uint32_t *>(det_sum + images * (GB_SEG * 2));
+            const uint32_t fin = L * GB_MAX_SEGS * GB_DET_PARTS;
+            if (det == 1) {
+                hipLaunchKernelGGL(k_gbin_det_zero, dim3(fin), dim3(GB_RTHREADS), 0, st, hdr, det_sum, det_bad, L);
+                FOC_CHECK_LAUNCH("grid_encode_backward(deterministic zero)");
+                hipLaunchKernelGGL((k_gbin_reduce<T, 1>), dim3(ub), dim3(GB_RTHREADS), 0, st, hdr, recs, max_recs, offsets, (T *)grad_emb, L, fact_mask, det_sum, det_bad);
+                FOC_CHECK_LAUNCH("grid_encode_backward(reduce)");
+                hipLaunchKernelGGL((k_gbin_det_finish<1>), dim3(fin), dim3(GB_RTHREADS), 0, st, hdr, det_sum, det_bad, ub, offsets, (__half *)grad_emb, L);
+            } else {
+                hipLaunchKernelGGL((k_gbin_reduce<T, 2>), dim3(ub), dim3(GB_RTHREADS), 0, st, hdr, recs, max_recs, offsets, (T *)grad_emb, L, fact_mask, det_sum, det_bad);
+                FOC_CHECK_LAUNCH("grid_encode_backward(reduce)");
+                hipLaunchKernelGGL((k_gbin_det_finish<2>), dim3(fin), dim3(GB_RTHREADS), 0, st, hdr, det_sum, det_bad, ub, offsets, (__half *)grad_emb, L);
+            }
+            FOC_CHECK_LAUNCH("grid_encode_backward(deterministic finish)");
+            return FOC_OK;
+        }
+    }
+    hipLaunchKernelGGL((k_gbin_reduce<T, 0>), dim3(ub), dim3(GB_RTHREADS), 0, st, hdr, recs, max_recs, offsets, (T *)grad_emb, L, fact_mask,
+                       (unsigned long long *)nullptr, (uint32_t *)nullptr);
     FOC_CHECK_LAUNCH("grid_encode_backward(reduce)");
     return FOC_OK;
 }
@@ -1726,6 +1843,8 @@ int foc_grid_encode_backward(const void *grad, const float *inputs, const void *
     FOC_REQUIRE(dtype == FOC_F32 || dtype == FOC_F16, FOC_E_DTYPE, "grid_encode_backward: dtype must be FOC_F32 or FOC_F16");
     FOC_REQUIRE(L >= 1 && L <= GE_MAX_LEVELS, FOC_E_INVALID, "grid_encode_backward: L must be in [1,%d]", GE_MAX_LEVELS);
     FOC_REQUIRE(gridtype <= 1 && interp <= 1, FOC_E_INVALID, "grid_encode_backward: bad gridtype/interp");
+    FOC_REQUIRE(!foc_opt(FOC_OPT_DETERMINISTIC), FOC_E_INVALID, "grid_encode_backward: FOC_DETERMINISTIC is set and this entry point scatters with float atomics "
+                "(arrival order); deterministic mode serves fp16 hash grids with D=3, C=2 through foc_grid_encode_backward_binned");
     if (B == 0) return FOC_OK;
     GeLevels lv;
     ge_make_levels(L, S, H, lv);
@@ -1750,15 +1869,17 @@ int foc_grid_encode_backward(const void *grad, const float *inputs, const void *
 
 uint64_t foc_grid_encode_backward_workspace_bytes(uint32_t B, uint32_t D, uint32_t C, uint32_t L, int dtype) {
     if (D != 3 || C != 2 || L > GE_MAX_LEVELS) return 0;       // 0: the binned path does not apply; use foc_grid_encode_backward
-    return gb_workspace_bytes(B, L, dtype);
+    return gb_workspace_bytes(B, L, dtype, gb_det_mode(dtype));       // sufficient under the CURRENT value of FOC_DETERMINISTIC
 }
 
+// det: the value of FOC_DETERMINISTIC this call runs under (gb_det_mode), read ONCE per call: the size asked for here and the launches agree
 static int gb_check(uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, uint32_t gridtype, uint32_t interp, int dtype,
-                    const int32_t *offsets_host, uint64_t workspace_bytes) {
+                    const int32_t *offsets_host, uint64_t workspace_bytes, int det = 0) {
     FOC_REQUIRE(dtype == FOC_F32 || dtype == FOC_F16, FOC_E_DTYPE, "grid_encode_backward_binned: dtype must be FOC_F32 or FOC_F16");
     FOC_REQUIRE(D == 3 && C == 2, FOC_E_INVALID, "grid_encode_backward_binned: only D=3, C=2 (got D=%u C=%u)", D, C);
     FOC_REQUIRE(L >= 1 && L <= GE_MAX_LEVELS && gridtype <= 1 && interp <= 1, FOC_E_INVALID, "grid_encode_backward_binned: bad L/gridtype/interp");
-    FOC_REQUIRE(workspace_bytes >= gb_workspace_bytes(B, L, dtype), FOC_E_INVALID, "grid_encode_backward_binned: workspace too small");
+    FOC_REQUIRE(workspace_bytes >= gb_workspace_bytes(B, L, dtype, det), FOC_E_INVALID, det ? "grid_encode_backward_binned: workspace too small (FOC_DETERMINISTIC adds "
+                "the int64 images: foc_grid_encode_backward_workspace_bytes)" : "grid_encode_backward_binned: workspace too small");
     FOC_REQUIRE((uint64_t)B * 8u * L < (1ull << 32), FOC_E_INVALID, "grid_encode_backward_binned: B*8*L must stay below 2^32 records");
     for (uint32_t l = 0; l < L; l++)
         FOC_REQUIRE((uint32_t)(offsets_host[l + 1] - offsets_host[l]) <= GB_SEG * GB_MAX_SEGS, FOC_E_INVALID,
@@ -1810,8 +1931,12 @@ static int gb_entry(const void *grad, const float *inputs, const int32_t *offset
                     const int32_t *offsets_host, void *workspace, uint64_t workspace_bytes, bool counted, void *stream) {
     if (B == 0) return FOC_OK;
     FOC_REQUIRE(grad && inputs && offsets && grad_embeddings && workspace && offsets_host, FOC_E_INVALID, "grid_encode_backward_binned: null pointer");
+    const int det_on = foc_opt(FOC_OPT_DETERMINISTIC);
+    FOC_REQUIRE(!(det_on && dtype == FOC_F32), FOC_E_INVALID, "grid_encode_backward_binned: FOC_DETERMINISTIC is set and the fp32-table reduce sums in an "
+                "order that depends on timing (its LDS sum is a double atomic); deterministic mode serves fp16 tables");
+    const int det = dtype == FOC_F16 && det_on ? (det_on == 2 ? 2 : 1) : 0;
     {
-        const int rc0 = gb_check(B, D, C, L, S, H, gridtype, interp, dtype, offsets_host, workspace_bytes);
+        const int rc0 = gb_check(B, D, C, L, S, H, gridtype, interp, dtype, offsets_host, workspace_bytes, det);
         if (rc0) return rc0;
     }
     GeLevels lv;
@@ -1821,8 +1946,8 @@ static int gb_entry(const void *grad, const float *inputs, const int32_t *offset
     const uint32_t fact_mask = gb_fact_mask(L, lv, offsets_host, gridtype, ac, dtype);
     GbSizes sz;
     for (uint32_t l = 0; l < GE_MAX_LEVELS; l++) sz.size[l] = l < L ? (uint32_t)(offsets_host[l + 1] - offsets_host[l]) : 0u;
-    int rc = dtype == FOC_F32 ? gb_run<float>(grad, inputs, offsets, grad_embeddings, B, L, lv, gridtype, ac, interp, bl, workspace, counted, 0u, sz, st)
-                              : gb_run<__half>(grad, inputs, offsets, grad_embeddings, B, L, lv, gridtype, ac, interp, bl, workspace, counted, fact_mask, sz, st);
+    int rc = dtype == FOC_F32 ? gb_run<float>(grad, inputs, offsets, grad_embeddings, B, L, lv, gridtype, ac, interp, bl, workspace, counted, 0u, sz, 0, st)
+                              : gb_run<__half>(grad, inputs, offsets, grad_embeddings, B, L, lv, gridtype, ac, interp, bl, workspace, counted, fact_mask, sz, det, st);
     if (rc) return rc;
     if (dy_dx && grad_inputs) {
         const uint32_t g = foc_grid_1d((uint64_t)B * 3, 256);
@@ -1866,6 +1991,7 @@ int foc_grad_total_variation(const void *inputs, const void *embeddings, void *g
     FOC_REQUIRE(inputs && embeddings && grad && offsets, FOC_E_INVALID, "grad_total_variation: null pointer");
     FOC_REQUIRE(dtype == FOC_F32 || dtype == FOC_F16, FOC_E_DTYPE, "grad_total_variation: dtype must be FOC_F32 or FOC_F16");
     FOC_REQUIRE(L >= 1 && L <= GE_MAX_LEVELS, FOC_E_INVALID, "grad_total_variation: L must be in [1,%d]", GE_MAX_LEVELS);
+    FOC_REQUIRE(!foc_opt(FOC_OPT_DETERMINISTIC), FOC_E_INVALID, "grad_total_variation: FOC_DETERMINISTIC is set and this entry point scatters with float atomics (arrival order)");
     if (B == 0) return FOC_OK;
     GeLevels lv;
     ge_make_levels(L, S, H, lv);

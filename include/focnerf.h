@@ -47,10 +47,42 @@ int         foc_abi_version(void);
 const char *foc_last_error(void);
 /* Tuning / test switches (csrc/common.h FocOpt): ints with a default, initialised once from the environment variable of the same name
  * (FOC_MLP_BWD_FUSED, FOC_FIELD_FWD_FUSED, FOC_GB_MERGE_MAX_RES, FOC_GB_FACTORED, FOC_GB_TAIL_SPLIT, FOC_GRID_FUSE_SMALL, FOC_GRID_PAIRS, FOC_GRID_FAST,
- * FOC_MARCH_SERIAL, FOC_MARCH_RAYS_ROW_MAX, FOC_OCC_MARCH_FORM, FOC_OCC_SAMPLE_MAJOR, FOC_OCC_FIELD_PIECE — INTEGRATION.md has the table)
- * and changeable at run time; no entry point reads the environment per call. Unknown name: FOC_E_INVALID. */
+ * FOC_MARCH_SERIAL, FOC_MARCH_RAYS_ROW_MAX, FOC_OCC_MARCH_FORM, FOC_OCC_SAMPLE_MAJOR, FOC_OCC_FIELD_PIECE, FOC_DETERMINISTIC — INTEGRATION.md has
+ * the table) and changeable at run time; no entry point reads the environment per call. Unknown name: FOC_E_INVALID. */
 int foc_set_option(const char *name, int value);
 int foc_get_option(const char *name, int *value);
+/* Deterministic mode — the option FOC_DETERMINISTIC (default 0; Python: focnerf_amd.use_deterministic / is_deterministic / deterministic).
+ *
+ * DEFAULT MODE. Five kinds of sums take their addends in arrival order, so their last bits change from run to run:
+ *   (a) foc_grid_encode_backward_binned[_counted], fp16 tables: inside a 32768-record chunk the sum is exact (2^24-scaled 64-bit
+ *       integers) and order-free, but the chunks of one (level, 8192-row segment) slot are each rounded to half and meet in
+ *       grad_embeddings through half2 atomics; fp32 tables: the in-chunk sum is a double LDS atomic, the chunks meet through fp32 atomics;
+ *   (b) foc_background_backward: fp32 atomics into grad_embeddings;
+ *   (c) foc_grid_update_apply: a double atomic across workgroups feeds the mean, hence the threshold and the bitfield;
+ *   (d) foc_ffmlp_backward[_planar] on its two-kernel path (hidden_dim 128 / 256, the general activations, FOC_MLP_BWD_FUSED=0): the
+ *       split-K weight gradient is summed with fp32 atomics;
+ *   (e) foc_grid_encode_backward (every shape, D = 4 / 5 included) and foc_grad_total_variation: scattered float atomics.
+ * Every other entry point gives the same bits on every run in both modes: the forwards and all inference, the marches and their
+ * ray order, the composites and tails, the fused MLP / colour-head backward (per-workgroup slots, summed in workgroup order),
+ * the background weight gradient, the occupancy-grid scatter (atomicMax).
+ *
+ * FOC_DETERMINISTIC != 0. Same GPU model, same build, same inputs and same option values give the same bits. Per entry point:
+ *   (a) fp16 tables: DETERMINISTIC FORM. Per table element the result is the exact integer sum S of ALL the slot's 2^24-scaled addends,
+ *       converted once: (_Float16)(float)((double)S / 2^24), NaN for a row that received an inf / NaN addend. A slot with one chunk
+ *       gives the default mode's bits; a slot with several is rounded once instead of once per chunk and once per add. The chunks
+ *       meet through 64-bit integer atomics into a zeroed int64 image in the workspace (1; integer addition is associative) or through
+ *       per-chunk planes summed in a second pass (2, kept for measurements) — identical results. The addends depend on the sample
+ *       ORDER where runs of equal cells are merged (levels up to FOC_GB_MERGE_MAX_RES), never on timing; with FOC_GB_MERGE_MAX_RES=0
+ *       the result is also independent of the order of the samples.
+ *       fp32 tables: REFUSED (FOC_E_INVALID).
+ *   (b) DETERMINISTIC FORM: the addends are summed as 2^-40-scaled 64-bit integers in a row table in the workspace (exact from 2^-16
+ *       up, |sum| < 2^23), each row's total is added to grad_embeddings once; at most 2^26 rays per call.
+ *   (c) DETERMINISTIC FORM: per-workgroup partial sums, added in workgroup order.
+ *   (d) DETERMINISTIC FORM: at most 32 split-K workgroups per layer, each with its own image of the blob, summed in workgroup order.
+ *   (e) REFUSED (FOC_E_INVALID before any launch; the message names the entry point and FOC_DETERMINISTIC).
+ * The *_workspace_bytes functions of (a) - (d) return a size that is sufficient under the CURRENT value of the option (larger when it
+ * is set); the entry points check `workspace_bytes` against the value they run under and refuse a buffer that is too small. The mode
+ * adds no host synchronisation and no memset node: it captures into a HIP graph like the default mode. */
 /* Which device an entry point makes current for its call (host-only query of the rule, for tests): a non-null stream's device; for the
  * NULL stream (it exists on every device) the device the first pointer argument lives on; else the current device. -1 = unknown. */
 int foc_guard_pick_device(int stream_is_null, int stream_device, int pointer_device, int current_device);
@@ -282,8 +314,13 @@ int foc_grid_encode_backward(const void *grad, const float *inputs, const void *
 
 /* Same result as foc_grid_encode_backward for D = 3, C = 2 tables, computed WITHOUT scattered atomics:
  * the (row, w*grad) contributions are partitioned by 8192-row table segment and summed per segment in
- * LDS (fp32), then added to grad_embeddings with contiguous atomics. Scattered memory-side atomics cap
+ * LDS, then added to grad_embeddings with contiguous atomics. Scattered memory-side atomics cap
  * the atomic entry point at ~2x10^10 corner updates/s on MI355X; this path streams instead.
+ * Order: a segment's records are summed in chunks of 32768. fp16 tables: the sum inside a chunk is exact (2^24-scaled 64-bit integers)
+ * and independent of order; the chunks of a segment are rounded to half each and meet in grad_embeddings through half2 atomics in
+ * arrival order, so the result repeats only to a few half ulps — unless FOC_DETERMINISTIC is set ("Deterministic mode" above: one
+ * exact integer total per element, rounded once; the workspace is then larger). fp32 tables: double LDS atomics inside a chunk, fp32
+ * atomics across chunks; order-dependent, and refused under FOC_DETERMINISTIC.
  * workspace: device scratch of foc_grid_encode_backward_workspace_bytes() bytes (0 = shape not
  * supported: call foc_grid_encode_backward). offsets_host (L+1 ints in HOST memory) is required.
  * Extension: no reference binding (the reference has only the atomic kernel, gridencoder.cu:248-340). */
@@ -792,7 +829,7 @@ int foc_background_forward(const float *rays_o, const float *rays_d, const float
                            const int32_t *offsets, float per_level_scale_log2, uint32_t base_resolution, const void *weights, void *rgb,
                            void *stream);
 /* grad_rgb [N,3] fp16 -> grad_embeddings [rows,2] fp32 (ADDED to: the caller zero-fills; fp32 atomics, so a row's sum depends on the
- * order of arrival) and grad_weights fp32 [64*32 + 16*64] (written whole; padding entries 0; a fixed-order reduction: the same bits on
+ * order of arrival — FOC_DETERMINISTIC: integer sums in a row table of the (then larger) workspace, one add per row) and grad_weights fp32 [64*32 + 16*64] (written whole; padding entries 0; a fixed-order reduction: the same bits on
  * every run). workspace: foc_background_backward_workspace_bytes(N) bytes, no zero fill; `workspace_bytes` = its size, a smaller
  * buffer is refused. The rays take no gradient. */
 uint64_t foc_background_backward_workspace_bytes(uint32_t N);
