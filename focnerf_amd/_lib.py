@@ -59,6 +59,18 @@ class FocOccTrainNode(ctypes.Structure):
     ]
 
 
+class FocOccTrainObject(ctypes.Structure):
+    """include/focnerf.h `FocOccTrainObject`, field for field: what an object-conditioned network adds to the node, beside it."""
+    _fields_ = [
+        ("struct_bytes", u32),
+        ("input_pad", f32),
+        ("obj_feat", c_vp),
+        ("ray_sumsq", c_vp),
+        ("grad_sumsq", c_vp),
+        ("grad_obj", c_vp),
+    ]
+
+
 # name -> (restype, [argtypes]) — one entry per declaration in include/focnerf.h
 SIGNATURES = {
     "foc_abi_version": (i32, []),
@@ -82,6 +94,10 @@ SIGNATURES = {
     "foc_occ_train_backward": (i32, [ctypes.POINTER(FocOccTrainNode), c_vp]),
     "foc_occ_train_forward_pad31": (i32, [ctypes.POINTER(FocOccTrainNode), f32, c_vp]),
     "foc_occ_train_backward_pad31": (i32, [ctypes.POINTER(FocOccTrainNode), f32, c_vp]),
+    "foc_occ_train_forward_obj": (i32, [ctypes.POINTER(FocOccTrainNode), ctypes.POINTER(FocOccTrainObject), c_vp]),
+    "foc_occ_train_backward_obj": (i32, [ctypes.POINTER(FocOccTrainNode), ctypes.POINTER(FocOccTrainObject), c_vp]),
+    "foc_occ_tail_forward_sumsq": (i32, [c_vp, c_vp, u32, c_vp, c_vp, u32, u32, f32, f32, c_vp, f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "foc_occ_tail_backward_sumsq": (i32, [c_vp, c_vp, c_vp, c_vp, u32, c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, f32, f32, c_vp, f32, c_vp, c_vp, c_vp, c_vp]),
     "foc_occ_tail_forward": (i32, [c_vp, c_vp, u32, c_vp, c_vp, u32, u32, f32, f32, c_vp, f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "foc_occ_tail_backward": (i32, [c_vp, c_vp, c_vp, c_vp, u32, c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, f32, f32, c_vp, f32, c_vp, c_vp, c_vp]),
     "foc_march_rays_train_scratch_bytes": (u64, [u32, u32]),
@@ -102,6 +118,9 @@ SIGNATURES = {
     "foc_occ_render_step_pad31": (i32, [u32, u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, f32, f32, u32, u32, u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                         c_vp, c_vp, c_vp, u32, f32, u32, c_vp, u32, c_vp, u32, u32, c_vp, f32, c_vp, c_vp, c_vp, c_vp, u32, c_vp, u32, u32, f32,
                                         c_vp]),
+    "foc_occ_render_step_pad": (i32, [u32, u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, f32, f32, u32, u32, u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                      c_vp, c_vp, c_vp, u32, f32, u32, c_vp, u32, c_vp, u32, u32, c_vp, f32, c_vp, c_vp, c_vp, c_vp, u32, c_vp, u32, u32, f32,
+                                      c_vp]),
     "foc_grid_encode_forward": (i32, [c_vp, c_vp, c_vp, c_vp, u32, u32, u32, u32, f32, u32, c_vp, u32, i32, u32,
                                       i32, c_vp, c_vp]),
     "foc_grid_encode_forward_bl": (i32, [c_vp, c_vp, c_vp, c_vp, u32, u32, u32, u32, f32, u32, c_vp, u32, i32, u32,

@@ -43,6 +43,7 @@ uint64_t foc_occ_render_step_scratch_bytes(uint32_t n_rays) {
 }
 
 // pad31 (foc_occ_render_step_pad31): the field through foc_nerf_field_inference_pad31, column 31 of the colour input = input_pad
+// pad47 (foc_occ_render_step_pad): the field through foc_nerf_field_inference_pad, column 47 of the object-conditioned colour input = input_pad
 static int occ_render_step(uint32_t n_alive, uint32_t n_step, const int32_t *rays_alive, int32_t *rays_alive_out, int32_t *count,
                            float *rays_t, const float *rays_o, const float *rays_d, float bound, float dt_gamma, uint32_t max_steps,
                            uint32_t C, uint32_t H, const uint8_t *grid, const float *nears, const float *fars, const float *noises,
@@ -50,7 +51,7 @@ static int occ_render_step(uint32_t n_alive, uint32_t n_step, const int32_t *ray
                            const void *embeddings, const int32_t *offsets, const int32_t *offsets_host, uint32_t L, float S, uint32_t base_res,
                            const void *sigma_weights, uint32_t sigma_layers, const void *color_weights, uint32_t color_layers, uint32_t activation,
                            const void *obj_feat, float T_thresh, float *weights_sum, float *depth, float *image, void *scratch, uint32_t flags, int32_t *deaths,
-                           uint32_t deaths_base, uint32_t deaths_len, float input_pad, bool pad31, void *stream) {
+                           uint32_t deaths_base, uint32_t deaths_len, float input_pad, bool pad31, bool pad47, void *stream) {
     FocDeviceGuard foc_guard_(stream, rays_alive);
     FOC_REQUIRE(count, FOC_E_INVALID, "occ_render_step: null pointer");
     if (pad31) {                                            // refused before anything is enqueued
@@ -58,6 +59,12 @@ static int occ_render_step(uint32_t n_alive, uint32_t n_step, const int32_t *ray
         FOC_REQUIRE(!obj_feat, FOC_E_INVALID, "occ_render_step_pad31: input_pad is column 31 of the 32-wide colour input, obj_feat must be NULL");
         FOC_REQUIRE(input_pad == 0.0f || lk == 12 || lk == 13 || lk == 22 || lk == 23 || lk == 33, FOC_E_INVALID,
                     "occ_render_step_pad31: a pad needs (sigma_layers, color_layers) in (1,2), (1,3), (2,2), (2,3), (3,3) (got %u, %u)", sigma_layers, color_layers);
+    }
+    if (pad47) {                                            // refused before anything is enqueued
+        const uint32_t lk = sigma_layers * 10 + color_layers;
+        FOC_REQUIRE(obj_feat || input_pad == 0.0f, FOC_E_INVALID, "occ_render_step_pad: input_pad is column 47 of the 48-wide colour input, it needs obj_feat");
+        FOC_REQUIRE(input_pad == 0.0f || lk == 12 || lk == 13 || lk == 22 || lk == 23 || lk == 33, FOC_E_INVALID,
+                    "occ_render_step_pad: a pad needs (sigma_layers, color_layers) in (1,2), (1,3), (2,2), (2,3), (3,3) (got %u, %u)", sigma_layers, color_layers);
     }
     hipStream_t st = (hipStream_t)stream;
     if (n_alive == 0) return foc_zero_async(count, sizeof(int32_t), st) == hipSuccess ? FOC_OK : FOC_E_LAUNCH;
@@ -93,6 +100,9 @@ static int occ_render_step(uint32_t n_alive, uint32_t n_step, const int32_t *ray
         if (rc) return rc;
         rc = pad31 ? foc_nerf_field_inference_pad31(planes, 1, dirs + 3 * m0, 1, 0, mc, sigma_weights, sigma_layers, color_weights, color_layers, 64, activation,
                                                     mc, sigma + m0, rgb + 3 * m0, obj_feat, input_pad, stream)
+           : (pad47 && input_pad != 0.0f)
+                   ? foc_nerf_field_inference_pad(planes, 1, dirs + 3 * m0, 1, 0, mc, sigma_weights, sigma_layers, color_weights, color_layers, 64, activation, mc,
+                                                  sigma + m0, rgb + 3 * m0, obj_feat, input_pad, stream)
                    : foc_nerf_field_inference(planes, 1, dirs + 3 * m0, 1, 0, mc, sigma_weights, sigma_layers, color_weights, color_layers, 64, activation, mc,
                                               sigma + m0, rgb + 3 * m0, obj_feat, stream);
         if (rc) return rc;
@@ -113,7 +123,7 @@ int foc_occ_render_step(uint32_t n_alive, uint32_t n_step, const int32_t *rays_a
                         uint32_t deaths_len, void *stream) {
     return occ_render_step(n_alive, n_step, rays_alive, rays_alive_out, count, rays_t, rays_o, rays_d, bound, dt_gamma, max_steps, C, H, grid, nears, fars, noises,
                            samples, planes, sigma, rgb, embeddings, offsets, offsets_host, L, S, base_res, sigma_weights, sigma_layers, color_weights, color_layers,
-                           activation, obj_feat, T_thresh, weights_sum, depth, image, scratch, flags, deaths, deaths_base, deaths_len, 0.0f, false, stream);
+                           activation, obj_feat, T_thresh, weights_sum, depth, image, scratch, flags, deaths, deaths_base, deaths_len, 0.0f, false, false, stream);
 }
 
 int foc_occ_render_step_pad31(uint32_t n_alive, uint32_t n_step, const int32_t *rays_alive, int32_t *rays_alive_out, int32_t *count,
@@ -126,7 +136,20 @@ int foc_occ_render_step_pad31(uint32_t n_alive, uint32_t n_step, const int32_t *
                               uint32_t deaths_base, uint32_t deaths_len, float input_pad, void *stream) {
     return occ_render_step(n_alive, n_step, rays_alive, rays_alive_out, count, rays_t, rays_o, rays_d, bound, dt_gamma, max_steps, C, H, grid, nears, fars, noises,
                            samples, planes, sigma, rgb, embeddings, offsets, offsets_host, L, S, base_res, sigma_weights, sigma_layers, color_weights, color_layers,
-                           activation, obj_feat, T_thresh, weights_sum, depth, image, scratch, flags, deaths, deaths_base, deaths_len, input_pad, true, stream);
+                           activation, obj_feat, T_thresh, weights_sum, depth, image, scratch, flags, deaths, deaths_base, deaths_len, input_pad, true, false, stream);
+}
+
+int foc_occ_render_step_pad(uint32_t n_alive, uint32_t n_step, const int32_t *rays_alive, int32_t *rays_alive_out, int32_t *count,
+                            float *rays_t, const float *rays_o, const float *rays_d, float bound, float dt_gamma, uint32_t max_steps,
+                            uint32_t C, uint32_t H, const uint8_t *grid, const float *nears, const float *fars, const float *noises,
+                            float *samples, void *planes, float *sigma, float *rgb,
+                            const void *embeddings, const int32_t *offsets, const int32_t *offsets_host, uint32_t L, float S, uint32_t base_res,
+                            const void *sigma_weights, uint32_t sigma_layers, const void *color_weights, uint32_t color_layers, uint32_t activation,
+                            const void *obj_feat, float T_thresh, float *weights_sum, float *depth, float *image, void *scratch, uint32_t flags, int32_t *deaths,
+                            uint32_t deaths_base, uint32_t deaths_len, float input_pad, void *stream) {
+    return occ_render_step(n_alive, n_step, rays_alive, rays_alive_out, count, rays_t, rays_o, rays_d, bound, dt_gamma, max_steps, C, H, grid, nears, fars, noises,
+                           samples, planes, sigma, rgb, embeddings, offsets, offsets_host, L, S, base_res, sigma_weights, sigma_layers, color_weights, color_layers,
+                           activation, obj_feat, T_thresh, weights_sum, depth, image, scratch, flags, deaths, deaths_base, deaths_len, input_pad, false, true, stream);
 }
 
 } // extern "C"

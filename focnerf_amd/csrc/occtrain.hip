@@ -31,26 +31,31 @@ __device__ __forceinline__ OtRay ot_ray(const int32_t *__restrict__ rays, uint32
 
 #define OT_PAD_BLOCKS 64u
 
+// CRIT (foc_occ_tail_forward_sumsq): also ray_sumsq[ray] = sum of exp(h0)^2 over ALL of the ray's samples, those behind the sample at
+// which the composite stopped included (0 for a ray that did not fit): lane l sums samples l, l + 64, ... in order, then one wave_sum.
+template <bool CRIT>
 __global__ void __launch_bounds__(256) k_occ_tail_fwd(const _Float16 *__restrict__ h, const _Float16 *__restrict__ c, uint32_t c_ld,
                                                       const float *__restrict__ deltas, const int32_t *__restrict__ rays, uint32_t M, uint32_t N,
                                                       float T_thresh, float density_scale, const float *__restrict__ bg_ray, float bg_scalar,
                                                       const float *__restrict__ nears, const float *__restrict__ fars,
                                                       float *__restrict__ weights_sum, float *__restrict__ image_raw, float *__restrict__ image,
-                                                      float *__restrict__ depth) {
+                                                      float *__restrict__ depth, float *__restrict__ ray_sumsq) {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t n = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (n >= N) return;
     const OtRay ry = ot_ray(rays, n, M);
-    float r = 0, g = 0, b = 0, ws = 0, d = 0;
+    float r = 0, g = 0, b = 0, ws = 0, d = 0, sq = 0;
     if (ry.fits) {
         float T_carry = 1.0f, t_carry = 0.0f;
-        for (uint32_t base = 0; base < ry.count; base += 64) {
+        uint32_t base = 0;
+        for (; base < ry.count; base += 64) {
             const uint32_t i = base + lane;
             const bool valid = i < ry.count;
             float sigma = 0, dt0 = 0, dt1 = 0, c0 = 0, c1 = 0, c2 = 0;
             if (valid) {
                 const uint64_t s = (uint64_t)ry.offset + i;
                 sigma = expf((float)h[s * 16]);                              // k_head_fwd
+                if constexpr (CRIT) sq = fmaf(sigma, sigma, sq);
                 if (density_scale != 1.0f) sigma = density_scale * sigma;
                 const float2 dl = *reinterpret_cast<const float2 *>(deltas + s * 2);
                 dt0 = dl.x; dt1 = dl.y;
@@ -73,9 +78,15 @@ __global__ void __launch_bounds__(256) k_occ_tail_fwd(const _Float16 *__restrict
             r = fmaf(w, c0, r); g = fmaf(w, c1, g); b = fmaf(w, c2, b);
             d = fmaf(w, tsum, d);
             ws += w;
-            if (term) break;
+            if (term) { base += 64; break; }
             T_carry = __shfl(T_after, 63, 64);
             t_carry = __shfl(tsum, 63, 64);
+        }
+        if constexpr (CRIT) {                                  // the samples behind the stop: the penalty is on the density, not on the composite
+            for (; base < ry.count; base += 64) {
+                if (base + lane < ry.count) { const float e = expf((float)h[((uint64_t)ry.offset + base + lane) * 16]); sq = fmaf(e, e, sq); }
+            }
+            sq = wave_sum(sq);
         }
         r = wave_sum(r); g = wave_sum(g); b = wave_sum(b); ws = wave_sum(ws); d = wave_sum(d);
     }
@@ -89,16 +100,21 @@ __global__ void __launch_bounds__(256) k_occ_tail_fwd(const _Float16 *__restrict
         image[k * 3] = r + rest * b0; image[k * 3 + 1] = g + rest * b1; image[k * 3 + 2] = b + rest * b2;
         const float nr = nears[k], dd = d - nr;
         depth[k] = (dd < 0.0f ? 0.0f : dd) / (fars[k] - nr);
+        if constexpr (CRIT) ray_sumsq[k] = sq;
     }
 }
 
 // grad_image [N,3] (of the FINAL image), grad_ws [N] or NULL -> grad_c [M,c_ld] fp16, grad_h0 [M] fp16 (every row written).
+// CRIT (foc_occ_tail_backward_sumsq): grad_sumsq [N] is the gradient of the forward's ray_sumsq; 2 exp(h0) grad_sumsq[ray] joins the
+// density path before trunc_exp's factor on EVERY row of a ray that fits — the rows behind the stop carry that term alone.
+template <bool CRIT>
 __global__ void __launch_bounds__(256) k_occ_tail_bwd(const float *__restrict__ grad_image, const float *__restrict__ grad_ws,
                                                       const _Float16 *__restrict__ h, const _Float16 *__restrict__ c, uint32_t c_ld,
                                                       const float *__restrict__ deltas, const int32_t *__restrict__ rays, const int32_t *__restrict__ counter,
                                                       const float *__restrict__ weights_sum, const float *__restrict__ image_raw, uint32_t M, uint32_t N,
                                                       float T_thresh, float density_scale, const float *__restrict__ bg_ray, float bg_scalar,
-                                                      _Float16 *__restrict__ grad_c, _Float16 *__restrict__ grad_h0) {
+                                                      _Float16 *__restrict__ grad_c, _Float16 *__restrict__ grad_h0,
+                                                      const float *__restrict__ grad_sumsq) {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t n = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (blockIdx.x >= (N + 3u) / 4u) {
@@ -133,6 +149,14 @@ __global__ void __launch_bounds__(256) k_occ_tail_bwd(const float *__restrict__ 
     const float gws = (grad_ws ? grad_ws[index] : 0.0f) - ((g0 * b0 + g1 * b1) + g2 * b2);
     const float r_final = image_raw[index * 3], g_final = image_raw[index * 3 + 1], b_final = image_raw[index * 3 + 2];
     const float ws_term = gws * (1 - weights_sum[index]);
+    float gsq2 = 0.0f;
+    if constexpr (CRIT) gsq2 = 2.0f * grad_sumsq[index];      // d(sum sigma^2) / d sigma = 2 sigma
+    // the criterion's share of a row's grad_h0: 2 exp(x) grad_sumsq * exp(clamp(x, -15, 15))
+    auto crit_only = [&](uint64_t s) {
+        const float x = (float)h[s * 16];
+        const float xc = x < -15.0f ? -15.0f : (x > 15.0f ? 15.0f : x);
+        return gsq2 * expf(x) * (xc != x ? expf(xc) : expf(x));
+    };
     float T_carry = 1.0f;
     float r_carry = 0, g_carry = 0, b_carry = 0;
     bool dead = false;                                         // wave-uniform: the ray became opaque in an earlier block of 64
@@ -140,11 +164,12 @@ __global__ void __launch_bounds__(256) k_occ_tail_bwd(const float *__restrict__ 
         const uint32_t i = base + lane;
         const bool valid = i < ry.count;
         const uint64_t s = (uint64_t)ry.offset + (valid ? i : 0);
-        if (dead) { if (valid) store(s, 0.0f, 0.0f, 0.0f, 0.0f); continue; }
-        float sigma = 0, e0 = 0, dt0 = 0, c0 = 0, c1 = 0, c2 = 0;
+        if (dead) { if (valid) store(s, CRIT ? crit_only(s) : 0.0f, 0.0f, 0.0f, 0.0f); continue; }
+        float sigma = 0, e0 = 0, dt0 = 0, c0 = 0, c1 = 0, c2 = 0, e_raw = 0;
         if (valid) {
             const float x = (float)h[s * 16];
             e0 = expf(x);
+            e_raw = e0;
             sigma = density_scale != 1.0f ? density_scale * e0 : e0;
             dt0 = deltas[s * 2];
             const uint2 raw = *reinterpret_cast<const uint2 *>(c + s * c_ld);
@@ -176,10 +201,11 @@ __global__ void __launch_bounds__(256) k_occ_tail_bwd(const float *__restrict__ 
             acc += ws_term;
             float gs = dt0 * acc;
             if (density_scale != 1.0f) gs = density_scale * gs;       // through `density_scale * sigmas`
+            if constexpr (CRIT) gs = fmaf(gsq2, e_raw, gs);
             // k_rgb_bwd: half(g) (1 - y) y;  k_head_bwd: grad_sigma * exp(clamp(h0))
             const float q0 = (float)(_Float16)(g0 * w), q1 = (float)(_Float16)(g1 * w), q2 = (float)(_Float16)(g2 * w);
             store(s, gs * e0, q0 * (1.0f - c0) * c0, q1 * (1.0f - c1) * c1, q2 * (1.0f - c2) * c2);
-        } else if (valid) store(s, 0.0f, 0.0f, 0.0f, 0.0f);
+        } else if (valid) store(s, CRIT ? gsq2 * e_raw * e0 : 0.0f, 0.0f, 0.0f, 0.0f);
         if (term) { dead = true; continue; }
         T_carry = __shfl(T_after, 63, 64);
         r_carry = __shfl(r_acc, 63, 64); g_carry = __shfl(g_acc, 63, 64); b_carry = __shfl(b_acc, 63, 64);
@@ -188,31 +214,67 @@ __global__ void __launch_bounds__(256) k_occ_tail_bwd(const float *__restrict__ 
 
 extern "C" {
 
+// ray_sumsq / grad_sumsq NULL: the plain kernels (foc_occ_tail_forward / _backward); `who` names the entry point in messages
+static int occ_tail_forward(const char *who, const void *h, const void *c, uint32_t c_width, const float *deltas, const int32_t *rays, uint32_t M, uint32_t N,
+                            float T_thresh, float density_scale, const float *bg_ray, float bg_scalar, const float *nears, const float *fars,
+                            float *weights_sum, float *image_raw, float *image, float *depth, float *ray_sumsq, void *stream) {
+    FocDeviceGuard foc_guard_(stream, h);
+    if (N == 0) return FOC_OK;
+    FOC_REQUIRE(c_width == 16 || c_width == 4, FOC_E_INVALID, "%s: c_width must be 16 or 4 (got %u)", who, c_width);
+    FOC_REQUIRE(rays && nears && fars && weights_sum && image_raw && image && depth && (M == 0 || (h && c && deltas)), FOC_E_INVALID, "%s: null pointer", who);
+    auto kern = ray_sumsq ? k_occ_tail_fwd<true> : k_occ_tail_fwd<false>;
+    hipLaunchKernelGGL(kern, dim3(foc_div_up(N, 4)), dim3(256), 0, (hipStream_t)stream, (const _Float16 *)h,
+                       (const _Float16 *)c, c_width, deltas, rays, M, N, T_thresh, density_scale, bg_ray, bg_scalar, nears, fars, weights_sum, image_raw, image, depth,
+                       ray_sumsq);
+    FOC_CHECK_LAUNCH(who);
+    return FOC_OK;
+}
+
+static int occ_tail_backward(const char *who, const float *grad_image, const float *grad_ws, const void *h, const void *c, uint32_t c_width, const float *deltas,
+                             const int32_t *rays, const int32_t *counter, const float *weights_sum, const float *image_raw, uint32_t M, uint32_t N,
+                             float T_thresh, float density_scale, const float *bg_ray, float bg_scalar, void *grad_c, void *grad_h0, const float *grad_sumsq,
+                             void *stream) {
+    FocDeviceGuard foc_guard_(stream, grad_image);
+    if (N == 0 || M == 0) return FOC_OK;
+    FOC_REQUIRE(c_width == 16 || c_width == 4, FOC_E_INVALID, "%s: c_width must be 16 or 4 (got %u)", who, c_width);
+    FOC_REQUIRE(grad_image && h && c && deltas && rays && counter && weights_sum && image_raw && grad_c && grad_h0, FOC_E_INVALID, "%s: null pointer", who);
+    auto kern = grad_sumsq ? k_occ_tail_bwd<true> : k_occ_tail_bwd<false>;
+    hipLaunchKernelGGL(kern, dim3(foc_div_up(N, 4) + OT_PAD_BLOCKS), dim3(256), 0, (hipStream_t)stream, grad_image,
+                       grad_ws, (const _Float16 *)h, (const _Float16 *)c, c_width, deltas, rays, counter, weights_sum, image_raw, M, N, T_thresh, density_scale, bg_ray,
+                       bg_scalar, (_Float16 *)grad_c, (_Float16 *)grad_h0, grad_sumsq);
+    FOC_CHECK_LAUNCH(who);
+    return FOC_OK;
+}
+
 int foc_occ_tail_forward(const void *h, const void *c, uint32_t c_width, const float *deltas, const int32_t *rays, uint32_t M, uint32_t N,
                          float T_thresh, float density_scale, const float *bg_ray, float bg_scalar, const float *nears, const float *fars,
                          float *weights_sum, float *image_raw, float *image, float *depth, void *stream) {
-    FocDeviceGuard foc_guard_(stream, h);
-    if (N == 0) return FOC_OK;
-    FOC_REQUIRE(c_width == 16 || c_width == 4, FOC_E_INVALID, "occ_tail_forward: c_width must be 16 or 4 (got %u)", c_width);
-    FOC_REQUIRE(rays && nears && fars && weights_sum && image_raw && image && depth && (M == 0 || (h && c && deltas)), FOC_E_INVALID, "occ_tail_forward: null pointer");
-    hipLaunchKernelGGL(k_occ_tail_fwd, dim3(foc_div_up(N, 4)), dim3(256), 0, (hipStream_t)stream, (const _Float16 *)h, (const _Float16 *)c, c_width, deltas, rays,
-                       M, N, T_thresh, density_scale, bg_ray, bg_scalar, nears, fars, weights_sum, image_raw, image, depth);
-    FOC_CHECK_LAUNCH("occ_tail_forward");
-    return FOC_OK;
+    return occ_tail_forward("occ_tail_forward", h, c, c_width, deltas, rays, M, N, T_thresh, density_scale, bg_ray, bg_scalar, nears, fars, weights_sum, image_raw,
+                            image, depth, nullptr, stream);
 }
 
 int foc_occ_tail_backward(const float *grad_image, const float *grad_ws, const void *h, const void *c, uint32_t c_width, const float *deltas,
                           const int32_t *rays, const int32_t *counter, const float *weights_sum, const float *image_raw, uint32_t M, uint32_t N,
                           float T_thresh, float density_scale, const float *bg_ray, float bg_scalar, void *grad_c, void *grad_h0, void *stream) {
-    FocDeviceGuard foc_guard_(stream, grad_image);
-    if (N == 0 || M == 0) return FOC_OK;
-    FOC_REQUIRE(c_width == 16 || c_width == 4, FOC_E_INVALID, "occ_tail_backward: c_width must be 16 or 4 (got %u)", c_width);
-    FOC_REQUIRE(grad_image && h && c && deltas && rays && counter && weights_sum && image_raw && grad_c && grad_h0, FOC_E_INVALID, "occ_tail_backward: null pointer");
-    hipLaunchKernelGGL(k_occ_tail_bwd, dim3(foc_div_up(N, 4) + OT_PAD_BLOCKS), dim3(256), 0, (hipStream_t)stream, grad_image, grad_ws, (const _Float16 *)h,
-                       (const _Float16 *)c, c_width, deltas, rays, counter, weights_sum, image_raw, M, N, T_thresh, density_scale, bg_ray, bg_scalar,
-                       (_Float16 *)grad_c, (_Float16 *)grad_h0);
-    FOC_CHECK_LAUNCH("occ_tail_backward");
-    return FOC_OK;
+    return occ_tail_backward("occ_tail_backward", grad_image, grad_ws, h, c, c_width, deltas, rays, counter, weights_sum, image_raw, M, N, T_thresh, density_scale,
+                             bg_ray, bg_scalar, grad_c, grad_h0, nullptr, stream);
+}
+
+int foc_occ_tail_forward_sumsq(const void *h, const void *c, uint32_t c_width, const float *deltas, const int32_t *rays, uint32_t M, uint32_t N,
+                               float T_thresh, float density_scale, const float *bg_ray, float bg_scalar, const float *nears, const float *fars,
+                               float *weights_sum, float *image_raw, float *image, float *depth, float *ray_sumsq, void *stream) {
+    FOC_REQUIRE(ray_sumsq || N == 0, FOC_E_INVALID, "occ_tail_forward_sumsq: null ray_sumsq");
+    return occ_tail_forward("occ_tail_forward_sumsq", h, c, c_width, deltas, rays, M, N, T_thresh, density_scale, bg_ray, bg_scalar, nears, fars, weights_sum,
+                            image_raw, image, depth, ray_sumsq, stream);
+}
+
+int foc_occ_tail_backward_sumsq(const float *grad_image, const float *grad_ws, const void *h, const void *c, uint32_t c_width, const float *deltas,
+                                const int32_t *rays, const int32_t *counter, const float *weights_sum, const float *image_raw, uint32_t M, uint32_t N,
+                                float T_thresh, float density_scale, const float *bg_ray, float bg_scalar, void *grad_c, void *grad_h0,
+                                const float *grad_sumsq, void *stream) {
+    FOC_REQUIRE(grad_sumsq || N == 0 || M == 0, FOC_E_INVALID, "occ_tail_backward_sumsq: null grad_sumsq");
+    return occ_tail_backward("occ_tail_backward_sumsq", grad_image, grad_ws, h, c, c_width, deltas, rays, counter, weights_sum, image_raw, M, N, T_thresh,
+                             density_scale, bg_ray, bg_scalar, grad_c, grad_h0, grad_sumsq, stream);
 }
 
 // ---------------------------------------------------------------- the node as one call each way
@@ -283,6 +345,86 @@ static int occ_train_backward(const FocOccTrainNode *n, float input_pad, bool pa
                                                n->grad_h, n->grad_w_color, n->mlp_workspace, n->mlp_workspace_bytes, n->c_width, nullptr, nullptr, input_pad, stream)
                : foc_color_head_backward(n->grad_c, n->h, n->sh_rows, 1, n->grad_h0, n->w_color, M, n->color_hidden, n->color_layers, n->color_activation, n->grad_h,
                                          n->grad_w_color, n->mlp_workspace, n->mlp_workspace_bytes, n->c_width, nullptr, nullptr, stream);
+    if (rc != FOC_OK) return rc;
+    rc = foc_ffmlp_backward_planar(n->grad_h, n->planes, n->w_sigma, M, n->sigma_input_dim, 16, n->sigma_hidden, n->sigma_layers, n->sigma_activation,
+                                   n->sigma_output_activation, 1, n->grad_planes, n->grad_w_sigma, n->mlp_workspace, n->mlp_workspace_bytes, stream);
+    if (rc != FOC_OK) return rc;
+    return (n->precounted ? foc_grid_encode_backward_binned_counted : foc_grid_encode_backward_binned)(
+        n->grad_planes, n->enc_in, n->embeddings, n->offsets, n->grad_embeddings, M, 3, 2, n->levels, n->per_level_scale_log2, n->base_resolution, nullptr, nullptr,
+        n->gridtype, n->align_corners, n->interp, n->table_dtype, 0, n->offsets_host, n->grid_workspace, n->grid_workspace_bytes, stream);
+}
+
+// ---------------------------------------------------------------- the node of an object-conditioned network (FocOccTrainObject beside the node)
+// The same sequence with the object arguments: the 48-wide colour head (foc_field_forward_train[_pad], foc_color_head_forward / _backward[_pad])
+// and, when the companion carries ray_sumsq / grad_sumsq, the tail that also sums sigma^2 per ray. Everything below is checked before the
+// first launch.
+static int ot_check_object(const FocOccTrainNode *n, const FocOccTrainObject *ob, const char *who) {
+    int rc = ot_check_node(n, who);
+    if (rc != FOC_OK) return rc;
+    FOC_REQUIRE(ob != nullptr, FOC_E_INVALID, "%s: null object", who);
+    FOC_REQUIRE(ob->struct_bytes == (uint32_t)sizeof(FocOccTrainObject), FOC_E_INVALID, "%s: object of %u bytes, this library's FocOccTrainObject has %zu", who,
+                ob->struct_bytes, sizeof(FocOccTrainObject));
+    FOC_REQUIRE(ob->obj_feat || ob->input_pad == 0.0f, FOC_E_INVALID, "%s: a pad (column 47 = %g) needs an object feature, obj_feat is NULL", who, (double)ob->input_pad);
+    FOC_REQUIRE(ob->obj_feat, FOC_E_INVALID, "%s: obj_feat is NULL (a network without an object feature takes foc_occ_train_forward / _backward)", who);
+    const uint32_t lk = n->sigma_layers * 10 + n->color_layers;
+    FOC_REQUIRE(lk == 12 || lk == 13 || lk == 22 || lk == 23 || lk == 33, FOC_E_INVALID,
+                "%s: (sigma_layers, color_layers) must be in (1,2), (1,3), (2,2), (2,3), (3,3) (got %u, %u)", who, n->sigma_layers, n->color_layers);
+    FOC_REQUIRE(n->sigma_input_dim == 32 && n->sigma_hidden == 64 && n->color_hidden == 64 && n->sigma_activation == n->color_activation &&
+                (n->sigma_activation == 0 || n->sigma_activation == 6) && n->sigma_output_activation == 6, FOC_E_INVALID,
+                "%s: the object node serves 32 -> 64 density and 48 -> 64 colour networks with one hidden activation, relu(0) or none(6)", who);
+    return FOC_OK;
+}
+
+int foc_occ_train_forward_obj(const FocOccTrainNode *n, const FocOccTrainObject *ob, void *stream) {
+    int rc = ot_check_object(n, ob, "occ_train_forward_obj");
+    if (rc != FOC_OK) return rc;
+    const uint32_t M = n->cap;
+    const bool pad = ob->input_pad != 0.0f;
+    rc = foc_march_rays_train_field(n->rays_o, n->rays_d, n->bitfield, n->bound, n->dt_gamma, n->max_steps, n->n_rays, n->cascade, n->grid_size, M, n->nears, n->fars,
+                                    n->enc_in, n->sh_rows, n->deltas, n->rays, n->counter, n->jitter, n->march_scratch, n->pad_align, n->aabb, n->min_near, stream);
+    if (rc != FOC_OK) return rc;
+    rc = foc_grid_encode_forward_counted(n->enc_in, n->embeddings, n->offsets, n->planes, M, 3, 2, n->levels, n->per_level_scale_log2, n->base_resolution, n->gridtype,
+                                         n->align_corners, n->interp, n->table_dtype, n->offsets_host, n->grid_workspace, n->grid_workspace_bytes, stream);
+    if (rc != FOC_OK) return rc;
+    if (foc_opt(FOC_OPT_FIELD_FWD_FUSED)) {
+        rc = pad ? foc_field_forward_train_pad(n->planes, n->w_sigma, n->sigma_layers, n->sh_rows, 1, n->w_color, n->color_layers, 64, n->sigma_activation, M, n->h,
+                                               n->c, n->c_width, ob->obj_feat, ob->input_pad, stream)
+                 : foc_field_forward_train(n->planes, n->w_sigma, n->sigma_layers, n->sh_rows, 1, n->w_color, n->color_layers, 64, n->sigma_activation, M, n->h, n->c,
+                                           n->c_width, ob->obj_feat, stream);
+        if (rc != FOC_OK) return rc;
+    } else {
+        rc = foc_ffmlp_forward_planar(n->planes, n->w_sigma, M, n->sigma_input_dim, 16, n->sigma_hidden, n->sigma_layers, n->sigma_activation, n->sigma_output_activation,
+                                      n->h, stream);
+        if (rc != FOC_OK) return rc;
+        rc = pad ? foc_color_head_forward_pad(n->h, n->sh_rows, 1, n->w_color, M, n->color_hidden, n->color_layers, n->color_activation, n->c, n->c_width, ob->obj_feat,
+                                              ob->input_pad, stream)
+                 : foc_color_head_forward(n->h, n->sh_rows, 1, n->w_color, M, n->color_hidden, n->color_layers, n->color_activation, n->c, n->c_width, ob->obj_feat,
+                                          stream);
+        if (rc != FOC_OK) return rc;
+    }
+    return ob->ray_sumsq ? foc_occ_tail_forward_sumsq(n->h, n->c, n->c_width, n->deltas, n->rays, M, n->n_rays, n->T_thresh, n->density_scale, n->bg_ray, n->bg_scalar,
+                                                      n->nears, n->fars, n->weights_sum, n->image_raw, n->image, n->depth, ob->ray_sumsq, stream)
+                         : foc_occ_tail_forward(n->h, n->c, n->c_width, n->deltas, n->rays, M, n->n_rays, n->T_thresh, n->density_scale, n->bg_ray, n->bg_scalar,
+                                                n->nears, n->fars, n->weights_sum, n->image_raw, n->image, n->depth, stream);
+}
+
+int foc_occ_train_backward_obj(const FocOccTrainNode *n, const FocOccTrainObject *ob, void *stream) {
+    int rc = ot_check_object(n, ob, "occ_train_backward_obj");
+    if (rc != FOC_OK) return rc;
+    FOC_REQUIRE(n->mlp_workspace_bytes >= foc_ffmlp_backward_workspace_bytes(48, 64, n->color_layers), FOC_E_INVALID,
+                "occ_train_backward_obj: MLP workspace of %llu bytes, the 48-wide colour head asks for foc_ffmlp_backward_workspace_bytes(48, 64, %u) = %llu",
+                (unsigned long long)n->mlp_workspace_bytes, n->color_layers, (unsigned long long)foc_ffmlp_backward_workspace_bytes(48, 64, n->color_layers));
+    const uint32_t M = n->cap;
+    rc = ob->grad_sumsq ? foc_occ_tail_backward_sumsq(n->grad_image, n->grad_ws, n->h, n->c, n->c_width, n->deltas, n->rays, n->counter, n->weights_sum, n->image_raw, M,
+                                                      n->n_rays, n->T_thresh, n->density_scale, n->bg_ray, n->bg_scalar, n->grad_c, n->grad_h0, ob->grad_sumsq, stream)
+                        : foc_occ_tail_backward(n->grad_image, n->grad_ws, n->h, n->c, n->c_width, n->deltas, n->rays, n->counter, n->weights_sum, n->image_raw, M,
+                                                n->n_rays, n->T_thresh, n->density_scale, n->bg_ray, n->bg_scalar, n->grad_c, n->grad_h0, stream);
+    if (rc != FOC_OK) return rc;
+    rc = ob->input_pad != 0.0f
+             ? foc_color_head_backward_pad(n->grad_c, n->h, n->sh_rows, 1, n->grad_h0, n->w_color, M, n->color_hidden, n->color_layers, n->color_activation, n->grad_h,
+                                           n->grad_w_color, n->mlp_workspace, n->mlp_workspace_bytes, n->c_width, ob->obj_feat, ob->grad_obj, ob->input_pad, stream)
+             : foc_color_head_backward(n->grad_c, n->h, n->sh_rows, 1, n->grad_h0, n->w_color, M, n->color_hidden, n->color_layers, n->color_activation, n->grad_h,
+                                       n->grad_w_color, n->mlp_workspace, n->mlp_workspace_bytes, n->c_width, ob->obj_feat, ob->grad_obj, stream);
     if (rc != FOC_OK) return rc;
     rc = foc_ffmlp_backward_planar(n->grad_h, n->planes, n->w_sigma, M, n->sigma_input_dim, 16, n->sigma_hidden, n->sigma_layers, n->sigma_activation,
                                    n->sigma_output_activation, 1, n->grad_planes, n->grad_w_sigma, n->mlp_workspace, n->mlp_workspace_bytes, stream);

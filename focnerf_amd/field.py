@@ -73,6 +73,8 @@ class FieldPlan:
     colour_input_pad: float = 0.0       # the colour input's last column: 47 of the 48-wide object-conditioned row (1.0: tinycudann layout,
                                         # network_tcnn.py), 31 of the 32-wide row (1.0: legacy tinycudann layout, network_tcnn_legacy.py)
     background: bool = False            # the background model (encoder_bg -> bg_net) as one kernel each way (background.py, csrc/background.hip)
+    occ_object: bool = False            # `occ` for an object-conditioned network: the node with the encoded object feature (occtrain._occ_train_obj)
+    native_loop_object: bool = False    # `native_loop` for an object-conditioned network: the step takes the feature (and the column-47 pad twin)
 
 
 def pad_twin(name, pad, obj):
@@ -129,14 +131,20 @@ def field_plan(model):
                   and bg_grid.gridtype == 0 and not bg_grid.align_corners and bg_grid.interpolation == 0
                   and isinstance(bg_mlp, PackedMLP) and bg_mlp.in_features == 24 and MlpShape.of(bg_mlp) == MlpShape(32, 64, 1, 0, 6, 16)
                   and bg_mlp.output_dim == 3 and isinstance(enc_dir, SHEncoder) and enc_dir.degree == 4 and _on("FOC_FUSED_BG"))
+    bg_radius = getattr(model, "bg_radius", 0)
+    occ_common = field and tail and same_activation and _on("FOC_FUSED_OCC")
+    native_common = infer and getattr(model, "density_scale", 1) == 1 and plain_grid and _on("FOC_RENDER_NATIVE")
     return FieldPlan(
         grid=grid, levels=enc.offsets.numel() - 1 if grid is not None else 0, sigma=sigma, colour=colour, uses_object_feature=obj,
         field=field, tail=tail, infer=infer,
         train_forward=(field and tail and whole_field and sigma.output_activation == 6 and get_option("FOC_FIELD_FWD_FUSED") != 0),
-        occ=field and tail and not obj and (getattr(model, "bg_radius", 0) <= 0 or background) and same_activation and _on("FOC_FUSED_OCC"),
-        native_loop=(infer and not obj and getattr(model, "density_scale", 1) == 1 and plain_grid and _on("FOC_RENDER_NATIVE")),
+        occ=occ_common and not obj and (bg_radius <= 0 or background),
+        native_loop=native_common and not obj,
         head=both and colour.input_dim == colour_in and colour_rows and pad == 0 and _on("FOC_FUSED_HEAD"), colour_input_pad=pad,
-        background=background)
+        background=background,
+        # an object-conditioned network: the object node sequences the whole-field kernels (their layer pairs), and no background model
+        occ_object=occ_common and obj and whole_field and bg_radius <= 0,
+        native_loop_object=native_common and obj and bg_radius <= 0)
 
 
 def _raw_stream_of(device):

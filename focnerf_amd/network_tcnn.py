@@ -141,6 +141,20 @@ class NeRFNetwork(_FocNetwork):
     def get_yolo_feat_encoder(self, yolo_feats_encoder_dim):
         return TcnnObjectEncoder(yolo_feats_encoder_dim, self.yolo_encoding_dim)
 
+    def forward(self, x, d, yolo_details=None):
+        """As network_foc's. With an encoded object feature and without autograd the whole-field kernel serves it even though the head
+        kernels do not (they write a 0 in column 47), so the occupancy grid's Python inference loop evaluates what the native loop
+        evaluates (network_tcnn_legacy.py does the same); without a feature the call is what it always was.
+        This holds for any direct `net(x, d, (_, _, obj16))` call under no_grad and autocast, on a `cuda_ray=False` model too (the renderer's
+        fixed-step path never makes one): such a call now returns the whole-field kernel's values, which agree with the torch colour path
+        it ran before within the fp16 bound of the other whole-field comparisons (tests/test_gpu_occ_object.py), not bit for bit."""
+        if yolo_details is not None and x.is_cuda and x.dim() == 2 and torch.is_autocast_enabled() and not torch.is_grad_enabled():
+            from .field import field_plan, field_infer
+            obj = torch.as_tensor(yolo_details[2], device=x.device)
+            if obj.numel() == self.yolo_encoding_dim and field_plan(self).infer:
+                return field_infer(self, (x + self.bound) / (2 * self.bound), d, obj_feat=obj)
+        return super().forward(x, d, yolo_details)
+
     def _color_torch(self, d, geo_feat, obj_feat):
         d = self.encoder_dir(d)
         obj = obj_feat.to(geo_feat.dtype)

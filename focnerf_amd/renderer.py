@@ -71,6 +71,22 @@ def _flat_rays(rays_o, rays_d):
     return rays_o.contiguous().view(-1, 3), rays_d.contiguous().view(-1, 3), lead
 
 
+def _outside_criterion(sigmas, rays, outside):
+    """FOC's outside-mask density criterion on a ragged sample list, for the op chain: sqrt(sum of sigma^2 over every sample of the rays
+    with outside[ray index]), subgradient 0 at 0. sigmas [M], rays [n,3] = (index, offset, count) of march_rays_train, outside bool [n].
+    Rays that did not fit the list contribute nothing. The per-sample weights come from the ranges' ends (+1 at the start, -1 behind
+    the end, a prefix sum over integers): no host round trip."""
+    from .fixedstep import _masked_norm
+    M = sigmas.shape[0]
+    index, first, count = rays[:, 0].long(), rays[:, 1].long(), rays[:, 2].long()
+    counted = ((count > 0) & (first + count <= M) & outside[index]).to(torch.int32)
+    ends = torch.zeros(M + 1, dtype=torch.int32, device=sigmas.device)
+    ends.index_add_(0, first.clamp(max=M), counted)
+    ends.index_add_(0, (first + count).clamp(max=M), -counted)
+    sigma32 = sigmas.float()
+    return _masked_norm.apply(sigma32 * sigma32, torch.cumsum(ends, 0)[:M].to(torch.float32))
+
+
 class NeRFRenderer(nn.Module):
     def __init__(self, bound=1, cuda_ray=False, density_scale=1, min_near=0.2, density_thresh=0.01, bg_radius=-1):
         super().__init__()
@@ -207,18 +223,45 @@ class NeRFRenderer(nn.Module):
         return sigmas if self.density_scale == 1 else self.density_scale * sigmas      # x * 1 == x: no launch for the default scale
 
     def run_cuda(self, rays_o, rays_d, dt_gamma=0, bg_color=None, perturb=False, force_all_rays=False, max_steps=1024, T_thresh=1e-4,
-                 device_compaction=None, **kwargs):
+                 device_compaction=None, yolo_details=None, **kwargs):
         """Samples only where the occupancy bitfield is set (legacy/nerf/renderer.py:256-376). Training: one marching pass, one
         evaluation of the field, one compositing node. Inference: rays advance a few samples at a time and leave the list once they are
-        opaque or out of the box."""
+        opaque or out of the box.
+        yolo_details = (ray mask or None, box, raw object feature) for an object-conditioned network (`uses_object_feature`): the colour
+        network takes the encoded feature, and the result carries 'criterion_outside_mask' — in training with a mask sqrt(sum of sigma^2
+        over every sample the march emitted for the rays outside the mask), sigma before density_scale; else None. The mask is per ray."""
         o, d, lead = _flat_rays(rays_o, rays_d)
         n, dev = o.shape[0], o.device
         out = {}
         from .field import field_plan
         plan = field_plan(self)
+        obj16 = outside = None
+        if yolo_details is not None and plan.uses_object_feature:
+            out['criterion_outside_mask'] = None
+            if self.training and yolo_details[0] is not None:
+                from .occtrain import ray_mask
+                outside = ~ray_mask(yolo_details[0], n).to(dev)       # a wrong size raises here, before any launch
+            obj16 = self.encode_object_feature(yolo_details, dev)
+            extra = ((None, None, obj16),)                            # forward() takes the ENCODED 16-vector in slot 2
+        else:
+            extra = ()
         if self.training:
             from .occtrain import render_occupancy_train
-            if o.is_cuda and torch.is_grad_enabled() and torch.is_autocast_enabled() and plan.occ:
+            if obj16 is not None and o.is_cuda and torch.is_grad_enabled() and torch.is_autocast_enabled() and plan.occ_object:
+                # the object-conditioned node (occtrain._occ_train_obj): the feature goes in as a tensor and gets its gradient back
+                from .occtrain import render_occupancy_train_object
+                from .fixedstep import _masked_norm
+                slot = self.step_counter[self.local_step % 16]
+                slot.zero_()
+                self.local_step += 1
+                image, opacity, depth, sumsq = render_occupancy_train_object(self, plan, o.float(), d.float(), slot, bg_color, perturb, force_all_rays, dt_gamma,
+                                                                             max_steps, T_thresh, _MARCH_ALIGN, obj16, outside is not None)
+                if outside is not None:
+                    out['criterion_outside_mask'] = _masked_norm.apply(sumsq, outside.to(torch.float32))
+                out['weights_sum'] = opacity
+                out['image'], out['depth'] = image.view(*lead, 3), depth.view(*lead)
+                return out
+            if obj16 is None and o.is_cuda and torch.is_grad_enabled() and torch.is_autocast_enabled() and plan.occ:
                 # the whole training forward as one autograd node (focnerf_amd/occtrain.py): same samples, same image; the box test of
                 # near_far_from_aabb rides in the march's count pass
                 slot = self.step_counter[self.local_step % 16]
@@ -240,9 +283,11 @@ class NeRFRenderer(nn.Module):
             xyzs, dirs, deltas, rays = raymarching.march_rays_train(o, d, self.bound, self.density_bitfield, self.cascade, self.grid_size, near,
                                                                     far, slot, self.mean_count, perturb, _MARCH_ALIGN, force_all_rays,
                                                                     dt_gamma, max_steps)
-            sigmas, rgbs = self(xyzs, dirs)
+            sigmas, rgbs = self(xyzs, dirs, *extra)
             opacity, depth, image = raymarching.composite_rays_train(self._scaled(sigmas), rgbs, deltas, rays, T_thresh)
             out['weights_sum'] = opacity
+            if outside is not None:
+                out['criterion_outside_mask'] = _outside_criterion(sigmas, rays, outside)
         else:
             opacity, depth, image = (torch.zeros(n, *tail, dtype=torch.float32, device=dev) for tail in ((), (), (3,)))
             alive = torch.arange(n, dtype=torch.int32, device=dev)
@@ -253,8 +298,8 @@ class NeRFRenderer(nn.Module):
             # list compacted on the device and its length read late; False = the reference's loop (boolean mask, a host round trip per iteration)
             # the native loop serves the networks of the whole-field kernel on the GPU, under autocast (fp16 table and weights): plan.native_loop
             if ((device_compaction is None or device_compaction) and o.is_cuda and torch.is_autocast_enabled() and not torch.is_grad_enabled()
-                    and plan.native_loop):
-                self._native_inference_loop(plan, o, d, near, far, alive, t_now, opacity, depth, image, perturb, dt_gamma, max_steps, T_thresh)
+                    and (plan.native_loop if obj16 is None else plan.native_loop_object)):
+                self._native_inference_loop(plan, o, d, near, far, alive, t_now, opacity, depth, image, perturb, dt_gamma, max_steps, T_thresh, obj16)
                 marched = max_steps                                   # the Python loop below has nothing left to do
             device_compaction = bool(device_compaction)
             import contextlib
@@ -280,7 +325,7 @@ class NeRFRenderer(nn.Module):
                     xyzs, dirs, deltas = raymarching.march_rays(live, burst, alive, t_now, o, d, self.bound, self.density_bitfield, self.cascade,
                                                                 self.grid_size, near, far, _MARCH_ALIGN, perturb and marched == 0, dt_gamma,
                                                                 max_steps, noises=None if (perturb and marched == 0) else still)
-                    sigmas, rgbs = self(xyzs, dirs)
+                    sigmas, rgbs = self(xyzs, dirs, *extra)
                     raymarching.composite_rays(live, burst, alive, t_now, self._scaled(sigmas), rgbs, deltas, opacity, depth, image, T_thresh)
                     if device_compaction and lag > 0:
                         kept, count = raymarching.compact_alive(alive, pad=True)
@@ -305,13 +350,14 @@ class NeRFRenderer(nn.Module):
         return out
 
     # ------------------------------------------------------------------ the inference loop, one native call per iteration
-    def _native_inference_loop(self, plan, o, d, near, far, alive, t_now, opacity, depth, image, perturb, dt_gamma, max_steps, T_thresh):
+    def _native_inference_loop(self, plan, o, d, near, far, alive, t_now, opacity, depth, image, perturb, dt_gamma, max_steps, T_thresh, obj16=None):
         """The loop of legacy/nerf/renderer.py:323-372 with every iteration ONE call into the library (csrc/occrender.hip: march, encode,
         whole-field kernel, composite, compaction) on buffers allocated once per view; bursts of FOC_RENDER_BURST samples per ray, the live
         count read `FOC_RENDER_COUNT_LAG` iterations late, the reference's stopping point reproduced. Same samples, same per-ray
         accumulation order: the same image and depth bit for bit on every configuration the tests run (jittered first samples with the
         same noise included), with one caveat spelled out at the burst rule below — a re-derivation of t that can differ by an ulp where a
-        single advance more than doubles t while fewer than half of the rays are alive."""
+        single advance more than doubles t while fewer than half of the rays are alive.
+        obj16: the encoded object feature of an object-conditioned network (plan.native_loop_object), handed to every step."""
         from ._lib import lib, ptr, stream_of, check
         from .field import _half_of, half_cache_scope, pad_twin, fused_mlp
         n, dev = o.shape[0], o.device
@@ -350,8 +396,10 @@ class NeRFRenderer(nn.Module):
         def rule(n_alive):                                      # renderer.py:337
             return max(min(n // n_alive, 8), 1)
 
-        # a constant last column of the colour input (network_tcnn_legacy.py: column 31 = 1.0): the step's twin, the pad before the stream
+        # a constant last column of the colour input (network_tcnn_legacy.py: column 31 = 1.0; network_tcnn.py: column 47 = 1.0): the step's
+        # twin, the pad before the stream
         render_step, pad_args = pad_twin("foc_occ_render_step", plan.colour_input_pad, plan.uses_object_feature)
+        obj_h = obj16.detach().reshape(-1).half().contiguous() if obj16 is not None else None
         with half_cache_scope():
             emb, ws, wc = _half_of(enc.embeddings), _half_of(sn.weights), _half_of(cn.weights)
             st = stream_of(o)
@@ -367,7 +415,7 @@ class NeRFRenderer(nn.Module):
                                               ptr(jitter if marched == 0 else still), ptr(samples), ptr(planes), ptr(sigma), ptr(rgb), ptr(emb),
                                               ptr(enc.offsets), None, L, plan.grid.log2_scale, plan.grid.base_resolution, ptr(ws), plan.sigma.num_layers, ptr(wc),
                                               plan.colour.num_layers, plan.sigma.activation,
-                                              None, float(T_thresh), ptr(opacity), ptr(depth), ptr(image), ptr(scratch), flags, ptr(deaths), marched, n_deaths,
+                                              ptr(obj_h), float(T_thresh), ptr(opacity), ptr(depth), ptr(image), ptr(scratch), flags, ptr(deaths), marched, n_deaths,
                                               *pad_args, st), "occ_render_step")
                 state["it"], state["marched"] = it + 1, marched + burst
 
@@ -495,7 +543,8 @@ class NeRFRenderer(nn.Module):
         `max_ray_batch` rays and assembles depth [B,N], image [B,N,3] and — when the chunks carry them — densities [B,N,T] and
         rgbs [B,N,T,3] for the whole view, as nerf/renderer.py:511-560 does (1.3 + 3.9 GB for 800 x 800 x 512)."""
         if self.cuda_ray:
-            return self.run_cuda(rays_o, rays_d, **kwargs)                    # the marching path knows no yolo_details (renderer.py:243)
+            # an object-conditioned network takes its yolo_details on the marching path too; every other network ignores them there
+            return self.run_cuda(rays_o, rays_d, yolo_details=yolo_details, **kwargs)
         if not staged:
             return self.run(rays_o, rays_d, yolo_details, **kwargs)
         B, N = rays_o.shape[:2]

@@ -256,6 +256,18 @@ int foc_occ_render_step_pad31(uint32_t n_alive, uint32_t n_step, const int32_t *
                               const void *sigma_weights, uint32_t sigma_layers, const void *color_weights, uint32_t color_layers, uint32_t activation,
                               const void *obj_feat, float T_thresh, float *weights_sum, float *depth, float *image, void *scratch, uint32_t flags,
                               int32_t *deaths, uint32_t deaths_base, uint32_t deaths_len, float input_pad, void *stream);
+/* foc_occ_render_step with input column 47 of the 48-wide object-conditioned colour row [SH16 | h[1:16] | obj_feat | input_pad] = input_pad:
+ * the field through foc_nerf_field_inference_pad (the tinycudann layout, focnerf_amd/network_tcnn.py, pad 1.0). input_pad != 0 needs
+ * obj_feat and (sigma_layers, color_layers) in (1,2), (1,3), (2,2), (2,3), (3,3); both are refused before anything is enqueued.
+ * input_pad = 0: the bits of foc_occ_render_step. */
+int foc_occ_render_step_pad(uint32_t n_alive, uint32_t n_step, const int32_t *rays_alive, int32_t *rays_alive_out, int32_t *count,
+                            float *rays_t, const float *rays_o, const float *rays_d, float bound, float dt_gamma, uint32_t max_steps,
+                            uint32_t C, uint32_t H, const uint8_t *grid, const float *nears, const float *fars, const float *noises,
+                            float *samples, void *planes, float *sigma, float *rgb,
+                            const void *embeddings, const int32_t *offsets, const int32_t *offsets_host, uint32_t L, float S, uint32_t base_res,
+                            const void *sigma_weights, uint32_t sigma_layers, const void *color_weights, uint32_t color_layers, uint32_t activation,
+                            const void *obj_feat, float T_thresh, float *weights_sum, float *depth, float *image, void *scratch, uint32_t flags,
+                            int32_t *deaths, uint32_t deaths_base, uint32_t deaths_len, float input_pad, void *stream);
 
 int foc_compact_alive(const int32_t *rays_alive, uint32_t n_alive, int32_t *out, int32_t *n_out,
                       int32_t *scratch, void *stream);
@@ -671,6 +683,20 @@ int foc_occ_tail_backward(const float *grad_image, const float *grad_ws, const v
                           const float *deltas, const int32_t *rays, const int32_t *counter, const float *weights_sum,
                           const float *image_raw, uint32_t M, uint32_t N, float T_thresh, float density_scale,
                           const float *bg_ray, float bg_scalar, void *grad_c, void *grad_h0, void *stream);
+/* The two above with FOC's outside-mask density criterion (legacy nerf/renderer.py:163-165 on a ragged list), as foc_fixed_tail_forward /
+ * _backward carry it: ray_sumsq [N] = sum of exp(h[:,0])^2 (sigma before density_scale) over ALL rays[n].count samples of the ray, those
+ * behind the sample at which the composite stopped at T_thresh included; 0 for a ray that did not fit the list. One wave per ray in a fixed
+ * order: the same bits on every run. Backward: grad_sumsq [N] is its gradient; 2 sigma grad_sumsq[ray] is added to the density path before
+ * trunc_exp's factor on every row of a ray that fits — the rows behind an early stop, zeros above, carry that term alone. Everything
+ * else is bit for bit the two entry points above. */
+int foc_occ_tail_forward_sumsq(const void *h, const void *c, uint32_t c_width, const float *deltas, const int32_t *rays,
+                               uint32_t M, uint32_t N, float T_thresh, float density_scale, const float *bg_ray, float bg_scalar,
+                               const float *nears, const float *fars, float *weights_sum, float *image_raw, float *image,
+                               float *depth, float *ray_sumsq, void *stream);
+int foc_occ_tail_backward_sumsq(const float *grad_image, const float *grad_ws, const void *h, const void *c, uint32_t c_width,
+                                const float *deltas, const int32_t *rays, const int32_t *counter, const float *weights_sum,
+                                const float *image_raw, uint32_t M, uint32_t N, float T_thresh, float density_scale,
+                                const float *bg_ray, float bg_scalar, void *grad_c, void *grad_h0, const float *grad_sumsq, void *stream);
 
 /* The whole occupancy-grid TRAINING node as ONE call each way (csrc/occtrain.hip): what legacy/nerf/renderer.py:256-322 (`run_cuda`, training
  * branch, a fixed sample budget) + nerf/network_ff.py:51-75 do between the rays and the image, in the order
@@ -724,6 +750,27 @@ int foc_occ_train_backward(const FocOccTrainNode *node, void *stream);
  * before anything is enqueued. input_pad = 0: the bits of the two entry points above. */
 int foc_occ_train_forward_pad31(const FocOccTrainNode *node, float input_pad, void *stream);
 int foc_occ_train_backward_pad31(const FocOccTrainNode *node, float input_pad, void *stream);
+/* The node of an object-conditioned network (focnerf_amd/network_foc.py, network_tcnn.py: a 48-wide colour input [SH16 | h[1:16] | obj_feat |
+ * input_pad]). FocOccTrainNode keeps its layout; what the object adds travels beside it in FocOccTrainObject, as input_pad does for the
+ * *_pad31 twins. The same sequence through foc_field_forward_train[_pad] / foc_color_head_forward[_pad] / foc_color_head_backward[_pad] with
+ * obj_feat, w_color and grad_w_color with 48-wide W0 rows, mlp_workspace sized for input_dim 48 (foc_ffmlp_backward_workspace_bytes(48, 64,
+ * color_layers)). ray_sumsq [n_rays] (may be NULL): the tail is foc_occ_tail_forward_sumsq; grad_sumsq [n_rays] (may be NULL): the backward's
+ * tail is foc_occ_tail_backward_sumsq. grad_obj [16] fp32 (may be NULL): the gradient of obj_feat, as foc_color_head_backward writes it.
+ * `struct_bytes` = sizeof(FocOccTrainObject). Refused before anything is enqueued: a wrong struct_bytes of either struct, a NULL obj_feat,
+ * input_pad != 0 without obj_feat, (sigma_layers, color_layers) outside (1,2), (1,3), (2,2), (2,3), (3,3), sigma_input_dim != 32, sigma_hidden
+ * or color_hidden != 64, sigma_activation != color_activation, a hidden activation other than relu (0) or none (6), sigma_output_activation
+ * != 6 (the shapes the 48-wide head and foc_field_forward_train are built for), a workspace too small. */
+typedef struct FocOccTrainObject {
+    uint32_t struct_bytes;
+    float input_pad;                    /* column 47 of the colour input: 0 (network_foc.py) or 1.0 (network_tcnn.py) */
+    const void *obj_feat;               /* [16] fp16, the ENCODED object feature */
+    float *ray_sumsq;
+    /* backward only */
+    const float *grad_sumsq;
+    float *grad_obj;
+} FocOccTrainObject;
+int foc_occ_train_forward_obj(const FocOccTrainNode *node, const FocOccTrainObject *object, void *stream);
+int foc_occ_train_backward_obj(const FocOccTrainNode *node, const FocOccTrainObject *object, void *stream);
 
 /* Extension (no reference binding; focnerf_amd/rayorder.py): perm [N] int64 = the order in which a staged render walks a view's rays —
  * tile_h x tile_w pixel tiles when rays_d [N,3] fp32 is a row-major H x W pixel grid (recognised from the directions: W >= 16, H >= 8),
