@@ -66,7 +66,7 @@ class HashGridCPU(nn.Module):
         super().__init__()
         if desired_resolution is not None:                                           # grid.py:101-102
             per_level_scale = np.exp2(np.log2(desired_resolution / base_resolution) / (num_levels - 1))
-        assert input_dim == 3
+        assert input_dim in (2, 3)
         self.input_dim, self.num_levels, self.level_dim = input_dim, num_levels, level_dim
         self.per_level_scale, self.base_resolution, self.log2_hashmap_size = per_level_scale, base_resolution, log2_hashmap_size
         self.output_dim = num_levels * level_dim
@@ -80,7 +80,8 @@ class HashGridCPU(nn.Module):
     def forward(self, inputs, bound=1):
         x = (inputs + bound) / (2 * bound)                                           # grid.py:149
         prefix = list(x.shape[:-1])
-        x = x.reshape(-1, 3)
+        D = self.input_dim
+        x = x.reshape(-1, D)
         S = np.float32(np.log2(self.per_level_scale))                                # the float the kernel receives (grid.py:153)
         inside = ((x >= 0) & (x <= 1)).all(-1, keepdim=True)                         # gridencoder.cu:110-135: a point outside [0,1]^3 encodes to zeros
         outs = []
@@ -92,13 +93,13 @@ class HashGridCPU(nn.Module):
             pg = torch.floor(pos)
             frac = pos - pg
             pg = pg.long()
-            stride1, stride2 = res + 1, (res + 1) * (res + 1)
-            dense = stride2 * (res + 1) <= size                                      # the stride loop of :66-74 runs to the end without overflowing
+            strides = [(res + 1) ** dim for dim in range(D)]
+            dense = (res + 1) ** D <= size                                           # the stride loop of :66-74 runs to the end without overflowing
             acc = 0
-            for corner in range(8):
+            for corner in range(1 << D):
                 w = 1.0
                 c = []
-                for dim in range(3):
+                for dim in range(D):
                     if corner & (1 << dim):
                         w = w * frac[:, dim]
                         c.append(pg[:, dim] + 1)
@@ -106,9 +107,11 @@ class HashGridCPU(nn.Module):
                         w = w * (1 - frac[:, dim])
                         c.append(pg[:, dim])
                 if dense:
-                    idx = c[0] + c[1] * stride1 + c[2] * stride2
+                    idx = sum(c[dim] * strides[dim] for dim in range(D))
                 else:                                                                 # fast_hash, uint32 wrap-around (:50-64)
-                    idx = (c[0] & 0xFFFFFFFF) ^ ((c[1] * 2654435761) & 0xFFFFFFFF) ^ ((c[2] * 805459861) & 0xFFFFFFFF)
+                    idx = (c[0] & 0xFFFFFFFF) ^ ((c[1] * 2654435761) & 0xFFFFFFFF)
+                    if D == 3:
+                        idx = idx ^ ((c[2] * 805459861) & 0xFFFFFFFF)
                 idx = idx % size + self._host_offsets[lvl]
                 acc = acc + w.unsqueeze(-1) * self.embeddings[idx]
             outs.append(acc)
