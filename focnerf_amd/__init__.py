@@ -6,4 +6,4 @@ from . import _lib  # noqa: F401  (raises ImportError when libfocnerf_hip.so is 
 from .determinism import use_deterministic, is_deterministic, deterministic  # noqa: F401  (FOC_DETERMINISTIC: bit-reproducible training steps)
 
 __all__ = ["raymarching", "gridencoder", "freqencoder", "ffmlp", "activation", "encoding", "shencoder",
-           "renderer", "network", "combine", "use_deterministic", "is_deterministic", "deterministic"]
+           "renderer", "network", "combine", "fixedcull", "use_deterministic", "is_deterministic", "deterministic"]

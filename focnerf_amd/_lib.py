@@ -155,7 +155,11 @@ SIGNATURES = {
     "foc_combine_select4": (i32, [c_vp, c_vp, u64, c_vp]),
     "foc_mo_select": (i32, [c_vp, c_vp, c_vp, c_vp, u64, u32, u32, c_vp]),
     "foc_fixed_field_pack": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, f32, u32, u32, f32, f32, c_vp, c_vp, c_vp, c_vp, u32, c_vp]),
-    "foc_composite_fixed_steps": (i32, [c_vp, c_vp, c_vp, c_vp, u32, u32, f32, c_vp, c_vp, c_vp]),
+    "foc_fixed_cull_scratch_bytes": (u64, [u32, u32]),
+    "foc_fixed_cull": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, f32, c_vp, u32, u32, c_vp, c_vp, c_vp, c_vp, u64, c_vp]),
+    "foc_fixed_cull_emit": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, f32, c_vp, c_vp, u32, c_vp, c_vp, c_vp]),
+    "foc_fixed_field_pack_culled": (i32, [c_vp, c_vp, c_vp, c_vp, u32, c_vp, c_vp, u32, u32, f32, f32, c_vp, c_vp]),
+    "foc_composite_fixed_steps":(i32, [c_vp, c_vp, c_vp, c_vp, u32, u32, f32, c_vp, c_vp, c_vp]),
     "foc_fixed_sample": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, f32, c_vp, c_vp, c_vp, u32, c_vp]),
     "foc_fixed_tail_forward": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, f32, u32, u32, f32, f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, u32, c_vp, c_vp]),
     "foc_fixed_tail_backward": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, f32, u32, u32, f32, f32, c_vp, c_vp, u32, c_vp, c_vp]),

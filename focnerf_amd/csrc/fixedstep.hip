@@ -14,37 +14,12 @@
 // gather -> MLP -> scatter, without the nonzero/index round trips).
 // SURVEY.md §8(f)-3; these entry points have no reference binding.
 #include "common.h"
+#include "fs_common.h"        // FsGeom, fs_geom, fs_z, fs_point, fs_block_row: the sample positions, shared with fixedcull.hip
 #include <float.h>
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 
-struct FsGeom { float near, far, span, sample_dist, step; };
-
-// Block-interleaved sample order of the inference path (k_fs_sample): rows of 64 consecutive rays interleaved by depth.
-#define FS_RAY_BLOCK 64u
-__host__ __device__ __forceinline__ uint64_t fs_block_row(uint32_t n, uint32_t i, uint32_t T) {
-    return (uint64_t)(n / FS_RAY_BLOCK) * FS_RAY_BLOCK * T + (uint64_t)i * FS_RAY_BLOCK + n % FS_RAY_BLOCK;
-}
-
-__device__ __forceinline__ FsGeom fs_geom(const float *__restrict__ nears, const float *__restrict__ fars, uint32_t n, uint32_t T) {
-    FsGeom g;
-    g.near = nears[n]; g.far = fars[n];
-    g.span = g.far - g.near;
-    g.sample_dist = g.span / (float)T;
-    g.step = 1.0f / (float)(T - 1);
-    return g;
-}
-// torch.linspace(0, 1, T) as torch's DEVICE kernel fills it: symmetric halves, and the upper half `end - step*k` is one
-// fused multiply-add (the device compilers — nvcc for the reference, hipcc for torch-ROCm — contract it; torch's CPU kernel
-// and therefore the CPU oracle round twice). Then z = near + span * lin [+ (u - 0.5) * sample_dist], separate torch ops.
-__device__ __forceinline__ float fs_z(const FsGeom &g, uint32_t i, uint32_t T, const float *__restrict__ noise, uint64_t s) {
-    const float lin = (i < T / 2) ? (g.step * (float)i) : fmaf(-g.step, (float)(T - 1 - i), 1.0f);
-    float z = g.near + g.span * lin;
-    if (noise) z = z + (noise[s] - 0.5f) * g.sample_dist;
-    return z;
-}
-
-// the same value from a noise draw that is already in a register (NOISE = false: no jitter term at all, like fs_z with a null pointer).
+// fs_z's value from a noise draw that is already in a register (NOISE = false: no jitter term at all, like fs_z with a null pointer).
 // The tail kernels load both draws a sample needs up front, unconditionally, so that all loads of an iteration are in flight together:
 // behind `if (noise)` / `if (i + 1 < T)` each load was its own round trip (s_waitcnt vmcnt(0) after every one of them).
 template <bool NOISE>
@@ -86,7 +61,7 @@ __global__ void __launch_bounds__(256) k_fs_sample(const float *__restrict__ ray
     // of the kernels downstream are then 64 NEIGHBOURING RAYS AT ONE DEPTH instead of 64 depths of one ray, and the level-major encoder
     // forward finds most of a wave's corner rows in a few cache lines (0.34 -> 0.17 ms per 2 M samples of an 800 x 800 view).
     const uint64_t total = ray_block ? (uint64_t)((N + FS_RAY_BLOCK - 1) / FS_RAY_BLOCK) * FS_RAY_BLOCK * T : (uint64_t)N * T;
-    const float a0 = aabb[0], a1 = aabb[1], a2 = aabb[2], a3 = aabb[3], a4 = aabb[4], a5 = aabb[5];
+    const FsBox box = fs_box(aabb);
     const float two_b = 2 * bound;
     for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s < total; s += (uint64_t)gridDim.x * 256) {
         uint32_t n, i;
@@ -102,11 +77,10 @@ __global__ void __launch_bounds__(256) k_fs_sample(const float *__restrict__ ray
         }
         const FsGeom g = fs_geom(nears, fars, n, T);
         const float z = fs_z(g, i, T, noise, (uint64_t)n * T + i);     // the noise array is ray-major in both orders
-        // torch: rays_o + rays_d * z (two kernels, two roundings), then min(max(., aabb_lo), aabb_hi)
-        float x = rays_o[n * 3] + rays_d[n * 3] * z, y = rays_o[n * 3 + 1] + rays_d[n * 3 + 1] * z, w = rays_o[n * 3 + 2] + rays_d[n * 3 + 2] * z;
-        x = fminf(fmaxf(x, a0), a3); y = fminf(fmaxf(y, a1), a4); w = fminf(fmaxf(w, a2), a5);
+        float x, y, w;
+        fs_point(rays_o[n * 3], rays_o[n * 3 + 1], rays_o[n * 3 + 2], rays_d[n * 3], rays_d[n * 3 + 1], rays_d[n * 3 + 2], z, box, x, y, w);
         if (xyzs) { xyzs[s * 3] = x; xyzs[s * 3 + 1] = y; xyzs[s * 3 + 2] = w; }
-        if (enc_in) { enc_in[s * 3] = (x + bound) / two_b; enc_in[s * 3 + 1] = (y + bound) / two_b; enc_in[s * 3 + 2] = (w + bound) / two_b; }
+        if (enc_in) { enc_in[s * 3] = fs_norm(x, bound, two_b); enc_in[s * 3 + 1] = fs_norm(y, bound, two_b); enc_in[s * 3 + 2] = fs_norm(w, bound, two_b); }
         if (ray_sh && i == 0 && own) {                     // the ray's SH row as it stands in the colour-net input (fp16), once per ray
             float sh[16];
             fs_sh16(rays_d[n * 3], rays_d[n * 3 + 1], rays_d[n * 3 + 2], sh);
@@ -446,37 +420,7 @@ __global__ void __launch_bounds__(256) k_fs_tail_bwd(const float *__restrict__ g
 // PACK: additionally (or only: image / depth / weights_sum may then be null) writes the object's per-sample field as ONE float4 per sample,
 // field4[s] = (sigma, rgb where w > thresh else 0) — the (`densities`, `rgbs`) pair COMBINED.py merges across objects (:598-618), in the
 // layout the per-ray exchange and the fused select + composite read with one 16-byte access per lane (csrc/combine.hip).
-struct FsRayAcc { float Tc, ws, dp, r, g, b; };
-
-// 64 samples of ray n, sample i on the lane (sigma / c0..c2 are that sample's values; unread where i >= T): weights by wave scan, the
-// masked sums on the lane, the per-sample outputs written ray-major.
-template <bool PACK>
-__device__ __forceinline__ void fs_infer_tile(FsRayAcc &a, const FsGeom &g, uint32_t n, uint32_t i, uint32_t lane, uint32_t T, float sigma, float c0, float c1,
-                                              float c2, const float *__restrict__ noise, float density_scale, float thresh, float *__restrict__ rgb_masked,
-                                              float4 *__restrict__ field4, float *__restrict__ sigma_rm) {
-    const bool valid = i < T;
-    const uint64_t s = (uint64_t)n * T + (valid ? i : T - 1);
-    const float z = fs_z(g, valid ? i : T - 1, T, noise, s);
-    float delta = g.sample_dist;
-    if (i + 1 < T) delta = fs_z(g, i + 1, T, noise, s + 1) - z;
-    const float alpha = valid ? 1 - expf((-delta * density_scale) * sigma) : 0.0f;
-    const float om = valid ? (1 - alpha + 1e-15f) : 1.0f;
-    const float P = wave_incl_prod(om, (int)lane);
-    float Pex = __shfl_up(P, 1, 64);
-    if (lane == 0) Pex = 1.0f;
-    const float w = alpha * (a.Tc * Pex);
-    if (valid) {
-        float oz = (z - g.near) / g.span;
-        oz = oz < 0.0f ? 0.0f : (oz > 1.0f ? 1.0f : oz);
-        a.ws += w; a.dp += w * oz;
-        const bool on = w > thresh;
-        if (on) { a.r += w * c0; a.g += w * c1; a.b += w * c2; }
-        if (rgb_masked) { rgb_masked[s * 3] = on ? c0 : 0.0f; rgb_masked[s * 3 + 1] = on ? c1 : 0.0f; rgb_masked[s * 3 + 2] = on ? c2 : 0.0f; }
-        if (PACK) field4[s] = make_float4(sigma, on ? c0 : 0.0f, on ? c1 : 0.0f, on ? c2 : 0.0f);
-        if (sigma_rm) sigma_rm[s] = sigma;
-    }
-    a.Tc *= __shfl(P, 63, 64);
-}
+// FsRayAcc and the per-tile pass fs_infer_tile are in fs_common.h (the culled pack of fixedcull.hip runs the same pass).
 
 template <bool PACK>
 __device__ __forceinline__ void fs_infer_finish(FsRayAcc &a, uint32_t n, uint32_t lane, const float *__restrict__ bg_ray, float bg_scalar,

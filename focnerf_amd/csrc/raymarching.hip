@@ -13,24 +13,14 @@
 // as explicit fmaf() exactly where oracle/oracle.c has them, so the marching control flow
 // (and therefore every sample index and position) is bit-identical to the oracle.
 #include "common.h"
+#include "occ_cell.h"
 #include <float.h>
 
 #define RM_SQRT3 1.7320508075688772f
 #define RM_RPI   0.3183098861837907f
 
 __device__ __forceinline__ float rm_sign(float x) { return copysignf(1.0f, x); }
-__device__ __forceinline__ float rm_clamp(float x, float lo, float hi) { return fminf(hi, fmaxf(lo, x)); }
 
-__device__ __forceinline__ uint32_t rm_expand_bits(uint32_t v) {
-    v = (v * 0x00010001u) & 0xFF0000FFu;
-    v = (v * 0x00000101u) & 0x0F00F00Fu;
-    v = (v * 0x00000011u) & 0xC30C30C3u;
-    v = (v * 0x00000005u) & 0x49249249u;
-    return v;
-}
-__device__ __forceinline__ uint32_t rm_morton3D(uint32_t x, uint32_t y, uint32_t z) {
-    return rm_expand_bits(x) | (rm_expand_bits(y) << 1) | (rm_expand_bits(z) << 2);
-}
 __device__ __forceinline__ uint32_t rm_morton3D_invert(uint32_t x) {
     x = x & 0x49249249u;
     x = (x | (x >> 2)) & 0xc30c30c3u;
@@ -38,14 +28,6 @@ __device__ __forceinline__ uint32_t rm_morton3D_invert(uint32_t x) {
     x = (x | (x >> 8)) & 0xff0000ffu;
     x = (x | (x >> 16)) & 0x0000ffffu;
     return x;
-}
-
-// frexpf exponent of a non-negative finite float without the libcall: for x = 0 frexpf
-// returns exponent 0; subnormals never reach a positive exponent, and only max(0, e) is used.
-__device__ __forceinline__ int rm_frexp_exp(float x) {
-    int e;
-    (void)frexpf(x, &e);
-    return e;
 }
 
 // ---------------------------------------------------------------- R1 (raymarching.cu:92-145)
@@ -169,20 +151,11 @@ __device__ __forceinline__ bool rm_cell(const uint8_t *__restrict__ grid, const 
     c.z = rm_clamp(fmaf(t, dz, oz), -p.bound, p.bound);
     c.dt = rm_clamp(t * p.dt_gamma, p.dt_min, p.dt_max);
     // mip_from_pos / mip_from_dt (:42-54): float min/max, then truncation
-    const float mx = fmaxf(fabsf(c.x), fmaxf(fabsf(c.y), fabsf(c.z)));
-    const int l1 = (int)fminf(p.Cf - 1, fmaxf(0.0f, (float)rm_frexp_exp(mx)));
+    const int l1 = rm_mip_from_pos(c.x, c.y, c.z, p.Cf);
     const float mdt = (float)((double)(c.dt * p.Hf) * 0.5);
     const int l2 = (int)fminf(p.Cf - 1, fmaxf(0.0f, (float)rm_frexp_exp(mdt)));
     const int level = l1 > l2 ? l1 : l2;
-    c.mip_bound = fminf(scalbnf(1.0f, level), p.bound);
-    const float mip_rbound = 1 / c.mip_bound;
-    // 0.5 * (x * mip_rbound + 1) * H in double, narrowed to float by clamp()'s parameter (:374-376)
-    c.nx = (int)rm_clamp((float)(0.5 * (double)fmaf(c.x, mip_rbound, 1.0f) * (double)p.H), 0.0f, p.Hm1);
-    c.ny = (int)rm_clamp((float)(0.5 * (double)fmaf(c.y, mip_rbound, 1.0f) * (double)p.H), 0.0f, p.Hm1);
-    c.nz = (int)rm_clamp((float)(0.5 * (double)fmaf(c.z, mip_rbound, 1.0f) * (double)p.H), 0.0f, p.Hm1);
-    // level * H3 + morton in float (:339,:378)
-    const uint32_t index = (uint32_t)fmaf((float)level, p.H3, (float)rm_morton3D((uint32_t)c.nx, (uint32_t)c.ny, (uint32_t)c.nz));
-    return (grid[index >> 3] & (1u << (index & 7u))) != 0;
+    return rm_cell_bit(grid, rm_cell_index(c.x, c.y, c.z, level, p.bound, p.H, p.Hm1, p.H3, c.mip_bound, c.nx, c.ny, c.nz));
 }
 
 // Empty cell: jump to the voxel exit (:389-398).

@@ -1,0 +1,121 @@
+"""Occupancy-culled fixed-step fields for the multi-object combiner (csrc/fixedcull.hip).
+
+The combiner's per-sample select (COMBINED.py `best_densities_and_colors_v3`) needs every object at the same T positions of the same
+rays, so an object cannot march ragged samples of its own. With an `Occupancy`, `fixedstep.render_field4` keeps the fixed positions,
+tests each against the object's occupancy bitfield and evaluates encoder + networks on the occupied ones only; every other sample
+has sigma = 0. That is the approximation `run_cuda` makes: densities below the grid's threshold are dropped, the transmittance behind
+such samples is slightly higher, and a sample whose own weight stood at the 1e-10 mask threshold can change sides.
+
+    occ = Occupancy.of(model)            # a cuda_ray network: its trained density_bitfield, no copy
+    occ = Occupancy.estimate(model)      # any network with density(x): the full-grid passes of update_extra_state on own buffers
+    render_field4(model, rays_o, rays_d, num_steps=T, out=buf, occupancy=occ)
+"""
+import torch
+
+from ._lib import lib, ptr, stream_of, check
+from .backend import _scratch
+
+
+class Occupancy:
+    """An object's occupancy bitfield with the grid it describes: uint8 [cascade * grid_size^3 / 8] in Morton order (what
+    `raymarching.packbits` writes), cascades of a box of half-width `bound`."""
+
+    def __init__(self, bitfield, cascade, grid_size, bound):
+        cascade, grid_size = int(cascade), int(grid_size)
+        if not torch.is_tensor(bitfield) or bitfield.dtype != torch.uint8:
+            raise ValueError("Occupancy: the bitfield must be a uint8 tensor")
+        if cascade < 1 or grid_size < 2 or grid_size & (grid_size - 1):
+            raise ValueError(f"Occupancy: cascade {cascade} / grid_size {grid_size}: need cascade >= 1 and a power-of-two grid_size")
+        if bitfield.numel() != cascade * grid_size ** 3 // 8:
+            raise ValueError(f"Occupancy: a bitfield of {bitfield.numel()} bytes does not describe {cascade} cascades of {grid_size}^3 cells")
+        self.bitfield, self.cascade, self.grid_size, self.bound = bitfield.contiguous().view(-1), cascade, grid_size, float(bound)
+
+    @classmethod
+    def of(cls, model):
+        """The trained grid of a `cuda_ray=True` network: its `density_bitfield`, `cascade`, `grid_size` and `bound`, without a copy (a
+        later `update_extra_state` shows through). An all-zero bitfield — a grid that was never trained or installed — is refused: it
+        would render nothing, silently."""
+        bits = getattr(model, "density_bitfield", None)
+        if not getattr(model, "cuda_ray", False) or bits is None:
+            raise ValueError("Occupancy.of: the model has no occupancy grid (cuda_ray=False); use Occupancy.estimate(model)")
+        if not bool(bits.any()):
+            raise ValueError("Occupancy.of: the model's density_bitfield is all zero (an untrained grid would render nothing)")
+        return cls(bits, model.cascade, model.grid_size, model.bound)
+
+    @classmethod
+    @torch.no_grad()
+    def estimate(cls, model, passes=16, decay=0.95, density_thresh=None, jitter=True, generator=None):
+        """A grid for any network with `density(x)` — FOC's default training is fixed-step, so most per-object checkpoints carry none.
+        Runs `passes` full-grid passes of `update_extra_state` (densitygrid.grid_cells_xyz -> model.density -> grid_update_apply: the
+        grid keeps max(old * decay, new), cells above min(mean, density_thresh or model.density_thresh) are occupied) on buffers of
+        its own, under fp16 autocast like the trainer's call; it neither needs nor touches the model's cuda_ray state. jitter=False
+        samples the cell centres (deterministic); `generator` (on the model's device) seeds the jitter."""
+        from . import densitygrid
+        dev = next(model.parameters()).device
+        C, H = int(model.cascade), int(model.grid_size)
+        thresh = float(model.density_thresh if density_thresh is None else density_thresh)
+        grid = torch.zeros(C, H ** 3, dtype=torch.float32, device=dev)
+        bits = torch.zeros(C * H ** 3 // 8, dtype=torch.uint8, device=dev)
+        for _ in range(int(passes)):
+            noise = torch.rand(C * H ** 3, 3, device=dev, generator=generator) if jitter else None
+            at = densitygrid.grid_cells_xyz(C, H, model.bound, noise, dev)
+            with torch.autocast("cuda", dtype=torch.float16, enabled=dev.type == "cuda"):      # as the trainer calls update_extra_state (--fp16)
+                sigmas = model.density(at)['sigma'].reshape(-1).detach()
+            densitygrid.grid_update_apply(grid, C, H, sigmas, None, model.density_scale, decay, thresh, bits)
+        return cls(bits, C, H, model.bound)
+
+
+def fixed_cull(rays_o, rays_d, nears, fars, aabb, T, occ):
+    """The cull pass for N rays x T fixed steps: -> (mask uint64-as-int64 [R], offsets uint32-as-int32 [R + 1], count int32 [1]) with
+    R = ceil(N/64) * T rows of the block-interleaved order (include/focnerf.h). No host synchronisation."""
+    N, dev = rays_o.shape[0], rays_o.device
+    R = -(-N // 64) * T
+    mask = torch.empty(R, dtype=torch.int64, device=dev)
+    offsets = torch.empty(R + 1, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    nbytes = lib.foc_fixed_cull_scratch_bytes(N, T)
+    scratch = _scratch.get("fixed_cull", nbytes, dev)
+    check(lib.foc_fixed_cull(ptr(rays_o), ptr(rays_d), ptr(nears), ptr(fars), ptr(aabb), N, T, occ.bound, ptr(occ.bitfield), occ.cascade, occ.grid_size,
+                             ptr(mask), ptr(offsets), ptr(count), ptr(scratch), nbytes, stream_of(rays_o)), "fixed_cull")
+    return mask, offsets, count
+
+
+def fixed_cull_emit(rays_o, rays_d, nears, fars, aabb, T, bound, mask, offsets, m_occ):
+    """-> enc_in_c [m_occ,3] (normalised positions of the occupied samples), dirs_c [m_occ,3] (their rays' directions)."""
+    N, dev = rays_o.shape[0], rays_o.device
+    enc_in_c = torch.empty(m_occ, 3, dtype=torch.float32, device=dev)
+    dirs_c = torch.empty(m_occ, 3, dtype=torch.float32, device=dev)
+    check(lib.foc_fixed_cull_emit(ptr(rays_o), ptr(rays_d), ptr(nears), ptr(fars), ptr(aabb), N, T, float(bound), ptr(mask), ptr(offsets), m_occ,
+                                  ptr(enc_in_c), ptr(dirs_c), stream_of(rays_o)), "fixed_cull_emit")
+    return enc_in_c, dirs_c
+
+
+def render_field4_culled(model, plan, rays_o, rays_d, T, weight_thresh, yolo_details, out, occ):
+    """`render_field4` with an Occupancy (rays_o / rays_d [N,3] fp32 contiguous, out [N,T,4]): near_far -> cull -> ONE host read of the
+    count -> encoder + whole-field kernel on the occupied samples -> culled pack."""
+    from . import raymarching
+    from .field import field_infer
+    if not isinstance(occ, Occupancy):
+        raise ValueError("render_field4: occupancy must be a focnerf_amd.fixedcull.Occupancy")
+    if not (plan.infer and model.bg_radius <= 0):
+        raise ValueError("render_field4: occupancy needs a network the fused inference serves (field_plan(model).infer) without a background "
+                         "model; this one would have to render dense")
+    if occ.bound != float(model.bound):
+        raise ValueError(f"render_field4: the occupancy grid covers bound {occ.bound}, the model bound {float(model.bound)}")
+    N, dev = rays_o.shape[0], rays_o.device
+    if N == 0:
+        return out
+    if occ.bitfield.device != dev:
+        raise ValueError(f"render_field4: the occupancy bitfield is on {occ.bitfield.device}, the rays on {dev}")
+    aabb = model.aabb_train if model.training else model.aabb_infer
+    nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, aabb, model.min_near)
+    mask, offsets, count = fixed_cull(rays_o, rays_d, nears, fars, aabb, T, occ)
+    m_occ = int(count.item())                                   # the host read: sizes the compact arrays and the field launch
+    sigma = rgb = None
+    if m_occ:
+        enc_in_c, dirs_c = fixed_cull_emit(rays_o, rays_d, nears, fars, aabb, T, model.bound, mask, offsets, m_occ)
+        obj_feat = model.encode_object_feature(yolo_details, dev) if plan.uses_object_feature else None
+        sigma, rgb = field_infer(model, enc_in_c, dirs_c, dir_div=1, dir_block=0, obj_feat=obj_feat)
+    check(lib.foc_fixed_field_pack_culled(ptr(sigma), ptr(rgb), ptr(mask), ptr(offsets), m_occ, ptr(nears), ptr(fars), N, T, float(model.density_scale),
+                                          float(weight_thresh), ptr(out), stream_of(out)), "fixed_field_pack_culled")
+    return out

@@ -399,11 +399,19 @@ def render_fixed_steps(model, rays_o, rays_d, yolo_details=None, num_steps=512, 
 
 
 @torch.no_grad()
-def render_field4(model, rays_o, rays_d, num_steps=512, weight_thresh=1e-10, yolo_details=None, out=None):
+def render_field4(model, rays_o, rays_d, num_steps=512, weight_thresh=1e-10, yolo_details=None, out=None, occupancy=None):
     """What the combiner needs from one object for a chunk of rays — COMBINED.py's `run` (:451-534 with upsample_steps=0, perturb off):
     `densities` [N,T] and `rgbs` [N,T,3] (zero where the object's own compositing weight is <= 1e-10) — PACKED as field4 [N,T,4] fp32
     (sigma, r, g, b), written into `out` when given. Fused path: sample -> encoder -> whole-field kernel -> weights + mask + pack
-    (foc_fixed_field_pack); other networks go through `model.run(..., return_fields=True)` and are packed with torch ops."""
+    (foc_fixed_field_pack); other networks go through `model.run(..., return_fields=True)` and are packed with torch ops.
+
+    occupancy (a `fixedcull.Occupancy`, default None = the dense path above, unchanged): the same T positions, but encoder and networks
+    run only on the samples whose cell of the object's occupancy grid is set; every other sample is (0, 0, 0, 0). Sequence: near_far ->
+    cull (csrc/fixedcull.hip) -> one host read of the occupied count -> encoder + whole-field kernel on that many rows -> culled pack.
+    It is the approximation `run_cuda` makes: densities below the grid's threshold are dropped, so the transmittance behind such
+    samples is slightly higher and a sample's own-weight mask can flip. The host read makes a call with `occupancy` uncapturable in a
+    HIP graph (the dense path is as capturable as before). Needs a network the fused inference serves and no background model
+    (ValueError otherwise: it never falls back to rendering dense), and a grid over the model's `bound`."""
     from .field import field_plan, field_infer
     rays_o = rays_o.contiguous().view(-1, 3).float()
     rays_d = rays_d.contiguous().view(-1, 3).float()
@@ -413,6 +421,9 @@ def render_field4(model, rays_o, rays_d, num_steps=512, weight_thresh=1e-10, yol
         out = torch.empty(N, T, 4, dtype=torch.float32, device=dev)
     assert out.shape == (N, T, 4) and out.dtype == torch.float32 and out.is_contiguous()
     plan = field_plan(model)
+    if occupancy is not None:
+        from .fixedcull import render_field4_culled
+        return render_field4_culled(model, plan, rays_o, rays_d, T, weight_thresh, yolo_details, out, occupancy)
     if plan.infer and model.bg_radius <= 0:
         aabb = model.aabb_train if model.training else model.aabb_infer
         nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, aabb, model.min_near)

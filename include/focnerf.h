@@ -806,6 +806,49 @@ int foc_fixed_field_pack(const float *sigma, const float *rgb, const float *near
                          float density_scale, float thresh, float *image, float *depth, float *weights_sum,
                          float *field4, uint32_t ray_block, void *stream);
 
+/* Occupancy-culled fixed-step field of ONE object for the multi-object combiner (csrc/fixedcull.hip; no reference binding). The
+ * combiner's per-sample select needs every object at the same T positions of the same rays, so the positions stay those of
+ * foc_fixed_sample(noise = NULL, ray_block = 64) — the same bits — and each is tested against the object's occupancy bitfield
+ * (uint8 [cascade * grid_size^3 / 8], Morton order, as foc_packbits writes it). The cell is the one foc_march_rays finds for that
+ * position, with the cascade level taken from the position alone (no dt term: a fixed-step sample has no marching step):
+ *   level = min(cascade - 1, max(0, frexp exponent of max |x|)); mip_bound = min(2^level, bound);
+ *   n = (int)clamp(0.5 * (x / mip_bound + 1) * grid_size, 0, grid_size - 1) per axis; index = level * grid_size^3 + morton3D(n);
+ *   occupied = bit (index & 7) of byte (index >> 3).
+ * Only occupied samples go through the encoder and the networks; every other sample has sigma = 0. That is the approximation the
+ * occupancy-grid renderer makes: densities below the grid's threshold are dropped.
+ *
+ * Rows: R = ceil(N/64) * T, row (n/64) * T + i holds sample i of the 64 rays of block n/64 (the block-interleaved order, one row =
+ * 64 consecutive samples of it). The compact list holds the occupied samples in that order:
+ *   slot(n, i) = offsets[row] + popcount(mask[row] & ((1 << (n % 64)) - 1)).
+ * Slots come from a prefix sum, not from atomics: the same list on every run.
+ *
+ * foc_fixed_cull       writes mask [R] uint64 (bit n % 64 of a row: sample i of ray n is occupied; bits of the padding lanes n >= N
+ *                      are never set), offsets [R + 1] uint32 (exclusive prefix sum of the rows' popcounts, offsets[R] = M_occ) and
+ *                      count [1] uint32 = M_occ. scratch: foc_fixed_cull_scratch_bytes(N, T) device bytes, no initialisation needed.
+ *                      cascade 1..16, grid_size a power of two <= 1024, cascade * grid_size^3 < 2^32, ceil(N/64) * 64 * T < 2^31,
+ *                      T >= 2. N = 0 writes offsets[0] = count = 0.
+ * foc_fixed_cull_emit  from that mask / offsets: enc_in_c [m_occ,3] = the occupied samples' normalised positions (foc_fixed_sample's
+ *                      enc_in rows) and dirs_c [m_occ,3] = their rays' directions. m_occ = the count the caller read; the arrays hold
+ *                      m_occ rows and nothing is written past them.
+ * Neither call synchronises; reading count on the host between them is the caller's one synchronisation. */
+uint64_t foc_fixed_cull_scratch_bytes(uint32_t N, uint32_t T);
+int foc_fixed_cull(const float *rays_o, const float *rays_d, const float *nears, const float *fars, const float *aabb,
+                   uint32_t N, uint32_t T, float bound, const uint8_t *bitfield, uint32_t cascade, uint32_t grid_size,
+                   uint64_t *mask, uint32_t *offsets, uint32_t *count, void *scratch, uint64_t scratch_bytes, void *stream);
+int foc_fixed_cull_emit(const float *rays_o, const float *rays_d, const float *nears, const float *fars, const float *aabb,
+                        uint32_t N, uint32_t T, float bound, const uint64_t *mask, const uint32_t *offsets, uint32_t m_occ,
+                        float *enc_in_c, float *dirs_c, void *stream);
+
+/* foc_fixed_field_pack(ray_block = 64, image = depth = weights_sum = NULL) for a culled object: sigma_c [m_occ] and rgb_c [m_occ,3]
+ * fp32 are the field on the compact list (foc_nerf_field_inference on enc_in_c / dirs_c with dir_div 1), mask / offsets as
+ * foc_fixed_cull wrote them. field4 [N,T,4] fp32, ray-major, 16-byte aligned: (sigma, rgb where the object's own weight
+ * alpha * cumprod > thresh else 0) at occupied samples, (0, 0, 0, 0) at every other. Bit for bit what foc_fixed_field_pack gives
+ * on dense block-interleaved arrays whose sigma was zeroed at the unoccupied samples; no dense per-sample array is read or
+ * written. m_occ = 0: sigma_c / rgb_c may be NULL, field4 is all zeros. */
+int foc_fixed_field_pack_culled(const float *sigma_c, const float *rgb_c, const uint64_t *mask, const uint32_t *offsets,
+                                uint32_t m_occ, const float *nears, const float *fars, uint32_t N, uint32_t T,
+                                float density_scale, float thresh, float *field4, void *stream);
+
 /* ---------------------------------------------------------------------------
  * Per-sample network glue for callers with arbitrary sample lists (the occupancy-grid paths): the torch
  * expressions of nerf/network_ff.py:51-75 between the sigma network, the SH-encoded direction and the
