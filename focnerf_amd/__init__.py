@@ -4,6 +4,7 @@ reference's Python operator API. The compute lives in libfocnerf_hip.so (C ABI i
 include/focnerf.h); importing this package fails loudly if that library is missing."""
 from . import _lib  # noqa: F401  (raises ImportError when libfocnerf_hip.so is absent)
 from .determinism import use_deterministic, is_deterministic, deterministic  # noqa: F401  (FOC_DETERMINISTIC: bit-reproducible training steps)
+from .combine import Attribution  # noqa: F401  (per-object mattes, depths and the instance map of a combined render)
 
 __all__ = ["raymarching", "gridencoder", "freqencoder", "ffmlp", "activation", "encoding", "shencoder",
-           "renderer", "network", "combine", "fixedcull", "use_deterministic", "is_deterministic", "deterministic"]
+           "renderer", "network", "combine", "fixedcull", "use_deterministic", "is_deterministic", "deterministic", "Attribution"]

@@ -29,9 +29,15 @@ The kernels live in libfocnerf_hip.so; `ops` can be replaced by a CPU implementa
 which exercise only the host/collective logic.
 """
 import os
+from collections import namedtuple
 
 import torch
 import torch.distributed as dist
+
+# Who the combined render came from (include/focnerf.h foc_combine_select_composite_attr): weights [N, n_obj] = each object's soft matte
+# (the composite's weights of the samples it won), depth [N, n_obj] = the same sums of weight x normalised depth, instance [N] int32 = the
+# object with the largest matte on the ray, -1 on an empty ray.
+Attribution = namedtuple("Attribution", "weights depth instance")
 
 
 class HipCombineOps:
@@ -101,6 +107,53 @@ class HipCombineOps:
             raise RuntimeError("combine select4: two contiguous float32 [...,4] tensors of one shape expected")
         check(lib.foc_combine_select4(ptr(field4), ptr(acc4), field4.numel() // 4, stream_of(acc4)), "combine_select4")
 
+    @staticmethod
+    def select_composite_attr(fields4, nears, fars, bgs, n_obj, ids=None, want_merged=False, want_winner=False):
+        """`select_composite` that keeps the select's decision. ids: per field its object id (an int) or, for a field pre-merged by
+        `select4_ids`, its uint8 [N,T] id plane; default: field k is object k. -> (image4 [len(bgs),N,4], depth [N],
+        Attribution(weights [N,n_obj], depth [N,n_obj], instance [N] int32), merged4 [N,T,4] or None, winner [N,T] uint8 or None)."""
+        import ctypes
+        from ._lib import lib, ptr, stream_of, check, require_cuda
+        K = len(fields4)
+        ids = list(range(K)) if ids is None else list(ids)
+        if len(ids) != K:
+            raise RuntimeError(f"combine select_composite_attr: {K} fields but {len(ids)} ids")
+        planes = [i for i in ids if torch.is_tensor(i)]
+        require_cuda(*fields4, nears, fars, *planes)
+        N, T = fields4[0].shape[0], fields4[0].shape[1]
+        for f in fields4:
+            if f.dtype != torch.float32 or not f.is_contiguous() or tuple(f.shape) != (N, T, 4):
+                raise RuntimeError("combine select_composite_attr: fields must be contiguous float32 [N,T,4] tensors of one shape")
+        for pl in planes:
+            if pl.dtype != torch.uint8 or not pl.is_contiguous() or tuple(pl.shape) != (N, T):
+                raise RuntimeError("combine select_composite_attr: an id plane must be a contiguous uint8 [N,T] tensor")
+        dev = fields4[0].device
+        n_obj = int(n_obj)
+        image4 = torch.empty(len(bgs), N, 4, dtype=torch.float32, device=dev)
+        depth = torch.empty(N, dtype=torch.float32, device=dev)
+        merged = torch.empty(N, T, 4, dtype=torch.float32, device=dev) if want_merged else None
+        winner = torch.empty(N, T, dtype=torch.uint8, device=dev) if want_winner else None
+        att = Attribution(torch.empty(N, max(n_obj, 0), dtype=torch.float32, device=dev), torch.empty(N, max(n_obj, 0), dtype=torch.float32, device=dev),
+                          torch.empty(N, dtype=torch.int32, device=dev))
+        ptrs = (ctypes.c_void_p * K)(*[f.data_ptr() for f in fields4])
+        cplanes = (ctypes.c_void_p * K)(*[i.data_ptr() if torch.is_tensor(i) else None for i in ids])
+        cids = (ctypes.c_uint32 * K)(*[0 if torch.is_tensor(i) else int(i) for i in ids])
+        cbgs = (ctypes.c_float * len(bgs))(*[float(b) for b in bgs])
+        check(lib.foc_combine_select_composite_attr(ptrs, K, cplanes, cids, n_obj, ptr(nears), ptr(fars), N, T, cbgs, len(bgs), ptr(image4), ptr(depth),
+                                                    ptr(merged), ptr(att.weights), ptr(att.depth), ptr(att.instance), ptr(winner),
+                                                    stream_of(fields4[0])), "combine_select_composite_attr")
+        return image4, depth, att, merged, winner
+
+    @staticmethod
+    def select4_ids(field4, obj_id, acc4, acc_ids):
+        """`select4` that keeps the identity: acc_ids (uint8, one per sample of acc4) takes `obj_id` where acc4 takes field4's rgb."""
+        from ._lib import lib, ptr, stream_of, check, require_cuda
+        require_cuda(field4, acc4, acc_ids)
+        if field4.shape != acc4.shape or field4.dtype != torch.float32 or acc4.dtype != torch.float32 or not (field4.is_contiguous() and acc4.is_contiguous()):
+            raise RuntimeError("combine select4_ids: two contiguous float32 [...,4] tensors of one shape expected")
+        if acc_ids.dtype != torch.uint8 or not acc_ids.is_contiguous() or acc_ids.shape != acc4.shape[:-1]:
+            raise RuntimeError("combine select4_ids: acc_ids must be a contiguous uint8 tensor with one entry per sample of acc4")
+        check(lib.foc_combine_select4_ids(ptr(field4), int(obj_id), ptr(acc4), ptr(acc_ids), field4.numel() // 4, stream_of(acc4)), "combine_select4_ids")
 
     @staticmethod
     def mo_select(sigma_new, feat_new, sigma_best, feat_best):
@@ -184,10 +237,18 @@ def pack_field4(densities, rgbs):
     return torch.cat([d, rgbs.float()], dim=-1).contiguous()
 
 
-def combine_packed(fields4, nears, fars, bgs=(1.0, 0.0), want_merged=False, ops=HipCombineOps):
+def combine_packed(fields4, nears, fars, bgs=(1.0, 0.0), want_merged=False, ops=HipCombineOps, attribution=False):
     """K resident objects on ONE device: the object loop of COMBINED.py:598-618 and image_depth_generation for every background in one
-    pass over the packed fields of a ray chunk. fields4: list of [N,T,4] in checkpoint order (more than 16: pre-merged in runs)."""
+    pass over the packed fields of a ray chunk. fields4: list of [N,T,4] in checkpoint order (more than 16: pre-merged in runs).
+    `attribution=True` (at most 16 fields; field k is object k) appends an `Attribution` to the returned tuple: every object's matte and
+    depth per ray and the instance map, from the same pass."""
     fields4 = list(fields4)
+    if attribution:
+        if len(fields4) > 16:
+            raise ValueError(f"combine_packed: attribution covers at most 16 objects, got {len(fields4)} fields")
+        image4, depth, att, merged, _ = ops.select_composite_attr(fields4, nears.contiguous().float(), fars.contiguous().float(), tuple(bgs), len(fields4),
+                                                                  want_merged=want_merged)
+        return (image4, depth, merged, att) if want_merged else (image4, depth, att)
     while len(fields4) > 16:                                   # kernel argument block holds 16 pointers
         acc = fields4[0].clone()
         for f in fields4[1:16]:
@@ -257,15 +318,17 @@ class ObjectCombiner:
     def _slice_len(self, n_rays):
         return (n_rays + self.world - 1) // self.world
 
-    def exchange_start(self, field4, bufs=None):
+    def exchange_start(self, field4, bufs=None, ids=None, id_bufs=None):
         """field4 [n,T,4] fp32: this rank's (pre-merged) objects on the n rays of one chunk. Starts the all-to-all that gives rank q rays
         [q*per, (q+1)*per) of every rank's field, per = ceil(n / world) (zero rows pad a ragged chunk). Returns a handle for
         `exchange_finish`; the caller may enqueue other work (the next chunk's field evaluation) in between.
-        `bufs` = (send, recv) of [world*per, T, 4] to reuse (double-buffered by render_view), else allocated here."""
+        `bufs` = (send, recv) of [world*per, T, 4] to reuse (double-buffered by render_view), else allocated here.
+        `ids` (attribution only): the uint8 [n,T] id plane of field4; it travels in a second all-to-all of uint8 [world*per, T]
+        (`id_bufs` = its (send, recv) to reuse) and the handle carries it to `exchange_finish`."""
         n, T = field4.shape[0], field4.shape[1]
         per = self._slice_len(n)
         if not self.xch:
-            return (None, field4.contiguous(), n, per)
+            return (None, field4.contiguous(), n, per) if ids is None else (None, field4.contiguous(), n, per, None, ids.contiguous())
         if bufs is None:
             bufs = (torch.empty(self.world * per, T, 4, dtype=torch.float32, device=field4.device),
                     torch.empty(self.world * per, T, 4, dtype=torch.float32, device=field4.device))
@@ -276,6 +339,18 @@ class ObjectCombiner:
             send[n:].zero_()
         work = dist.all_to_all_single(recv, send, group=self.group, async_op=True)
         self.bytes_sent += (self.world - 1) * per * T * 16
+        if ids is not None:
+            if id_bufs is None:
+                id_bufs = (torch.empty(self.world * per, T, dtype=torch.uint8, device=field4.device),
+                           torch.empty(self.world * per, T, dtype=torch.uint8, device=field4.device))
+            id_send, id_recv = id_bufs[0][: self.world * per], id_bufs[1][: self.world * per]
+            if id_send.data_ptr() != ids.data_ptr():
+                id_send[:n].copy_(ids)
+            if self.world * per > n:
+                id_send[n:].zero_()
+            id_work = dist.all_to_all_single(id_recv, id_send, group=self.group, async_op=True)
+            self.bytes_sent += (self.world - 1) * per * T
+            return (work, recv, n, per, id_work, id_recv)
         return (work, recv, n, per)
 
     def my_slice(self, values, n, per, fill):
@@ -286,24 +361,34 @@ class ObjectCombiner:
         out[: hi - lo] = values[lo:hi]
         return out
 
-    def exchange_finish(self, handle, nears_mine, fars_mine, bgs=(1.0, 0.0)):
+    def exchange_finish(self, handle, nears_mine, fars_mine, bgs=(1.0, 0.0), n_objects=None):
         """-> (image4 [len(bgs), per, 4], depth [per]) of THIS rank's ray slice of the chunk (rows past the chunk's end are padding).
         nears_mine / fars_mine [per]: `my_slice` of the chunk's nears / fars — of the view's own (unedited) rays, because
-        image_depth_generation composites along data['rays_o'] (COMBINED.py:143-149)."""
-        work, recv, n, per = handle
+        image_depth_generation composites along data['rays_o'] (COMBINED.py:143-149).
+        A handle started with `ids` gives (image4, depth, Attribution) of the slice over the scene's `n_objects`: one id plane per
+        received field."""
+        work, recv, n, per = handle[:4]
         if work is not None:
             work.wait()
         fields = [recv[k * per:(k + 1) * per] for k in range(self.world)] if self.world > 1 else [recv]
+        if len(handle) > 4:
+            id_work, id_recv = handle[4], handle[5]
+            if id_work is not None:
+                id_work.wait()
+            planes = [id_recv[k * per:(k + 1) * per] for k in range(self.world)] if self.world > 1 else [id_recv]
+            return self.ops.select_composite_attr(fields, nears_mine, fars_mine, tuple(bgs), n_objects, ids=planes)[:3]
         return self.ops.select_composite(fields, nears_mine, fars_mine, tuple(bgs))
 
-    def render_view(self, field_fns, n_rays, nears, fars, T, bgs=(1.0, 0.0), max_ray_batch=16384, overlap=True):
+    def render_view(self, field_fns, n_rays, nears, fars, T, bgs=(1.0, 0.0), max_ray_batch=16384, overlap=True, attribution=None):
         """`_render_view` (below), on a stream of this combiner's own while collectives are in flight. Measured with one rank on RCCL
         (tools/time_rccl_one_rank.py, NOTEBOOK.md rounds 1-4 section 7): when RCCL's stream is the first stream a process uses after the default one —
         bench.py at N > 1, or a fresh COMBINED.py-style process — it shares a hardware queue with the DEFAULT stream, and an all-to-all
         "under" a field evaluation enqueued on the default stream runs strictly in turn with it (44.5 ms per view overlapped = not
         overlapped); with the evaluation on any other stream the two run side by side (43.1), whichever of the two was created first.
         To the caller nothing changes: the work is ordered behind what the caller's current stream holds, and the returned tensors
-        may be used on that stream. FOC_COMBINE_SIDE_STREAM=0 evaluates on the caller's stream as before."""
+        may be used on that stream. FOC_COMBINE_SIDE_STREAM=0 evaluates on the caller's stream as before.
+        `attribution=(first_object, n_objects)` — this rank's first object's index in checkpoint order and the scene's number of objects
+        (at most 16) — returns (image4, depth, Attribution) for the whole view on every rank; see `_render_view`."""
         dev = nears.device
         if self.xch and overlap and dev.type == "cuda" and os.environ.get("FOC_COMBINE_SIDE_STREAM", "1") != "0":
             cur = torch.cuda.current_stream(dev)
@@ -314,25 +399,37 @@ class ObjectCombiner:
                 side.wait_stream(cur)
                 try:
                     with torch.cuda.stream(side):
-                        image4, depth = self._render_view(field_fns, n_rays, nears, fars, T, bgs, max_ray_batch, overlap)
+                        out = self._render_view(field_fns, n_rays, nears, fars, T, bgs, max_ray_batch, overlap, attribution)
                 finally:
                     cur.wait_stream(side)              # also when a field function raised: kernels on `side` may still read the caller's buffers
-                image4.record_stream(cur)              # allocated under `side`, consumed by the caller on `cur`
-                depth.record_stream(cur)
-                return image4, depth
-        return self._render_view(field_fns, n_rays, nears, fars, T, bgs, max_ray_batch, overlap)
+                for t in out[:2] + (tuple(out[2]) if attribution is not None else ()):
+                    t.record_stream(cur)               # allocated under `side`, consumed by the caller on `cur`
+                return out
+        return self._render_view(field_fns, n_rays, nears, fars, T, bgs, max_ray_batch, overlap, attribution)
 
-    def _render_view(self, field_fns, n_rays, nears, fars, T, bgs=(1.0, 0.0), max_ray_batch=16384, overlap=True):
+    def _render_view(self, field_fns, n_rays, nears, fars, T, bgs=(1.0, 0.0), max_ray_batch=16384, overlap=True, attribution=None):
         """One view, the loop of COMBINED.py:592-618 + compute_metrics_both_backgrounds' composites, sharded by object and exchanged by ray.
         field_fns: THIS rank's objects in checkpoint order, each `fn(lo, hi, out)` -> packed field4 [hi-lo, T, 4] fp32 of the object on
         rays lo:hi of the view (it may write into `out`, a [hi-lo, T, 4] buffer, and return it). Ranks hold consecutive runs of the
         checkpoint list (rank order = checkpoint order). nears / fars [n_rays]: of the view's own rays. `max_ray_batch` = rays per piece (field
         evaluation and exchange granularity; 16384: 134 MB per object and piece at 512 samples — 10 % faster per view than 4096-ray pieces).
-        Returns (image4 [len(bgs), n_rays, 4], depth [n_rays]) on every rank."""
+        Returns (image4 [len(bgs), n_rays, 4], depth [n_rays]) on every rank.
+        attribution = (first_object, n_objects): additionally an Attribution (weights / depth [n_rays, n_objects], instance [n_rays]). The
+        protocol is the same on every rank, whatever it holds: a uint8 [n,T] id plane per piece — filled with the first local object's id,
+        the later ones pre-merged with `select4_ids` — travels in a second all-to-all beside the field's, the owner of a ray slice runs
+        `select_composite_attr` with one plane per received field, and the view's gather carries the three extra tensors in its one
+        flat buffer (instance bit-viewed as float32)."""
         dev = nears.device
         p, chunk = self.world, int(max_ray_batch)
         n_chunks = (n_rays + chunk - 1) // chunk
+        first_obj, n_obj = (int(attribution[0]), int(attribution[1])) if attribution is not None else (0, 0)
+        if attribution is not None and not (1 <= n_obj <= 16 and 0 <= first_obj and first_obj + len(field_fns) <= n_obj):
+            raise ValueError(f"render_view: attribution=(first_object={first_obj}, n_objects={n_obj}) with {len(field_fns)} local objects: "
+                             "1 <= n_objects <= 16 and first_object + local objects <= n_objects expected")
         if n_chunks == 0:
+            if attribution is not None:
+                return (torch.zeros(len(bgs), 0, 4, device=dev), torch.zeros(0, device=dev),
+                        Attribution(torch.zeros(0, n_obj, device=dev), torch.zeros(0, n_obj, device=dev), torch.zeros(0, dtype=torch.int32, device=dev)))
             return torch.zeros(len(bgs), 0, 4, device=dev), torch.zeros(0, device=dev)
         per = self._slice_len(min(chunk, n_rays))                          # slice length of a full chunk
         n_last = n_rays - (n_chunks - 1) * chunk
@@ -351,12 +448,22 @@ class ObjectCombiner:
         mine4 = torch.zeros(n_chunks, len(bgs), per, 4, dtype=torch.float32, device=dev)
         mined = torch.zeros(n_chunks, per, dtype=torch.float32, device=dev)
         bufs = [tuple(torch.empty(p * per, T, 4, dtype=torch.float32, device=dev) for _ in range(2)) for _ in range(2)] if self.xch else None
+        if attribution is not None:
+            minew = torch.zeros(n_chunks, per, n_obj, dtype=torch.float32, device=dev)
+            minez = torch.zeros(n_chunks, per, n_obj, dtype=torch.float32, device=dev)
+            minei = torch.full((n_chunks, per), -1, dtype=torch.int32, device=dev)
+            # the id planes are double-buffered like the fields: [send, recv] x 2 with an exchange, else one plane per piece in turn
+            id_bufs = [tuple(torch.empty(p * per, T, dtype=torch.uint8, device=dev) for _ in range(2)) for _ in range(2)]
         self.bytes_sent = 0
 
         def finish(pending):
             handle, c = pending
             k = handle[3]
-            i4, d = self.exchange_finish(handle, near_tab[c, :k], far_tab[c, :k], bgs)
+            if attribution is not None:
+                i4, d, att = self.exchange_finish(handle, near_tab[c, :k], far_tab[c, :k], bgs, n_objects=n_obj)
+                minew[c, :k], minez[c, :k], minei[c, :k] = att.weights, att.depth, att.instance
+            else:
+                i4, d = self.exchange_finish(handle, near_tab[c, :k], far_tab[c, :k], bgs)
             mine4[c, :, :k] = i4
             mined[c, :k] = d
 
@@ -366,13 +473,20 @@ class ObjectCombiner:
             k = self._slice_len(hi - lo)
             out = bufs[c % 2][0][: hi - lo] if bufs is not None else None
             acc = None
-            for fn in field_fns:
+            plane = id_bufs[c % 2][0][: hi - lo].fill_(first_obj) if attribution is not None else None
+            for j, fn in enumerate(field_fns):
                 f4 = fn(lo, hi, out if acc is None else None)
                 if acc is None:
                     acc = f4
+                elif plane is not None:
+                    self.ops.select4_ids(f4.contiguous(), first_obj + j, acc, plane)    # ... and the plane takes the id where acc takes the rgb
                 else:
                     self.ops.select4(f4.contiguous(), acc)                 # this rank's later objects, same strict-'>' rule
-            handle = self.exchange_start(acc, (bufs[c % 2][0][: p * k], bufs[c % 2][1][: p * k]) if bufs is not None else None)
+            if plane is not None:
+                handle = self.exchange_start(acc, (bufs[c % 2][0][: p * k], bufs[c % 2][1][: p * k]) if bufs is not None else None, ids=plane,
+                                             id_bufs=(id_bufs[c % 2][0][: p * k], id_bufs[c % 2][1][: p * k]))
+            else:
+                handle = self.exchange_start(acc, (bufs[c % 2][0][: p * k], bufs[c % 2][1][: p * k]) if bufs is not None else None)
             if pending is not None:
                 finish(pending)                                            # chunk c-1: its all-to-all ran under chunk c's evaluation
             pending = (handle, c)
@@ -382,15 +496,22 @@ class ObjectCombiner:
         if pending is not None:
             finish(pending)
         if not self.xch:
-            return mine4.permute(1, 0, 2, 3).reshape(len(bgs), -1, 4)[:, :n_rays].contiguous(), mined.reshape(-1)[:n_rays].contiguous()
+            image4, depth = mine4.permute(1, 0, 2, 3).reshape(len(bgs), -1, 4)[:, :n_rays].contiguous(), mined.reshape(-1)[:n_rays].contiguous()
+            if attribution is not None:
+                return image4, depth, Attribution(minew.reshape(-1, n_obj)[:n_rays].contiguous(), minez.reshape(-1, n_obj)[:n_rays].contiguous(),
+                                                  minei.reshape(-1)[:n_rays].contiguous())
+            return image4, depth
         # ONE gather per view: image rows and depths of this rank's slices in one flat buffer
-        flat = torch.cat([mine4.reshape(-1), mined.reshape(-1)])
+        if attribution is not None:   # ... and the mattes, their depths and the instance map (int32 bits carried as float32; nothing computes on them)
+            flat = torch.cat([mine4.reshape(-1), mined.reshape(-1), minew.reshape(-1), minez.reshape(-1), minei.reshape(-1).view(torch.float32)])
+        else:
+            flat = torch.cat([mine4.reshape(-1), mined.reshape(-1)])
         gathered = torch.empty(p * flat.numel(), dtype=torch.float32, device=dev)
         dist.all_gather_into_tensor(gathered, flat, group=self.group)
         self.bytes_sent += (p - 1) * flat.numel() * 4
         gathered = gathered.view(p, flat.numel())
         g4 = gathered[:, : mine4.numel()].reshape(p, *mine4.shape)
-        gd = gathered[:, mine4.numel():].reshape(p, *mined.shape)
+        gd = gathered[:, mine4.numel(): mine4.numel() + mined.numel()].reshape(p, *mined.shape)
         image4 = torch.empty(len(bgs), n_rays, 4, dtype=torch.float32, device=dev)
         depth = torch.empty(n_rays, dtype=torch.float32, device=dev)
         full = n_chunks - 1 if (n_last != chunk or per_last != per) else n_chunks
@@ -400,6 +521,19 @@ class ObjectCombiner:
         if full < n_chunks:   # the shorter last chunk was cut into slices of per_last rays
             image4[:, full * chunk:] = g4[:, full, :, :per_last].permute(1, 0, 2, 3).reshape(len(bgs), p * per_last, 4)[:, :n_last]
             depth[full * chunk:] = gd[:, full, :per_last].reshape(p * per_last)[:n_last]
+        if attribution is not None:
+            def rows(g):                          # [rank, chunk, per, C] of every rank's slices -> [n_rays, C], the same walk as depth's
+                o = torch.empty(n_rays, g.shape[-1], dtype=g.dtype, device=dev)
+                if full > 0:
+                    o[: full * chunk] = g[:, :full].permute(1, 0, 2, 3).reshape(full, p * per, -1)[:, :chunk].reshape(full * chunk, -1)
+                if full < n_chunks:
+                    o[full * chunk:] = g[:, full, :per_last].reshape(p * per_last, -1)[:n_last]
+                return o
+            at = mine4.numel() + mined.numel()
+            gw = gathered[:, at: at + minew.numel()].reshape(p, *minew.shape)
+            gz = gathered[:, at + minew.numel(): at + 2 * minew.numel()].reshape(p, *minew.shape)
+            gi = gathered[:, at + 2 * minew.numel():].view(torch.int32).reshape(p, *minei.shape, 1)
+            return image4, depth, Attribution(rows(gw), rows(gz), rows(gi).reshape(n_rays))
         return image4, depth
 
     # ---- north_star's cheaper model: per-ray sums of independently composited objects

@@ -113,13 +113,29 @@ __global__ void __launch_bounds__(256) k_composite_fixed(const float *__restrict
 // object, 20 B written per ray and background. n_bg backgrounds (the reference composites every view twice, white and black,
 // compute_metrics_both_backgrounds): image4 [n_bg,N,4]. merged4 (optional) [N,T] receives (max density, best rgb) for callers that
 // keep the reference's max_densities / max_rgbs.
-#define FOC_COMBINE_MAX_OBJECTS 16
 struct CombineFields { const float4 *p[FOC_COMBINE_MAX_OBJECTS]; };
 
-__global__ void __launch_bounds__(256) k_combine_select_composite(CombineFields fields, uint32_t K, const float *__restrict__ nears,
-                                                                  const float *__restrict__ fars, uint32_t N, uint32_t T, float bg0, float bg1,
-                                                                  uint32_t n_bg, float *__restrict__ image4, float *__restrict__ depth,
-                                                                  float4 *__restrict__ merged4) {
+// Attribution (foc_combine_select_composite_attr): who supplied the surviving sample. Field k carries a constant object id, or a uint8
+// [N,T] plane when it is itself a pre-merge of several objects (k_combine_select4_ids).
+struct CombineAttr {
+    const uint8_t *plane[FOC_COMBINE_MAX_OBJECTS];     // nullptr: the constant id[k]
+    uint32_t id[FOC_COMBINE_MAX_OBJECTS];
+    uint32_t n_obj;
+    float *obj_weights, *obj_depth;                    // [N, n_obj]
+    int32_t *instance;                                 // [N]
+    uint8_t *winner;                                   // [N,T] or nullptr
+};
+
+// The body of both kernels. NOBJ == 0: select + composite, nothing else (every attribution statement is compiled out and `at` is never
+// read). NOBJ = 4 / 8 / 16 >= n_obj: the winner id travels with the rgb through the select — replaced by the very comparison that replaces
+// the rgb — and each lane keeps NOBJ weight and NOBJ depth accumulators updated with compare-selects; the loops over objects are bounded by
+// the template argument, so the accumulators are registers (an array indexed by the winner itself would live in scratch memory). The
+// composite's own arithmetic is the same statements in the same order: image4 / depth / merged4 are bit for bit those of NOBJ == 0.
+template <int NOBJ>
+__device__ __forceinline__ void combine_select_composite_body(const CombineFields &fields, const CombineAttr *at, uint32_t K,
+                                                              const float *__restrict__ nears, const float *__restrict__ fars, uint32_t N,
+                                                              uint32_t T, float bg0, float bg1, uint32_t n_bg, float *__restrict__ image4,
+                                                              float *__restrict__ depth, float4 *__restrict__ merged4) {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t n = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (n >= N) return;
@@ -128,20 +144,35 @@ __global__ void __launch_bounds__(256) k_combine_select_composite(CombineFields 
     const float sample_dist = span / (float)T;
     const float step = 1.0f / (float)(T - 1);
     float Tc = 1.0f, r = 0, g = 0, b = 0, a = 0, d = 0, ws = 0;
+    float aw[NOBJ > 0 ? NOBJ : 1], ad[NOBJ > 0 ? NOBJ : 1];
+    (void)aw; (void)ad;
+    if constexpr (NOBJ > 0) {
+#pragma unroll
+        for (int k = 0; k < NOBJ; k++) aw[k] = ad[k] = 0.0f;
+    }
     for (uint32_t base = 0; base < T; base += 64) {
         const uint32_t i = base + lane;
         const bool valid = i < T;
         float alpha = 0, sigma = 0, c0 = 0, c1 = 0, c2 = 0, oz = 0;
+        uint32_t win = 0xFFu;                                                    // lanes past T hold no sample: no column
         if (valid) {
             const uint64_t s = (uint64_t)n * T + i;
             float4 best = fields.p[0][s];
+            if constexpr (NOBJ > 0) win = at->plane[0] ? (uint32_t)at->plane[0][s] : at->id[0];
             for (uint32_t k = 1; k < K; k++) {
                 const float4 f = fields.p[k][s];
                 const float m = best.x;
+                if constexpr (NOBJ > 0) {
+                    const uint32_t idk = at->plane[k] ? (uint32_t)at->plane[k][s] : at->id[k];
+                    if (f.x > m) win = idk;
+                }
                 if (f.x > m) { best.y = f.y; best.z = f.z; best.w = f.w; }
                 best.x = (f.x != f.x || m != m) ? __builtin_nanf("") : (f.x > m ? f.x : m);      // torch.maximum propagates NaN
             }
             if (merged4) merged4[s] = best;
+            if constexpr (NOBJ > 0) {
+                if (at->winner) at->winner[s] = (uint8_t)win;
+            }
             sigma = best.x; c0 = best.y; c1 = best.z; c2 = best.w;
             const float l0 = (i < T / 2) ? (step * (float)i) : fmaf(-step, (float)(T - 1 - i), 1.0f);   // device linspace: see fixedstep.hip
             const float z = near + span * l0;
@@ -162,9 +193,36 @@ __global__ void __launch_bounds__(256) k_combine_select_composite(CombineFields 
         const float w = alpha * (Tc * Pex);
         r = fmaf(w, c0, r); g = fmaf(w, c1, g); b = fmaf(w, c2, b);
         a = fmaf(w, sigma, a); d = fmaf(w, oz, d); ws += w;
+        if constexpr (NOBJ > 0) {
+#pragma unroll
+            for (int k = 0; k < NOBJ; k++) {                                     // the statements of `ws` and `d`, kept by the winner's column only
+                const bool mine = win == (uint32_t)k;
+                aw[k] = mine ? aw[k] + w : aw[k];
+                ad[k] = mine ? fmaf(w, oz, ad[k]) : ad[k];
+            }
+        }
         Tc *= __shfl(P, 63, 64);
     }
     r = wave_sum(r); g = wave_sum(g); b = wave_sum(b); a = wave_sum(a); d = wave_sum(d); ws = wave_sum(ws);
+    if constexpr (NOBJ > 0) {
+        // one fixed tree per used column (no atomics: run-to-run bit-stable); every lane ends up with every sum, lane k stores column k
+        const uint32_t n_obj = at->n_obj;
+        float my_w = 0.0f, my_d = 0.0f, top = 0.0f;
+        int32_t inst = -1;
+#pragma unroll
+        for (int k = 0; k < NOBJ; k++) {
+            if ((uint32_t)k < n_obj) {                                           // wave-uniform
+                const float sw = wave_sum(aw[k]), sd = wave_sum(ad[k]);
+                if (lane == (uint32_t)k) { my_w = sw; my_d = sd; }
+                if (sw > top) { top = sw; inst = k; }                            // strict: the first of equal columns; NaN and 0 never
+            }
+        }
+        if (lane < n_obj) {
+            at->obj_weights[(uint64_t)n * n_obj + lane] = my_w;
+            at->obj_depth[(uint64_t)n * n_obj + lane] = my_d;
+        }
+        if (lane == 0) at->instance[n] = inst;
+    }
     if (lane == 0) {
         for (uint32_t q = 0; q < n_bg; q++) {
             const float rest = (1 - ws) * (q == 0 ? bg0 : bg1);
@@ -176,6 +234,21 @@ __global__ void __launch_bounds__(256) k_combine_select_composite(CombineFields 
     }
 }
 
+__global__ void __launch_bounds__(256) k_combine_select_composite(CombineFields fields, uint32_t K, const float *__restrict__ nears,
+                                                                  const float *__restrict__ fars, uint32_t N, uint32_t T, float bg0, float bg1,
+                                                                  uint32_t n_bg, float *__restrict__ image4, float *__restrict__ depth,
+                                                                  float4 *__restrict__ merged4) {
+    combine_select_composite_body<0>(fields, nullptr, K, nears, fars, N, T, bg0, bg1, n_bg, image4, depth, merged4);
+}
+
+template <int NOBJ>
+__global__ void __launch_bounds__(256) k_combine_select_composite_attr(CombineFields fields, CombineAttr at, uint32_t K,
+                                                                       const float *__restrict__ nears, const float *__restrict__ fars, uint32_t N,
+                                                                       uint32_t T, float bg0, float bg1, uint32_t n_bg, float *__restrict__ image4,
+                                                                       float *__restrict__ depth, float4 *__restrict__ merged4) {
+    combine_select_composite_body<NOBJ>(fields, &at, K, nears, fars, N, T, bg0, bg1, n_bg, image4, depth, merged4);
+}
+
 // Pre-merge of the objects that share a rank before the exchange (K objects on fewer GPUs): acc4 <- select(acc4, f4), same rule. The
 // select is associative over the object order, so merging a rank's consecutive objects first and the ranks afterwards equals the
 // reference's one sequential pass.
@@ -185,6 +258,20 @@ __global__ void __launch_bounds__(256) k_combine_select4(const float4 *__restric
         float4 best = acc4[i];
         const float m = best.x;
         if (f.x > m) { best.y = f.y; best.z = f.z; best.w = f.w; }
+        best.x = (f.x != f.x || m != m) ? __builtin_nanf("") : (f.x > m ? f.x : m);
+        acc4[i] = best;
+    }
+}
+
+// The same pre-merge when the view's attribution is asked for: acc_ids [n] holds, per sample, the id of the object whose rgb acc4 holds (the
+// caller fills it with the first object's id); the incoming field is ONE object, and the plane takes its id exactly where the rgb is taken.
+__global__ void __launch_bounds__(256) k_combine_select4_ids(const float4 *__restrict__ f4, uint8_t id, float4 *__restrict__ acc4,
+                                                             uint8_t *__restrict__ acc_ids, uint64_t n) {
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
+        const float4 f = f4[i];
+        float4 best = acc4[i];
+        const float m = best.x;
+        if (f.x > m) { best.y = f.y; best.z = f.z; best.w = f.w; acc_ids[i] = id; }
         best.x = (f.x != f.x || m != m) ? __builtin_nanf("") : (f.x > m ? f.x : m);
         acc4[i] = best;
     }
@@ -300,6 +387,64 @@ int foc_combine_select4(const float *field4, float *acc4, uint64_t n, void *stre
     hipLaunchKernelGGL(k_combine_select4, dim3(foc_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float4 *>(field4),
                        reinterpret_cast<float4 *>(acc4), n);
     FOC_CHECK_LAUNCH("combine_select4");
+    return FOC_OK;
+}
+
+int foc_combine_select_composite_attr(const float *const *fields4, uint32_t K, const uint8_t *const *id_planes, const uint32_t *ids,
+                                      uint32_t n_obj, const float *nears, const float *fars, uint32_t N, uint32_t T, const float *bgs,
+                                      uint32_t n_bg, float *image4, float *depth, float *merged4, float *obj_weights, float *obj_depth,
+                                      int32_t *instance, uint8_t *winner, void *stream) {
+    FocDeviceGuard foc_guard_(stream, nears);
+    FOC_REQUIRE(K >= 1 && K <= FOC_COMBINE_MAX_OBJECTS, FOC_E_INVALID, "combine_select_composite_attr: 1 <= K <= %d fields per call (got %u)",
+                FOC_COMBINE_MAX_OBJECTS, K);
+    FOC_REQUIRE(n_obj >= 1 && n_obj <= FOC_COMBINE_MAX_OBJECTS, FOC_E_INVALID, "combine_select_composite_attr: 1 <= n_obj <= %d objects (got %u)",
+                FOC_COMBINE_MAX_OBJECTS, n_obj);
+    FOC_REQUIRE(n_bg >= 1 && n_bg <= 2 && bgs, FOC_E_INVALID, "combine_select_composite_attr: one or two backgrounds");
+    FOC_REQUIRE(T >= 2, FOC_E_INVALID, "combine_select_composite_attr: T must be >= 2");
+    FOC_REQUIRE(fields4, FOC_E_INVALID, "combine_select_composite_attr: fields4 is null");
+    CombineFields f;
+    CombineAttr at;
+    for (uint32_t k = 0; k < FOC_COMBINE_MAX_OBJECTS; k++) {
+        const uint32_t j = k < K ? k : 0;
+        at.plane[k] = id_planes ? id_planes[j] : nullptr;
+        FOC_REQUIRE(at.plane[k] || ids, FOC_E_INVALID, "combine_select_composite_attr: field %u has neither an id plane nor a constant id (ids is null)", j);
+        at.id[k] = at.plane[k] ? 0u : ids[j];
+        FOC_REQUIRE(at.id[k] < n_obj, FOC_E_INVALID, "combine_select_composite_attr: ids[%u] = %u is not below n_obj = %u", j, at.id[k], n_obj);
+    }
+    if (N == 0) return FOC_OK;
+    FOC_REQUIRE(nears && fars && image4 && depth, FOC_E_INVALID, "combine_select_composite_attr: null pointer");
+    FOC_REQUIRE(obj_weights && obj_depth && instance, FOC_E_INVALID, "combine_select_composite_attr: obj_weights, obj_depth and instance must not be null");
+    for (uint32_t k = 0; k < FOC_COMBINE_MAX_OBJECTS; k++) {
+        f.p[k] = reinterpret_cast<const float4 *>(k < K ? fields4[k] : fields4[0]);
+        FOC_REQUIRE(f.p[k] && ((uintptr_t)f.p[k] & 15) == 0, FOC_E_INVALID, "combine_select_composite_attr: field %u is null or not 16-byte aligned", k);
+    }
+    FOC_REQUIRE(((uintptr_t)merged4 & 15) == 0, FOC_E_INVALID, "combine_select_composite_attr: merged4 must be 16-byte aligned");
+    FOC_REQUIRE(((uintptr_t)obj_weights & 3) == 0 && ((uintptr_t)obj_depth & 3) == 0 && ((uintptr_t)instance & 3) == 0, FOC_E_INVALID,
+                "combine_select_composite_attr: obj_weights, obj_depth and instance must be 4-byte aligned");
+    at.n_obj = n_obj;
+    at.obj_weights = obj_weights; at.obj_depth = obj_depth; at.instance = instance; at.winner = winner;
+    const dim3 grid(foc_div_up(N, 4)), block(256);
+    const float bg1 = n_bg > 1 ? bgs[1] : 0.0f;
+    float4 *m4 = reinterpret_cast<float4 *>(merged4);
+    if (n_obj <= 4)
+        hipLaunchKernelGGL(k_combine_select_composite_attr<4>, grid, block, 0, (hipStream_t)stream, f, at, K, nears, fars, N, T, bgs[0], bg1, n_bg, image4, depth, m4);
+    else if (n_obj <= 8)
+        hipLaunchKernelGGL(k_combine_select_composite_attr<8>, grid, block, 0, (hipStream_t)stream, f, at, K, nears, fars, N, T, bgs[0], bg1, n_bg, image4, depth, m4);
+    else
+        hipLaunchKernelGGL(k_combine_select_composite_attr<16>, grid, block, 0, (hipStream_t)stream, f, at, K, nears, fars, N, T, bgs[0], bg1, n_bg, image4, depth, m4);
+    FOC_CHECK_LAUNCH("combine_select_composite_attr");
+    return FOC_OK;
+}
+
+int foc_combine_select4_ids(const float *field4, uint32_t id, float *acc4, uint8_t *acc_ids, uint64_t n, void *stream) {
+    FocDeviceGuard foc_guard_(stream, field4);
+    FOC_REQUIRE(id < FOC_COMBINE_MAX_OBJECTS, FOC_E_INVALID, "combine_select4_ids: id %u is not below %d", id, FOC_COMBINE_MAX_OBJECTS);
+    FOC_REQUIRE(n == 0 || (field4 && acc4 && acc_ids), FOC_E_INVALID, "combine_select4_ids: null pointer");
+    FOC_REQUIRE((((uintptr_t)field4 | (uintptr_t)acc4) & 15) == 0, FOC_E_INVALID, "combine_select4_ids: fields must be 16-byte aligned");
+    if (n == 0) return FOC_OK;
+    hipLaunchKernelGGL(k_combine_select4_ids, dim3(foc_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float4 *>(field4),
+                       (uint8_t)id, reinterpret_cast<float4 *>(acc4), acc_ids, n);
+    FOC_CHECK_LAUNCH("combine_select4_ids");
     return FOC_OK;
 }
 

@@ -589,6 +589,8 @@ int foc_composite_fixed_steps(const float *sigmas, const float *rgbs, const floa
                               const float *fars, uint32_t N, uint32_t T, float bg,
                               float *image4, float *depth, void *stream);
 
+#define FOC_COMBINE_MAX_OBJECTS 16 /* fields per fused call (the kernel's argument block), and objects per attributed scene */
+
 /* The same select and composite fused over K objects' PACKED fields, the form the one-object-per-GPU exchange moves
  * (focnerf_amd/combine.py): fields4[k] -> device pointer to object k's [N,T,4] fp32 rows (sigma, r, g, b), k in checkpoint
  * order (host array of K device pointers, K <= 16; more objects: pre-merge with foc_combine_select4, the rule is
@@ -601,6 +603,39 @@ int foc_combine_select_composite(const float *const *fields4, uint32_t K, const 
 
 /* acc4 <- select(acc4, field4) on n packed samples (same rule; acc4 holds the earlier objects). */
 int foc_combine_select4(const float *field4, float *acc4, uint64_t n, void *stream);
+
+/* Attribution of the combined render: foc_combine_select_composite that also says WHICH object each part of the result came
+ * from (no reference counterpart: COMBINED.py forgets the select's decision; a caller would have to store merged4 and repeat
+ * the select). Inputs as above, plus an identity per field: the constant object id ids[k], or — for a field that is already a
+ * pre-merge of several objects (foc_combine_select4_ids) — a uint8 [N,T] plane id_planes[k] with the id per sample.
+ * id_planes: host array of K device pointers, an entry or the whole array may be NULL (= use ids[k]); ids: host array of K
+ * values, read only for fields without a plane (NULL allowed when every field has one). n_obj = number of objects in the
+ * scene, 1 <= n_obj <= FOC_COMBINE_MAX_OBJECTS; every id is < n_obj.
+ *
+ * Winner of a sample = the id travelling with the rgb the select keeps: field 0's id to begin with; field k's id replaces it
+ * exactly when `sigma_k > running max` at k's turn — the comparison that replaces the rgb. So the first object keeps ties and
+ * a NaN density never takes the rgb and therefore never the id.
+ * Per ray, with w_i = alpha_i * T_i the composite's own weight of sample i and oz_i its clamped normalised depth:
+ *   obj_weights [N, n_obj]  sum of w_i over the samples whose winner is that object. Columns of objects that never win are
+ *                           exactly 0; a row sums to the ray's weights_sum up to rounding.
+ *   obj_depth   [N, n_obj]  sum of w_i * oz_i over the same samples; a row sums to depth[n] up to rounding.
+ *   instance    [N] int32   the first index of the row's largest obj_weights entry, or -1 when no entry is > 0 (an empty
+ *                           ray; NaN entries are never the largest, a row of NaN gives -1).
+ *   winner      [N,T] uint8 (optional, NULL: not written) the winner per sample.
+ * image4, depth and merged4 are what foc_combine_select_composite writes, bit for bit. No atomics: a ray's sums are one
+ * wave's fixed tree, so every output is run-to-run bit-stable whatever FOC_DETERMINISTIC says.
+ * Constant ids are checked here (ids[k] >= n_obj: FOC_E_INVALID). The bytes of an id plane cannot be: a sample whose plane
+ * says id >= n_obj is counted in NO column and can never be the instance; it still composites into image4 / depth. */
+int foc_combine_select_composite_attr(const float *const *fields4, uint32_t K, const uint8_t *const *id_planes,
+                                      const uint32_t *ids, uint32_t n_obj, const float *nears, const float *fars,
+                                      uint32_t N, uint32_t T, const float *bgs, uint32_t n_bg, float *image4, float *depth,
+                                      float *merged4, float *obj_weights, float *obj_depth, int32_t *instance,
+                                      uint8_t *winner, void *stream);
+
+/* foc_combine_select4 that keeps the identity: acc_ids [n] uint8 holds, per sample, the id of the object whose rgb acc4 holds
+ * (the caller fills it with the first object's id). field4 is ONE object with the constant id `id` (< FOC_COMBINE_MAX_OBJECTS);
+ * acc_ids[i] takes it exactly where acc4 takes field4's rgb. acc4 is updated as by foc_combine_select4, bit for bit. */
+int foc_combine_select4_ids(const float *field4, uint32_t id, float *acc4, uint8_t *acc_ids, uint64_t n, void *stream);
 
 /* MONeRFNetwork's running select (reference: nerf/multiobjectnetwork.py:66-82 — torch.max over stack([new, best]) with
  * take_along_dim of the rows that travel with the density: geo_feat [n,15] in density(), colour [n,3] in color()).
