@@ -9,7 +9,7 @@
 //   * the sphere coordinates: k_sph_from_ray (raymarching.hip), then (x + 1) / 2 as GridEncoder.forward takes it;
 //   * the grid: gridencoder.hip's D = 2 forward (same index math, corner order and fmaf chain); the fp32 table is rounded to fp16 on
 //     load, which gives the values of the op path's `.half()` copy, and each level's pair is rounded to fp16;
-//   * SH: head.hip's k_sh_encode expressions in fp32, rounded to fp16 (autocast casts the promoted cat to fp16 for nn.Linear);
+//   * SH: sample_math.h foc_sh16 (k_sh_encode's row) in fp32, rounded to fp16 (autocast casts the promoted cat to fp16 for nn.Linear);
 //   * the MLP: fp32 sums of fp16 products, rounded to fp16 per layer, ReLU on the rounded value, sigmoid in fp32 rounded to fp16.
 // The MLP sums run in another order than the GEMMs of the op path: rgb agrees within a few fp16 ulps (tests/test_gpu_network_linear.py).
 //
@@ -26,6 +26,7 @@
 //     in LDS and sums every weight's products over its rays in ray order, chunk after chunk; k_bg_dw_reduce adds the workgroups'
 //     partials in workgroup order. The assignment of rays to workgroups depends only on N: the same bits on every run.
 #include "common.h"
+#include "sample_math.h"
 #include <math.h>
 
 #define BG_LEVELS 4
@@ -47,27 +48,6 @@ struct BgLevels {
     uint32_t resolution[BG_LEVELS];
 };
 
-// degree-4 real spherical harmonics: head.hip hd_sh16's expressions
-__device__ __forceinline__ void bg_sh16(float x, float y, float z, float (&o)[16]) {
-    const float xy = x * y, xz = x * z, yz = y * z, x2 = x * x, y2 = y * y, z2 = z * z;
-    o[0] = 0.28209479177387814f;
-    o[1] = -0.48860251190291987f * y;
-    o[2] = 0.48860251190291987f * z;
-    o[3] = -0.48860251190291987f * x;
-    o[4] = 1.0925484305920792f * xy;
-    o[5] = -1.0925484305920792f * yz;
-    o[6] = 0.94617469575755997f * z2 - 0.31539156525251999f;
-    o[7] = -1.0925484305920792f * xz;
-    o[8] = 0.54627421529603959f * x2 - 0.54627421529603959f * y2;
-    o[9] = 0.59004358992664352f * y * (-3.0f * x2 + y2);
-    o[10] = 2.8906114426405538f * xy * z;
-    o[11] = 0.45704579946446572f * y * (1.0f - 5.0f * z2);
-    o[12] = 0.3731763325901154f * z * (5.0f * z2 - 3.0f);
-    o[13] = 0.45704579946446572f * x * (1.0f - 5.0f * z2);
-    o[14] = 1.4453057213202769f * z * (x2 - y2);
-    o[15] = 0.59004358992664352f * x * (-x2 + 3.0f * y2);
-}
-
 __device__ __forceinline__ float bg_h(float v) { return (float)foc_f2h(v); }
 
 // gridencoder.hip ge_index<2> (gridencoder.cu:50-84) for align_corners = false, gridtype hash
@@ -88,7 +68,7 @@ __device__ __forceinline__ bool bg_input(const float *__restrict__ rays_o, const
                                          const BgLevels &lv, float (&x)[BG_IN], uint32_t (&rows)[BG_LEVELS][4], float (&wts)[BG_LEVELS][4]) {
     const float dx = rays_d[(uint64_t)n * 3], dy = rays_d[(uint64_t)n * 3 + 1], dz = rays_d[(uint64_t)n * 3 + 2];
     float sh[16];
-    bg_sh16(dx, dy, dz, sh);
+    foc_sh16(dx, dy, dz, sh);
 #pragma unroll
     for (int j = 0; j < 16; j++) x[j] = bg_h(sh[j]);
     float cx, cy;
@@ -164,7 +144,9 @@ __device__ __forceinline__ void bg_mlp(const float *w, const float (&x)[BG_IN], 
     for (int k = 0; k < BG_OUT; k++) o[k] = bg_h(o[k]);
 }
 
-// torch.sigmoid on a half tensor: evaluated in fp32, rounded to half (head.hip hd_sigmoid_h)
+// torch.sigmoid on a half tensor: evaluated in fp32, rounded to half — sample_math.h foc_sigmoid_h's expression, rounded through foc_f2h
+// (bg_h, like every rounding of this file) where foc_sigmoid_h casts directly. The values are the same; the barrier in foc_f2h makes the
+// compiler emit another instruction sequence for k_bg_forward / k_bg_backward, so this form stays here, with the kernels it was measured in.
 __device__ __forceinline__ float bg_sigmoid_h(float v) { return bg_h(1.0f / (1.0f + expf(-v))); }
 
 __global__ void __launch_bounds__(256) k_bg_forward(const float *__restrict__ rays_o, const float *__restrict__ rays_d, const float *__restrict__ coords,

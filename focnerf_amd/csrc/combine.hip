@@ -9,6 +9,7 @@
 //   torch.cumprod (COMBINED.py:141-200 / nerf/renderer.py:169-221), one wave per ray with a
 //   wave product-scan over 64 samples at a time.
 #include "common.h"
+#include "fs_common.h"        // fs_geom, fs_sample, fs_trans_scan: the fixed-step sample step of fixedstep.hip
 #include <string.h>
 
 // ---------------------------------------------------------------- error plumbing
@@ -52,48 +53,32 @@ __global__ void __launch_bounds__(256) k_combine_unpack(const uint64_t *__restri
     }
 }
 
-// One wave per ray. z_i = near + (far-near)*lin_i with lin = torch.linspace(0,1,T) evaluated the way
-// torch fills it (symmetric halves); deltas = diff(z), last = (far-near)/T;
-// w_i = alpha_i * prod_{j<i}(1 - alpha_j + 1e-15).
+// One wave per ray. z_i, deltas = diff(z) with last = (far-near)/T and the depth's oz: fs_common.h fs_sample without noise;
+// w_i = alpha_i * prod_{j<i}(1 - alpha_j + 1e-15) (fs_trans_scan). alpha is this file's own rounding: 1 - __expf(-delta * sigma).
 __global__ void __launch_bounds__(256) k_composite_fixed(const float *__restrict__ sigmas, const float *__restrict__ rgbs,
                                                          const float *__restrict__ nears, const float *__restrict__ fars,
                                                          uint32_t N, uint32_t T, float bg, float *__restrict__ image4, float *__restrict__ depth) {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t n = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (n >= N) return;
-    const float near = nears[n], far = fars[n];
-    const float span = far - near;
-    const float sample_dist = span / (float)T;
-    const float step = 1.0f / (float)(T - 1);
+    const FsGeom geo = fs_geom(nears, fars, n, T);
     float Tc = 1.0f, r = 0, g = 0, b = 0, a = 0, d = 0, ws = 0;
     for (uint32_t base = 0; base < T; base += 64) {
         const uint32_t i = base + lane;
         const bool valid = i < T;
         float alpha = 0, sigma = 0, c0 = 0, c1 = 0, c2 = 0, oz = 0;
         if (valid) {
-            const float l0 = (i < T / 2) ? (step * (float)i) : fmaf(-step, (float)(T - 1 - i), 1.0f);   // device linspace: see fixedstep.hip
-            const float z = near + span * l0;
-            float delta = sample_dist;
-            if (i + 1 < T) {
-                const uint32_t i1 = i + 1;
-                const float l1 = (i1 < T / 2) ? (step * (float)i1) : fmaf(-step, (float)(T - 1 - i1), 1.0f);
-                delta = (near + span * l1) - z;
-            }
+            const FsSample p = fs_sample(geo, i, i, T, false, 0.0f, 0.0f);
             const uint64_t s = (uint64_t)n * T + i;
             sigma = sigmas[s];
             c0 = rgbs[s * 3]; c1 = rgbs[s * 3 + 1]; c2 = rgbs[s * 3 + 2];
-            alpha = 1 - __expf(-delta * sigma);
-            oz = (z - near) / span;
-            oz = oz < 0 ? 0 : (oz > 1 ? 1 : oz);
+            alpha = 1 - __expf(-p.delta * sigma);
+            oz = p.oz;
         }
         const float om = valid ? (1 - alpha + 1e-15f) : 1.0f;
-        const float P = wave_incl_prod(om, (int)lane);
-        float Pex = __shfl_up(P, 1, 64);
-        if (lane == 0) Pex = 1.0f;
-        const float w = alpha * (Tc * Pex);
+        const float w = alpha * fs_trans_scan(om, lane, Tc);
         r = fmaf(w, c0, r); g = fmaf(w, c1, g); b = fmaf(w, c2, b);
         a = fmaf(w, sigma, a); d = fmaf(w, oz, d); ws += w;
-        Tc *= __shfl(P, 63, 64);
     }
     r = wave_sum(r); g = wave_sum(g); b = wave_sum(b); a = wave_sum(a); d = wave_sum(d); ws = wave_sum(ws);
     if (lane == 0) {
@@ -139,10 +124,7 @@ __device__ __forceinline__ void combine_select_composite_body(const CombineField
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t n = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (n >= N) return;
-    const float near = nears[n], far = fars[n];
-    const float span = far - near;
-    const float sample_dist = span / (float)T;
-    const float step = 1.0f / (float)(T - 1);
+    const FsGeom geo = fs_geom(nears, fars, n, T);
     float Tc = 1.0f, r = 0, g = 0, b = 0, a = 0, d = 0, ws = 0;
     float aw[NOBJ > 0 ? NOBJ : 1], ad[NOBJ > 0 ? NOBJ : 1];
     (void)aw; (void)ad;
@@ -174,23 +156,12 @@ __device__ __forceinline__ void combine_select_composite_body(const CombineField
                 if (at->winner) at->winner[s] = (uint8_t)win;
             }
             sigma = best.x; c0 = best.y; c1 = best.z; c2 = best.w;
-            const float l0 = (i < T / 2) ? (step * (float)i) : fmaf(-step, (float)(T - 1 - i), 1.0f);   // device linspace: see fixedstep.hip
-            const float z = near + span * l0;
-            float delta = sample_dist;
-            if (i + 1 < T) {
-                const uint32_t i1 = i + 1;
-                const float l1 = (i1 < T / 2) ? (step * (float)i1) : fmaf(-step, (float)(T - 1 - i1), 1.0f);
-                delta = (near + span * l1) - z;
-            }
-            alpha = 1 - __expf(-delta * sigma);
-            oz = (z - near) / span;
-            oz = oz < 0 ? 0 : (oz > 1 ? 1 : oz);
+            const FsSample p = fs_sample(geo, i, i, T, false, 0.0f, 0.0f);
+            alpha = 1 - __expf(-p.delta * sigma);
+            oz = p.oz;
         }
         const float om = valid ? (1 - alpha + 1e-15f) : 1.0f;
-        const float P = wave_incl_prod(om, (int)lane);
-        float Pex = __shfl_up(P, 1, 64);
-        if (lane == 0) Pex = 1.0f;
-        const float w = alpha * (Tc * Pex);
+        const float w = alpha * fs_trans_scan(om, lane, Tc);
         r = fmaf(w, c0, r); g = fmaf(w, c1, g); b = fmaf(w, c2, b);
         a = fmaf(w, sigma, a); d = fmaf(w, oz, d); ws += w;
         if constexpr (NOBJ > 0) {
@@ -201,7 +172,6 @@ __device__ __forceinline__ void combine_select_composite_body(const CombineField
                 ad[k] = mine ? fmaf(w, oz, ad[k]) : ad[k];
             }
         }
-        Tc *= __shfl(P, 63, 64);
     }
     r = wave_sum(r); g = wave_sum(g); b = wave_sum(b); a = wave_sum(a); d = wave_sum(d); ws = wave_sum(ws);
     if constexpr (NOBJ > 0) {

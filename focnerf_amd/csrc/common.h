@@ -148,6 +148,14 @@ __device__ __forceinline__ float wave_incl_prod(float v, int lane) {
     }
     return v;
 }
+// The transmittance scan of every one-wave-per-ray composite: P = inclusive product of `om` over the lanes, the return value the
+// exclusive one (1 on lane 0). A ray's transmittance before / after lane's sample is carry * exclusive / carry * P.
+__device__ __forceinline__ float wave_prod_scan(float om, uint32_t lane, float &P) {
+    P = wave_incl_prod(om, (int)lane);
+    float Pex = __shfl_up(P, 1, 64);
+    if (lane == 0) Pex = 1.0f;
+    return Pex;
+}
 __device__ __forceinline__ float wave_incl_sum(float v, int lane) {
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {

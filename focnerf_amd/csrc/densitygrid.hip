@@ -13,23 +13,7 @@
 // The network evaluation between sample and apply stays with the caller. Randomness comes in as tensors (like `noises` of
 // march_rays_train), so the CPU oracle can replay a call exactly. These entry points have no reference binding.
 #include "common.h"
-
-__device__ __forceinline__ uint32_t dg_expand_bits(uint32_t v) {
-    v = (v * 0x00010001u) & 0xFF0000FFu;
-    v = (v * 0x00000101u) & 0x0F00F00Fu;
-    v = (v * 0x00000011u) & 0xC30C30C3u;
-    v = (v * 0x00000005u) & 0x49249249u;
-    return v;
-}
-__device__ __forceinline__ uint32_t dg_morton3D(uint32_t x, uint32_t y, uint32_t z) { return dg_expand_bits(x) | (dg_expand_bits(y) << 1) | (dg_expand_bits(z) << 2); }
-__device__ __forceinline__ uint32_t dg_compact_bits(uint32_t x) {
-    x = x & 0x49249249u;
-    x = (x | (x >> 2)) & 0xc30c30c3u;
-    x = (x | (x >> 4)) & 0x0f00f00fu;
-    x = (x | (x >> 8)) & 0xff0000ffu;
-    x = (x | (x >> 16)) & 0x0000ffffu;
-    return x;
-}
+#include "occ_cell.h"        // rm_morton3D, rm_morton3D_invert
 
 struct DgCascades { float scale[8]; float half[8]; };       // per cascade: float(bound_c - bound_c/H), float(bound_c/H), bound_c = min(2^c, bound)
 
@@ -53,8 +37,8 @@ __global__ void __launch_bounds__(256) k_dg_mark_untrained(const float *__restri
     const float Hm1 = (float)(H - 1);
     for (uint32_t g = blockIdx.x * 256 + threadIdx.x; g < C * H3; g += gridDim.x * 256) {
         const uint32_t cas = g / H3, m = g - cas * H3;
-        const float wx = dg_world(dg_compact_bits(m), Hm1) * cs.scale[cas], wy = dg_world(dg_compact_bits(m >> 1), Hm1) * cs.scale[cas],
-                    wz = dg_world(dg_compact_bits(m >> 2), Hm1) * cs.scale[cas];
+        const float wx = dg_world(rm_morton3D_invert(m), Hm1) * cs.scale[cas], wy = dg_world(rm_morton3D_invert(m >> 1), Hm1) * cs.scale[cas],
+                    wz = dg_world(rm_morton3D_invert(m >> 2), Hm1) * cs.scale[cas];
         const float h2 = cs.half[cas] * 2.0f;                  // `half_grid_size * 2` is exact in either precision
         int32_t count = 0;
         for (uint32_t b = 0; b < B; b++) {
@@ -77,7 +61,7 @@ __global__ void __launch_bounds__(256) k_dg_mark_untrained(const float *__restri
 // ---------------------------------------------------------------- query points
 __device__ __forceinline__ void dg_store_xyz(float *__restrict__ xyzs, uint64_t s, uint32_t m, float Hm1, float scale, float half,
                                              const float *__restrict__ jitter) {
-    float x = dg_world(dg_compact_bits(m), Hm1) * scale, y = dg_world(dg_compact_bits(m >> 1), Hm1) * scale, z = dg_world(dg_compact_bits(m >> 2), Hm1) * scale;
+    float x = dg_world(rm_morton3D_invert(m), Hm1) * scale, y = dg_world(rm_morton3D_invert(m >> 1), Hm1) * scale, z = dg_world(rm_morton3D_invert(m >> 2), Hm1) * scale;
     if (jitter) {   // cas_xyzs += (torch.rand_like(cas_xyzs) * 2 - 1) * half_grid_size
         x += (jitter[s * 3] * 2.0f - 1.0f) * half; y += (jitter[s * 3 + 1] * 2.0f - 1.0f) * half; z += (jitter[s * 3 + 2] * 2.0f - 1.0f) * half;
     }
@@ -148,7 +132,7 @@ __global__ void __launch_bounds__(256) k_dg_sample(DgCascades cs, uint32_t C, ui
         uint32_t m;
         const uint32_t j = i < N ? i : i - N;
         const int32_t *rc = rand_coords + ((uint64_t)cas * N + j) * 3;
-        const uint32_t m_rand = dg_morton3D((uint32_t)rc[0], (uint32_t)rc[1], (uint32_t)rc[2]);
+        const uint32_t m_rand = rm_morton3D((uint32_t)rc[0], (uint32_t)rc[1], (uint32_t)rc[2]);
         if (i < N) {
             m = m_rand;                                         // coords = torch.randint(0, H, (N,3)); indices = morton3D(coords)  (:479-480)
         } else {

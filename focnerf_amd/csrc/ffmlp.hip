@@ -1010,6 +1010,8 @@ __global__ void __launch_bounds__(256) k_mlp_dw_finalize_obj(const float *__rest
 //   rgb = sigmoid(color_net(cin)[0:3])   rounded to fp16 like the half sigmoid, stored as fp32
 // Per sample this reads 64 B of encoding + the direction and writes 16 B, instead of also writing and re-reading h (32 B), cin (64 B)
 // and the colour logits (32 B). Values are bit-identical to the separate kernels (same MFMA order, same roundings).
+// Half h (0: entries 0..7, 1: entries 8..15) of sample_math.h foc_sh16's row, the shared definition: the same expressions, repeated
+// here because the half is chosen by a runtime index and only its eight are evaluated.
 __device__ __forceinline__ void nf_sh16_half(float x, float y, float z, int h, h8 &out) {
     const float xy = x * y, xz = x * z, yz = y * z, x2 = x * x, y2 = y * y, z2 = z * z;
     float o[8];

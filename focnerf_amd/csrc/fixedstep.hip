@@ -14,42 +14,8 @@
 // gather -> MLP -> scatter, without the nonzero/index round trips).
 // SURVEY.md §8(f)-3; these entry points have no reference binding.
 #include "common.h"
-#include "fs_common.h"        // FsGeom, fs_geom, fs_z, fs_point, fs_block_row: the sample positions, shared with fixedcull.hip
+#include "fs_common.h"        // the sample positions (shared with fixedcull.hip), the per-sample step and scan (with combine.hip), sample_math.h
 #include <float.h>
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-
-// fs_z's value from a noise draw that is already in a register (NOISE = false: no jitter term at all, like fs_z with a null pointer).
-// The tail kernels load both draws a sample needs up front, unconditionally, so that all loads of an iteration are in flight together:
-// behind `if (noise)` / `if (i + 1 < T)` each load was its own round trip (s_waitcnt vmcnt(0) after every one of them).
-template <bool NOISE>
-__device__ __forceinline__ float fs_zu(const FsGeom &g, uint32_t i, uint32_t T, float u) {
-    const float lin = (i < T / 2) ? (g.step * (float)i) : fmaf(-g.step, (float)(T - 1 - i), 1.0f);
-    float z = g.near + g.span * lin;
-    if (NOISE) z = z + (u - 0.5f) * g.sample_dist;
-    return z;
-}
-
-// degree-4 real spherical harmonics (focnerf_amd/shencoder.py), same expressions in fp32
-__device__ __forceinline__ void fs_sh16(float x, float y, float z, float (&o)[16]) {
-    const float xy = x * y, xz = x * z, yz = y * z, x2 = x * x, y2 = y * y, z2 = z * z;
-    o[0] = 0.28209479177387814f;
-    o[1] = -0.48860251190291987f * y;
-    o[2] = 0.48860251190291987f * z;
-    o[3] = -0.48860251190291987f * x;
-    o[4] = 1.0925484305920792f * xy;
-    o[5] = -1.0925484305920792f * yz;
-    o[6] = 0.94617469575755997f * z2 - 0.31539156525251999f;
-    o[7] = -1.0925484305920792f * xz;
-    o[8] = 0.54627421529603959f * x2 - 0.54627421529603959f * y2;
-    o[9] = 0.59004358992664352f * y * (-3.0f * x2 + y2);
-    o[10] = 2.8906114426405538f * xy * z;
-    o[11] = 0.45704579946446572f * y * (1.0f - 5.0f * z2);
-    o[12] = 0.3731763325901154f * z * (5.0f * z2 - 3.0f);
-    o[13] = 0.45704579946446572f * x * (1.0f - 5.0f * z2);
-    o[14] = 1.4453057213202769f * z * (x2 - y2);
-    o[15] = 0.59004358992664352f * x * (-x2 + 3.0f * y2);
-}
 
 // ---------------------------------------------------------------- sample generation
 __global__ void __launch_bounds__(256) k_fs_sample(const float *__restrict__ rays_o, const float *__restrict__ rays_d, const float *__restrict__ nears,
@@ -82,11 +48,8 @@ __global__ void __launch_bounds__(256) k_fs_sample(const float *__restrict__ ray
         if (xyzs) { xyzs[s * 3] = x; xyzs[s * 3 + 1] = y; xyzs[s * 3 + 2] = w; }
         if (enc_in) { enc_in[s * 3] = fs_norm(x, bound, two_b); enc_in[s * 3 + 1] = fs_norm(y, bound, two_b); enc_in[s * 3 + 2] = fs_norm(w, bound, two_b); }
         if (ray_sh && i == 0 && own) {                     // the ray's SH row as it stands in the colour-net input (fp16), once per ray
-            float sh[16];
-            fs_sh16(rays_d[n * 3], rays_d[n * 3 + 1], rays_d[n * 3 + 2], sh);
             h8 lo, hi;
-#pragma unroll
-            for (int k = 0; k < 8; k++) { lo[k] = foc_f2h(sh[k]); hi[k] = foc_f2h(sh[8 + k]); }
+            foc_sh16_h(rays_d[n * 3], rays_d[n * 3 + 1], rays_d[n * 3 + 2], lo, hi);
             h8 *dst = reinterpret_cast<h8 *>(ray_sh + (uint64_t)n * 16);
             dst[0] = lo; dst[1] = hi;
         }
@@ -109,10 +72,7 @@ __global__ void __launch_bounds__(256) k_fs_head_fwd(const _Float16 *__restrict_
     h8 ob1 = {0, 0, 0, 0, 0, 0, 0, 0}, ob2 = {0, 0, 0, 0, 0, 0, 0, 0};   // cin columns 32..39 / 40..47 of the 48-wide form: obj[1..8], obj[9..15] | 0
     _Float16 ob0 = (_Float16)0;                                          // column 31: obj[0] (the 32-wide form has its zero pad there)
     if (cin) {
-        float sh[16];
-        fs_sh16(rays_d[n * 3], rays_d[n * 3 + 1], rays_d[n * 3 + 2], sh);
-#pragma unroll
-        for (int k = 0; k < 8; k++) { shlo[k] = foc_f2h(sh[k]); shhi[k] = foc_f2h(sh[8 + k]); }
+        foc_sh16_h(rays_d[n * 3], rays_d[n * 3 + 1], rays_d[n * 3 + 2], shlo, shhi);
         if (obj) {
             ob0 = obj[0];
 #pragma unroll
@@ -130,21 +90,14 @@ __global__ void __launch_bounds__(256) k_fs_head_fwd(const _Float16 *__restrict_
         if (cin) { r0 = *reinterpret_cast<const h8 *>(h + s * 16); r1 = *reinterpret_cast<const h8 *>(h + s * 16 + 8); }
         else r0[0] = h[s * 16];
         const float sigma = expf((float)r0[0]);                                  // trunc_exp forward (activation.py:9)
-        const float z = fs_z(g, valid ? i : T - 1, T, noise, s);
-        float delta = g.sample_dist;
-        if (i + 1 < T) delta = fs_z(g, i + 1, T, noise, s + 1) - z;
-        const float alpha = valid ? 1 - expf((-delta * density_scale) * sigma) : 0.0f;
+        const FsSample p = fs_sample_ld(g, i, valid ? i : T - 1, T, noise, s);
+        const float alpha = valid ? 1 - expf((-p.delta * density_scale) * sigma) : 0.0f;
         const float om = valid ? (1 - alpha + 1e-15f) : 1.0f;
-        const float P = wave_incl_prod(om, (int)lane);
-        float Pex = __shfl_up(P, 1, 64);
-        if (lane == 0) Pex = 1.0f;
-        const float Tb = Tc * Pex;
+        const float Tb = fs_trans_scan(om, lane, Tc);
         const float w = alpha * Tb;
         if (valid) {
             sigma_out[s] = sigma; trans_out[s] = Tb; weights_out[s] = w;
-            float oz = (z - g.near) / g.span;
-            oz = oz < 0.0f ? 0.0f : (oz > 1.0f ? 1.0f : oz);                       // keeps NaN (0/0 on rays that miss the box), like torch.clamp
-            ws += w; dp += w * oz;
+            ws += w; dp += w * p.oz;
             if (cin) {
                 h8 c2, c3;
 #pragma unroll
@@ -155,20 +108,9 @@ __global__ void __launch_bounds__(256) k_fs_head_fwd(const _Float16 *__restrict_
                 if (cin_ld == 48) { dst[4] = ob1; dst[5] = ob2; }
             }
         }
-        Tc *= __shfl(P, 63, 64);
     }
     ws = wave_sum(ws); dp = wave_sum(dp);
     if (lane == 0) { weights_sum[n] = ws; depth[n] = dp; }
-}
-
-// reverse (suffix) inclusive sum across the wave
-__device__ __forceinline__ float wave_suffix_incl_sum(float v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float u = __shfl_down(v, o, 64);
-        if (lane + o < 64) v += u;
-    }
-    return v;
 }
 
 // ---------------------------------------------------------------- density head, backward
@@ -191,23 +133,9 @@ __global__ void __launch_bounds__(256) k_fs_head_bwd(const _Float16 *__restrict_
         const bool valid = i < T;
         const uint64_t s = (uint64_t)n * T + (valid ? i : T - 1);
         const float sigma = sigma_in[s], Tb = trans_in[s];
-        const float z = fs_z(g, valid ? i : T - 1, T, noise, s);
-        float delta = g.sample_dist;
-        if (i + 1 < T) delta = fs_z(g, i + 1, T, noise, s + 1) - z;
-        const float ex = expf((-delta * density_scale) * sigma);            // 1 - alpha
-        const float alpha = 1 - ex;
-        const float om = 1 - alpha + 1e-15f;
-        float oz = (z - g.near) / g.span;
-        oz = oz < 0.0f ? 0.0f : (oz > 1.0f ? 1.0f : oz);
-        float gi = (grad_w ? grad_w[s] : 0.0f) + gws;
-        if (gdp != 0.0f) gi += gdp * oz;
-        const float gw_i = valid ? gi * (alpha * Tb) : 0.0f;                // g_i * w_i
-        const float incl = wave_suffix_incl_sum(gw_i, (int)lane);
-        const float S_i = S_carry + (incl - gw_i);                          // strictly after i
-        const float dalpha = gi * Tb - S_i / om;
-        const float dsigma = dalpha * (delta * density_scale) * ex;
-        const _Float16 h0 = h[s * 16];
-        const float dh0 = dsigma * expf(fminf(fmaxf((float)h0, -15.0f), 15.0f));   // trunc_exp backward (activation.py:15)
+        const FsSample p = fs_sample_ld(g, i, valid ? i : T - 1, T, noise, s);
+        const float dsigma = fs_head_bwd_step(p, valid, sigma, Tb, (grad_w ? grad_w[s] : 0.0f) + gws, gdp, density_scale, lane, S_carry);
+        const float dh0 = dsigma * foc_trunc_exp_bwd((float)h[s * 16]);
         if (valid) {
             h8 o0, o1;
             if (grad_cin) {
@@ -223,17 +151,11 @@ __global__ void __launch_bounds__(256) k_fs_head_bwd(const _Float16 *__restrict_
             h8 *dst = reinterpret_cast<h8 *>(grad_h + s * 16);
             dst[0] = o0; dst[1] = o1;
         }
-        S_carry += __shfl(incl, 0, 64);
     }
 }
 
 // ---------------------------------------------------------------- composite, forward / backward
 // c [M,16] fp16 (colour-net output, rgb logits in columns 0..2), weights [M]; bg: per-ray [N,3] or scalar.
-__device__ __forceinline__ float fs_sigmoid_h(float x) {
-    // the reference applies torch.sigmoid to the HALF tensor (network_ff.py:117): fp32 math, one rounding to fp16
-    return (float)(_Float16)(1.0f / (1.0f + expf(-x)));
-}
-
 __global__ void __launch_bounds__(256) k_fs_composite_fwd(const _Float16 *__restrict__ c, const float *__restrict__ weights, const float *__restrict__ bg_ray,
                                                           float bg_scalar, uint32_t N, uint32_t T, float thresh, float *__restrict__ image) {
     const uint32_t lane = threadIdx.x & 63;
@@ -247,13 +169,13 @@ __global__ void __launch_bounds__(256) k_fs_composite_fwd(const _Float16 *__rest
         if (w > thresh) {
             const uint2 raw = *reinterpret_cast<const uint2 *>(c + s * 16);
             const _Float16 *cc = reinterpret_cast<const _Float16 *>(&raw);
-            r += w * fs_sigmoid_h((float)cc[0]); g += w * fs_sigmoid_h((float)cc[1]); b += w * fs_sigmoid_h((float)cc[2]);
+            r += w * foc_sigmoid_h((float)cc[0]); g += w * foc_sigmoid_h((float)cc[1]); b += w * foc_sigmoid_h((float)cc[2]);
         }
     }
     r = wave_sum(r); g = wave_sum(g); b = wave_sum(b); ws = wave_sum(ws);
     if (lane == 0) {
-        const float b0 = bg_ray ? bg_ray[n * 3] : bg_scalar, b1 = bg_ray ? bg_ray[n * 3 + 1] : bg_scalar, b2 = bg_ray ? bg_ray[n * 3 + 2] : bg_scalar;
-        image[n * 3] = r + (1 - ws) * b0; image[n * 3 + 1] = g + (1 - ws) * b1; image[n * 3 + 2] = b + (1 - ws) * b2;
+        const FocBg bg = foc_bg(bg_ray, bg_scalar, n);
+        image[n * 3] = r + (1 - ws) * bg.b0; image[n * 3 + 1] = g + (1 - ws) * bg.b1; image[n * 3 + 2] = b + (1 - ws) * bg.b2;
     }
 }
 
@@ -263,29 +185,18 @@ __global__ void __launch_bounds__(256) k_fs_composite_bwd(const float *__restric
     const uint64_t total = (uint64_t)N * T;
     for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s < total; s += (uint64_t)gridDim.x * 256) {
         const uint32_t n = (uint32_t)(s / T);
-        const float g0 = grad_image[n * 3], g1 = grad_image[n * 3 + 1], g2 = grad_image[n * 3 + 2];
-        const float b0 = bg_ray ? bg_ray[n * 3] : bg_scalar, b1 = bg_ray ? bg_ray[n * 3 + 1] : bg_scalar, b2 = bg_ray ? bg_ray[n * 3 + 2] : bg_scalar;
-        const float w = weights[s];
-        float gw = -(g0 * b0 + g1 * b1 + g2 * b2);
-        h8 o0, o1;
-#pragma unroll
-        for (int k = 0; k < 8; k++) { o0[k] = (_Float16)0; o1[k] = (_Float16)0; }
-        if (w > thresh) {
-            const uint2 raw = *reinterpret_cast<const uint2 *>(c + s * 16);
-            const _Float16 *cc = reinterpret_cast<const _Float16 *>(&raw);
-            const float y0 = fs_sigmoid_h((float)cc[0]), y1 = fs_sigmoid_h((float)cc[1]), y2 = fs_sigmoid_h((float)cc[2]);
-            gw += g0 * y0 + g1 * y1 + g2 * y2;
-            o0[0] = foc_f2h(g0 * w * y0 * (1 - y0)); o0[1] = foc_f2h(g1 * w * y1 * (1 - y1)); o0[2] = foc_f2h(g2 * w * y2 * (1 - y2));
-        }
-        grad_w[s] = gw;
+        const FsRayGrad q = fs_ray_grad(grad_image, bg_ray, bg_scalar, n);
+        h8 o0;
+        const h8 o1 = {0, 0, 0, 0, 0, 0, 0, 0};
+        grad_w[s] = fs_composite_bwd_sample(q, weights[s], thresh, c + s * 16, o0);
         h8 *dst = reinterpret_cast<h8 *>(grad_c + s * 16);
         dst[0] = o0; dst[1] = o1;
     }
 }
 
 // ---------------------------------------------------------------- training tail: density head + composite in one pass per direction
-// What k_fs_head_fwd (without the colour-net input) and k_fs_composite_fwd compute, one wave per ray, with the same per-lane
-// accumulation order, so the results are the same bits; the weights are not re-read. c [M,16] fp16 = colour-net output.
+// What k_fs_head_fwd (without the colour-net input) and k_fs_composite_fwd compute, one wave per ray, through the same fs_sample /
+// fs_trans_scan / foc_sigmoid_h and with the same per-lane accumulation order, so the results are the same bits; the weights are not re-read. c [M,16] fp16 = colour-net output.
 template <bool NOISE>
 __global__ void __launch_bounds__(256) k_fs_tail_fwd(const _Float16 *__restrict__ h, const _Float16 *__restrict__ c, const float *__restrict__ nears,
                                                      const float *__restrict__ fars, const float *__restrict__ noise, const float *__restrict__ bg_ray,
@@ -308,27 +219,19 @@ __global__ void __launch_bounds__(256) k_fs_tail_fwd(const _Float16 *__restrict_
         float u0 = 0.0f, u1 = 0.0f;
         if (NOISE) { u0 = noise[s]; u1 = noise[(uint64_t)n * T + min(ic + 1u, T - 1u)]; }
         const float sigma = expf((float)h0);                                    // trunc_exp forward (activation.py:9)
-        const float z = fs_zu<NOISE>(g, ic, T, u0);
-        float delta = g.sample_dist;
-        if (i + 1 < T) delta = fs_zu<NOISE>(g, i + 1, T, u1) - z;
-        const float alpha = valid ? 1 - expf((-delta * density_scale) * sigma) : 0.0f;
+        const FsSample p = fs_sample(g, i, ic, T, NOISE, u0, u1);
+        const float alpha = valid ? 1 - expf((-p.delta * density_scale) * sigma) : 0.0f;
         const float om = valid ? (1 - alpha + 1e-15f) : 1.0f;
-        const float P = wave_incl_prod(om, (int)lane);
-        float Pex = __shfl_up(P, 1, 64);
-        if (lane == 0) Pex = 1.0f;
-        const float Tb = Tc * Pex;
+        const float Tb = fs_trans_scan(om, lane, Tc);
         const float w = alpha * Tb;
         if (valid) {
             sigma_out[s] = sigma; trans_out[s] = Tb; weights_out[s] = w;
-            float oz = (z - g.near) / g.span;
-            oz = oz < 0.0f ? 0.0f : (oz > 1.0f ? 1.0f : oz);
-            ws += w; dp += w * oz; sq = fmaf(sigma, sigma, sq);
+            ws += w; dp += w * p.oz; sq = fmaf(sigma, sigma, sq);
             if (w > thresh) {
                 const _Float16 *cc = reinterpret_cast<const _Float16 *>(&raw);
-                r += w * fs_sigmoid_h((float)cc[0]); gg += w * fs_sigmoid_h((float)cc[1]); b += w * fs_sigmoid_h((float)cc[2]);
+                r += w * foc_sigmoid_h((float)cc[0]); gg += w * foc_sigmoid_h((float)cc[1]); b += w * foc_sigmoid_h((float)cc[2]);
             }
         }
-        Tc *= __shfl(P, 63, 64);
     }
     ws = wave_sum(ws); dp = wave_sum(dp); r = wave_sum(r); gg = wave_sum(gg); b = wave_sum(b);
     if (ray_sumsq) {                                       // wave-uniform
@@ -336,18 +239,16 @@ __global__ void __launch_bounds__(256) k_fs_tail_fwd(const _Float16 *__restrict_
         if (lane == 0) ray_sumsq[n] = sq;
     }
     if (lane == 0) {
-        const float b0 = bg_ray ? bg_ray[n * 3] : bg_scalar, b1 = bg_ray ? bg_ray[n * 3 + 1] : bg_scalar, b2 = bg_ray ? bg_ray[n * 3 + 2] : bg_scalar;
-        image[n * 3] = r + (1 - ws) * b0; image[n * 3 + 1] = gg + (1 - ws) * b1; image[n * 3 + 2] = b + (1 - ws) * b2;
+        const FocBg bg = foc_bg(bg_ray, bg_scalar, n);
+        image[n * 3] = r + (1 - ws) * bg.b0; image[n * 3 + 1] = gg + (1 - ws) * bg.b1; image[n * 3 + 2] = b + (1 - ws) * bg.b2;
         weights_sum[n] = ws; depth[n] = dp;
     }
 }
 
-// a value the compiler cannot fold: exp(+-15) below must come out of the device's expf like every other exp of this file
-__device__ __forceinline__ float fs_opaque(float v) { asm volatile("" : "+v"(v)); return v; }
-
 // k_fs_composite_bwd and k_fs_head_bwd (column 0 only) in one pass: grad_image [N,3], grad_ws / grad_depth [N] (may be null)
-// -> grad_c [M,16] fp16 and grad_h0 [M] fp16. The gradient of the weights never leaves the lane. trunc_exp's backward factor
-// exp(clamp(h0, -15, 15)) is taken as clamp(sigma, exp(-15), exp(15)) — the same bits, expf being monotonic — so h is not read.
+// -> grad_c [M,16] fp16 and grad_h0 [M] fp16, through the two steps those kernels are written in (fs_composite_bwd_sample,
+// fs_head_bwd_step). The gradient of the weights never leaves the lane. trunc_exp's backward factor is taken from sigma
+// (foc_trunc_exp_bwd_of_sigma), so h is not read.
 template <bool NOISE>
 __global__ void __launch_bounds__(256) k_fs_tail_bwd(const float *__restrict__ grad_image, const float *__restrict__ grad_ws, const float *__restrict__ grad_depth,
                                                      const _Float16 *__restrict__ c, const float *__restrict__ sigma_in, const float *__restrict__ trans_in,
@@ -361,9 +262,8 @@ __global__ void __launch_bounds__(256) k_fs_tail_bwd(const float *__restrict__ g
     const FsGeom g = fs_geom(nears, fars, n, T);
     const float gws = grad_ws ? grad_ws[n] : 0.0f, gdp = grad_depth ? grad_depth[n] : 0.0f;
     const float gsq2 = grad_sumsq ? 2.0f * grad_sumsq[n] : 0.0f;      // d(sum sigma^2)/d sigma = 2 sigma
-    const float g0 = grad_image[n * 3], g1 = grad_image[n * 3 + 1], g2 = grad_image[n * 3 + 2];
-    const float b0 = bg_ray ? bg_ray[n * 3] : bg_scalar, b1 = bg_ray ? bg_ray[n * 3 + 1] : bg_scalar, b2 = bg_ray ? bg_ray[n * 3 + 2] : bg_scalar;
-    const float e_lo = expf(fs_opaque(-15.0f)), e_hi = expf(fs_opaque(15.0f));
+    const FsRayGrad q = fs_ray_grad(grad_image, bg_ray, bg_scalar, n);
+    const FocExp15 e15 = foc_exp15();
     float S_carry = 0.0f;
     const uint32_t n_chunks = (T + 63) / 64;
     for (uint32_t cidx = n_chunks; cidx-- > 0;) {
@@ -376,40 +276,19 @@ __global__ void __launch_bounds__(256) k_fs_tail_bwd(const float *__restrict__ g
         float u0 = 0.0f, u1 = 0.0f;
         if (NOISE) { u0 = noise[s]; u1 = noise[(uint64_t)n * T + min(ic + 1u, T - 1u)]; }
         // ---- composite backward (k_fs_composite_bwd)
-        float gw = -(g0 * b0 + g1 * b1 + g2 * b2);
-        h8 o0, o1;
-#pragma unroll
-        for (int k = 0; k < 8; k++) { o0[k] = (_Float16)0; o1[k] = (_Float16)0; }
-        if (w > thresh) {
-            const _Float16 *cc = reinterpret_cast<const _Float16 *>(&raw);
-            const float y0 = fs_sigmoid_h((float)cc[0]), y1 = fs_sigmoid_h((float)cc[1]), y2 = fs_sigmoid_h((float)cc[2]);
-            gw += g0 * y0 + g1 * y1 + g2 * y2;
-            o0[0] = foc_f2h(g0 * w * y0 * (1 - y0)); o0[1] = foc_f2h(g1 * w * y1 * (1 - y1)); o0[2] = foc_f2h(g2 * w * y2 * (1 - y2));
-        }
+        h8 o0;
+        const h8 o1 = {0, 0, 0, 0, 0, 0, 0, 0};
+        const float gw = fs_composite_bwd_sample(q, w, thresh, reinterpret_cast<const _Float16 *>(&raw), o0);
         if (valid) {
             if (c_ld == 4u) *reinterpret_cast<uint2 *>(grad_c + s * 4) = *reinterpret_cast<const uint2 *>(&o0);     // rgb + 1 zero: the columns that exist
             else { h8 *dst = reinterpret_cast<h8 *>(grad_c + s * 16); dst[0] = o0; dst[1] = o1; }
         }
         // ---- density head backward (k_fs_head_bwd)
-        const float z = fs_zu<NOISE>(g, ic, T, u0);
-        float delta = g.sample_dist;
-        if (i + 1 < T) delta = fs_zu<NOISE>(g, i + 1, T, u1) - z;
-        const float ex = expf((-delta * density_scale) * sigma);
-        const float alpha = 1 - ex;
-        const float om = 1 - alpha + 1e-15f;
-        float oz = (z - g.near) / g.span;
-        oz = oz < 0.0f ? 0.0f : (oz > 1.0f ? 1.0f : oz);
-        float gi = gw + gws;
-        if (gdp != 0.0f) gi += gdp * oz;
-        const float gw_i = valid ? gi * (alpha * Tb) : 0.0f;
-        const float incl = wave_suffix_incl_sum(gw_i, (int)lane);
-        const float S_i = S_carry + (incl - gw_i);
-        const float dalpha = gi * Tb - S_i / om;
-        float dsigma = dalpha * (delta * density_scale) * ex;
+        const FsSample p = fs_sample(g, i, ic, T, NOISE, u0, u1);
+        float dsigma = fs_head_bwd_step(p, valid, sigma, Tb, gw + gws, gdp, density_scale, lane, S_carry);
         if (gsq2 != 0.0f) dsigma = fmaf(gsq2, sigma, dsigma);          // the outside-mask density criterion's share (nerf/renderer.py:163-165)
-        const float dh0 = dsigma * fminf(fmaxf(sigma, e_lo), e_hi);
+        const float dh0 = dsigma * foc_trunc_exp_bwd_of_sigma(sigma, e15);
         if (valid) grad_h0[s] = foc_f2h(dh0);
-        S_carry += __shfl(incl, 0, 64);
     }
 }
 
@@ -427,8 +306,8 @@ __device__ __forceinline__ void fs_infer_finish(FsRayAcc &a, uint32_t n, uint32_
                                                 float *__restrict__ image, float *__restrict__ depth, float *__restrict__ weights_sum) {
     const float ws = wave_sum(a.ws), dp = wave_sum(a.dp), r = wave_sum(a.r), gg = wave_sum(a.g), b = wave_sum(a.b);
     if (lane == 0 && (!PACK || image)) {
-        const float b0 = bg_ray ? bg_ray[n * 3] : bg_scalar, b1 = bg_ray ? bg_ray[n * 3 + 1] : bg_scalar, b2 = bg_ray ? bg_ray[n * 3 + 2] : bg_scalar;
-        image[n * 3] = r + (1 - ws) * b0; image[n * 3 + 1] = gg + (1 - ws) * b1; image[n * 3 + 2] = b + (1 - ws) * b2;
+        const FocBg bg = foc_bg(bg_ray, bg_scalar, n);
+        image[n * 3] = r + (1 - ws) * bg.b0; image[n * 3 + 1] = gg + (1 - ws) * bg.b1; image[n * 3 + 2] = b + (1 - ws) * bg.b2;
         depth[n] = dp;
         weights_sum[n] = ws;
     }

@@ -9,29 +9,8 @@
 // two backward, one thread per sample, 16-byte accesses. fixedstep.hip holds the one-wave-per-ray forms of the same glue
 // for the fixed-step renderer. These entry points have no reference binding.
 #include "common.h"
+#include "sample_math.h"     // foc_sh16, foc_sigmoid_h, foc_trunc_exp_bwd: shared with the fused tails
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-
-// degree-4 real spherical harmonics (focnerf_amd/shencoder.py), same expressions in fp32
-__device__ __forceinline__ void hd_sh16(float x, float y, float z, float (&o)[16]) {
-    const float xy = x * y, xz = x * z, yz = y * z, x2 = x * x, y2 = y * y, z2 = z * z;
-    o[0] = 0.28209479177387814f;
-    o[1] = -0.48860251190291987f * y;
-    o[2] = 0.48860251190291987f * z;
-    o[3] = -0.48860251190291987f * x;
-    o[4] = 1.0925484305920792f * xy;
-    o[5] = -1.0925484305920792f * yz;
-    o[6] = 0.94617469575755997f * z2 - 0.31539156525251999f;
-    o[7] = -1.0925484305920792f * xz;
-    o[8] = 0.54627421529603959f * x2 - 0.54627421529603959f * y2;
-    o[9] = 0.59004358992664352f * y * (-3.0f * x2 + y2);
-    o[10] = 2.8906114426405538f * xy * z;
-    o[11] = 0.45704579946446572f * y * (1.0f - 5.0f * z2);
-    o[12] = 0.3731763325901154f * z * (5.0f * z2 - 3.0f);
-    o[13] = 0.45704579946446572f * x * (1.0f - 5.0f * z2);
-    o[14] = 1.4453057213202769f * z * (x2 - y2);
-    o[15] = 0.59004358992664352f * x * (-x2 + 3.0f * y2);
-}
 
 // h [M,16] fp16 (sigma-net output), dirs [M,3] fp32 -> sigma [M] fp32 = exp(h[:,0]), cin [M,32] fp16 = [SH16(dir) | h[:,1:16] | 0]
 __global__ void __launch_bounds__(256) k_head_fwd(const _Float16 *__restrict__ h, const float *__restrict__ dirs, uint64_t M,
@@ -50,11 +29,8 @@ __global__ void __launch_bounds__(256) k_head_fwd(const _Float16 *__restrict__ h
         const h8 r0 = *reinterpret_cast<const h8 *>(h + s * 16), r1 = *reinterpret_cast<const h8 *>(h + s * 16 + 8);
         if (sigma) sigma[s] = expf((float)r0[0]);
         if (cin) {
-            float sh[16];
-            hd_sh16(dirs[s * 3], dirs[s * 3 + 1], dirs[s * 3 + 2], sh);
             h8 c0, c1, c2, c3;
-#pragma unroll
-            for (int k = 0; k < 8; k++) { c0[k] = foc_f2h(sh[k]); c1[k] = foc_f2h(sh[8 + k]); }
+            foc_sh16_h(dirs[s * 3], dirs[s * 3 + 1], dirs[s * 3 + 2], c0, c1);
 #pragma unroll
             for (int k = 0; k < 7; k++) { c2[k] = r0[k + 1]; c3[k] = r1[k + 1]; }
             c2[7] = r1[0]; c3[7] = ob0;
@@ -74,9 +50,8 @@ __global__ void __launch_bounds__(256) k_head_bwd(const _Float16 *__restrict__ h
         if (grad_cin) { g2 = *reinterpret_cast<const h8 *>(grad_cin + s * cin_ld + 16); g3 = *reinterpret_cast<const h8 *>(grad_cin + s * cin_ld + 24); }
         float g0 = 0.0f;
         if (grad_sigma) {
-            float x = (float)h[s * 16];
-            x = x < -15.0f ? -15.0f : (x > 15.0f ? 15.0f : x);
-            g0 = grad_sigma[s] * expf(x);
+            const float e = foc_trunc_exp_bwd((float)h[s * 16]);
+            g0 = grad_sigma[s] * e;
         }
         h8 o0, o1;
         o0[0] = foc_f2h(g0);
@@ -88,14 +63,11 @@ __global__ void __launch_bounds__(256) k_head_bwd(const _Float16 *__restrict__ h
     }
 }
 
-// torch.sigmoid on a half tensor: evaluated in fp32, rounded to half
-__device__ __forceinline__ float hd_sigmoid_h(float x) { return (float)(_Float16)(1.0f / (1.0f + expf(-x))); }
-
 // c [M,16] fp16 (colour-net output) -> rgb [M,3] fp32 holding the half-rounded sigmoid of columns 0..2
 __global__ void __launch_bounds__(256) k_rgb_fwd(const _Float16 *__restrict__ c, uint64_t M, float *__restrict__ rgb) {
     for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s < M; s += (uint64_t)gridDim.x * 256) {
         const _Float16 *p = c + s * 16;
-        rgb[s * 3] = hd_sigmoid_h((float)p[0]); rgb[s * 3 + 1] = hd_sigmoid_h((float)p[1]); rgb[s * 3 + 2] = hd_sigmoid_h((float)p[2]);
+        rgb[s * 3] = foc_sigmoid_h((float)p[0]); rgb[s * 3 + 1] = foc_sigmoid_h((float)p[1]); rgb[s * 3 + 2] = foc_sigmoid_h((float)p[2]);
     }
 }
 
@@ -107,7 +79,7 @@ __global__ void __launch_bounds__(256) k_rgb_bwd(const _Float16 *__restrict__ c,
         const h8 z = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
         for (int k = 0; k < 3; k++) {
-            const float y = hd_sigmoid_h((float)c[s * 16 + k]);
+            const float y = foc_sigmoid_h((float)c[s * 16 + k]);
             const float g = (float)(_Float16)grad_rgb[s * 3 + k];
             o0[k] = foc_f2h(g * (1.0f - y) * y);
         }
@@ -120,7 +92,7 @@ __global__ void __launch_bounds__(256) k_rgb_bwd(const _Float16 *__restrict__ c,
 __global__ void __launch_bounds__(256) k_sh_encode(const float *__restrict__ dirs, uint64_t M, float *__restrict__ out) {
     for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s < M; s += (uint64_t)gridDim.x * 256) {
         float sh[16];
-        hd_sh16(dirs[s * 3], dirs[s * 3 + 1], dirs[s * 3 + 2], sh);
+        foc_sh16(dirs[s * 3], dirs[s * 3 + 1], dirs[s * 3 + 2], sh);
         float4 *dst = reinterpret_cast<float4 *>(out + s * 16);
 #pragma unroll
         for (int k = 0; k < 4; k++) dst[k] = make_float4(sh[4 * k], sh[4 * k + 1], sh[4 * k + 2], sh[4 * k + 3]);

@@ -1,5 +1,6 @@
 // occ_cell.h — the occupancy-grid cell of a position (raymarching.cu:42-54, :361-379), shared by the marching kernels
-// (raymarching.hip rm_cell) and the fixed-step cull (fixedcull.hip): cascade level, cell coordinates, Morton index.
+// (raymarching.hip rm_cell) and the fixed-step cull (fixedcull.hip): cascade level, cell coordinates, Morton index. The Morton expand / compact pair
+// is defined here once (densitygrid.hip enumerates and draws cells with it).
 #pragma once
 #include "common.h"
 
@@ -14,6 +15,15 @@ __device__ __forceinline__ uint32_t rm_expand_bits(uint32_t v) {
 }
 __device__ __forceinline__ uint32_t rm_morton3D(uint32_t x, uint32_t y, uint32_t z) {
     return rm_expand_bits(x) | (rm_expand_bits(y) << 1) | (rm_expand_bits(z) << 2);
+}
+
+__device__ __forceinline__ uint32_t rm_morton3D_invert(uint32_t x) {
+    x = x & 0x49249249u;
+    x = (x | (x >> 2)) & 0xc30c30c3u;
+    x = (x | (x >> 4)) & 0x0f00f00fu;
+    x = (x | (x >> 8)) & 0xff0000ffu;
+    x = (x | (x >> 16)) & 0x0000ffffu;
+    return x;
 }
 
 // frexpf exponent of a non-negative finite float without the libcall: for x = 0 frexpf

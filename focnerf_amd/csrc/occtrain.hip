@@ -8,26 +8,16 @@
 //     depth = clamp(depth - nears, min=0) / (fars - nears)            (:314, no gradient)
 // and their derivatives (raymarching.cu:601-693; trunc_exp's g * exp(clamp(x, -15, 15)); the half sigmoid's g (1 - y) y).
 // h [M,16] fp16 is the density network's output, c [M,c_width] fp16 the colour network's (c_width 4: rgb logits + one pad column,
-// the form foc_color_head_forward / _backward exchange; 16: the padded FFMLP output). Per sample and lane the arithmetic is that of
-// k_head_fwd / k_rgb_fwd / k_composite_train_fwd (head.hip, raymarching.hip) in the same order, so the forward values are the
+// the form foc_color_head_forward / _backward exchange; 16: the padded FFMLP output). Per sample and lane the arithmetic is the shared
+// definitions k_head_fwd / k_rgb_fwd / k_composite_train_fwd are written in (sample_math.h, ragged.h ot_step), so the forward values are the
 // bits of the three-kernel chain; sigma [M], rgbs [M,3] and their gradients are never stored (4 x 16 B per sample and direction).
 //
 // The backward writes EVERY row of grad_c and grad_h0: a ray's wave covers the ray's whole slot range (zeros behind the sample at which
 // the ray became opaque, zeros for a ray that did not fit the list), and the rows behind the last ray's range are zeroed by spare
 // waves — the colour network's backward reads all M rows, and the caller's zero fill of them was a launch of its own.
 #include "common.h"
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ float ot_sigmoid_h(float x) { return (float)(_Float16)(1.0f / (1.0f + expf(-x))); }       // head.hip hd_sigmoid_h
-
-struct OtRay { uint32_t index, offset, count; bool fits; };
-__device__ __forceinline__ OtRay ot_ray(const int32_t *__restrict__ rays, uint32_t n, uint32_t M) {
-    OtRay r;
-    r.index = (uint32_t)rays[n * 3]; r.offset = (uint32_t)rays[n * 3 + 1]; r.count = (uint32_t)rays[n * 3 + 2];
-    r.fits = r.count != 0u && (uint64_t)r.offset + r.count <= M;           // raymarching.cu:515: empty rays and rays past the list are skipped
-    return r;
-}
+#include "sample_math.h"     // foc_sigmoid_h, foc_trunc_exp_bwd, foc_bg, h8
+#include "ragged.h"          // ot_ray, ot_step, ot_grad_acc: the composite, shared with k_composite_train_fwd / _bwd
 
 #define OT_PAD_BLOCKS 64u
 
@@ -61,25 +51,15 @@ __global__ void __launch_bounds__(256) k_occ_tail_fwd(const _Float16 *__restrict
                 dt0 = dl.x; dt1 = dl.y;
                 const uint2 raw = *reinterpret_cast<const uint2 *>(c + s * c_ld);
                 const _Float16 *cc = reinterpret_cast<const _Float16 *>(&raw);
-                c0 = ot_sigmoid_h((float)cc[0]); c1 = ot_sigmoid_h((float)cc[1]); c2 = ot_sigmoid_h((float)cc[2]);      // k_rgb_fwd
+                c0 = foc_sigmoid_h((float)cc[0]); c1 = foc_sigmoid_h((float)cc[1]); c2 = foc_sigmoid_h((float)cc[2]);      // k_rgb_fwd
             }
-            // from here on: k_composite_train_fwd
-            const float alpha = valid ? 1.0f - __expf(-sigma * dt0) : 0.0f;
-            const float om = 1.0f - alpha;
-            const float P = wave_incl_prod(om, (int)lane);
-            float Pex = __shfl_up(P, 1, 64);
-            if (lane == 0) Pex = 1.0f;
-            const float T_before = T_carry * Pex;
-            const float T_after = T_carry * P;
+            const OtStep st = ot_step(valid, sigma, dt0, T_carry, T_thresh, lane);
             const float tsum = t_carry + wave_incl_sum(dt1, (int)lane);
-            const unsigned long long term = __ballot(valid && (T_after < T_thresh));
-            const int first = term ? (int)__ffsll((long long)term) - 1 : 64;
-            const float w = (valid && (int)lane <= first) ? alpha * T_before : 0.0f;
-            r = fmaf(w, c0, r); g = fmaf(w, c1, g); b = fmaf(w, c2, b);
-            d = fmaf(w, tsum, d);
-            ws += w;
-            if (term) { base += 64; break; }
-            T_carry = __shfl(T_after, 63, 64);
+            r = fmaf(st.w, c0, r); g = fmaf(st.w, c1, g); b = fmaf(st.w, c2, b);
+            d = fmaf(st.w, tsum, d);
+            ws += st.w;
+            if (st.term) { base += 64; break; }
+            T_carry = __shfl(st.T_after, 63, 64);
             t_carry = __shfl(tsum, 63, 64);
         }
         if constexpr (CRIT) {                                  // the samples behind the stop: the penalty is on the density, not on the composite
@@ -96,8 +76,8 @@ __global__ void __launch_bounds__(256) k_occ_tail_fwd(const _Float16 *__restrict
         image_raw[k * 3] = r; image_raw[k * 3 + 1] = g; image_raw[k * 3 + 2] = b;
         const float rest = 1 - ws;
         // `image + rest` for the default white background ((1 - w) * 1 is (1 - w)), `image + rest * bg` otherwise: the caller's two torch forms
-        const float b0 = bg_ray ? bg_ray[k * 3] : bg_scalar, b1 = bg_ray ? bg_ray[k * 3 + 1] : bg_scalar, b2 = bg_ray ? bg_ray[k * 3 + 2] : bg_scalar;
-        image[k * 3] = r + rest * b0; image[k * 3 + 1] = g + rest * b1; image[k * 3 + 2] = b + rest * b2;
+        const FocBg bg = foc_bg(bg_ray, bg_scalar, k);
+        image[k * 3] = r + rest * bg.b0; image[k * 3 + 1] = g + rest * bg.b1; image[k * 3 + 2] = b + rest * bg.b2;
         const float nr = nears[k], dd = d - nr;
         depth[k] = (dd < 0.0f ? 0.0f : dd) / (fars[k] - nr);
         if constexpr (CRIT) ray_sumsq[k] = sq;
@@ -143,22 +123,20 @@ __global__ void __launch_bounds__(256) k_occ_tail_bwd(const float *__restrict__ 
         return;
     }
     const uint32_t index = ry.index;
-    const float g0 = grad_image[index * 3], g1 = grad_image[index * 3 + 1], g2 = grad_image[index * 3 + 2];
     // image = raw + (1 - ws) bg: the background term hands -(g . bg) to the opacity's gradient (white: -(g0 + g1 + g2), torch's sum over the channel axis)
-    const float b0 = bg_ray ? bg_ray[index * 3] : bg_scalar, b1 = bg_ray ? bg_ray[index * 3 + 1] : bg_scalar, b2 = bg_ray ? bg_ray[index * 3 + 2] : bg_scalar;
-    const float gws = (grad_ws ? grad_ws[index] : 0.0f) - ((g0 * b0 + g1 * b1) + g2 * b2);
-    const float r_final = image_raw[index * 3], g_final = image_raw[index * 3 + 1], b_final = image_raw[index * 3 + 2];
-    const float ws_term = gws * (1 - weights_sum[index]);
+    const FocBg bg = foc_bg(bg_ray, bg_scalar, index);
+    const float g0 = grad_image[index * 3], g1 = grad_image[index * 3 + 1], g2 = grad_image[index * 3 + 2];
+    const float gws = (grad_ws ? grad_ws[index] : 0.0f) - ((g0 * bg.b0 + g1 * bg.b1) + g2 * bg.b2);
+    const OtRayGrad q = ot_ray_grad(grad_image, image_raw, weights_sum, index, gws);
     float gsq2 = 0.0f;
     if constexpr (CRIT) gsq2 = 2.0f * grad_sumsq[index];      // d(sum sigma^2) / d sigma = 2 sigma
     // the criterion's share of a row's grad_h0: 2 exp(x) grad_sumsq * exp(clamp(x, -15, 15))
     auto crit_only = [&](uint64_t s) {
-        const float x = (float)h[s * 16];
-        const float xc = x < -15.0f ? -15.0f : (x > 15.0f ? 15.0f : x);
-        return gsq2 * expf(x) * (xc != x ? expf(xc) : expf(x));
+        const float x = (float)h[s * 16], e = expf(x);
+        return gsq2 * e * foc_trunc_exp_bwd(x, e);
     };
     float T_carry = 1.0f;
-    float r_carry = 0, g_carry = 0, b_carry = 0;
+    OtColour carry = {0, 0, 0};
     bool dead = false;                                         // wave-uniform: the ray became opaque in an earlier block of 64
     for (uint32_t base = 0; base < ry.count; base += 64) {
         const uint32_t i = base + lane;
@@ -168,47 +146,28 @@ __global__ void __launch_bounds__(256) k_occ_tail_bwd(const float *__restrict__ 
         float sigma = 0, e0 = 0, dt0 = 0, c0 = 0, c1 = 0, c2 = 0, e_raw = 0;
         if (valid) {
             const float x = (float)h[s * 16];
-            e0 = expf(x);
-            e_raw = e0;
-            sigma = density_scale != 1.0f ? density_scale * e0 : e0;
+            e_raw = expf(x);
+            sigma = density_scale != 1.0f ? density_scale * e_raw : e_raw;
             dt0 = deltas[s * 2];
             const uint2 raw = *reinterpret_cast<const uint2 *>(c + s * c_ld);
             const _Float16 *cc = reinterpret_cast<const _Float16 *>(&raw);
-            c0 = ot_sigmoid_h((float)cc[0]); c1 = ot_sigmoid_h((float)cc[1]); c2 = ot_sigmoid_h((float)cc[2]);
-            // trunc_exp's backward factor exp(clamp(x, -15, 15)) (activation.py:16-18)
-            const float xc = x < -15.0f ? -15.0f : (x > 15.0f ? 15.0f : x);
-            if (xc != x) e0 = expf(xc);
+            c0 = foc_sigmoid_h((float)cc[0]); c1 = foc_sigmoid_h((float)cc[1]); c2 = foc_sigmoid_h((float)cc[2]);
+            e0 = foc_trunc_exp_bwd(x, e_raw);
         }
-        const float alpha = valid ? 1.0f - __expf(-sigma * dt0) : 0.0f;
-        const float om = 1.0f - alpha;
-        const float P = wave_incl_prod(om, (int)lane);
-        float Pex = __shfl_up(P, 1, 64);
-        if (lane == 0) Pex = 1.0f;
-        const float T_before = T_carry * Pex;
-        const float T_after = T_carry * P;
-        const unsigned long long term = __ballot(valid && (T_after < T_thresh));
-        const int first = term ? (int)__ffsll((long long)term) - 1 : 64;
-        const bool act = valid && (int)lane <= first;
-        const float w = act ? alpha * T_before : 0.0f;
-        const float r_acc = r_carry + wave_incl_sum(w * c0, (int)lane);
-        const float g_acc = g_carry + wave_incl_sum(w * c1, (int)lane);
-        const float b_acc = b_carry + wave_incl_sum(w * c2, (int)lane);
-        if (act) {
+        const OtStep st = ot_step(valid, sigma, dt0, T_carry, T_thresh, lane);
+        const OtColour acc = ot_running(carry, st.w, c0, c1, c2, lane);
+        if (st.act) {
             // k_composite_train_bwd: grad_rgbs = g w; grad_sigmas = dt0 (...)
-            float acc = g0 * fmaf(T_after, c0, -(r_final - r_acc));
-            acc = fmaf(g1, fmaf(T_after, c1, -(g_final - g_acc)), acc);
-            acc = fmaf(g2, fmaf(T_after, c2, -(b_final - b_acc)), acc);
-            acc += ws_term;
-            float gs = dt0 * acc;
+            float gs = dt0 * ot_grad_acc(q, st.T_after, c0, c1, c2, acc);
             if (density_scale != 1.0f) gs = density_scale * gs;       // through `density_scale * sigmas`
             if constexpr (CRIT) gs = fmaf(gsq2, e_raw, gs);
             // k_rgb_bwd: half(g) (1 - y) y;  k_head_bwd: grad_sigma * exp(clamp(h0))
-            const float q0 = (float)(_Float16)(g0 * w), q1 = (float)(_Float16)(g1 * w), q2 = (float)(_Float16)(g2 * w);
+            const float q0 = (float)(_Float16)(g0 * st.w), q1 = (float)(_Float16)(g1 * st.w), q2 = (float)(_Float16)(g2 * st.w);
             store(s, gs * e0, q0 * (1.0f - c0) * c0, q1 * (1.0f - c1) * c1, q2 * (1.0f - c2) * c2);
         } else if (valid) store(s, CRIT ? gsq2 * e_raw * e0 : 0.0f, 0.0f, 0.0f, 0.0f);
-        if (term) { dead = true; continue; }
-        T_carry = __shfl(T_after, 63, 64);
-        r_carry = __shfl(r_acc, 63, 64); g_carry = __shfl(g_acc, 63, 64); b_carry = __shfl(b_acc, 63, 64);
+        if (st.term) { dead = true; continue; }
+        T_carry = __shfl(st.T_after, 63, 64);
+        carry = ot_last(acc);
     }
 }
 

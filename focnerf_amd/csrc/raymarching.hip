@@ -14,21 +14,14 @@
 // (and therefore every sample index and position) is bit-identical to the oracle.
 #include "common.h"
 #include "occ_cell.h"
+#include "sample_math.h"
+#include "ragged.h"
 #include <float.h>
 
 #define RM_SQRT3 1.7320508075688772f
 #define RM_RPI   0.3183098861837907f
 
 __device__ __forceinline__ float rm_sign(float x) { return copysignf(1.0f, x); }
-
-__device__ __forceinline__ uint32_t rm_morton3D_invert(uint32_t x) {
-    x = x & 0x49249249u;
-    x = (x | (x >> 2)) & 0xc30c30c3u;
-    x = (x | (x >> 4)) & 0x0f00f00fu;
-    x = (x | (x >> 8)) & 0xff0000ffu;
-    x = (x | (x >> 16)) & 0x0000ffffu;
-    return x;
-}
 
 // ---------------------------------------------------------------- R1 (raymarching.cu:92-145)
 // slab test of one ray against the box a[0..5]; a miss gives FLT_MAX twice
@@ -420,34 +413,13 @@ __global__ void __launch_bounds__(1024) k_march_scan(const int32_t *__restrict__
     if (tid == 0) { counter[0] = base0 + s_total; counter[1] = ray0 + (int32_t)N; }
 }
 
-// degree-4 real spherical harmonics of a direction, the expressions of head.hip hd_sh16 (focnerf_amd/shencoder.py)
-__device__ __forceinline__ void rm_sh16(float x, float y, float z, float (&o)[16]) {
-    const float xy = x * y, xz = x * z, yz = y * z, x2 = x * x, y2 = y * y, z2 = z * z;
-    o[0] = 0.28209479177387814f;
-    o[1] = -0.48860251190291987f * y;
-    o[2] = 0.48860251190291987f * z;
-    o[3] = -0.48860251190291987f * x;
-    o[4] = 1.0925484305920792f * xy;
-    o[5] = -1.0925484305920792f * yz;
-    o[6] = 0.94617469575755997f * z2 - 0.31539156525251999f;
-    o[7] = -1.0925484305920792f * xz;
-    o[8] = 0.54627421529603959f * x2 - 0.54627421529603959f * y2;
-    o[9] = 0.59004358992664352f * y * (-3.0f * x2 + y2);
-    o[10] = 2.8906114426405538f * xy * z;
-    o[11] = 0.45704579946446572f * y * (1.0f - 5.0f * z2);
-    o[12] = 0.3731763325901154f * z * (5.0f * z2 - 3.0f);
-    o[13] = 0.45704579946446572f * x * (1.0f - 5.0f * z2);
-    o[14] = 1.4453057213202769f * z * (x2 - y2);
-    o[15] = 0.59004358992664352f * x * (-x2 + 3.0f * y2);
-}
-
 // ---------------------------------------------------------------- R6 pass 3: emit (raymarching.cu:415-479)
 // One wave per ray, lane k = sample k: t_k from the strip; xyz = clamp(o + t d), dt = clamp(t dt_gamma) exactly as rm_cell forms them;
 // deltas = (dt_k, (t_k + dt_k) - last_t) with last_t = t_{k-1} + dt_{k-1} (the start t for k = 0), as the loop accumulates them.
 // Stores are contiguous across the wave (768 B of xyz per 64 samples).
 // FIELD: the sample list in the layout the fused training path consumes (foc_march_rays_train_field) — `xyzs` receives the encoder's
 // [0,1] coordinates (x + bound) * 1 / (2 bound) (rm_out), `dirs` is not written, and `sh` [M,16] fp16 receives each sample's degree-4
-// SH row (the first k-chunk of the colour network's input, head.hip hd_sh16 rounded like k_head_fwd rounds it): one row per sample of
+// SH row (the first k-chunk of the colour network's input, sample_math.h foc_sh16_h as k_head_fwd stores it): one row per sample of
 // a ray, all equal. Every row of both arrays is written — rays that do not fit the list and the rows behind the last ray get zeros
 // (spare workgroups; `counter` from k_march_scan) — so the caller needs no zero fill.
 #define RM_PAD_BLOCKS 64u
@@ -463,7 +435,6 @@ __global__ void __launch_bounds__(256) k_march_emit(const float *__restrict__ ra
                                                     float *__restrict__ xyzs, float *__restrict__ dirs, float *__restrict__ deltas,
                                                     _Float16 *__restrict__ sh, int32_t *__restrict__ counter, uint32_t pad_align,
                                                     const int32_t *__restrict__ counts) {
-    typedef _Float16 rm_h8 __attribute__((ext_vector_type(8)));
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t n = blockIdx.x * 4 + (threadIdx.x >> 6);
     uint32_t scan_point = 0, scan_steps = 0, scan_total = 0;
@@ -524,13 +495,8 @@ __global__ void __launch_bounds__(256) k_march_emit(const float *__restrict__ ra
     float t0 = nears[n];
     t0 = fmaf(rm_clamp(t0 * p.dt_gamma, p.dt_min, p.dt_max), noises[n], t0);
     const float *strip = tstrip + (uint64_t)n * max_steps;
-    rm_h8 sh0, sh1;
-    if constexpr (FIELD) {
-        float o[16];
-        rm_sh16(dx, dy, dz, o);
-#pragma unroll
-        for (int k = 0; k < 8; k++) { sh0[k] = foc_f2h(o[k]); sh1[k] = foc_f2h(o[8 + k]); }
-    }
+    h8 sh0, sh1;
+    if constexpr (FIELD) foc_sh16_h(dx, dy, dz, sh0, sh1);
     for (uint32_t k = lane; k < num_steps; k += 64) {
         const float t = strip[k];
         const float dt = rm_clamp(t * p.dt_gamma, p.dt_min, p.dt_max);
@@ -540,14 +506,14 @@ __global__ void __launch_bounds__(256) k_march_emit(const float *__restrict__ ra
         xyzs[s * 3] = rm_out(p, rm_clamp(fmaf(t, dx, ox), -p.bound, p.bound));
         xyzs[s * 3 + 1] = rm_out(p, rm_clamp(fmaf(t, dy, oy), -p.bound, p.bound));
         xyzs[s * 3 + 2] = rm_out(p, rm_clamp(fmaf(t, dz, oz), -p.bound, p.bound));
-        if constexpr (FIELD) { *reinterpret_cast<rm_h8 *>(sh + s * 16) = sh0; *reinterpret_cast<rm_h8 *>(sh + s * 16 + 8) = sh1; }
+        if constexpr (FIELD) { *reinterpret_cast<h8 *>(sh + s * 16) = sh0; *reinterpret_cast<h8 *>(sh + s * 16 + 8) = sh1; }
         else { dirs[s * 3] = dx; dirs[s * 3 + 1] = dy; dirs[s * 3 + 2] = dz; }
         deltas[s * 2] = dt;
         deltas[s * 2 + 1] = (t + dt) - last_t;
     }
 }
 
-// ---------------------------------------------------------------- R7 (raymarching.cu:500-577), one wave per ray
+// ---------------------------------------------------------------- R7 (raymarching.cu:500-577), one wave per ray; the step is ragged.h ot_step
 __global__ void __launch_bounds__(256) k_composite_train_fwd(const float *__restrict__ sigmas, const float *__restrict__ rgbs,
                                       const float *__restrict__ deltas, const int32_t *__restrict__ rays,
                                       uint32_t M, uint32_t N, float T_thresh,
@@ -555,41 +521,32 @@ __global__ void __launch_bounds__(256) k_composite_train_fwd(const float *__rest
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t n = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (n >= N) return;
-    const uint32_t index = (uint32_t)rays[n * 3], offset = (uint32_t)rays[n * 3 + 1], num_steps = (uint32_t)rays[n * 3 + 2];
-    if (num_steps == 0 || offset + num_steps > M) {
+    const OtRay ry = ot_ray(rays, n, M);
+    const uint32_t index = ry.index;
+    if (!ry.fits) {
         if (lane == 0) { weights_sum[index] = 0; depth[index] = 0; image[index * 3] = 0; image[index * 3 + 1] = 0; image[index * 3 + 2] = 0; }
         return;
     }
     float T_carry = 1.0f, t_carry = 0.0f;
     float r = 0, g = 0, b = 0, ws = 0, d = 0;
-    for (uint32_t base = 0; base < num_steps; base += 64) {
+    for (uint32_t base = 0; base < ry.count; base += 64) {
         const uint32_t i = base + lane;
-        const bool valid = i < num_steps;
+        const bool valid = i < ry.count;
         float sigma = 0, dt0 = 0, dt1 = 0, c0 = 0, c1 = 0, c2 = 0;
         if (valid) {
-            const uint64_t s = (uint64_t)offset + i;
+            const uint64_t s = (uint64_t)ry.offset + i;
             sigma = sigmas[s];
             const float2 dl = *reinterpret_cast<const float2 *>(deltas + s * 2);
             dt0 = dl.x; dt1 = dl.y;
             c0 = rgbs[s * 3]; c1 = rgbs[s * 3 + 1]; c2 = rgbs[s * 3 + 2];
         }
-        const float alpha = valid ? 1.0f - __expf(-sigma * dt0) : 0.0f;
-        const float om = 1.0f - alpha;
-        const float P = wave_incl_prod(om, (int)lane);
-        float Pex = __shfl_up(P, 1, 64);
-        if (lane == 0) Pex = 1.0f;
-        const float T_before = T_carry * Pex;
-        const float T_after = T_carry * P;
+        const OtStep st = ot_step(valid, sigma, dt0, T_carry, T_thresh, lane);
         const float tsum = t_carry + wave_incl_sum(dt1, (int)lane);
-        // the reference breaks AFTER accumulating the sample whose T drops below the threshold
-        const unsigned long long term = __ballot(valid && (T_after < T_thresh));
-        const int first = term ? (int)__ffsll((long long)term) - 1 : 64;
-        const float w = (valid && (int)lane <= first) ? alpha * T_before : 0.0f;
-        r = fmaf(w, c0, r); g = fmaf(w, c1, g); b = fmaf(w, c2, b);
-        d = fmaf(w, tsum, d);
-        ws += w;
-        if (term) break;
-        T_carry = __shfl(T_after, 63, 64);
+        r = fmaf(st.w, c0, r); g = fmaf(st.w, c1, g); b = fmaf(st.w, c2, b);
+        d = fmaf(st.w, tsum, d);
+        ws += st.w;
+        if (st.term) break;
+        T_carry = __shfl(st.T_after, 63, 64);
         t_carry = __shfl(tsum, 63, 64);
     }
     r = wave_sum(r); g = wave_sum(g); b = wave_sum(b); ws = wave_sum(ws); d = wave_sum(d);
@@ -609,50 +566,30 @@ __global__ void __launch_bounds__(256) k_composite_train_bwd(const float *__rest
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t n = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (n >= N) return;
-    const uint32_t index = (uint32_t)rays[n * 3], offset = (uint32_t)rays[n * 3 + 1], num_steps = (uint32_t)rays[n * 3 + 2];
-    if (num_steps == 0 || offset + num_steps > M) return;
-    const float g0 = grad_image[index * 3], g1 = grad_image[index * 3 + 1], g2 = grad_image[index * 3 + 2];
-    const float gws = grad_weights_sum ? grad_weights_sum[index] : 0.0f;
-    const float r_final = image[index * 3], g_final = image[index * 3 + 1], b_final = image[index * 3 + 2];
-    const float ws_term = gws * (1 - weights_sum[index]);
+    const OtRay ry = ot_ray(rays, n, M);
+    if (!ry.fits) return;
+    const OtRayGrad q = ot_ray_grad(grad_image, image, weights_sum, ry.index, grad_weights_sum ? grad_weights_sum[ry.index] : 0.0f);
     float T_carry = 1.0f;
-    float r_carry = 0, g_carry = 0, b_carry = 0;
-    for (uint32_t base = 0; base < num_steps; base += 64) {
+    OtColour carry = {0, 0, 0};
+    for (uint32_t base = 0; base < ry.count; base += 64) {
         const uint32_t i = base + lane;
-        const bool valid = i < num_steps;
-        const uint64_t s = (uint64_t)offset + (valid ? i : 0);
+        const bool valid = i < ry.count;
+        const uint64_t s = (uint64_t)ry.offset + (valid ? i : 0);
         float sigma = 0, dt0 = 0, c0 = 0, c1 = 0, c2 = 0;
         if (valid) {
             sigma = sigmas[s];
             dt0 = deltas[s * 2];
             c0 = rgbs[s * 3]; c1 = rgbs[s * 3 + 1]; c2 = rgbs[s * 3 + 2];
         }
-        const float alpha = valid ? 1.0f - __expf(-sigma * dt0) : 0.0f;
-        const float om = 1.0f - alpha;
-        const float P = wave_incl_prod(om, (int)lane);
-        float Pex = __shfl_up(P, 1, 64);
-        if (lane == 0) Pex = 1.0f;
-        const float T_before = T_carry * Pex;
-        const float T_after = T_carry * P;
-        const unsigned long long term = __ballot(valid && (T_after < T_thresh));
-        const int first = term ? (int)__ffsll((long long)term) - 1 : 64;
-        const bool act = valid && (int)lane <= first;
-        const float w = act ? alpha * T_before : 0.0f;
-        // running colour INCLUDING this sample (:648-650)
-        const float r_acc = r_carry + wave_incl_sum(w * c0, (int)lane);
-        const float g_acc = g_carry + wave_incl_sum(w * c1, (int)lane);
-        const float b_acc = b_carry + wave_incl_sum(w * c2, (int)lane);
-        if (act) {
-            grad_rgbs[s * 3] = g0 * w; grad_rgbs[s * 3 + 1] = g1 * w; grad_rgbs[s * 3 + 2] = g2 * w;
-            float acc = g0 * fmaf(T_after, c0, -(r_final - r_acc));
-            acc = fmaf(g1, fmaf(T_after, c1, -(g_final - g_acc)), acc);
-            acc = fmaf(g2, fmaf(T_after, c2, -(b_final - b_acc)), acc);
-            acc += ws_term;
-            grad_sigmas[s] = dt0 * acc;
+        const OtStep st = ot_step(valid, sigma, dt0, T_carry, T_thresh, lane);
+        const OtColour acc = ot_running(carry, st.w, c0, c1, c2, lane);
+        if (st.act) {
+            grad_rgbs[s * 3] = q.g0 * st.w; grad_rgbs[s * 3 + 1] = q.g1 * st.w; grad_rgbs[s * 3 + 2] = q.g2 * st.w;
+            grad_sigmas[s] = dt0 * ot_grad_acc(q, st.T_after, c0, c1, c2, acc);
         }
-        if (term) break;
-        T_carry = __shfl(T_after, 63, 64);
-        r_carry = __shfl(r_acc, 63, 64); g_carry = __shfl(g_acc, 63, 64); b_carry = __shfl(b_acc, 63, 64);
+        if (st.term) break;
+        T_carry = __shfl(st.T_after, 63, 64);
+        carry = ot_last(acc);
     }
 }
 

@@ -1,0 +1,246 @@
+#!/usr/bin/env python3
+"""tools/output_digest.py [out.json]: sha256 of every output of the per-sample, ragged-composite, fixed-step and combine kernels on seeded
+inputs, as one JSON object {case: {output: digest}} — the bits of one library build — printed, or written to out.json with a one-line
+summary printed instead. Run it once per build on the same GPU (FOCNERF_LIB_PATH selects the library) and compare the two objects:
+equal = the same bits on every case.
+
+The cases are the smallest that reach every branch of those kernels: ray counts and step counts below, at and above one 64-lane step,
+with and without noise, scalar and per-ray background, density_scale 1 and 2, colour widths 4 and 16, a ray list with an empty ray, a
+ray that does not fit the list and spare rows behind the last ray, stops in the first step and in a later one.
+
+Left out: the gradient of the background model's table (foc_background_backward: fp32 atomics, not bit-stable run to run in the default
+mode) and with it the whole background backward; the forward is covered. Every input is drawn on the host from a seeded generator.
+"""
+import hashlib
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+from focnerf_amd._lib import lib, ptr, stream_of, check        # noqa: E402
+import background_ref as br                                     # noqa: E402
+import ragged_ref as rr                                         # noqa: E402
+
+OUT = {}
+NAN32 = float("nan")
+
+
+def put(case, **tensors):
+    torch.cuda.synchronize()
+    OUT[case] = {k: hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest() for k, t in tensors.items() if t is not None}
+
+
+def cuda(a):
+    return torch.as_tensor(np.ascontiguousarray(a)).cuda() if a is not None else None
+
+
+def full(shape, dtype=torch.float32):
+    """An output buffer with a recognisable fill: a row the kernel does not write shows up as such in both builds alike."""
+    return torch.full(shape if isinstance(shape, tuple) else (shape,), -3.0, dtype=dtype, device="cuda")
+
+
+def call(fn, *args):
+    check(fn(*args, stream_of(None)), fn.__name__)
+
+
+# ---------------------------------------------------------------- per-sample ops (head.hip, background.hip, Morton, density grid)
+def per_sample():
+    rng = np.random.default_rng(11)
+    M = 130
+    d = rng.normal(0, 1, (M, 3)); d /= np.linalg.norm(d, axis=1, keepdims=True)
+    h = rng.normal(0, 3, (M, 16)); h[:8, 0] = [15.0, -15.0, 15.0078125, -15.0078125, 16.5, -20.0, 0.0, 14.5]
+    dirs, h16 = cuda(d.astype(np.float32)), cuda(h.astype(np.float16))
+    sh = full((M, 16))
+    call(lib.foc_sh_encode, ptr(dirs), M, ptr(sh))
+    put("sh_encode", sh=sh)
+    obj = cuda(rng.normal(0, 1, 16).astype(np.float16))
+    for width in (32, 48):
+        sigma, cin = full(M), full((M, width), torch.float16)
+        call(lib.foc_sample_head_forward, ptr(h16), ptr(dirs), M, ptr(sigma), ptr(cin), ptr(obj if width == 48 else None), width)
+        g_sigma, g_cin, g_h = cuda(rng.normal(0, 1, M).astype(np.float32)), cuda(rng.normal(0, 1, (M, width)).astype(np.float16)), full((M, 16), torch.float16)
+        call(lib.foc_sample_head_backward, ptr(h16), ptr(g_sigma), ptr(g_cin), M, ptr(g_h), width)
+        put(f"sample_head[{width}]", sigma=sigma, cin=cin, grad_h=g_h)
+    c16 = cuda(rng.normal(0, 3, (M, 16)).astype(np.float16))
+    rgb, g_c = full((M, 3)), full((M, 16), torch.float16)
+    call(lib.foc_rgb_head_forward, ptr(c16), M, ptr(rgb))
+    g_rgb = cuda(rng.normal(0, 1, (M, 3)).astype(np.float32))
+    call(lib.foc_rgb_head_backward, ptr(c16), ptr(g_rgb), M, ptr(g_c))
+    put("rgb_head", rgb=rgb, grad_c=g_c)
+
+    # the background forward at N = 130 (coordinates form), grid "b" of the float64 reference's cases
+    W0, W1 = br.weights("lin")
+    emb, off, blob = cuda(br.table("b", 0.5)), cuda(np.asarray(br.GRIDS["b"], np.int32)), cuda(br.pack_blob(W0, W1))
+    coords = cuda(rng.uniform(-1, 1, (M, 2)).astype(np.float32))
+    bg = full((M, 3), torch.float16)
+    call(lib.foc_background_forward, None, ptr(dirs), ptr(coords), 0.0, M, ptr(emb), ptr(off), br.LOG2_SCALE, br.BASE_RESOLUTION, ptr(blob), ptr(bg))
+    put("background_forward", rgb=bg)
+
+    H = 32
+    xyz = cuda(rng.integers(0, H, (M, 3)).astype(np.int32))
+    idx, back = full(M, torch.int32), full((M, 3), torch.int32)
+    call(lib.foc_morton3D, ptr(xyz), M, ptr(idx))
+    call(lib.foc_morton3D_invert, ptr(idx), M, ptr(back))
+    cells = full((H ** 3, 3))
+    call(lib.foc_grid_cells_xyz, 1, H, 1.0, None, ptr(cells))
+    grid = cuda(rng.uniform(-1, 2, (1, H ** 3)).astype(np.float32))
+    Mc = 4096
+    sig, ind = cuda(rng.uniform(0, 30, Mc).astype(np.float32)), cuda(rng.integers(0, H ** 3, Mc).astype(np.int32))
+    bits, mean = torch.zeros(H ** 3 // 8, dtype=torch.uint8, device="cuda"), full(1)
+    nbytes = lib.foc_grid_update_apply_workspace_bytes(1, H)
+    ws = torch.zeros(max(int(nbytes), 1), dtype=torch.uint8, device="cuda")
+    call(lib.foc_grid_update_apply, ptr(grid), 1, H, ptr(sig), ptr(ind), Mc, 1.0, 0.95, 10.0, ptr(bits), ptr(mean), ptr(ws), nbytes)
+    put("morton_and_grid[32]", indices=idx, coords=back, cells=cells, density_grid=grid, bitfield=bits, mean=mean)
+
+
+# ---------------------------------------------------------------- ragged composite (raymarching.hip R7 / R8, occtrain.hip)
+def ragged():
+    for T_thresh in (1e-4, 0.5):
+        # (count, stop): empty, one sample, a full step, one past it (stop in the second step), two steps and a bit (stops in the first
+        # step, in the third, never)
+        pairs = [(0, None), (1, 0), (64, None), (65, 64), (130, 10), (130, 129), (130, None), (64, 63)]
+        for ds in (1.0, 2.0):
+            c = rr.constructed_case(pairs, 5, T_thresh, ds=ds)
+            N, M, total = c["N"] + 1, c["M"], c["total"]
+            assert M > total + 3                                           # spare rows behind the last ray
+            rays = np.concatenate([c["rays"], [[N - 1, M - 3, 10]]]).astype(np.int32)       # the added ray does not fit the list
+            rng = np.random.default_rng(17)
+            ext = lambda a, v: np.concatenate([a, v]).astype(np.float32)
+            nears, fars = ext(c["nears"], [0.3]), ext(c["fars"], [1.7])
+            bg_ray = ext(c["bg"], rng.random((1, 3)))
+            g = {k: cuda(ext(v, rng.normal(0, 1, (1,) + v.shape[1:]))) for k, v in c["grads"].items()}
+            d_rays, d_deltas, d_h, counter = cuda(rays), cuda(c["deltas"]), cuda(np.repeat(c["h0"][:, None], 16, 1)), cuda(np.array([total, N], np.int32))
+            c16 = np.zeros((M, 16), np.float16); c16[:, :3] = c["c"]
+            d_c = {16: cuda(c16), 4: cuda(c16[:, :4])}
+            d_near, d_far, d_bg = cuda(nears), cuda(fars), cuda(bg_ray)
+            tag = f"[T_thresh={T_thresh:g},ds={ds:g}]"
+
+            sig, rgb = rr.composite_inputs(c)
+            d_sig, d_rgb = cuda(sig), cuda(rgb)
+            ws, dep, img = full(N), full(N), full((N, 3))
+            call(lib.foc_composite_rays_train_forward, ptr(d_sig), ptr(d_rgb), ptr(d_deltas), ptr(d_rays), M, N, T_thresh, ptr(ws), ptr(dep), ptr(img))
+            res = dict(weights_sum=ws, depth=dep, image=img)
+            for with_ws in (True, False):
+                g_sig, g_rgb = torch.zeros(M, device="cuda"), torch.zeros(M, 3, device="cuda")
+                call(lib.foc_composite_rays_train_backward, ptr(g["grad_ws"] if with_ws else None), ptr(g["grad_image"]), ptr(d_sig), ptr(d_rgb), ptr(d_deltas),
+                     ptr(d_rays), ptr(ws), ptr(img), M, N, T_thresh, ptr(g_sig), ptr(g_rgb))
+                res.update({f"grad_sigmas[ws={with_ws}]": g_sig, f"grad_rgbs[ws={with_ws}]": g_rgb})
+            put("composite_rays_train" + tag, **res)
+
+            for cw in (4, 16):
+                for bgr in (d_bg, None):
+                    for crit in (False, True):
+                        ws, raw, img, dep, sq = full(N), full((N, 3)), full((N, 3)), full(N), full(N) if crit else None
+                        args = (ptr(d_h), ptr(d_c[cw]), cw, ptr(d_deltas), ptr(d_rays), M, N, T_thresh, ds, ptr(bgr), rr.BG_SCALAR, ptr(d_near), ptr(d_far), ptr(ws), ptr(raw),
+                                ptr(img), ptr(dep))
+                        call(lib.foc_occ_tail_forward_sumsq, *args, ptr(sq)) if crit else call(lib.foc_occ_tail_forward, *args)
+                        res = dict(weights_sum=ws, image_raw=raw, image=img, depth=dep, ray_sumsq=sq)
+                        for with_ws in (True, False):
+                            g_c, g_h0 = full((M, cw), torch.float16), full(M, torch.float16)
+                            args = (ptr(g["grad_image"]), ptr(g["grad_ws"] if with_ws else None), ptr(d_h), ptr(d_c[cw]), cw, ptr(d_deltas), ptr(d_rays), ptr(counter),
+                                    ptr(ws), ptr(raw), M, N, T_thresh, ds, ptr(bgr), rr.BG_SCALAR, ptr(g_c), ptr(g_h0))
+                            call(lib.foc_occ_tail_backward_sumsq, *args, ptr(g["grad_sumsq"])) if crit else call(lib.foc_occ_tail_backward, *args)
+                            res.update({f"grad_c[ws={with_ws}]": g_c, f"grad_h0[ws={with_ws}]": g_h0})
+                        put(f"occ_tail{tag}[c_width={cw},bg_ray={bgr is not None},sumsq={crit}]", **res)
+
+
+# ---------------------------------------------------------------- fixed-step family (fixedstep.hip) and the combiner (combine.hip)
+def fixed(N, T, noisy, per_ray_bg, ds):
+    rng = np.random.default_rng(1000 * N + 10 * T + 2 * noisy + per_ray_bg)
+    M = N * T
+    f32 = lambda a: cuda(np.asarray(a, np.float32))
+    h = rng.normal(0, 2, (M, 16)); h[::7, 0] = rng.choice([15.0, -15.0, 16.5, -17.0, 15.0078125], len(h[::7]))
+    h16, c16 = cuda(h.astype(np.float16)), cuda(rng.normal(0, 2, (M, 16)).astype(np.float16))
+    d = rng.normal(0, 1, (N, 3)); d /= np.linalg.norm(d, axis=1, keepdims=True)
+    near = rng.uniform(0.1, 0.6, N)
+    nears, fars, dirs = f32(near), f32(near + rng.uniform(0.5, 2.5, N)), f32(d)
+    noise = f32(rng.random((N, T))) if noisy else None
+    bg_ray, bg = (f32(rng.random((N, 3))) if per_ray_bg else None), 0.7
+    thresh = 1e-3                                                          # weights on both sides of it
+    g_img, g_ws, g_dp, g_sq = f32(rng.normal(0, 1, (N, 3))), f32(rng.normal(0, 0.5, N)), f32(rng.normal(0, 0.5, N)), f32(rng.normal(0, 1e-3, N))
+    tag = f"[N={N},T={T},noise={noisy},bg_ray={per_ray_bg},ds={ds:g}]"
+
+    width = 48 if ds == 2.0 else 32
+    obj = cuda(rng.normal(0, 1, 16).astype(np.float16)) if width == 48 else None
+    sigma, trans, w, ws, dp, cin = full(M), full(M), full(M), full(N), full(N), full((M, width), torch.float16)
+    call(lib.foc_fixed_head_forward, ptr(h16), ptr(dirs), ptr(nears), ptr(fars), ptr(noise), N, T, ds, ptr(sigma), ptr(trans), ptr(w), ptr(ws), ptr(dp), ptr(cin), ptr(obj), width)
+    g_w, g_cin, g_h = f32(rng.normal(0, 1, M)), cuda(rng.normal(0, 1, (M, width)).astype(np.float16)), full((M, 16), torch.float16)
+    call(lib.foc_fixed_head_backward, ptr(h16), ptr(sigma), ptr(trans), ptr(nears), ptr(fars), ptr(noise), ptr(g_w), ptr(g_ws), ptr(g_dp), ptr(g_cin), N, T, ds, ptr(g_h), width)
+    g_h_nc = full((M, 16), torch.float16)                                 # without grad_cin / grad_depth
+    call(lib.foc_fixed_head_backward, ptr(h16), ptr(sigma), ptr(trans), ptr(nears), ptr(fars), ptr(noise), ptr(g_w), None, None, None, N, T, ds, ptr(g_h_nc), width)
+    img, g_c, g_wc = full((N, 3)), full((M, 16), torch.float16), full(M)
+    call(lib.foc_fixed_composite_forward, ptr(c16), ptr(w), ptr(bg_ray), bg, N, T, thresh, ptr(img))
+    call(lib.foc_fixed_composite_backward, ptr(g_img), ptr(c16), ptr(w), ptr(bg_ray), bg, N, T, thresh, ptr(g_c), ptr(g_wc))
+    put("fixed_head+composite" + tag, sigma=sigma, trans=trans, weights=w, weights_sum=ws, depth=dp, cin=cin, grad_h=g_h, grad_h_plain=g_h_nc, image=img, grad_c=g_c, grad_w=g_wc)
+
+    for cw in (4, 16):
+        c = c16[:, :4].contiguous() if cw == 4 else c16
+        for crit in (False, True):
+            sigma, trans, w, ws, dp, img, sq = full(M), full(M), full(M), full(N), full(N), full((N, 3)), full(N) if crit else None
+            call(lib.foc_fixed_tail_forward, ptr(h16), ptr(c), ptr(nears), ptr(fars), ptr(noise), ptr(bg_ray), bg, N, T, ds, thresh, ptr(sigma), ptr(trans), ptr(w), ptr(ws), ptr(dp),
+                 ptr(img), cw, ptr(sq))
+            g_c, g_h0 = full((M, cw), torch.float16), full(M, torch.float16)
+            call(lib.foc_fixed_tail_backward, ptr(g_img), ptr(g_ws), ptr(g_dp), ptr(c), ptr(sigma), ptr(trans), ptr(w), ptr(nears), ptr(fars), ptr(noise), ptr(bg_ray), bg, N, T, ds,
+                 thresh, ptr(g_c), ptr(g_h0), cw, ptr(g_sq if crit else None))
+            put(f"fixed_tail{tag}[c_width={cw},sumsq={crit}]", sigma=sigma, trans=trans, weights=w, weights_sum=ws, depth=dp, image=img, ray_sumsq=sq, grad_c=g_c, grad_h0=g_h0)
+
+    for ray_block in (0, 64):
+        rows = (N + 63) // 64 * 64 * T if ray_block else M
+        sig_in, rgb_in = f32(np.exp(rng.normal(0, 2, rows))), f32(rng.random((rows, 3)))
+        img, dp, ws, masked, sig_rm = full((N, 3)), full(N), full(N), full((M, 3)), full(M) if ray_block else None
+        call(lib.foc_fixed_render_inference, ptr(sig_in), ptr(rgb_in), ptr(nears), ptr(fars), ptr(noise), ptr(bg_ray), bg, N, T, ds, thresh, ptr(img), ptr(dp), ptr(ws), ptr(masked),
+             ray_block, ptr(sig_rm))
+        img2, dp2, ws2, f4 = full((N, 3)), full(N), full(N), full((M, 4))
+        call(lib.foc_fixed_field_pack, ptr(sig_in), ptr(rgb_in), ptr(nears), ptr(fars), ptr(noise), ptr(bg_ray), bg, N, T, ds, thresh, ptr(img2), ptr(dp2), ptr(ws2), ptr(f4), ray_block)
+        put(f"fixed_inference{tag}[ray_block={ray_block}]", image=img, depth=dp, weights_sum=ws, rgb_masked=masked, sigma_raymajor=sig_rm, pack_image=img2, pack_depth=dp2,
+            pack_weights_sum=ws2, field4=f4)
+
+
+def combine(T):
+    from focnerf_amd.combine import HipCombineOps as ops
+    rng = np.random.default_rng(300 + T)
+    N = 5
+    near = rng.uniform(0.1, 0.6, N)
+    nears, fars = cuda(near.astype(np.float32)), cuda((near + rng.uniform(0.5, 2.5, N)).astype(np.float32))
+    fields = []
+    for k in range(3):
+        f = rng.random((N, T, 4)); f[..., 0] = np.exp(rng.normal(0, 2, (N, T)))
+        fields.append(cuda(f.astype(np.float32)))
+    fields[1][0, 0, 0] = NAN32                                             # torch.maximum's NaN propagation
+    image4, depth = ops.composite(fields[0][..., 0].contiguous(), fields[0][..., 1:].contiguous(), nears, fars, 1.0)
+    res = dict(fixed_image4=image4, fixed_depth=depth)
+    for K in (1, 3):
+        image4, depth, merged = ops.select_composite(fields[:K], nears, fars, (1.0, 0.0), want_merged=True)
+        res.update({f"image4[K={K}]": image4, f"depth[K={K}]": depth, f"merged4[K={K}]": merged})
+    image4, depth, att, merged, winner = ops.select_composite_attr(fields, nears, fars, (1.0, 0.0), 3, want_merged=True, want_winner=True)
+    res.update(attr_image4=image4, attr_depth=depth, attr_merged4=merged, attr_winner=winner, obj_weights=att.weights, obj_depth=att.depth, instance=att.instance)
+    put(f"combine[N={N},T={T}]", **res)
+
+
+def main():
+    per_sample()
+    ragged()
+    for N in (1, 5, 130):
+        for T in (2, 65, 130):
+            for noisy in (False, True):
+                for per_ray_bg in (False, True):
+                    for ds in (1.0, 2.0):
+                        fixed(N, T, noisy, per_ray_bg, ds)
+    for T in (2, 65, 130):
+        combine(T)
+    text = json.dumps(OUT, indent=0, sort_keys=True)
+    if len(sys.argv) < 2:
+        print(text)
+        return
+    with open(sys.argv[1], "w") as f:
+        f.write(text + "\n")
+    print(json.dumps({"cases": len(OUT), "outputs": sum(len(v) for v in OUT.values()), "sha256": hashlib.sha256(text.encode()).hexdigest()}))
+
+
+if __name__ == "__main__":
+    main()
