@@ -1616,10 +1616,10 @@ int foc_ffmlp_backward_planar(const void *grad, const void *inputs_planar, const
                          calc_grad_inputs, nullptr, grad_inputs_planar, grad_weights, workspace, workspace_bytes, 1, stream);
 }
 
-static int nerf_field_inference(const void *enc, int enc_planar, const float *dirs, uint32_t dir_div, uint32_t dir_block, uint32_t n_dirs,
-                                const void *sigma_weights, uint32_t sigma_layers, const void *color_weights, uint32_t color_layers, uint32_t hidden_dim,
-                                uint32_t activation, uint32_t B, float *sigma, float *rgb, const void *obj_feat, float input_pad, bool pad31,
-                                void *stream) {
+int nerf_field_inference(const void *enc, int enc_planar, const float *dirs, uint32_t dir_div, uint32_t dir_block, uint32_t n_dirs,
+                         const void *sigma_weights, uint32_t sigma_layers, const void *color_weights, uint32_t color_layers, uint32_t hidden_dim,
+                         uint32_t activation, uint32_t B, float *sigma, float *rgb, const void *obj_feat, float input_pad, bool pad31,
+                         void *stream) {
     FocDeviceGuard foc_guard_(stream, enc);
     if (B == 0) return FOC_OK;
     FOC_REQUIRE(enc && dirs && sigma_weights && color_weights && rgb, FOC_E_INVALID, "nerf_field_inference: null pointer");
@@ -1668,9 +1668,9 @@ int foc_nerf_field_inference_pad31(const void *enc, int enc_planar, const float 
 }
 
 // The colour network of the fixed-step training path, fed from the sigma network's output rows and a per-ray SH table (input mode 2).
-static int color_head_forward(const void *h, const void *ray_sh, uint32_t samples_per_ray, const void *weights, uint32_t B, uint32_t hidden_dim,
-                              uint32_t num_layers, uint32_t activation, void *outputs, uint32_t out_width, const void *obj_feat, float input_pad, bool pad31,
-                              void *stream) {
+int color_head_forward(const void *h, const void *ray_sh, uint32_t samples_per_ray, const void *weights, uint32_t B, uint32_t hidden_dim,
+                       uint32_t num_layers, uint32_t activation, void *outputs, uint32_t out_width, const void *obj_feat, float input_pad, bool pad31,
+                       void *stream) {
     FocDeviceGuard foc_guard_(stream, h);
     int rc = mlp_check("color_head_forward", B, 32, 16, hidden_dim, num_layers, activation, 6);
     if (rc) return rc;
@@ -1705,10 +1705,10 @@ int foc_color_head_forward_pad31(const void *h, const void *ray_sh, uint32_t sam
                               stream);
 }
 
-static int color_head_backward(const void *grad, const void *h, const void *ray_sh, uint32_t samples_per_ray, const void *grad_h0, const void *weights,
-                               uint32_t B, uint32_t hidden_dim, uint32_t num_layers, uint32_t activation, void *grad_h, void *grad_weights, void *workspace,
-                               uint64_t workspace_bytes, uint32_t out_width, const void *obj_feat, float *grad_obj, float input_pad, bool pad31,
-                               void *stream) {
+int color_head_backward(const void *grad, const void *h, const void *ray_sh, uint32_t samples_per_ray, const void *grad_h0, const void *weights,
+                        uint32_t B, uint32_t hidden_dim, uint32_t num_layers, uint32_t activation, void *grad_h, void *grad_weights, void *workspace,
+                        uint64_t workspace_bytes, uint32_t out_width, const void *obj_feat, float *grad_obj, float input_pad, bool pad31,
+                        void *stream) {
     FocDeviceGuard foc_guard_(stream, grad);
     int rc = mlp_check("color_head_backward", B, 32, 16, hidden_dim, num_layers, activation, 6);
     if (rc) return rc;

@@ -194,9 +194,9 @@ static int ff_launch_act(const void *planes, const void *w_sigma, const void *w_
     return relu ? ff_launch<NLS, NLC, true>(planes, w_sigma, w_color, h, c, B, hd, st) : ff_launch<NLS, NLC, false>(planes, w_sigma, w_color, h, c, B, hd, st);
 }
 
-static int field_forward_train(const void *planes, const void *sigma_weights, uint32_t sigma_layers, const void *ray_sh, uint32_t samples_per_ray,
-                               const void *color_weights, uint32_t color_layers, uint32_t hidden_dim, uint32_t activation, uint32_t B, void *h, void *c,
-                               uint32_t out_width, const void *obj_feat, float input_pad, bool pad31, void *stream) {
+int field_forward_train(const void *planes, const void *sigma_weights, uint32_t sigma_layers, const void *ray_sh, uint32_t samples_per_ray,
+                        const void *color_weights, uint32_t color_layers, uint32_t hidden_dim, uint32_t activation, uint32_t B, void *h, void *c,
+                        uint32_t out_width, const void *obj_feat, float input_pad, bool pad31, void *stream) {
     FocDeviceGuard foc_guard_(stream, planes);
     if (B == 0) return FOC_OK;
     FOC_REQUIRE(planes && sigma_weights && ray_sh && color_weights && h && c, FOC_E_INVALID, "field_forward_train: null pointer");

@@ -132,6 +132,30 @@ static inline int head_pad_check(const char *who, bool pad31, const void *obj_fe
     else FOC_REQUIRE(input_pad == 0.0f || obj_feat, FOC_E_INVALID, "%s: input_pad is column 47 of the 48-wide colour input and needs obj_feat", who);
     return FOC_OK;
 }
+// Host: the (sigma_layers, color_layers) pairs the kernels of both networks are built for (field_fwd.hip, k_nerf_infer), and with them
+// the pairs a pad can go with
+static inline bool head_layer_pair(uint32_t sigma_layers, uint32_t color_layers) {
+    const uint32_t lk = sigma_layers * 10 + color_layers;
+    return lk == 12 || lk == 13 || lk == 22 || lk == 23 || lk == 33;
+}
+// Host: the bodies behind the exported foc_<name>, foc_<name>_pad (pad31 false) and foc_<name>_pad31 (pad31 true) entry points, for the
+// sequences inside the library (occtrain.hip, occrender.hip) that serve every layout of the colour input. field_fwd.hip, ffmlp.hip.
+extern "C" {
+#define FOC_INTERNAL __attribute__((visibility("hidden")))
+FOC_INTERNAL int field_forward_train(const void *planes, const void *sigma_weights, uint32_t sigma_layers, const void *ray_sh, uint32_t samples_per_ray,
+                                     const void *color_weights, uint32_t color_layers, uint32_t hidden_dim, uint32_t activation, uint32_t B, void *h, void *c,
+                                     uint32_t out_width, const void *obj_feat, float input_pad, bool pad31, void *stream);
+FOC_INTERNAL int nerf_field_inference(const void *enc, int enc_planar, const float *dirs, uint32_t dir_div, uint32_t dir_block, uint32_t n_dirs,
+                                      const void *sigma_weights, uint32_t sigma_layers, const void *color_weights, uint32_t color_layers, uint32_t hidden_dim,
+                                      uint32_t activation, uint32_t B, float *sigma, float *rgb, const void *obj_feat, float input_pad, bool pad31, void *stream);
+FOC_INTERNAL int color_head_forward(const void *h, const void *ray_sh, uint32_t samples_per_ray, const void *weights, uint32_t B, uint32_t hidden_dim,
+                                    uint32_t num_layers, uint32_t activation, void *outputs, uint32_t out_width, const void *obj_feat, float input_pad, bool pad31,
+                                    void *stream);
+FOC_INTERNAL int color_head_backward(const void *grad, const void *h, const void *ray_sh, uint32_t samples_per_ray, const void *grad_h0, const void *weights,
+                                     uint32_t B, uint32_t hidden_dim, uint32_t num_layers, uint32_t activation, void *grad_h, void *grad_weights, void *workspace,
+                                     uint64_t workspace_bytes, uint32_t out_width, const void *obj_feat, float *grad_obj, float input_pad, bool pad31,
+                                     void *stream);
+}
 // The same layout for the 32-wide row without an object feature: bias = W0[n][31] * pad (one product, exact for pad = 1). `W0` has 32-wide rows.
 __device__ __forceinline__ void stage_pad31_bias(const _Float16 *__restrict__ W0, float pad, float *bias, uint32_t hidden) {
     if (threadIdx.x < hidden) {

@@ -14,13 +14,13 @@
 //             positions leave already normalised, x -> (x + bound) * (1 / (2 bound))  (gridencoder/grid.py:149 as torch evaluates it:
 //             division by a scalar = multiplication by its reciprocal) — nobody but the encoder reads them here
 //   encode    foc_grid_encode_forward ([L, M, 2] planes)
-//   field     foc_nerf_field_inference (sigma net -> head -> colour net, per-sample directions)
+//   field     nerf_field_inference (the body of foc_nerf_field_inference[_pad | _pad31]: sigma net -> head -> colour net, per-sample directions)
 //   composite foc_composite_compact: composite_rays in place (weights_sum, depth, image, rays_t; finished rays marked -1; a burst's samples
 //             loaded at once), its waves counting their survivors and recording where rays died, then scan + ordered scatter into the output
 //             list, whose tail stays -1 (march / composite skip such entries)
 //
 // The live count stays on the device (`count`, one int); the caller reads it late (focnerf_amd/renderer.py) and passes an upper bound.
-#include "common.h"
+#include "mlp_common.h"     // host: nerf_field_inference, head_layer_pair
 #include <cstdlib>
 
 __global__ void __launch_bounds__(256) k_occ_prepare(uint32_t *__restrict__ samples, uint64_t n_sample_words, int32_t *__restrict__ list_out, uint32_t n_list,
@@ -42,8 +42,9 @@ uint64_t foc_occ_render_step_scratch_bytes(uint32_t n_rays) {
     return wl + cc;
 }
 
-// pad31 (foc_occ_render_step_pad31): the field through foc_nerf_field_inference_pad31, column 31 of the colour input = input_pad
-// pad47 (foc_occ_render_step_pad): the field through foc_nerf_field_inference_pad, column 47 of the object-conditioned colour input = input_pad
+// The colour input's layout is (obj_feat, input_pad, pad31), as nerf_field_inference takes it (mlp_common.h). pad31
+// (foc_occ_render_step_pad31): input_pad is column 31 of the 32-wide row; else column 47 of the object-conditioned 48-wide row
+// (foc_occ_render_step_pad), and with input_pad 0 that is the plain step (foc_occ_render_step), which nothing below can refuse.
 static int occ_render_step(uint32_t n_alive, uint32_t n_step, const int32_t *rays_alive, int32_t *rays_alive_out, int32_t *count,
                            float *rays_t, const float *rays_o, const float *rays_d, float bound, float dt_gamma, uint32_t max_steps,
                            uint32_t C, uint32_t H, const uint8_t *grid, const float *nears, const float *fars, const float *noises,
@@ -51,21 +52,15 @@ static int occ_render_step(uint32_t n_alive, uint32_t n_step, const int32_t *ray
                            const void *embeddings, const int32_t *offsets, const int32_t *offsets_host, uint32_t L, float S, uint32_t base_res,
                            const void *sigma_weights, uint32_t sigma_layers, const void *color_weights, uint32_t color_layers, uint32_t activation,
                            const void *obj_feat, float T_thresh, float *weights_sum, float *depth, float *image, void *scratch, uint32_t flags, int32_t *deaths,
-                           uint32_t deaths_base, uint32_t deaths_len, float input_pad, bool pad31, bool pad47, void *stream) {
+                           uint32_t deaths_base, uint32_t deaths_len, float input_pad, bool pad31, void *stream) {
     FocDeviceGuard foc_guard_(stream, rays_alive);
     FOC_REQUIRE(count, FOC_E_INVALID, "occ_render_step: null pointer");
-    if (pad31) {                                            // refused before anything is enqueued
-        const uint32_t lk = sigma_layers * 10 + color_layers;
-        FOC_REQUIRE(!obj_feat, FOC_E_INVALID, "occ_render_step_pad31: input_pad is column 31 of the 32-wide colour input, obj_feat must be NULL");
-        FOC_REQUIRE(input_pad == 0.0f || lk == 12 || lk == 13 || lk == 22 || lk == 23 || lk == 33, FOC_E_INVALID,
-                    "occ_render_step_pad31: a pad needs (sigma_layers, color_layers) in (1,2), (1,3), (2,2), (2,3), (3,3) (got %u, %u)", sigma_layers, color_layers);
-    }
-    if (pad47) {                                            // refused before anything is enqueued
-        const uint32_t lk = sigma_layers * 10 + color_layers;
-        FOC_REQUIRE(obj_feat || input_pad == 0.0f, FOC_E_INVALID, "occ_render_step_pad: input_pad is column 47 of the 48-wide colour input, it needs obj_feat");
-        FOC_REQUIRE(input_pad == 0.0f || lk == 12 || lk == 13 || lk == 22 || lk == 23 || lk == 33, FOC_E_INVALID,
-                    "occ_render_step_pad: a pad needs (sigma_layers, color_layers) in (1,2), (1,3), (2,2), (2,3), (3,3) (got %u, %u)", sigma_layers, color_layers);
-    }
+    // refused before anything is enqueued
+    if (pad31) FOC_REQUIRE(!obj_feat, FOC_E_INVALID, "occ_render_step_pad31: input_pad is column 31 of the 32-wide colour input, obj_feat must be NULL");
+    else FOC_REQUIRE(obj_feat || input_pad == 0.0f, FOC_E_INVALID, "occ_render_step_pad: input_pad is column 47 of the 48-wide colour input, it needs obj_feat");
+    FOC_REQUIRE(input_pad == 0.0f || head_layer_pair(sigma_layers, color_layers), FOC_E_INVALID,
+                "occ_render_step_%s: a pad needs (sigma_layers, color_layers) in (1,2), (1,3), (2,2), (2,3), (3,3) (got %u, %u)", pad31 ? "pad31" : "pad", sigma_layers,
+                color_layers);
     hipStream_t st = (hipStream_t)stream;
     if (n_alive == 0) return foc_zero_async(count, sizeof(int32_t), st) == hipSuccess ? FOC_OK : FOC_E_LAUNCH;
     FOC_REQUIRE(rays_alive && rays_alive_out && rays_t && rays_o && rays_d && grid && fars && noises && samples && planes && sigma && rgb && embeddings &&
@@ -98,13 +93,8 @@ static int occ_render_step(uint32_t n_alive, uint32_t n_step, const int32_t *ray
         const uint32_t mc = (uint32_t)(M - m0 < piece ? M - m0 : piece);
         rc = foc_grid_encode_forward(xyzs + 3 * m0, embeddings, offsets, planes, mc, 3, 2, L, S, base_res, nullptr, 0, 0, 0, FOC_F16, offsets_host, stream);
         if (rc) return rc;
-        rc = pad31 ? foc_nerf_field_inference_pad31(planes, 1, dirs + 3 * m0, 1, 0, mc, sigma_weights, sigma_layers, color_weights, color_layers, 64, activation,
-                                                    mc, sigma + m0, rgb + 3 * m0, obj_feat, input_pad, stream)
-           : (pad47 && input_pad != 0.0f)
-                   ? foc_nerf_field_inference_pad(planes, 1, dirs + 3 * m0, 1, 0, mc, sigma_weights, sigma_layers, color_weights, color_layers, 64, activation, mc,
-                                                  sigma + m0, rgb + 3 * m0, obj_feat, input_pad, stream)
-                   : foc_nerf_field_inference(planes, 1, dirs + 3 * m0, 1, 0, mc, sigma_weights, sigma_layers, color_weights, color_layers, 64, activation, mc,
-                                              sigma + m0, rgb + 3 * m0, obj_feat, stream);
+        rc = nerf_field_inference(planes, 1, dirs + 3 * m0, 1, 0, mc, sigma_weights, sigma_layers, color_weights, color_layers, 64, activation, mc, sigma + m0,
+                                  rgb + 3 * m0, obj_feat, input_pad, pad31, stream);
         if (rc) return rc;
     }
     // composite marks finished rays in the INPUT list; the compaction then writes the survivors to the output list
@@ -123,7 +113,7 @@ int foc_occ_render_step(uint32_t n_alive, uint32_t n_step, const int32_t *rays_a
                         uint32_t deaths_len, void *stream) {
     return occ_render_step(n_alive, n_step, rays_alive, rays_alive_out, count, rays_t, rays_o, rays_d, bound, dt_gamma, max_steps, C, H, grid, nears, fars, noises,
                            samples, planes, sigma, rgb, embeddings, offsets, offsets_host, L, S, base_res, sigma_weights, sigma_layers, color_weights, color_layers,
-                           activation, obj_feat, T_thresh, weights_sum, depth, image, scratch, flags, deaths, deaths_base, deaths_len, 0.0f, false, false, stream);
+                           activation, obj_feat, T_thresh, weights_sum, depth, image, scratch, flags, deaths, deaths_base, deaths_len, 0.0f, false, stream);
 }
 
 int foc_occ_render_step_pad31(uint32_t n_alive, uint32_t n_step, const int32_t *rays_alive, int32_t *rays_alive_out, int32_t *count,
@@ -136,7 +126,7 @@ int foc_occ_render_step_pad31(uint32_t n_alive, uint32_t n_step, const int32_t *
                               uint32_t deaths_base, uint32_t deaths_len, float input_pad, void *stream) {
     return occ_render_step(n_alive, n_step, rays_alive, rays_alive_out, count, rays_t, rays_o, rays_d, bound, dt_gamma, max_steps, C, H, grid, nears, fars, noises,
                            samples, planes, sigma, rgb, embeddings, offsets, offsets_host, L, S, base_res, sigma_weights, sigma_layers, color_weights, color_layers,
-                           activation, obj_feat, T_thresh, weights_sum, depth, image, scratch, flags, deaths, deaths_base, deaths_len, input_pad, true, false, stream);
+                           activation, obj_feat, T_thresh, weights_sum, depth, image, scratch, flags, deaths, deaths_base, deaths_len, input_pad, true, stream);
 }
 
 int foc_occ_render_step_pad(uint32_t n_alive, uint32_t n_step, const int32_t *rays_alive, int32_t *rays_alive_out, int32_t *count,
@@ -149,7 +139,7 @@ int foc_occ_render_step_pad(uint32_t n_alive, uint32_t n_step, const int32_t *ra
                             uint32_t deaths_base, uint32_t deaths_len, float input_pad, void *stream) {
     return occ_render_step(n_alive, n_step, rays_alive, rays_alive_out, count, rays_t, rays_o, rays_d, bound, dt_gamma, max_steps, C, H, grid, nears, fars, noises,
                            samples, planes, sigma, rgb, embeddings, offsets, offsets_host, L, S, base_res, sigma_weights, sigma_layers, color_weights, color_layers,
-                           activation, obj_feat, T_thresh, weights_sum, depth, image, scratch, flags, deaths, deaths_base, deaths_len, input_pad, false, true, stream);
+                           activation, obj_feat, T_thresh, weights_sum, depth, image, scratch, flags, deaths, deaths_base, deaths_len, input_pad, false, stream);
 }
 
 } // extern "C"

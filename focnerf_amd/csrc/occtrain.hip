@@ -15,9 +15,13 @@
 // The backward writes EVERY row of grad_c and grad_h0: a ray's wave covers the ray's whole slot range (zeros behind the sample at which
 // the ray became opaque, zeros for a ray that did not fit the list), and the rows behind the last ray's range are zeroed by spare
 // waves — the colour network's backward reads all M rows, and the caller's zero fill of them was a launch of its own.
+//
+// Below the kernels: the whole training node as one call each way (foc_occ_train_forward / _backward and their _pad31 and _obj forms).
+// One forward and one backward sequence serve every layout of the colour input; the six entry points differ in their checks only.
 #include "common.h"
 #include "sample_math.h"     // foc_sigmoid_h, foc_trunc_exp_bwd, foc_bg, h8
 #include "ragged.h"          // ot_ray, ot_step, ot_grad_acc: the composite, shared with k_composite_train_fwd / _bwd
+#include "mlp_common.h"      // host: the colour-input layouts' shared bodies (field_forward_train, color_head_forward / _backward), head_layer_pair
 
 #define OT_PAD_BLOCKS 64u
 
@@ -237,7 +241,10 @@ int foc_occ_tail_backward_sumsq(const float *grad_image, const float *grad_ws, c
 }
 
 // ---------------------------------------------------------------- the node as one call each way
-// Sequencing only: each step is the public entry point a caller would have called itself, with its own argument checks and device guard.
+// ONE sequence each way for the three layouts of the colour input (mlp_common.h MlpHead): plain (32 wide, last column 0), pad31 (32 wide,
+// column 31 = input_pad: network_tcnn_legacy.py) and object-conditioned (48 wide, obj_feat [16], column 47 = input_pad: network_foc.py,
+// network_tcnn.py). Sequencing only: each step is the body of the public entry point a caller would have called itself, with its own
+// argument checks and device guard. The six exported entry points at the end run their own checks, all before the first launch.
 static int ot_check_node(const FocOccTrainNode *n, const char *who) {
     FOC_REQUIRE(n != nullptr, FOC_E_INVALID, "%s: null node", who);
     FOC_REQUIRE(n->struct_bytes == (uint32_t)sizeof(FocOccTrainNode), FOC_E_INVALID, "%s: node of %u bytes, this library's FocOccTrainNode has %zu", who,
@@ -247,76 +254,19 @@ static int ot_check_node(const FocOccTrainNode *n, const char *who) {
     return FOC_OK;
 }
 
-// The *_pad31 twins (pad31): column 31 of the colour input holds input_pad (the legacy tinycudann layout, network_tcnn_legacy.py), through
-// foc_field_forward_train_pad31 / foc_color_head_forward_pad31 / foc_color_head_backward_pad31, and the one-kernel forward of both networks
-// also serves one sigma hidden layer ((1, 2), (1, 3): bit for bit the two calls, as at the other pairs).
 static int ot_check_pad31(const FocOccTrainNode *n, float input_pad, const char *who) {
-    const uint32_t lk = n->sigma_layers * 10 + n->color_layers;
-    FOC_REQUIRE(input_pad == 0.0f || lk == 12 || lk == 13 || lk == 22 || lk == 23 || lk == 33, FOC_E_INVALID,
+    FOC_REQUIRE(input_pad == 0.0f || head_layer_pair(n->sigma_layers, n->color_layers), FOC_E_INVALID,
                 "%s: a pad needs (sigma_layers, color_layers) in (1,2), (1,3), (2,2), (2,3), (3,3) (got %u, %u)", who, n->sigma_layers, n->color_layers);
     return FOC_OK;
 }
 
-static int occ_train_forward(const FocOccTrainNode *n, float input_pad, bool pad31, void *stream) {
-    int rc = ot_check_node(n, pad31 ? "occ_train_forward_pad31" : "occ_train_forward");
-    if (rc != FOC_OK) return rc;
-    if (pad31 && (rc = ot_check_pad31(n, input_pad, "occ_train_forward_pad31")) != FOC_OK) return rc;
-    const uint32_t M = n->cap;
-    rc = foc_march_rays_train_field(n->rays_o, n->rays_d, n->bitfield, n->bound, n->dt_gamma, n->max_steps, n->n_rays, n->cascade, n->grid_size, M, n->nears, n->fars,
-                                    n->enc_in, n->sh_rows, n->deltas, n->rays, n->counter, n->jitter, n->march_scratch, n->pad_align, n->aabb, n->min_near, stream);
-    if (rc != FOC_OK) return rc;
-    rc = foc_grid_encode_forward_counted(n->enc_in, n->embeddings, n->offsets, n->planes, M, 3, 2, n->levels, n->per_level_scale_log2, n->base_resolution, n->gridtype,
-                                         n->align_corners, n->interp, n->table_dtype, n->offsets_host, n->grid_workspace, n->grid_workspace_bytes, stream);
-    if (rc != FOC_OK) return rc;
-    // both networks in one kernel when the shapes are FOC's (csrc/field_fwd.hip: bit for bit the two calls below)
-    const uint32_t lk = n->sigma_layers * 10 + n->color_layers;
-    if (n->sigma_input_dim == 32 && n->sigma_hidden == 64 && n->color_hidden == 64 && (lk == 22 || lk == 23 || lk == 33 || (pad31 && (lk == 12 || lk == 13))) &&
-        n->sigma_activation == n->color_activation && (n->sigma_activation == 0 || n->sigma_activation == 6) && n->sigma_output_activation == 6 &&
-        foc_opt(FOC_OPT_FIELD_FWD_FUSED)) {
-        rc = pad31 ? foc_field_forward_train_pad31(n->planes, n->w_sigma, n->sigma_layers, n->sh_rows, 1, n->w_color, n->color_layers, 64, n->sigma_activation,
-                                                   M, n->h, n->c, n->c_width, nullptr, input_pad, stream)
-                   : foc_field_forward_train(n->planes, n->w_sigma, n->sigma_layers, n->sh_rows, 1, n->w_color, n->color_layers, 64, n->sigma_activation, M, n->h,
-                                             n->c, n->c_width, nullptr, stream);
-        if (rc != FOC_OK) return rc;
-    } else {
-        rc = foc_ffmlp_forward_planar(n->planes, n->w_sigma, M, n->sigma_input_dim, 16, n->sigma_hidden, n->sigma_layers, n->sigma_activation, n->sigma_output_activation,
-                                      n->h, stream);
-        if (rc != FOC_OK) return rc;
-        rc = pad31 ? foc_color_head_forward_pad31(n->h, n->sh_rows, 1, n->w_color, M, n->color_hidden, n->color_layers, n->color_activation, n->c, n->c_width,
-                                                  nullptr, input_pad, stream)
-                   : foc_color_head_forward(n->h, n->sh_rows, 1, n->w_color, M, n->color_hidden, n->color_layers, n->color_activation, n->c, n->c_width, nullptr,
-                                            stream);
-        if (rc != FOC_OK) return rc;
-    }
-    return foc_occ_tail_forward(n->h, n->c, n->c_width, n->deltas, n->rays, M, n->n_rays, n->T_thresh, n->density_scale, n->bg_ray, n->bg_scalar, n->nears, n->fars,
-                                n->weights_sum, n->image_raw, n->image, n->depth, stream);
+// the shapes of the kernel that runs both networks (csrc/field_fwd.hip)
+static bool ot_whole_field(const FocOccTrainNode *n) {
+    return n->sigma_input_dim == 32 && n->sigma_hidden == 64 && n->color_hidden == 64 && head_layer_pair(n->sigma_layers, n->color_layers) &&
+           n->sigma_activation == n->color_activation && (n->sigma_activation == 0 || n->sigma_activation == 6) && n->sigma_output_activation == 6;
 }
 
-static int occ_train_backward(const FocOccTrainNode *n, float input_pad, bool pad31, void *stream) {
-    int rc = ot_check_node(n, pad31 ? "occ_train_backward_pad31" : "occ_train_backward");
-    if (rc != FOC_OK) return rc;
-    if (pad31 && (rc = ot_check_pad31(n, input_pad, "occ_train_backward_pad31")) != FOC_OK) return rc;
-    const uint32_t M = n->cap;
-    rc = foc_occ_tail_backward(n->grad_image, n->grad_ws, n->h, n->c, n->c_width, n->deltas, n->rays, n->counter, n->weights_sum, n->image_raw, M, n->n_rays, n->T_thresh,
-                               n->density_scale, n->bg_ray, n->bg_scalar, n->grad_c, n->grad_h0, stream);
-    if (rc != FOC_OK) return rc;
-    rc = pad31 ? foc_color_head_backward_pad31(n->grad_c, n->h, n->sh_rows, 1, n->grad_h0, n->w_color, M, n->color_hidden, n->color_layers, n->color_activation,
-                                               n->grad_h, n->grad_w_color, n->mlp_workspace, n->mlp_workspace_bytes, n->c_width, nullptr, nullptr, input_pad, stream)
-               : foc_color_head_backward(n->grad_c, n->h, n->sh_rows, 1, n->grad_h0, n->w_color, M, n->color_hidden, n->color_layers, n->color_activation, n->grad_h,
-                                         n->grad_w_color, n->mlp_workspace, n->mlp_workspace_bytes, n->c_width, nullptr, nullptr, stream);
-    if (rc != FOC_OK) return rc;
-    rc = foc_ffmlp_backward_planar(n->grad_h, n->planes, n->w_sigma, M, n->sigma_input_dim, 16, n->sigma_hidden, n->sigma_layers, n->sigma_activation,
-                                   n->sigma_output_activation, 1, n->grad_planes, n->grad_w_sigma, n->mlp_workspace, n->mlp_workspace_bytes, stream);
-    if (rc != FOC_OK) return rc;
-    return (n->precounted ? foc_grid_encode_backward_binned_counted : foc_grid_encode_backward_binned)(
-        n->grad_planes, n->enc_in, n->embeddings, n->offsets, n->grad_embeddings, M, 3, 2, n->levels, n->per_level_scale_log2, n->base_resolution, nullptr, nullptr,
-        n->gridtype, n->align_corners, n->interp, n->table_dtype, 0, n->offsets_host, n->grid_workspace, n->grid_workspace_bytes, stream);
-}
-
-// ---------------------------------------------------------------- the node of an object-conditioned network (FocOccTrainObject beside the node)
-// The same sequence with the object arguments: the 48-wide colour head (foc_field_forward_train[_pad], foc_color_head_forward / _backward[_pad])
-// and, when the companion carries ray_sumsq / grad_sumsq, the tail that also sums sigma^2 per ray. Everything below is checked before the
-// first launch.
+// the companion of an object-conditioned network (FocOccTrainObject beside the node)
 static int ot_check_object(const FocOccTrainNode *n, const FocOccTrainObject *ob, const char *who) {
     int rc = ot_check_node(n, who);
     if (rc != FOC_OK) return rc;
@@ -325,65 +275,52 @@ static int ot_check_object(const FocOccTrainNode *n, const FocOccTrainObject *ob
                 ob->struct_bytes, sizeof(FocOccTrainObject));
     FOC_REQUIRE(ob->obj_feat || ob->input_pad == 0.0f, FOC_E_INVALID, "%s: a pad (column 47 = %g) needs an object feature, obj_feat is NULL", who, (double)ob->input_pad);
     FOC_REQUIRE(ob->obj_feat, FOC_E_INVALID, "%s: obj_feat is NULL (a network without an object feature takes foc_occ_train_forward / _backward)", who);
-    const uint32_t lk = n->sigma_layers * 10 + n->color_layers;
-    FOC_REQUIRE(lk == 12 || lk == 13 || lk == 22 || lk == 23 || lk == 33, FOC_E_INVALID,
+    FOC_REQUIRE(head_layer_pair(n->sigma_layers, n->color_layers), FOC_E_INVALID,
                 "%s: (sigma_layers, color_layers) must be in (1,2), (1,3), (2,2), (2,3), (3,3) (got %u, %u)", who, n->sigma_layers, n->color_layers);
-    FOC_REQUIRE(n->sigma_input_dim == 32 && n->sigma_hidden == 64 && n->color_hidden == 64 && n->sigma_activation == n->color_activation &&
-                (n->sigma_activation == 0 || n->sigma_activation == 6) && n->sigma_output_activation == 6, FOC_E_INVALID,
+    FOC_REQUIRE(ot_whole_field(n), FOC_E_INVALID,
                 "%s: the object node serves 32 -> 64 density and 48 -> 64 colour networks with one hidden activation, relu(0) or none(6)", who);
     return FOC_OK;
 }
 
-int foc_occ_train_forward_obj(const FocOccTrainNode *n, const FocOccTrainObject *ob, void *stream) {
-    int rc = ot_check_object(n, ob, "occ_train_forward_obj");
-    if (rc != FOC_OK) return rc;
+// march -> counted encode -> both networks (one kernel, or sigma MLP + colour head) -> tail. ray_sumsq [n_rays] or NULL: the tail that
+// also sums sigma^2 per ray.
+static int occ_train_forward(const FocOccTrainNode *n, const void *obj_feat, float input_pad, bool pad31, float *ray_sumsq, void *stream) {
     const uint32_t M = n->cap;
-    const bool pad = ob->input_pad != 0.0f;
-    rc = foc_march_rays_train_field(n->rays_o, n->rays_d, n->bitfield, n->bound, n->dt_gamma, n->max_steps, n->n_rays, n->cascade, n->grid_size, M, n->nears, n->fars,
-                                    n->enc_in, n->sh_rows, n->deltas, n->rays, n->counter, n->jitter, n->march_scratch, n->pad_align, n->aabb, n->min_near, stream);
+    int rc = foc_march_rays_train_field(n->rays_o, n->rays_d, n->bitfield, n->bound, n->dt_gamma, n->max_steps, n->n_rays, n->cascade, n->grid_size, M, n->nears,
+                                        n->fars, n->enc_in, n->sh_rows, n->deltas, n->rays, n->counter, n->jitter, n->march_scratch, n->pad_align, n->aabb, n->min_near,
+                                        stream);
     if (rc != FOC_OK) return rc;
     rc = foc_grid_encode_forward_counted(n->enc_in, n->embeddings, n->offsets, n->planes, M, 3, 2, n->levels, n->per_level_scale_log2, n->base_resolution, n->gridtype,
                                          n->align_corners, n->interp, n->table_dtype, n->offsets_host, n->grid_workspace, n->grid_workspace_bytes, stream);
     if (rc != FOC_OK) return rc;
-    if (foc_opt(FOC_OPT_FIELD_FWD_FUSED)) {
-        rc = pad ? foc_field_forward_train_pad(n->planes, n->w_sigma, n->sigma_layers, n->sh_rows, 1, n->w_color, n->color_layers, 64, n->sigma_activation, M, n->h,
-                                               n->c, n->c_width, ob->obj_feat, ob->input_pad, stream)
-                 : foc_field_forward_train(n->planes, n->w_sigma, n->sigma_layers, n->sh_rows, 1, n->w_color, n->color_layers, 64, n->sigma_activation, M, n->h, n->c,
-                                           n->c_width, ob->obj_feat, stream);
+    // both networks in one kernel when the shapes are FOC's (csrc/field_fwd.hip: bit for bit the two calls below). The plain layout takes
+    // that kernel from two sigma layers on; one sigma hidden layer ((1, 2), (1, 3)) came with the pad31 and object layouts.
+    if (ot_whole_field(n) && (n->sigma_layers > 1 || pad31 || obj_feat) && foc_opt(FOC_OPT_FIELD_FWD_FUSED)) {
+        rc = field_forward_train(n->planes, n->w_sigma, n->sigma_layers, n->sh_rows, 1, n->w_color, n->color_layers, 64, n->sigma_activation, M, n->h, n->c,
+                                 n->c_width, obj_feat, input_pad, pad31, stream);
         if (rc != FOC_OK) return rc;
     } else {
         rc = foc_ffmlp_forward_planar(n->planes, n->w_sigma, M, n->sigma_input_dim, 16, n->sigma_hidden, n->sigma_layers, n->sigma_activation, n->sigma_output_activation,
                                       n->h, stream);
         if (rc != FOC_OK) return rc;
-        rc = pad ? foc_color_head_forward_pad(n->h, n->sh_rows, 1, n->w_color, M, n->color_hidden, n->color_layers, n->color_activation, n->c, n->c_width, ob->obj_feat,
-                                              ob->input_pad, stream)
-                 : foc_color_head_forward(n->h, n->sh_rows, 1, n->w_color, M, n->color_hidden, n->color_layers, n->color_activation, n->c, n->c_width, ob->obj_feat,
-                                          stream);
+        rc = color_head_forward(n->h, n->sh_rows, 1, n->w_color, M, n->color_hidden, n->color_layers, n->color_activation, n->c, n->c_width, obj_feat, input_pad, pad31,
+                                stream);
         if (rc != FOC_OK) return rc;
     }
-    return ob->ray_sumsq ? foc_occ_tail_forward_sumsq(n->h, n->c, n->c_width, n->deltas, n->rays, M, n->n_rays, n->T_thresh, n->density_scale, n->bg_ray, n->bg_scalar,
-                                                      n->nears, n->fars, n->weights_sum, n->image_raw, n->image, n->depth, ob->ray_sumsq, stream)
-                         : foc_occ_tail_forward(n->h, n->c, n->c_width, n->deltas, n->rays, M, n->n_rays, n->T_thresh, n->density_scale, n->bg_ray, n->bg_scalar,
-                                                n->nears, n->fars, n->weights_sum, n->image_raw, n->image, n->depth, stream);
+    return occ_tail_forward(ray_sumsq ? "occ_tail_forward_sumsq" : "occ_tail_forward", n->h, n->c, n->c_width, n->deltas, n->rays, M, n->n_rays, n->T_thresh,
+                            n->density_scale, n->bg_ray, n->bg_scalar, n->nears, n->fars, n->weights_sum, n->image_raw, n->image, n->depth, ray_sumsq, stream);
 }
 
-int foc_occ_train_backward_obj(const FocOccTrainNode *n, const FocOccTrainObject *ob, void *stream) {
-    int rc = ot_check_object(n, ob, "occ_train_backward_obj");
-    if (rc != FOC_OK) return rc;
-    FOC_REQUIRE(n->mlp_workspace_bytes >= foc_ffmlp_backward_workspace_bytes(48, 64, n->color_layers), FOC_E_INVALID,
-                "occ_train_backward_obj: MLP workspace of %llu bytes, the 48-wide colour head asks for foc_ffmlp_backward_workspace_bytes(48, 64, %u) = %llu",
-                (unsigned long long)n->mlp_workspace_bytes, n->color_layers, (unsigned long long)foc_ffmlp_backward_workspace_bytes(48, 64, n->color_layers));
+// tail -> colour head -> sigma MLP -> binned encoder backward. grad_sumsq [n_rays] or NULL: the gradient of the forward's ray_sumsq;
+// grad_obj [16] fp32 or NULL: the object feature's gradient.
+static int occ_train_backward(const FocOccTrainNode *n, const void *obj_feat, float input_pad, bool pad31, const float *grad_sumsq, float *grad_obj, void *stream) {
     const uint32_t M = n->cap;
-    rc = ob->grad_sumsq ? foc_occ_tail_backward_sumsq(n->grad_image, n->grad_ws, n->h, n->c, n->c_width, n->deltas, n->rays, n->counter, n->weights_sum, n->image_raw, M,
-                                                      n->n_rays, n->T_thresh, n->density_scale, n->bg_ray, n->bg_scalar, n->grad_c, n->grad_h0, ob->grad_sumsq, stream)
-                        : foc_occ_tail_backward(n->grad_image, n->grad_ws, n->h, n->c, n->c_width, n->deltas, n->rays, n->counter, n->weights_sum, n->image_raw, M,
-                                                n->n_rays, n->T_thresh, n->density_scale, n->bg_ray, n->bg_scalar, n->grad_c, n->grad_h0, stream);
+    int rc = occ_tail_backward(grad_sumsq ? "occ_tail_backward_sumsq" : "occ_tail_backward", n->grad_image, n->grad_ws, n->h, n->c, n->c_width, n->deltas, n->rays,
+                               n->counter, n->weights_sum, n->image_raw, M, n->n_rays, n->T_thresh, n->density_scale, n->bg_ray, n->bg_scalar, n->grad_c, n->grad_h0,
+                               grad_sumsq, stream);
     if (rc != FOC_OK) return rc;
-    rc = ob->input_pad != 0.0f
-             ? foc_color_head_backward_pad(n->grad_c, n->h, n->sh_rows, 1, n->grad_h0, n->w_color, M, n->color_hidden, n->color_layers, n->color_activation, n->grad_h,
-                                           n->grad_w_color, n->mlp_workspace, n->mlp_workspace_bytes, n->c_width, ob->obj_feat, ob->grad_obj, ob->input_pad, stream)
-             : foc_color_head_backward(n->grad_c, n->h, n->sh_rows, 1, n->grad_h0, n->w_color, M, n->color_hidden, n->color_layers, n->color_activation, n->grad_h,
-                                       n->grad_w_color, n->mlp_workspace, n->mlp_workspace_bytes, n->c_width, ob->obj_feat, ob->grad_obj, stream);
+    rc = color_head_backward(n->grad_c, n->h, n->sh_rows, 1, n->grad_h0, n->w_color, M, n->color_hidden, n->color_layers, n->color_activation, n->grad_h,
+                             n->grad_w_color, n->mlp_workspace, n->mlp_workspace_bytes, n->c_width, obj_feat, grad_obj, input_pad, pad31, stream);
     if (rc != FOC_OK) return rc;
     rc = foc_ffmlp_backward_planar(n->grad_h, n->planes, n->w_sigma, M, n->sigma_input_dim, 16, n->sigma_hidden, n->sigma_layers, n->sigma_activation,
                                    n->sigma_output_activation, 1, n->grad_planes, n->grad_w_sigma, n->mlp_workspace, n->mlp_workspace_bytes, stream);
@@ -393,9 +330,42 @@ int foc_occ_train_backward_obj(const FocOccTrainNode *n, const FocOccTrainObject
         n->gridtype, n->align_corners, n->interp, n->table_dtype, 0, n->offsets_host, n->grid_workspace, n->grid_workspace_bytes, stream);
 }
 
-int foc_occ_train_forward(const FocOccTrainNode *n, void *stream) { return occ_train_forward(n, 0.0f, false, stream); }
-int foc_occ_train_backward(const FocOccTrainNode *n, void *stream) { return occ_train_backward(n, 0.0f, false, stream); }
-int foc_occ_train_forward_pad31(const FocOccTrainNode *n, float input_pad, void *stream) { return occ_train_forward(n, input_pad, true, stream); }
-int foc_occ_train_backward_pad31(const FocOccTrainNode *n, float input_pad, void *stream) { return occ_train_backward(n, input_pad, true, stream); }
+int foc_occ_train_forward(const FocOccTrainNode *n, void *stream) {
+    const int rc = ot_check_node(n, "occ_train_forward");
+    return rc != FOC_OK ? rc : occ_train_forward(n, nullptr, 0.0f, false, nullptr, stream);
+}
+
+int foc_occ_train_backward(const FocOccTrainNode *n, void *stream) {
+    const int rc = ot_check_node(n, "occ_train_backward");
+    return rc != FOC_OK ? rc : occ_train_backward(n, nullptr, 0.0f, false, nullptr, nullptr, stream);
+}
+
+// column 31 of the 32-wide colour input holds input_pad (the legacy tinycudann layout)
+int foc_occ_train_forward_pad31(const FocOccTrainNode *n, float input_pad, void *stream) {
+    int rc = ot_check_node(n, "occ_train_forward_pad31");
+    if (rc == FOC_OK) rc = ot_check_pad31(n, input_pad, "occ_train_forward_pad31");
+    return rc != FOC_OK ? rc : occ_train_forward(n, nullptr, input_pad, true, nullptr, stream);
+}
+
+int foc_occ_train_backward_pad31(const FocOccTrainNode *n, float input_pad, void *stream) {
+    int rc = ot_check_node(n, "occ_train_backward_pad31");
+    if (rc == FOC_OK) rc = ot_check_pad31(n, input_pad, "occ_train_backward_pad31");
+    return rc != FOC_OK ? rc : occ_train_backward(n, nullptr, input_pad, true, nullptr, nullptr, stream);
+}
+
+// the 48-wide colour head of an object-conditioned network: the feature, its pad (column 47) and the sums of sigma^2 travel in `ob`
+int foc_occ_train_forward_obj(const FocOccTrainNode *n, const FocOccTrainObject *ob, void *stream) {
+    const int rc = ot_check_object(n, ob, "occ_train_forward_obj");
+    return rc != FOC_OK ? rc : occ_train_forward(n, ob->obj_feat, ob->input_pad, false, ob->ray_sumsq, stream);
+}
+
+int foc_occ_train_backward_obj(const FocOccTrainNode *n, const FocOccTrainObject *ob, void *stream) {
+    const int rc = ot_check_object(n, ob, "occ_train_backward_obj");
+    if (rc != FOC_OK) return rc;
+    FOC_REQUIRE(n->mlp_workspace_bytes >= foc_ffmlp_backward_workspace_bytes(48, 64, n->color_layers), FOC_E_INVALID,
+                "occ_train_backward_obj: MLP workspace of %llu bytes, the 48-wide colour head asks for foc_ffmlp_backward_workspace_bytes(48, 64, %u) = %llu",
+                (unsigned long long)n->mlp_workspace_bytes, n->color_layers, (unsigned long long)foc_ffmlp_backward_workspace_bytes(48, 64, n->color_layers));
+    return occ_train_backward(n, ob->obj_feat, ob->input_pad, false, ob->grad_sumsq, ob->grad_obj, stream);
+}
 
 } // extern "C"

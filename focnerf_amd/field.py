@@ -73,7 +73,7 @@ class FieldPlan:
     colour_input_pad: float = 0.0       # the colour input's last column: 47 of the 48-wide object-conditioned row (1.0: tinycudann layout,
                                         # network_tcnn.py), 31 of the 32-wide row (1.0: legacy tinycudann layout, network_tcnn_legacy.py)
     background: bool = False            # the background model (encoder_bg -> bg_net) as one kernel each way (background.py, csrc/background.hip)
-    occ_object: bool = False            # `occ` for an object-conditioned network: the node with the encoded object feature (occtrain._occ_train_obj)
+    occ_object: bool = False            # `occ` for an object-conditioned network: the node with the encoded object feature (occtrain._occ_train with the feature)
     native_loop_object: bool = False    # `native_loop` for an object-conditioned network: the step takes the feature (and the column-47 pad twin)
 
 
@@ -85,6 +85,16 @@ def pad_twin(name, pad, obj):
     if pad == 0:
         return getattr(lib, name), ()
     return getattr(lib, name + ("_pad" if obj else "_pad31")), (float(pad),)
+
+
+def object_feature_half(obj_feat, who):
+    """The ENCODED object feature as the kernels read it: a detached, contiguous fp16 [16] (None for None: a network without one)."""
+    if obj_feat is None:
+        return None
+    obj16 = obj_feat.detach().reshape(-1).half().contiguous()
+    if obj16.numel() != 16:
+        raise RuntimeError(f"{who}: the encoded object feature has {obj16.numel()} elements, the colour head takes 16")
+    return obj16
 
 
 def _on(switch):
@@ -268,7 +278,7 @@ class _hashgrid_mlp(Function):
             cweights, cshape, ray_sh, T, c_width, obj_feat = colour[:6]
             pad = float(colour[6]) if len(colour) > 6 else 0.0
             wc = _half_of(cweights)
-            obj16 = obj_feat.detach().reshape(-1).half().contiguous() if obj_feat is not None else None
+            obj16 = object_feature_half(obj_feat, "hashgrid_mlp colour branch")
             c = torch.empty(B, c_width, device=x.device, dtype=torch.half)
             args = (ptr(enc), ptr(w), sigma.num_layers, ptr(ray_sh), int(T), ptr(wc), int(cshape.num_layers), 64, int(sigma.activation), B, ptr(h),
                     ptr(c), int(c_width), ptr(obj16))
@@ -325,8 +335,7 @@ def field_infer(model, xn, dirs, dir_div=1, dir_block=0, obj_feat=None):
     if getattr(model, "uses_object_feature", False):
         if obj_feat is None:
             raise RuntimeError("field_infer: an object-conditioned network needs its encoded object feature")
-        obj16 = obj_feat.detach().reshape(-1).half().contiguous()
-        assert obj16.numel() == 16
+        obj16 = object_feature_half(obj_feat, "field_infer")
     args = (ptr(planes), 1, ptr(dirs), int(dir_div), int(dir_block), dirs.shape[0], ptr(ws), sn.num_layers, ptr(wc), cn.num_layers, 64, sn.activation, M,
             ptr(sigma), ptr(rgb), ptr(obj16))
     # the tinycudann layouts (network_tcnn.py, network_tcnn_legacy.py): the last column of the colour input is a constant

@@ -63,6 +63,7 @@ class _density_head(Function):
     @staticmethod
     def forward(ctx, h, rays_d, nears, fars, noise, N, T, density_scale, obj_feat=None):
         """obj_feat: None -> cin [M,32]; [16] half (FOC network's encoded object feature) -> cin [M,48]."""
+        from .field import object_feature_half
         h = h.contiguous()
         assert h.dtype == torch.float16 and h.shape == (N * T, 16)
         dev = h.device
@@ -73,9 +74,7 @@ class _density_head(Function):
         ws = torch.empty(N, dtype=torch.float32, device=dev)
         depth = torch.empty(N, dtype=torch.float32, device=dev)
         width = 32 if obj_feat is None else 48
-        if obj_feat is not None:
-            obj_feat = obj_feat.detach().reshape(-1).half().contiguous()
-            assert obj_feat.numel() == 16
+        obj_feat = object_feature_half(obj_feat, "_density_head")
         cin = torch.empty(M, width, dtype=torch.float16, device=dev)
         check(lib.foc_fixed_head_forward(ptr(h), ptr(rays_d), ptr(nears), ptr(fars), ptr(noise), N, T, float(density_scale), ptr(sigma), ptr(trans),
                                          ptr(weights), ptr(ws), ptr(depth), ptr(cin), ptr(obj_feat), width, stream_of(h)), "fixed_head_forward")
@@ -166,7 +165,7 @@ class _render_tail(Function):
                 want_sumsq=False, c_pre=None, w16_pre=None, input_pad=0.0):
         # c_pre [M,4] half: the colour logits already computed from this h, these weights and this ray_sh by the encoder -> sigma node's fused
         # forward (field._hashgrid_mlp with `colour`, foc_field_forward_train: the bits foc_color_head_forward would give) — then no launch here
-        from .field import _half_of, pad_twin
+        from .field import _half_of, pad_twin, object_feature_half
         h = h.contiguous()
         assert h.dtype == torch.float16 and h.shape == (N * T, 16)
         assert ray_sh.dtype == torch.float16 and ray_sh.shape == (N, 16) and ray_sh.is_contiguous()
@@ -174,10 +173,8 @@ class _render_tail(Function):
         st = stream_of(h)
         w16 = w16_pre if w16_pre is not None else _half_of(cweights)     # w16_pre: the half copy the fused forward already made of THESE weights
         # of the colour network's 16 padded outputs only the rgb logits are ever read: they travel as [M,4] rows (as does their gradient)
-        obj16 = None
-        if obj_feat is not None:
-            obj16 = obj_feat.detach().reshape(-1).half().contiguous()
-            assert obj16.numel() == 16 and w16.numel() == 64 * (48 + 64 * (int(num_layers) - 1) + 16)
+        obj16 = object_feature_half(obj_feat, "_render_tail")
+        assert obj16 is None or w16.numel() == 64 * (48 + 64 * (int(num_layers) - 1) + 16)
         if c_pre is not None:
             assert c_pre.dtype == torch.float16 and c_pre.shape == (M, _C_WIDTH) and c_pre.is_contiguous()
             c = c_pre

@@ -246,31 +246,21 @@ class NeRFRenderer(nn.Module):
         else:
             extra = ()
         if self.training:
-            from .occtrain import render_occupancy_train
-            if obj16 is not None and o.is_cuda and torch.is_grad_enabled() and torch.is_autocast_enabled() and plan.occ_object:
-                # the object-conditioned node (occtrain._occ_train_obj): the feature goes in as a tensor and gets its gradient back
-                from .occtrain import render_occupancy_train_object
+            if o.is_cuda and torch.is_grad_enabled() and torch.is_autocast_enabled() and (plan.occ_object if obj16 is not None else plan.occ):
+                # the whole training forward as one autograd node (focnerf_amd/occtrain.py): same samples, same image; the box test of
+                # near_far_from_aabb rides in the march's count pass. An object-conditioned network's feature goes in as a tensor and gets
+                # its gradient back
+                from .occtrain import render_occupancy_train
                 from .fixedstep import _masked_norm
                 slot = self.step_counter[self.local_step % 16]
                 slot.zero_()
                 self.local_step += 1
-                image, opacity, depth, sumsq = render_occupancy_train_object(self, plan, o.float(), d.float(), slot, bg_color, perturb, force_all_rays, dt_gamma,
-                                                                             max_steps, T_thresh, _MARCH_ALIGN, obj16, outside is not None)
-                if outside is not None:
-                    out['criterion_outside_mask'] = _masked_norm.apply(sumsq, outside.to(torch.float32))
-                out['weights_sum'] = opacity
-                out['image'], out['depth'] = image.view(*lead, 3), depth.view(*lead)
-                return out
-            if obj16 is None and o.is_cuda and torch.is_grad_enabled() and torch.is_autocast_enabled() and plan.occ:
-                # the whole training forward as one autograd node (focnerf_amd/occtrain.py): same samples, same image; the box test of
-                # near_far_from_aabb rides in the march's count pass
-                slot = self.step_counter[self.local_step % 16]
-                slot.zero_()
-                self.local_step += 1
-                if self.bg_radius > 0:                            # the background model (plan.occ: network_linear.py, plan.background)
+                if obj16 is None and self.bg_radius > 0:          # the background model (plan.occ: network_linear.py, plan.background)
                     bg_color = self._background_colour(o, d, bg_color)
-                image, opacity, depth = render_occupancy_train(self, plan, o.float(), d.float(), slot, bg_color, perturb, force_all_rays, dt_gamma, max_steps, T_thresh,
-                                                               _MARCH_ALIGN)
+                image, opacity, depth, sumsq = render_occupancy_train(self, plan, o.float(), d.float(), slot, bg_color, perturb, force_all_rays, dt_gamma, max_steps,
+                                                                      T_thresh, _MARCH_ALIGN, obj16, outside is not None)
+                if sumsq is not None:
+                    out['criterion_outside_mask'] = _masked_norm.apply(sumsq, outside.to(torch.float32))
                 out['weights_sum'] = opacity
                 out['image'], out['depth'] = image.view(*lead, 3), depth.view(*lead)
                 return out
@@ -359,7 +349,7 @@ class NeRFRenderer(nn.Module):
         single advance more than doubles t while fewer than half of the rays are alive.
         obj16: the encoded object feature of an object-conditioned network (plan.native_loop_object), handed to every step."""
         from ._lib import lib, ptr, stream_of, check
-        from .field import _half_of, half_cache_scope, pad_twin, fused_mlp
+        from .field import _half_of, half_cache_scope, pad_twin, fused_mlp, object_feature_half
         n, dev = o.shape[0], o.device
         enc, sn, cn = self.encoder, fused_mlp(self, "sigma_net"), fused_mlp(self, "color_net")
         L = plan.levels
@@ -399,7 +389,7 @@ class NeRFRenderer(nn.Module):
         # a constant last column of the colour input (network_tcnn_legacy.py: column 31 = 1.0; network_tcnn.py: column 47 = 1.0): the step's
         # twin, the pad before the stream
         render_step, pad_args = pad_twin("foc_occ_render_step", plan.colour_input_pad, plan.uses_object_feature)
-        obj_h = obj16.detach().reshape(-1).half().contiguous() if obj16 is not None else None
+        obj_h = object_feature_half(obj16, "native inference loop")
         with half_cache_scope():
             emb, ws, wc = _half_of(enc.embeddings), _half_of(sn.weights), _half_of(cn.weights)
             st = stream_of(o)

@@ -2,7 +2,7 @@
 
   1. the feature is used: two object features give two images (training and eval), the object encoder gets gradients, the criterion is there;
   2. the op chain (FOC_FUSED_OCC=0) is march_rays_train -> net(x, d, (None, None, obj16)) -> composite_rays_train, bit for bit;
-  3. the node (occtrain._occ_train_obj) against that chain, on the cases of tests/test_gpu_occtrain.py;
+  3. the node (occtrain._occ_train with the feature) against that chain, on the cases of tests/test_gpu_occtrain.py;
   4. the criterion kernels (foc_occ_tail_forward_sumsq / _backward_sumsq) against a float64 torch expression;
   5. the node as one library call against the call-by-call node, bit for bit;
   6. inference: the native loop against the Python loop, bit for bit;

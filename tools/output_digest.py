@@ -1,12 +1,23 @@
 #!/usr/bin/env python3
-"""tools/output_digest.py [out.json]: sha256 of every output of the per-sample, ragged-composite, fixed-step and combine kernels on seeded
-inputs, as one JSON object {case: {output: digest}} — the bits of one library build — printed, or written to out.json with a one-line
-summary printed instead. Run it once per build on the same GPU (FOCNERF_LIB_PATH selects the library) and compare the two objects:
-equal = the same bits on every case.
+"""tools/output_digest.py [out.json] [--sections a,b] [--root DIR]: sha256 of every output of the per-sample, ragged-composite, fixed-step
+and combine kernels on seeded inputs, and of the occupancy node driven from Python, as one JSON object {case: {output: digest}} — the bits
+of one build — printed, or written to out.json with a one-line summary printed instead. Run it once per build on the same GPU
+(FOCNERF_LIB_PATH selects the library) and compare the two objects: equal = the same bits on every case.
+--sections: of per_sample, ragged, fixed, combine, node (default: all). --root DIR: the checkout whose focnerf_amd package (and library)
+is imported instead of this one's — the `node` section runs the package's Python, so one copy of this tool serves both commits of a
+comparison.
 
 The cases are the smallest that reach every branch of those kernels: ray counts and step counts below, at and above one 64-lane step,
 with and without noise, scalar and per-ray background, density_scale 1 and 2, colour widths 4 and 16, a ray list with an empty ray, a
 ray that does not fit the list and spare rows behind the last ray, stops in the first step and in a later one.
+
+`node` (FOC_DETERMINISTIC on): a training step of `NeRFRenderer.run_cuda` on the five network kinds — plain, network_linear with its
+background model, network_tcnn_legacy (column 31 = 1), network_foc and network_tcnn (object feature, column 47 = 0 / 1) — through the
+one-call node and the call-by-call chain (FOC_OCC_NATIVE_NODE 1 / 0), at 1, 63, 64, 65 and 300 rays, max_steps 16 and 64, with default,
+scalar and per-ray backgrounds, the object networks with and without a ray mask, a list that overflows and an unbudgeted one; image, depth,
+weights_sum, the criterion (the masked norm of ray_sumsq), the marched counts and every parameter gradient. Then one evaluation view per
+kind through the native render loop. Run a build twice before comparing two builds: an output that differs between the two runs of one
+build (an fp32 atomic of torch's own backward) says nothing about the builds.
 
 Left out: the gradient of the background model's table (foc_background_backward: fp32 atomics, not bit-stable run to run in the default
 mode) and with it the whole background backward; the forward is covered. Every input is drawn on the host from a seeded generator.
@@ -19,7 +30,26 @@ import sys
 import numpy as np
 import torch
 
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+ARGS = sys.argv[1:]
+
+
+def _option(name):
+    """The value behind `name` in the argument list (removed from it), or None."""
+    if name not in ARGS:
+        return None
+    i = ARGS.index(name)
+    if i + 1 >= len(ARGS):
+        sys.exit(f"usage: output_digest.py [out.json] [--sections a,b] [--root DIR]: {name} needs a value")
+    value = ARGS[i + 1]
+    del ARGS[i: i + 2]
+    return value
+
+
+ROOT = _option("--root") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+ALL_SECTIONS = ("per_sample", "ragged", "fixed", "combine", "node")
+SECTIONS = (_option("--sections") or ",".join(ALL_SECTIONS)).split(",")
+if set(SECTIONS) - set(ALL_SECTIONS):
+    sys.exit(f"usage: output_digest.py [out.json] [--sections a,b] [--root DIR]: sections are {', '.join(ALL_SECTIONS)}, got {', '.join(SECTIONS)}")
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
@@ -31,9 +61,19 @@ OUT = {}
 NAN32 = float("nan")
 
 
+def digest(t):
+    t = t.detach().contiguous()
+    if t.numel() <= 1 << 20:
+        return hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()
+    # a table-sized tensor (the hash grid's gradient: almost all zero bits): the shape, and where the other bits are and what they are
+    bits = t.view(-1).view({2: torch.int16, 4: torch.int32}[t.element_size()])
+    at = bits.nonzero().view(-1)
+    return hashlib.sha256(repr(tuple(t.shape)).encode() + at.cpu().numpy().tobytes() + bits[at].cpu().numpy().tobytes()).hexdigest()
+
+
 def put(case, **tensors):
     torch.cuda.synchronize()
-    OUT[case] = {k: hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest() for k, t in tensors.items() if t is not None}
+    OUT[case] = {k: digest(t) for k, t in tensors.items() if t is not None}
 
 
 def cuda(a):
@@ -222,24 +262,120 @@ def combine(T):
     put(f"combine[N={N},T={T}]", **res)
 
 
+# ---------------------------------------------------------------- the occupancy node and the native render loop, from Python
+NODE_KINDS = ("plain", "linear_bg", "tcnn_legacy", "foc", "tcnn")
+MARCHED = []         # samples marched by each training step of the node section (the summary says which remainders they leave)
+
+
+def node_model(kind, bound=2):
+    from focnerf_amd import network, network_foc, network_linear, network_tcnn, network_tcnn_legacy, synthetic
+    torch.manual_seed(0)
+    if kind == "plain":
+        m = network.NeRFNetwork(bound=bound, cuda_ray=True).cuda()
+    elif kind == "linear_bg":
+        m = network_linear.NeRFNetwork(bound=bound, cuda_ray=True, density_scale=1, min_near=0.05, bg_radius=32.0).cuda()
+    elif kind == "tcnn_legacy":
+        m = network_tcnn_legacy.NeRFNetwork(bound=bound, cuda_ray=True, density_scale=1, min_near=0.05).cuda()
+    else:
+        m = {"foc": network_foc, "tcnn": network_tcnn}[kind].NeRFNetwork(bound=bound, cuda_ray=True).cuda()
+    with torch.no_grad():
+        m.encoder.embeddings.uniform_(-0.5, 0.5)
+        if kind == "linear_bg":
+            m.encoder_bg.embeddings.uniform_(-1.0, 1.0)
+            for layer in list(m.sigma_net) + list(m.color_net):
+                layer.weight.mul_(3.0)
+    m.set_density_grid(synthetic.analytic_density_grid(bound, device="cuda"))
+    return m
+
+
+def node_rays(bound, n, seed, w=64):
+    from focnerf_amd import synthetic
+    o, d = synthetic.make_view_rays(w, w, bound, 1, seed=seed, device="cuda")
+    pick = torch.randperm(o.shape[1], generator=torch.Generator().manual_seed(seed))[:n].cuda()
+    return o[:, pick].contiguous(), d[:, pick].contiguous()
+
+
+def node_step(case, m, o, d, yolo, **kw):
+    """One training step of `m.render` (the jitter seeded) -> the digests of its outputs and of every parameter gradient."""
+    m.train()
+    m.zero_grad(set_to_none=True)
+    torch.manual_seed(7)
+    with torch.autocast("cuda", dtype=torch.float16):
+        out = m.render(o, d, yolo, staged=False, dt_gamma=1 / 128, perturb=True, **kw)
+        loss = torch.nn.functional.mse_loss(out["image"], 0.5 + 0.5 * torch.sin(3.0 * d)) + 1e-3 * out["weights_sum"].mean()
+        crit = out.get("criterion_outside_mask")
+        if crit is not None:
+            loss = loss + 1e-3 * crit
+    (loss * 4096.0).backward()
+    grads = {"grad." + name: p.grad for name, p in m.named_parameters() if p.grad is not None}
+    marched = m.step_counter[(m.local_step - 1) % 16]
+    put(case, image=out["image"], depth=out["depth"], weights_sum=out["weights_sum"], criterion_outside_mask=crit, marched=marched, **grads)
+    MARCHED.append(int(marched[0]))
+
+
+def node():
+    from focnerf_amd import deterministic
+    bound = 2
+    backgrounds = {1: None, 63: 0.25, 64: "ray", 65: None, 300: "ray"}
+    with deterministic():
+        for kind in NODE_KINDS:
+            m = node_model(kind, bound)
+            with_object = kind in ("foc", "tcnn")
+            for n, bg in backgrounds.items():
+                o, d = node_rays(bound, n, 3 + n)
+                g = torch.Generator().manual_seed(n)
+                bg_color = torch.rand(n, 3, generator=g).cuda() if bg == "ray" else bg
+                feature = torch.randn(144, generator=g).cuda()
+                masks = ((torch.rand(1, n, generator=g) < 0.5).cuda(), None) if with_object else (None,)
+                for mask in masks:
+                    yolo = (mask, None, feature) if with_object else None
+                    for max_steps in (16, 64):
+                        # the budgeted list (mean_count > 0) is what the one-call node takes: room for every sample; at 300 rays also a
+                        # list that drops the last rays, and the unbudgeted list (cut to the samples marched) through the chain
+                        lists = [("room", n * max_steps, False)] + ([("overflow", 2 * max_steps, False), ("all_rays", -1, True)] if n == 300 else [])
+                        for name, mean_count, force_all_rays in lists:
+                            for native in ("1", "0"):
+                                os.environ["FOC_OCC_NATIVE_NODE"] = native
+                                m.mean_count = mean_count
+                                node_step(f"node[{kind},n={n},max_steps={max_steps},bg={bg},mask={mask is not None},list={name},native={native}]", m, o, d, yolo,
+                                          max_steps=max_steps, bg_color=bg_color, force_all_rays=force_all_rays)
+            os.environ.pop("FOC_OCC_NATIVE_NODE", None)
+            # one evaluation view through the native render loop
+            m.eval()
+            o, d = node_rays(bound, 32 * 32, 5, w=32)
+            yolo = (None, None, torch.randn(144, generator=torch.Generator().manual_seed(5)).cuda()) if with_object else None
+            with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16):
+                out = m.render(o, d, yolo, staged=False, dt_gamma=1 / 128, max_steps=64, perturb=False, bg_color=1.0)
+            put(f"render_loop[{kind}]", image=out["image"], depth=out["depth"])
+            del m
+
+
 def main():
-    per_sample()
-    ragged()
-    for N in (1, 5, 130):
+    if "per_sample" in SECTIONS:
+        per_sample()
+    if "ragged" in SECTIONS:
+        ragged()
+    for N in (1, 5, 130) if "fixed" in SECTIONS else ():
         for T in (2, 65, 130):
             for noisy in (False, True):
                 for per_ray_bg in (False, True):
                     for ds in (1.0, 2.0):
                         fixed(N, T, noisy, per_ray_bg, ds)
-    for T in (2, 65, 130):
+    for T in (2, 65, 130) if "combine" in SECTIONS else ():
         combine(T)
+    if "node" in SECTIONS:
+        node()
     text = json.dumps(OUT, indent=0, sort_keys=True)
-    if len(sys.argv) < 2:
+    if not ARGS:
         print(text)
         return
-    with open(sys.argv[1], "w") as f:
+    with open(ARGS[0], "w") as f:
         f.write(text + "\n")
-    print(json.dumps({"cases": len(OUT), "outputs": sum(len(v) for v in OUT.values()), "sha256": hashlib.sha256(text.encode()).hexdigest()}))
+    summary = {"cases": len(OUT), "outputs": sum(len(v) for v in OUT.values()), "sha256": hashlib.sha256(text.encode()).hexdigest()}
+    if MARCHED:
+        summary["node_marched"] = {"min": min(MARCHED), "max": max(MARCHED), "not_multiple_of_8": sum(c % 8 != 0 for c in MARCHED),
+                                   "multiple_of_32": sum(c % 32 == 0 for c in MARCHED)}
+    print(json.dumps(summary))
 
 
 if __name__ == "__main__":
