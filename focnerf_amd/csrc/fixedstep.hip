@@ -197,18 +197,22 @@ __global__ void __launch_bounds__(256) k_fs_composite_bwd(const float *__restric
 // ---------------------------------------------------------------- training tail: density head + composite in one pass per direction
 // What k_fs_head_fwd (without the colour-net input) and k_fs_composite_fwd compute, one wave per ray, through the same fs_sample /
 // fs_trans_scan / foc_sigmoid_h and with the same per-lane accumulation order, so the results are the same bits; the weights are not re-read. c [M,16] fp16 = colour-net output.
-template <bool NOISE>
+// DIST (foc_fixed_tail_forward_dist): also ray_dist [N] = the ray's distortion and ray_wm [N] = sum w m (fs_common.h fs_dist_fwd_step), both 0 on
+// a ray with !(far > near); every other output is the bits of the plain instantiation.
+template <bool NOISE, bool DIST>
 __global__ void __launch_bounds__(256) k_fs_tail_fwd(const _Float16 *__restrict__ h, const _Float16 *__restrict__ c, const float *__restrict__ nears,
                                                      const float *__restrict__ fars, const float *__restrict__ noise, const float *__restrict__ bg_ray,
                                                      float bg_scalar, uint32_t N, uint32_t T, float density_scale, float thresh,
                                                      float *__restrict__ sigma_out, float *__restrict__ trans_out, float *__restrict__ weights_out,
                                                      float *__restrict__ weights_sum, float *__restrict__ depth, float *__restrict__ image, uint32_t c_ld,
-                                                     float *__restrict__ ray_sumsq) {
+                                                     float *__restrict__ ray_sumsq, float *__restrict__ ray_dist, float *__restrict__ ray_wm) {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t n = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (n >= N) return;
     const FsGeom g = fs_geom(nears, fars, n, T);
     float Tc = 1.0f, ws = 0, dp = 0, r = 0, gg = 0, b = 0, sq = 0;
+    FsDist dist = {0, 0, 0};
+    const bool live = g.far > g.near;                      // wave-uniform; a ray that misses the box has no distortion (its m may be non-finite)
     for (uint32_t base = 0; base < T; base += 64) {
         const uint32_t i = base + lane;
         const bool valid = i < T;
@@ -224,6 +228,9 @@ __global__ void __launch_bounds__(256) k_fs_tail_fwd(const _Float16 *__restrict_
         const float om = valid ? (1 - alpha + 1e-15f) : 1.0f;
         const float Tb = fs_trans_scan(om, lane, Tc);
         const float w = alpha * Tb;
+        if constexpr (DIST) {
+            if (live) fs_dist_fwd_step(dist, w, fs_dist_m(g, p), p.delta, lane);
+        }
         if (valid) {
             sigma_out[s] = sigma; trans_out[s] = Tb; weights_out[s] = w;
             ws += w; dp += w * p.oz; sq = fmaf(sigma, sigma, sq);
@@ -238,6 +245,10 @@ __global__ void __launch_bounds__(256) k_fs_tail_fwd(const _Float16 *__restrict_
         sq = wave_sum(sq);
         if (lane == 0) ray_sumsq[n] = sq;
     }
+    if constexpr (DIST) {
+        const float ds = wave_sum(dist.acc);
+        if (lane == 0) { ray_dist[n] = ds; ray_wm[n] = dist.WM; }
+    }
     if (lane == 0) {
         const FocBg bg = foc_bg(bg_ray, bg_scalar, n);
         image[n * 3] = r + (1 - ws) * bg.b0; image[n * 3 + 1] = gg + (1 - ws) * bg.b1; image[n * 3 + 2] = b + (1 - ws) * bg.b2;
@@ -249,19 +260,28 @@ __global__ void __launch_bounds__(256) k_fs_tail_fwd(const _Float16 *__restrict_
 // -> grad_c [M,16] fp16 and grad_h0 [M] fp16, through the two steps those kernels are written in (fs_composite_bwd_sample,
 // fs_head_bwd_step). The gradient of the weights never leaves the lane. trunc_exp's backward factor is taken from sigma
 // (foc_trunc_exp_bwd_of_sigma), so h is not read.
-template <bool NOISE>
+// DIST (foc_fixed_tail_backward_dist): grad_dist [N] is the gradient of the forward's ray_dist; grad_dist[ray] G_i (fs_dist_bwd_step) joins the
+// gradient of the lane's weight. W_total = weights_sum, WM_total = ray_wm of the forward. A ray with !(far > near) or grad_dist == 0 adds nothing.
+template <bool NOISE, bool DIST>
 __global__ void __launch_bounds__(256) k_fs_tail_bwd(const float *__restrict__ grad_image, const float *__restrict__ grad_ws, const float *__restrict__ grad_depth,
                                                      const _Float16 *__restrict__ c, const float *__restrict__ sigma_in, const float *__restrict__ trans_in,
                                                      const float *__restrict__ weights, const float *__restrict__ nears, const float *__restrict__ fars,
                                                      const float *__restrict__ noise, const float *__restrict__ bg_ray, float bg_scalar, uint32_t N, uint32_t T,
                                                      float density_scale, float thresh, _Float16 *__restrict__ grad_c, _Float16 *__restrict__ grad_h0, uint32_t c_ld,
-                                                     const float *__restrict__ grad_sumsq) {
+                                                     const float *__restrict__ grad_sumsq, const float *__restrict__ weights_sum,
+                                                     const float *__restrict__ ray_wm, const float *__restrict__ grad_dist) {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t n = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (n >= N) return;
     const FsGeom g = fs_geom(nears, fars, n, T);
     const float gws = grad_ws ? grad_ws[n] : 0.0f, gdp = grad_depth ? grad_depth[n] : 0.0f;
     const float gsq2 = grad_sumsq ? 2.0f * grad_sumsq[n] : 0.0f;      // d(sum sigma^2)/d sigma = 2 sigma
+    float gdist = 0.0f, W_total = 0.0f, WM_total = 0.0f;
+    FsDist dist = {0, 0, 0};
+    if constexpr (DIST) {
+        if (g.far > g.near) gdist = grad_dist[n];          // wave-uniform
+        W_total = weights_sum[n]; WM_total = ray_wm[n];
+    }
     const FsRayGrad q = fs_ray_grad(grad_image, bg_ray, bg_scalar, n);
     const FocExp15 e15 = foc_exp15();
     float S_carry = 0.0f;
@@ -285,7 +305,11 @@ __global__ void __launch_bounds__(256) k_fs_tail_bwd(const float *__restrict__ g
         }
         // ---- density head backward (k_fs_head_bwd)
         const FsSample p = fs_sample(g, i, ic, T, NOISE, u0, u1);
-        float dsigma = fs_head_bwd_step(p, valid, sigma, Tb, gw + gws, gdp, density_scale, lane, S_carry);
+        float gi = gw + gws;
+        if constexpr (DIST) {
+            if (gdist != 0.0f) gi = fmaf(gdist, fs_dist_bwd_step(dist, valid ? w : 0.0f, fs_dist_m(g, p), p.delta, W_total, WM_total, lane), gi);
+        }
+        float dsigma = fs_head_bwd_step(p, valid, sigma, Tb, gi, gdp, density_scale, lane, S_carry);
         if (gsq2 != 0.0f) dsigma = fmaf(gsq2, sigma, dsigma);          // the outside-mask density criterion's share (nerf/renderer.py:163-165)
         const float dh0 = dsigma * foc_trunc_exp_bwd_of_sigma(sigma, e15);
         if (valid) grad_h0[s] = foc_f2h(dh0);
@@ -499,18 +523,52 @@ int foc_fixed_composite_backward(const float *grad_image, const void *c, const f
     return FOC_OK;
 }
 
+// ray_dist / ray_wm NULL: the plain kernels (foc_fixed_tail_forward); `who` names the entry point in messages
+static int fixed_tail_forward(const char *who, const void *h, const void *c, const float *nears, const float *fars, const float *noise, const float *bg_ray,
+                              float bg_scalar, uint32_t N, uint32_t T, float density_scale, float thresh, float *sigma, float *trans, float *weights,
+                              float *weights_sum, float *depth, float *image, uint32_t c_width, float *ray_sumsq, float *ray_dist, float *ray_wm, void *stream) {
+    FocDeviceGuard foc_guard_(stream, h);
+    if (N == 0) return FOC_OK;
+    FOC_REQUIRE(c_width == 16 || c_width == 4, FOC_E_INVALID, "%s: c_width must be 16 or 4 (got %u)", who, c_width);
+    FOC_REQUIRE(h && c && nears && fars && sigma && trans && weights && weights_sum && depth && image, FOC_E_INVALID, "%s: null pointer", who);
+    FOC_REQUIRE(T >= 2, FOC_E_INVALID, "%s: T must be >= 2", who);
+    auto kern = ray_dist ? (noise ? k_fs_tail_fwd<true, true> : k_fs_tail_fwd<false, true>) : (noise ? k_fs_tail_fwd<true, false> : k_fs_tail_fwd<false, false>);
+    hipLaunchKernelGGL(kern, dim3(foc_div_up(N, 4)), dim3(256), 0, (hipStream_t)stream, (const _Float16 *)h, (const _Float16 *)c, nears, fars, noise,
+                       bg_ray, bg_scalar, N, T, density_scale, thresh, sigma, trans, weights, weights_sum, depth, image, c_width, ray_sumsq, ray_dist, ray_wm);
+    FOC_CHECK_LAUNCH(who);
+    return FOC_OK;
+}
+
 int foc_fixed_tail_forward(const void *h, const void *c, const float *nears, const float *fars, const float *noise, const float *bg_ray, float bg_scalar,
                            uint32_t N, uint32_t T, float density_scale, float thresh, float *sigma, float *trans, float *weights, float *weights_sum,
                            float *depth, float *image, uint32_t c_width, float *ray_sumsq, void *stream) {
-    FocDeviceGuard foc_guard_(stream, h);
+    return fixed_tail_forward("fixed_tail_forward", h, c, nears, fars, noise, bg_ray, bg_scalar, N, T, density_scale, thresh, sigma, trans, weights, weights_sum,
+                              depth, image, c_width, ray_sumsq, nullptr, nullptr, stream);
+}
+
+int foc_fixed_tail_forward_dist(const void *h, const void *c, const float *nears, const float *fars, const float *noise, const float *bg_ray, float bg_scalar,
+                                uint32_t N, uint32_t T, float density_scale, float thresh, float *sigma, float *trans, float *weights, float *weights_sum,
+                                float *depth, float *image, uint32_t c_width, float *ray_sumsq, float *ray_dist, float *ray_wm, void *stream) {
+    FOC_REQUIRE((ray_dist && ray_wm) || N == 0, FOC_E_INVALID, "fixed_tail_forward_dist: null ray_dist / ray_wm");
+    return fixed_tail_forward("fixed_tail_forward_dist", h, c, nears, fars, noise, bg_ray, bg_scalar, N, T, density_scale, thresh, sigma, trans, weights,
+                              weights_sum, depth, image, c_width, ray_sumsq, ray_dist, ray_wm, stream);
+}
+
+// grad_dist NULL: the plain kernels (foc_fixed_tail_backward)
+static int fixed_tail_backward(const char *who, const float *grad_image, const float *grad_ws, const float *grad_depth, const void *c, const float *sigma,
+                               const float *trans, const float *weights, const float *nears, const float *fars, const float *noise, const float *bg_ray,
+                               float bg_scalar, uint32_t N, uint32_t T, float density_scale, float thresh, void *grad_c, void *grad_h0, uint32_t c_width,
+                               const float *grad_sumsq, const float *weights_sum, const float *ray_wm, const float *grad_dist, void *stream) {
+    FocDeviceGuard foc_guard_(stream, grad_image);
     if (N == 0) return FOC_OK;
-    FOC_REQUIRE(c_width == 16 || c_width == 4, FOC_E_INVALID, "fixed_tail_forward: c_width must be 16 or 4 (got %u)", c_width);
-    FOC_REQUIRE(h && c && nears && fars && sigma && trans && weights && weights_sum && depth && image, FOC_E_INVALID, "fixed_tail_forward: null pointer");
-    FOC_REQUIRE(T >= 2, FOC_E_INVALID, "fixed_tail_forward: T must be >= 2");
-    auto kern = noise ? k_fs_tail_fwd<true> : k_fs_tail_fwd<false>;
-    hipLaunchKernelGGL(kern, dim3(foc_div_up(N, 4)), dim3(256), 0, (hipStream_t)stream, (const _Float16 *)h, (const _Float16 *)c, nears, fars, noise,
-                       bg_ray, bg_scalar, N, T, density_scale, thresh, sigma, trans, weights, weights_sum, depth, image, c_width, ray_sumsq);
-    FOC_CHECK_LAUNCH("fixed_tail_forward");
+    FOC_REQUIRE(c_width == 16 || c_width == 4, FOC_E_INVALID, "%s: c_width must be 16 or 4 (got %u)", who, c_width);
+    FOC_REQUIRE(grad_image && c && sigma && trans && weights && nears && fars && grad_c && grad_h0, FOC_E_INVALID, "%s: null pointer", who);
+    FOC_REQUIRE(T >= 2, FOC_E_INVALID, "%s: T must be >= 2", who);
+    auto kern = grad_dist ? (noise ? k_fs_tail_bwd<true, true> : k_fs_tail_bwd<false, true>) : (noise ? k_fs_tail_bwd<true, false> : k_fs_tail_bwd<false, false>);
+    hipLaunchKernelGGL(kern, dim3(foc_div_up(N, 4)), dim3(256), 0, (hipStream_t)stream, grad_image, grad_ws, grad_depth, (const _Float16 *)c, sigma,
+                       trans, weights, nears, fars, noise, bg_ray, bg_scalar, N, T, density_scale, thresh, (_Float16 *)grad_c, (_Float16 *)grad_h0, c_width,
+                       grad_sumsq, weights_sum, ray_wm, grad_dist);
+    FOC_CHECK_LAUNCH(who);
     return FOC_OK;
 }
 
@@ -518,17 +576,18 @@ int foc_fixed_tail_backward(const float *grad_image, const float *grad_ws, const
                             const float *weights, const float *nears, const float *fars, const float *noise, const float *bg_ray, float bg_scalar,
                             uint32_t N, uint32_t T, float density_scale, float thresh, void *grad_c, void *grad_h0, uint32_t c_width, const float *grad_sumsq,
                             void *stream) {
-    FocDeviceGuard foc_guard_(stream, grad_image);
-    if (N == 0) return FOC_OK;
-    FOC_REQUIRE(c_width == 16 || c_width == 4, FOC_E_INVALID, "fixed_tail_backward: c_width must be 16 or 4 (got %u)", c_width);
-    FOC_REQUIRE(grad_image && c && sigma && trans && weights && nears && fars && grad_c && grad_h0, FOC_E_INVALID, "fixed_tail_backward: null pointer");
-    FOC_REQUIRE(T >= 2, FOC_E_INVALID, "fixed_tail_backward: T must be >= 2");
-    auto kern = noise ? k_fs_tail_bwd<true> : k_fs_tail_bwd<false>;
-    hipLaunchKernelGGL(kern, dim3(foc_div_up(N, 4)), dim3(256), 0, (hipStream_t)stream, grad_image, grad_ws, grad_depth, (const _Float16 *)c, sigma,
-                       trans, weights, nears, fars, noise, bg_ray, bg_scalar, N, T, density_scale, thresh, (_Float16 *)grad_c, (_Float16 *)grad_h0, c_width,
-                       grad_sumsq);
-    FOC_CHECK_LAUNCH("fixed_tail_backward");
-    return FOC_OK;
+    return fixed_tail_backward("fixed_tail_backward", grad_image, grad_ws, grad_depth, c, sigma, trans, weights, nears, fars, noise, bg_ray, bg_scalar, N, T,
+                               density_scale, thresh, grad_c, grad_h0, c_width, grad_sumsq, nullptr, nullptr, nullptr, stream);
+}
+
+int foc_fixed_tail_backward_dist(const float *grad_image, const float *grad_ws, const float *grad_depth, const void *c, const float *sigma, const float *trans,
+                                 const float *weights, const float *weights_sum, const float *nears, const float *fars, const float *noise, const float *bg_ray,
+                                 float bg_scalar, uint32_t N, uint32_t T, float density_scale, float thresh, void *grad_c, void *grad_h0, uint32_t c_width,
+                                 const float *grad_sumsq, const float *ray_wm, const float *ray_dist, const float *grad_dist, void *stream) {
+    (void)ray_dist;                                         // the fixed-step backward walks from the ray's end and needs no total of G w
+    FOC_REQUIRE(!grad_dist || (weights_sum && ray_wm) || N == 0, FOC_E_INVALID, "fixed_tail_backward_dist: grad_dist needs weights_sum and ray_wm");
+    return fixed_tail_backward("fixed_tail_backward_dist", grad_image, grad_ws, grad_depth, c, sigma, trans, weights, nears, fars, noise, bg_ray, bg_scalar, N,
+                               T, density_scale, thresh, grad_c, grad_h0, c_width, grad_sumsq, weights_sum, ray_wm, grad_dist, stream);
 }
 
 int foc_fixed_render_inference(const float *sigma, const float *rgb, const float *nears, const float *fars, const float *noise, const float *bg_ray,

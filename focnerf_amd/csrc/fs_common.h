@@ -99,6 +99,35 @@ __device__ __forceinline__ float fs_head_bwd_step(const FsSample &p, bool valid,
     return dalpha * (p.delta * density_scale) * ex;
 }
 
+// ---------------------------------------------------------------- ray distortion (include/focnerf.h foc_fixed_tail_forward_dist)
+// dist = sum_i (1/3) delta_i w_i^2 + 2 sum_i w_i (m_i W_<i - WM_<i), W_<i = sum_{j<i} w_j, WM_<i = sum_{j<i} w_j m_j: the interval midpoint
+// m_i = (z_i - near) + delta_i / 2 and the interval delta_i of the FsSample, the raw weight. One 64-sample step: the two running sums by
+// wave scan (W, WM = their values in front of the step, moved behind it), the lane's own terms added to `acc` (summed over the wave by
+// the caller at the end). w = 0 on lanes without a sample. The backward walks from the ray's end, so there W / WM are the sums BEHIND the
+// step and the sums in front of a sample are total - behind - own; it returns G_i = d dist / d w_i =
+// (2/3) delta_i w_i + 2 (m_i (W_<i - W_>i) + (WM_>i - WM_<i)).
+struct FsDist { float W, WM, acc; };
+__device__ __forceinline__ float fs_dist_m(const FsGeom &g, const FsSample &p) { return (p.z - g.near) + 0.5f * p.delta; }
+__device__ __forceinline__ void fs_dist_fwd_step(FsDist &d, float w, float m, float delta, uint32_t lane) {
+    const float wm = w * m;
+    const float iw = wave_incl_sum(w, (int)lane), iwm = wave_incl_sum(wm, (int)lane);
+    float ew = __shfl_up(iw, 1, 64), ewm = __shfl_up(iwm, 1, 64);       // the sums in front of the lane, within the step
+    if (lane == 0) { ew = 0.0f; ewm = 0.0f; }
+    const float Wb = d.W + ew, WMb = d.WM + ewm;
+    d.acc += (1.0f / 3.0f) * delta * (w * w) + 2.0f * (w * (m * Wb - WMb));
+    d.W += __shfl(iw, 63, 64); d.WM += __shfl(iwm, 63, 64);
+}
+__device__ __forceinline__ float fs_dist_bwd_step(FsDist &d, float w, float m, float delta, float W_total, float WM_total, uint32_t lane) {
+    const float wm = w * m;
+    const float iw = wave_suffix_incl_sum(w, (int)lane), iwm = wave_suffix_incl_sum(wm, (int)lane);
+    float ew = __shfl_down(iw, 1, 64), ewm = __shfl_down(iwm, 1, 64);   // the sums behind the lane, within the step
+    if (lane == 63) { ew = 0.0f; ewm = 0.0f; }
+    const float Wa = d.W + ew, WMa = d.WM + ewm;
+    const float Wb = (W_total - Wa) - w, WMb = (WM_total - WMa) - wm;
+    d.W += __shfl(iw, 0, 64); d.WM += __shfl(iwm, 0, 64);
+    return (2.0f / 3.0f) * delta * w + 2.0f * (m * (Wb - Wa) + (WMa - WMb));
+}
+
 // The composite's backward for one sample (k_fs_composite_bwd, k_fs_tail_bwd): returns the gradient of its weight and sets o0 = columns
 // 0..7 of its grad_c row (rgb logits in 0..2 where the weight passes the threshold, zeros otherwise). cc -> the sample's rgb logits,
 // read above the threshold only.

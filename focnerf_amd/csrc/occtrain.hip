@@ -27,18 +27,22 @@
 
 // CRIT (foc_occ_tail_forward_sumsq): also ray_sumsq[ray] = sum of exp(h0)^2 over ALL of the ray's samples, those behind the sample at
 // which the composite stopped included (0 for a ray that did not fit): lane l sums samples l, l + 64, ... in order, then one wave_sum.
-template <bool CRIT>
+// DIST (foc_occ_tail_forward_dist): also ray_dist[ray] = the ray's distortion and ray_wm[ray] = sum w m over the samples that count (ragged.h
+// ot_dist_fwd_step; both 0 for a ray that did not fit); every other output is the bits of the instantiation without it.
+template <bool CRIT, bool DIST>
 __global__ void __launch_bounds__(256) k_occ_tail_fwd(const _Float16 *__restrict__ h, const _Float16 *__restrict__ c, uint32_t c_ld,
                                                       const float *__restrict__ deltas, const int32_t *__restrict__ rays, uint32_t M, uint32_t N,
                                                       float T_thresh, float density_scale, const float *__restrict__ bg_ray, float bg_scalar,
                                                       const float *__restrict__ nears, const float *__restrict__ fars,
                                                       float *__restrict__ weights_sum, float *__restrict__ image_raw, float *__restrict__ image,
-                                                      float *__restrict__ depth, float *__restrict__ ray_sumsq) {
+                                                      float *__restrict__ depth, float *__restrict__ ray_sumsq, float *__restrict__ ray_dist,
+                                                      float *__restrict__ ray_wm) {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t n = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (n >= N) return;
     const OtRay ry = ot_ray(rays, n, M);
     float r = 0, g = 0, b = 0, ws = 0, d = 0, sq = 0;
+    OtDist dist = {0, 0, 0};
     if (ry.fits) {
         float T_carry = 1.0f, t_carry = 0.0f;
         uint32_t base = 0;
@@ -62,6 +66,7 @@ __global__ void __launch_bounds__(256) k_occ_tail_fwd(const _Float16 *__restrict
             r = fmaf(st.w, c0, r); g = fmaf(st.w, c1, g); b = fmaf(st.w, c2, b);
             d = fmaf(st.w, tsum, d);
             ws += st.w;
+            if constexpr (DIST) ot_dist_fwd_step(dist, st.w, tsum, dt0, lane);
             if (st.term) { base += 64; break; }
             T_carry = __shfl(st.T_after, 63, 64);
             t_carry = __shfl(tsum, 63, 64);
@@ -73,6 +78,7 @@ __global__ void __launch_bounds__(256) k_occ_tail_fwd(const _Float16 *__restrict
             sq = wave_sum(sq);
         }
         r = wave_sum(r); g = wave_sum(g); b = wave_sum(b); ws = wave_sum(ws); d = wave_sum(d);
+        if constexpr (DIST) dist.acc = wave_sum(dist.acc);
     }
     if (lane == 0) {
         const uint32_t k = ry.index;
@@ -85,20 +91,25 @@ __global__ void __launch_bounds__(256) k_occ_tail_fwd(const _Float16 *__restrict
         const float nr = nears[k], dd = d - nr;
         depth[k] = (dd < 0.0f ? 0.0f : dd) / (fars[k] - nr);
         if constexpr (CRIT) ray_sumsq[k] = sq;
+        if constexpr (DIST) { ray_dist[k] = dist.acc; ray_wm[k] = dist.WM; }
     }
 }
 
 // grad_image [N,3] (of the FINAL image), grad_ws [N] or NULL -> grad_c [M,c_ld] fp16, grad_h0 [M] fp16 (every row written).
 // CRIT (foc_occ_tail_backward_sumsq): grad_sumsq [N] is the gradient of the forward's ray_sumsq; 2 exp(h0) grad_sumsq[ray] joins the
 // density path before trunc_exp's factor on EVERY row of a ray that fits — the rows behind the stop carry that term alone.
-template <bool CRIT>
+// DIST (foc_occ_tail_backward_dist): grad_dist [N] is the gradient of the forward's ray_dist; with g = grad_dist[ray] and G_i = d dist / d w_i
+// (ragged.h ot_dist_bwd_step) grad_sigma_i gains dt0_i (g G_i T_after_i - g sum_{j>i} G_j w_j) on the samples that count. Rows behind a stop
+// and rays that did not fit get nothing from it; a ray whose grad_dist is 0 is the plain backward's bits.
+template <bool CRIT, bool DIST>
 __global__ void __launch_bounds__(256) k_occ_tail_bwd(const float *__restrict__ grad_image, const float *__restrict__ grad_ws,
                                                       const _Float16 *__restrict__ h, const _Float16 *__restrict__ c, uint32_t c_ld,
                                                       const float *__restrict__ deltas, const int32_t *__restrict__ rays, const int32_t *__restrict__ counter,
                                                       const float *__restrict__ weights_sum, const float *__restrict__ image_raw, uint32_t M, uint32_t N,
                                                       float T_thresh, float density_scale, const float *__restrict__ bg_ray, float bg_scalar,
                                                       _Float16 *__restrict__ grad_c, _Float16 *__restrict__ grad_h0,
-                                                      const float *__restrict__ grad_sumsq) {
+                                                      const float *__restrict__ grad_sumsq, const float *__restrict__ ray_wm,
+                                                      const float *__restrict__ ray_dist, const float *__restrict__ grad_dist) {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t n = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (blockIdx.x >= (N + 3u) / 4u) {
@@ -139,6 +150,9 @@ __global__ void __launch_bounds__(256) k_occ_tail_bwd(const float *__restrict__ 
         const float x = (float)h[s * 16], e = expf(x);
         return gsq2 * e * foc_trunc_exp_bwd(x, e);
     };
+    float gdist = 0.0f, W_total = 0.0f, WM_total = 0.0f, dist2 = 0.0f, t_carry = 0.0f;
+    OtDist dist = {0, 0, 0};
+    if constexpr (DIST) { gdist = grad_dist[index]; W_total = weights_sum[index]; WM_total = ray_wm[index]; dist2 = 2.0f * ray_dist[index]; }
     float T_carry = 1.0f;
     OtColour carry = {0, 0, 0};
     bool dead = false;                                         // wave-uniform: the ray became opaque in an earlier block of 64
@@ -147,12 +161,13 @@ __global__ void __launch_bounds__(256) k_occ_tail_bwd(const float *__restrict__ 
         const bool valid = i < ry.count;
         const uint64_t s = (uint64_t)ry.offset + (valid ? i : 0);
         if (dead) { if (valid) store(s, CRIT ? crit_only(s) : 0.0f, 0.0f, 0.0f, 0.0f); continue; }
-        float sigma = 0, e0 = 0, dt0 = 0, c0 = 0, c1 = 0, c2 = 0, e_raw = 0;
+        float sigma = 0, e0 = 0, dt0 = 0, dt1 = 0, c0 = 0, c1 = 0, c2 = 0, e_raw = 0;
         if (valid) {
             const float x = (float)h[s * 16];
             e_raw = expf(x);
             sigma = density_scale != 1.0f ? density_scale * e_raw : e_raw;
-            dt0 = deltas[s * 2];
+            if constexpr (DIST) { const float2 dl = *reinterpret_cast<const float2 *>(deltas + s * 2); dt0 = dl.x; dt1 = dl.y; }
+            else dt0 = deltas[s * 2];
             const uint2 raw = *reinterpret_cast<const uint2 *>(c + s * c_ld);
             const _Float16 *cc = reinterpret_cast<const _Float16 *>(&raw);
             c0 = foc_sigmoid_h((float)cc[0]); c1 = foc_sigmoid_h((float)cc[1]); c2 = foc_sigmoid_h((float)cc[2]);
@@ -160,9 +175,21 @@ __global__ void __launch_bounds__(256) k_occ_tail_bwd(const float *__restrict__ 
         }
         const OtStep st = ot_step(valid, sigma, dt0, T_carry, T_thresh, lane);
         const OtColour acc = ot_running(carry, st.w, c0, c1, c2, lane);
+        float dist_term = 0.0f;                                // g (G_i T_after_i - sum_{j>i} G_j w_j)
+        if constexpr (DIST) {
+            if (gdist != 0.0f) {                               // wave-uniform
+                const float tsum = t_carry + wave_incl_sum(dt1, (int)lane);        // the forward's running t
+                float Gw_incl;
+                const float G = ot_dist_bwd_step(dist, st.w, tsum, dt0, W_total, WM_total, lane, Gw_incl);
+                dist_term = gdist * (G * st.T_after - (dist2 - Gw_incl));
+                t_carry = __shfl(tsum, 63, 64);
+            }
+        }
         if (st.act) {
             // k_composite_train_bwd: grad_rgbs = g w; grad_sigmas = dt0 (...)
-            float gs = dt0 * ot_grad_acc(q, st.T_after, c0, c1, c2, acc);
+            float ga = ot_grad_acc(q, st.T_after, c0, c1, c2, acc);
+            if constexpr (DIST) { if (gdist != 0.0f) ga += dist_term; }
+            float gs = dt0 * ga;
             if (density_scale != 1.0f) gs = density_scale * gs;       // through `density_scale * sigmas`
             if constexpr (CRIT) gs = fmaf(gsq2, e_raw, gs);
             // k_rgb_bwd: half(g) (1 - y) y;  k_head_bwd: grad_sigma * exp(clamp(h0))
@@ -180,15 +207,15 @@ extern "C" {
 // ray_sumsq / grad_sumsq NULL: the plain kernels (foc_occ_tail_forward / _backward); `who` names the entry point in messages
 static int occ_tail_forward(const char *who, const void *h, const void *c, uint32_t c_width, const float *deltas, const int32_t *rays, uint32_t M, uint32_t N,
                             float T_thresh, float density_scale, const float *bg_ray, float bg_scalar, const float *nears, const float *fars,
-                            float *weights_sum, float *image_raw, float *image, float *depth, float *ray_sumsq, void *stream) {
+                            float *weights_sum, float *image_raw, float *image, float *depth, float *ray_sumsq, float *ray_dist, float *ray_wm, void *stream) {
     FocDeviceGuard foc_guard_(stream, h);
     if (N == 0) return FOC_OK;
     FOC_REQUIRE(c_width == 16 || c_width == 4, FOC_E_INVALID, "%s: c_width must be 16 or 4 (got %u)", who, c_width);
     FOC_REQUIRE(rays && nears && fars && weights_sum && image_raw && image && depth && (M == 0 || (h && c && deltas)), FOC_E_INVALID, "%s: null pointer", who);
-    auto kern = ray_sumsq ? k_occ_tail_fwd<true> : k_occ_tail_fwd<false>;
+    auto kern = ray_dist ? (ray_sumsq ? k_occ_tail_fwd<true, true> : k_occ_tail_fwd<false, true>) : (ray_sumsq ? k_occ_tail_fwd<true, false> : k_occ_tail_fwd<false, false>);
     hipLaunchKernelGGL(kern, dim3(foc_div_up(N, 4)), dim3(256), 0, (hipStream_t)stream, (const _Float16 *)h,
                        (const _Float16 *)c, c_width, deltas, rays, M, N, T_thresh, density_scale, bg_ray, bg_scalar, nears, fars, weights_sum, image_raw, image, depth,
-                       ray_sumsq);
+                       ray_sumsq, ray_dist, ray_wm);
     FOC_CHECK_LAUNCH(who);
     return FOC_OK;
 }
@@ -196,15 +223,15 @@ static int occ_tail_forward(const char *who, const void *h, const void *c, uint3
 static int occ_tail_backward(const char *who, const float *grad_image, const float *grad_ws, const void *h, const void *c, uint32_t c_width, const float *deltas,
                              const int32_t *rays, const int32_t *counter, const float *weights_sum, const float *image_raw, uint32_t M, uint32_t N,
                              float T_thresh, float density_scale, const float *bg_ray, float bg_scalar, void *grad_c, void *grad_h0, const float *grad_sumsq,
-                             void *stream) {
+                             const float *ray_wm, const float *ray_dist, const float *grad_dist, void *stream) {
     FocDeviceGuard foc_guard_(stream, grad_image);
     if (N == 0 || M == 0) return FOC_OK;
     FOC_REQUIRE(c_width == 16 || c_width == 4, FOC_E_INVALID, "%s: c_width must be 16 or 4 (got %u)", who, c_width);
     FOC_REQUIRE(grad_image && h && c && deltas && rays && counter && weights_sum && image_raw && grad_c && grad_h0, FOC_E_INVALID, "%s: null pointer", who);
-    auto kern = grad_sumsq ? k_occ_tail_bwd<true> : k_occ_tail_bwd<false>;
+    auto kern = grad_dist ? (grad_sumsq ? k_occ_tail_bwd<true, true> : k_occ_tail_bwd<false, true>) : (grad_sumsq ? k_occ_tail_bwd<true, false> : k_occ_tail_bwd<false, false>);
     hipLaunchKernelGGL(kern, dim3(foc_div_up(N, 4) + OT_PAD_BLOCKS), dim3(256), 0, (hipStream_t)stream, grad_image,
                        grad_ws, (const _Float16 *)h, (const _Float16 *)c, c_width, deltas, rays, counter, weights_sum, image_raw, M, N, T_thresh, density_scale, bg_ray,
-                       bg_scalar, (_Float16 *)grad_c, (_Float16 *)grad_h0, grad_sumsq);
+                       bg_scalar, (_Float16 *)grad_c, (_Float16 *)grad_h0, grad_sumsq, ray_wm, ray_dist, grad_dist);
     FOC_CHECK_LAUNCH(who);
     return FOC_OK;
 }
@@ -213,14 +240,14 @@ int foc_occ_tail_forward(const void *h, const void *c, uint32_t c_width, const f
                          float T_thresh, float density_scale, const float *bg_ray, float bg_scalar, const float *nears, const float *fars,
                          float *weights_sum, float *image_raw, float *image, float *depth, void *stream) {
     return occ_tail_forward("occ_tail_forward", h, c, c_width, deltas, rays, M, N, T_thresh, density_scale, bg_ray, bg_scalar, nears, fars, weights_sum, image_raw,
-                            image, depth, nullptr, stream);
+                            image, depth, nullptr, nullptr, nullptr, stream);
 }
 
 int foc_occ_tail_backward(const float *grad_image, const float *grad_ws, const void *h, const void *c, uint32_t c_width, const float *deltas,
                           const int32_t *rays, const int32_t *counter, const float *weights_sum, const float *image_raw, uint32_t M, uint32_t N,
                           float T_thresh, float density_scale, const float *bg_ray, float bg_scalar, void *grad_c, void *grad_h0, void *stream) {
     return occ_tail_backward("occ_tail_backward", grad_image, grad_ws, h, c, c_width, deltas, rays, counter, weights_sum, image_raw, M, N, T_thresh, density_scale,
-                             bg_ray, bg_scalar, grad_c, grad_h0, nullptr, stream);
+                             bg_ray, bg_scalar, grad_c, grad_h0, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int foc_occ_tail_forward_sumsq(const void *h, const void *c, uint32_t c_width, const float *deltas, const int32_t *rays, uint32_t M, uint32_t N,
@@ -228,7 +255,7 @@ int foc_occ_tail_forward_sumsq(const void *h, const void *c, uint32_t c_width, c
                                float *weights_sum, float *image_raw, float *image, float *depth, float *ray_sumsq, void *stream) {
     FOC_REQUIRE(ray_sumsq || N == 0, FOC_E_INVALID, "occ_tail_forward_sumsq: null ray_sumsq");
     return occ_tail_forward("occ_tail_forward_sumsq", h, c, c_width, deltas, rays, M, N, T_thresh, density_scale, bg_ray, bg_scalar, nears, fars, weights_sum,
-                            image_raw, image, depth, ray_sumsq, stream);
+                            image_raw, image, depth, ray_sumsq, nullptr, nullptr, stream);
 }
 
 int foc_occ_tail_backward_sumsq(const float *grad_image, const float *grad_ws, const void *h, const void *c, uint32_t c_width, const float *deltas,
@@ -237,7 +264,25 @@ int foc_occ_tail_backward_sumsq(const float *grad_image, const float *grad_ws, c
                                 const float *grad_sumsq, void *stream) {
     FOC_REQUIRE(grad_sumsq || N == 0 || M == 0, FOC_E_INVALID, "occ_tail_backward_sumsq: null grad_sumsq");
     return occ_tail_backward("occ_tail_backward_sumsq", grad_image, grad_ws, h, c, c_width, deltas, rays, counter, weights_sum, image_raw, M, N, T_thresh,
-                             density_scale, bg_ray, bg_scalar, grad_c, grad_h0, grad_sumsq, stream);
+                             density_scale, bg_ray, bg_scalar, grad_c, grad_h0, grad_sumsq, nullptr, nullptr, nullptr, stream);
+}
+
+// the two tails with the ray distortion (include/focnerf.h); ray_sumsq / grad_sumsq may be NULL: with or without the criterion
+int foc_occ_tail_forward_dist(const void *h, const void *c, uint32_t c_width, const float *deltas, const int32_t *rays, uint32_t M, uint32_t N,
+                              float T_thresh, float density_scale, const float *bg_ray, float bg_scalar, const float *nears, const float *fars,
+                              float *weights_sum, float *image_raw, float *image, float *depth, float *ray_sumsq, float *ray_dist, float *ray_wm, void *stream) {
+    FOC_REQUIRE((ray_dist && ray_wm) || N == 0, FOC_E_INVALID, "occ_tail_forward_dist: null ray_dist / ray_wm");
+    return occ_tail_forward("occ_tail_forward_dist", h, c, c_width, deltas, rays, M, N, T_thresh, density_scale, bg_ray, bg_scalar, nears, fars, weights_sum,
+                            image_raw, image, depth, ray_sumsq, ray_dist, ray_wm, stream);
+}
+
+int foc_occ_tail_backward_dist(const float *grad_image, const float *grad_ws, const void *h, const void *c, uint32_t c_width, const float *deltas,
+                               const int32_t *rays, const int32_t *counter, const float *weights_sum, const float *image_raw, uint32_t M, uint32_t N,
+                               float T_thresh, float density_scale, const float *bg_ray, float bg_scalar, void *grad_c, void *grad_h0,
+                               const float *grad_sumsq, const float *ray_wm, const float *ray_dist, const float *grad_dist, void *stream) {
+    FOC_REQUIRE(!grad_dist || (ray_wm && ray_dist) || N == 0 || M == 0, FOC_E_INVALID, "occ_tail_backward_dist: grad_dist needs ray_wm and ray_dist");
+    return occ_tail_backward("occ_tail_backward_dist", grad_image, grad_ws, h, c, c_width, deltas, rays, counter, weights_sum, image_raw, M, N, T_thresh,
+                             density_scale, bg_ray, bg_scalar, grad_c, grad_h0, grad_sumsq, ray_wm, ray_dist, grad_dist, stream);
 }
 
 // ---------------------------------------------------------------- the node as one call each way
@@ -308,7 +353,8 @@ static int occ_train_forward(const FocOccTrainNode *n, const void *obj_feat, flo
         if (rc != FOC_OK) return rc;
     }
     return occ_tail_forward(ray_sumsq ? "occ_tail_forward_sumsq" : "occ_tail_forward", n->h, n->c, n->c_width, n->deltas, n->rays, M, n->n_rays, n->T_thresh,
-                            n->density_scale, n->bg_ray, n->bg_scalar, n->nears, n->fars, n->weights_sum, n->image_raw, n->image, n->depth, ray_sumsq, stream);
+                            n->density_scale, n->bg_ray, n->bg_scalar, n->nears, n->fars, n->weights_sum, n->image_raw, n->image, n->depth, ray_sumsq, nullptr, nullptr,
+                            stream);
 }
 
 // tail -> colour head -> sigma MLP -> binned encoder backward. grad_sumsq [n_rays] or NULL: the gradient of the forward's ray_sumsq;
@@ -317,7 +363,7 @@ static int occ_train_backward(const FocOccTrainNode *n, const void *obj_feat, fl
     const uint32_t M = n->cap;
     int rc = occ_tail_backward(grad_sumsq ? "occ_tail_backward_sumsq" : "occ_tail_backward", n->grad_image, n->grad_ws, n->h, n->c, n->c_width, n->deltas, n->rays,
                                n->counter, n->weights_sum, n->image_raw, M, n->n_rays, n->T_thresh, n->density_scale, n->bg_ray, n->bg_scalar, n->grad_c, n->grad_h0,
-                               grad_sumsq, stream);
+                               grad_sumsq, nullptr, nullptr, nullptr, stream);
     if (rc != FOC_OK) return rc;
     rc = color_head_backward(n->grad_c, n->h, n->sh_rows, 1, n->grad_h0, n->w_color, M, n->color_hidden, n->color_layers, n->color_activation, n->grad_h,
                              n->grad_w_color, n->mlp_workspace, n->mlp_workspace_bytes, n->c_width, obj_feat, grad_obj, input_pad, pad31, stream);

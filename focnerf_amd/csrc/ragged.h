@@ -52,3 +52,35 @@ __device__ __forceinline__ float ot_grad_acc(const OtRayGrad &q, float T_after, 
     a = fmaf(q.g2, fmaf(T_after, c2, -(q.b_final - acc.b)), a);
     return a + q.ws_term;
 }
+
+// ---------------------------------------------------------------- ray distortion (include/focnerf.h foc_occ_tail_forward_dist)
+// dist = sum_i (1/3) dt0_i w_i^2 + 2 sum_i w_i (m_i W_<i - WM_<i), W_<i = sum_{j<i} w_j, WM_<i = sum_{j<i} w_j m_j, over the samples that count:
+// m_i = the running sum of dt1 including sample i (the forward's tsum), the interval dt0_i, w = OtStep::w (0 behind the stop). One step of
+// 64 samples: the two running sums by wave scan (W, WM = their values in front of the step, moved behind it). The forward adds the lane's
+// own terms to `acc` (summed over the wave by the caller at the end). The backward, which walks from the front too, takes the sums behind
+// a sample as total - front - own and returns G_i = d dist / d w_i = (2/3) dt0_i w_i + 2 (m_i (W_<i - W_>i) + (WM_>i - WM_<i)); `acc` is
+// then the running sum of G_j w_j in front of the step, and Gw_incl the one including the lane's sample: sum_{j>i} G_j w_j =
+// 2 dist - Gw_incl, because sum_j G_j w_j = 2 dist (dist is homogeneous of degree 2 in w) — the forward's output supplies the total.
+struct OtDist { float W, WM, acc; };
+__device__ __forceinline__ void ot_dist_front(OtDist &d, float w, float wm, uint32_t lane, float &Wb, float &WMb) {
+    const float iw = wave_incl_sum(w, (int)lane), iwm = wave_incl_sum(wm, (int)lane);
+    float ew = __shfl_up(iw, 1, 64), ewm = __shfl_up(iwm, 1, 64);       // the sums in front of the lane, within the step
+    if (lane == 0) { ew = 0.0f; ewm = 0.0f; }
+    Wb = d.W + ew; WMb = d.WM + ewm;
+    d.W += __shfl(iw, 63, 64); d.WM += __shfl(iwm, 63, 64);
+}
+__device__ __forceinline__ void ot_dist_fwd_step(OtDist &d, float w, float m, float dt0, uint32_t lane) {
+    float Wb, WMb;
+    ot_dist_front(d, w, w * m, lane, Wb, WMb);
+    d.acc += (1.0f / 3.0f) * dt0 * (w * w) + 2.0f * (w * (m * Wb - WMb));
+}
+__device__ __forceinline__ float ot_dist_bwd_step(OtDist &d, float w, float m, float dt0, float W_total, float WM_total, uint32_t lane, float &Gw_incl) {
+    const float wm = w * m;
+    float Wb, WMb;
+    ot_dist_front(d, w, wm, lane, Wb, WMb);
+    const float Wa = (W_total - Wb) - w, WMa = (WM_total - WMb) - wm;
+    const float G = (2.0f / 3.0f) * dt0 * w + 2.0f * (m * (Wb - Wa) + (WMa - WMb));
+    Gw_incl = d.acc + wave_incl_sum(G * w, (int)lane);
+    d.acc = __shfl(Gw_incl, 63, 64);
+    return G;
+}

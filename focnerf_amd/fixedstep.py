@@ -158,11 +158,14 @@ class _render_tail(Function):
     want_sumsq: a seventh, differentiable output sumsq [N] = sum_t sigma^2 per ray (the samples' share of the outside-mask criterion).
     input_pad: the last column of the colour input: 0, or 1.0 for the tinycudann layouts — column 47 of the 48-wide row with obj_feat
     (network_tcnn.py), column 31 of the 32-wide row without (network_tcnn_legacy.py); then the *_pad / *_pad31 twins of the colour-head
-    kernels run."""
+    kernels run.
+    want_dist: one more differentiable output, after sumsq when both are asked for: dist [N] = the ray's distortion (loss.ray_distortion of
+    the raw weights with m = (z - near) + delta / 2 and the interval delta; foc_fixed_tail_forward_dist / _backward_dist). Off: the calls, the
+    buffers and the values of the node without it."""
 
     @staticmethod
     def forward(ctx, h, cweights, ray_sh, nears, fars, noise, bg_ray, bg_scalar, N, T, density_scale, thresh, num_layers, activation, obj_feat=None,
-                want_sumsq=False, c_pre=None, w16_pre=None, input_pad=0.0):
+                want_sumsq=False, c_pre=None, w16_pre=None, input_pad=0.0, want_dist=False):
         # c_pre [M,4] half: the colour logits already computed from this h, these weights and this ray_sh by the encoder -> sigma node's fused
         # forward (field._hashgrid_mlp with `colour`, foc_field_forward_train: the bits foc_color_head_forward would give) — then no launch here
         from .field import _half_of, pad_twin, object_feature_half
@@ -190,27 +193,35 @@ class _render_tail(Function):
         depth = torch.empty(N, dtype=torch.float32, device=dev)
         image = torch.empty(N, 3, dtype=torch.float32, device=dev)
         sumsq = torch.empty(N, dtype=torch.float32, device=dev) if want_sumsq else None
-        check(lib.foc_fixed_tail_forward(ptr(h), ptr(c), ptr(nears), ptr(fars), ptr(noise), ptr(bg_ray), float(bg_scalar), N, T, float(density_scale),
-                                         float(thresh), ptr(sigma), ptr(trans), ptr(weights), ptr(ws), ptr(depth), ptr(image), _C_WIDTH, ptr(sumsq), st),
-              "fixed_tail_forward")
+        tail = (ptr(h), ptr(c), ptr(nears), ptr(fars), ptr(noise), ptr(bg_ray), float(bg_scalar), N, T, float(density_scale), float(thresh), ptr(sigma),
+                ptr(trans), ptr(weights), ptr(ws), ptr(depth), ptr(image), _C_WIDTH, ptr(sumsq))
+        dist = wm = None
+        if want_dist:
+            dist, wm = torch.empty(N, dtype=torch.float32, device=dev), torch.empty(N, dtype=torch.float32, device=dev)
+            check(lib.foc_fixed_tail_forward_dist(*tail, ptr(dist), ptr(wm), st), "fixed_tail_forward_dist")
+        else:
+            check(lib.foc_fixed_tail_forward(*tail, st), "fixed_tail_forward")
         empty = torch.empty(0, device=dev)
         ctx.bg_grad = bg_ray is not None and ctx.needs_input_grad[6]         # a learned background (network_linear.py): g_image * (1 - ws)
         ctx.save_for_backward(h, w16, sigma, trans, weights, c, ray_sh, nears, fars, noise if noise is not None else empty,
-                              bg_ray if bg_ray is not None else empty, obj16 if obj16 is not None else empty, ws if ctx.bg_grad else empty)
+                              bg_ray if bg_ray is not None else empty, obj16 if obj16 is not None else empty,
+                              ws if ctx.bg_grad or want_dist else empty, wm if want_dist else empty)
+        ctx.outputs = (bool(want_sumsq), bool(want_dist))
         ctx.flags = (noise is not None, bg_ray is not None, obj16 is not None, obj_feat.dtype if obj_feat is not None else None,
                      tuple(obj_feat.shape) if obj_feat is not None else None)
         ctx.dims = (N, T, float(density_scale), float(thresh), float(bg_scalar), int(num_layers), int(activation), float(input_pad))
         ctx.mark_non_differentiable(sigma, weights, c)
         ctx.set_materialize_grads(False)          # unused outputs arrive as None in backward, not as five freshly zero-filled tensors (25 us)
-        if want_sumsq:
-            return image, ws, depth, sigma, weights, c, sumsq
-        return image, ws, depth, sigma, weights, c
+        return (image, ws, depth, sigma, weights, c) + ((sumsq,) if want_sumsq else ()) + ((dist,) if want_dist else ())
 
     @staticmethod
-    def backward(ctx, g_image, g_ws, g_depth, _g_sigma, _g_weights, _g_c, g_sumsq=None):
+    def backward(ctx, g_image, g_ws, g_depth, _g_sigma, _g_weights, _g_c, *g_extra):
         from .backend import _scratch
         from .field import pad_twin
-        h, w16, sigma, trans, weights, c, ray_sh, nears, fars, noise, bg_ray, obj16, ws = ctx.saved_tensors
+        h, w16, sigma, trans, weights, c, ray_sh, nears, fars, noise, bg_ray, obj16, ws, wm = ctx.saved_tensors
+        g_extra = list(g_extra)
+        g_sumsq = g_extra.pop(0) if ctx.outputs[0] else None
+        g_dist = g_extra.pop(0) if ctx.outputs[1] else None
         has_noise, has_bg, has_obj, obj_dtype, obj_shape = ctx.flags
         obj16 = obj16 if has_obj else None
         N, T, ds, thresh, bg_scalar, num_layers, activation, input_pad = ctx.dims
@@ -224,9 +235,15 @@ class _render_tail(Function):
         g_sumsq = g_sumsq.contiguous().float() if g_sumsq is not None else None
         grad_c = torch.empty_like(c)
         grad_h0 = torch.empty(M, dtype=torch.float16, device=dev)
-        check(lib.foc_fixed_tail_backward(ptr(g_image), ptr(g_ws), ptr(g_depth), ptr(c), ptr(sigma), ptr(trans), ptr(weights), ptr(nears), ptr(fars),
-                                          ptr(noise), ptr(bg_ray), bg_scalar, N, T, ds, thresh, ptr(grad_c), ptr(grad_h0), _C_WIDTH, ptr(g_sumsq), st),
-              "fixed_tail_backward")
+        if g_dist is not None:
+            g_dist = g_dist.contiguous().float()
+            check(lib.foc_fixed_tail_backward_dist(ptr(g_image), ptr(g_ws), ptr(g_depth), ptr(c), ptr(sigma), ptr(trans), ptr(weights), ptr(ws), ptr(nears),
+                                                   ptr(fars), ptr(noise), ptr(bg_ray), bg_scalar, N, T, ds, thresh, ptr(grad_c), ptr(grad_h0), _C_WIDTH,
+                                                   ptr(g_sumsq), ptr(wm), None, ptr(g_dist), st), "fixed_tail_backward_dist")
+        else:
+            check(lib.foc_fixed_tail_backward(ptr(g_image), ptr(g_ws), ptr(g_depth), ptr(c), ptr(sigma), ptr(trans), ptr(weights), ptr(nears), ptr(fars),
+                                              ptr(noise), ptr(bg_ray), bg_scalar, N, T, ds, thresh, ptr(grad_c), ptr(grad_h0), _C_WIDTH, ptr(g_sumsq), st),
+                  "fixed_tail_backward")
         grad_h = torch.empty_like(h)
         g_w = torch.empty_like(w16)
         wsb = _scratch.get("ffmlp_ws", lib.foc_ffmlp_backward_workspace_bytes(48 if has_obj else 32, 64, num_layers), dev)
@@ -237,7 +254,7 @@ class _render_tail(Function):
         check(fn(*args, *extra, st), "color_head_backward")
         g_obj = g_obj32.to(obj_dtype).view(obj_shape) if g_obj32 is not None else None
         g_bg = g_image * (1 - ws).unsqueeze(-1) if ctx.bg_grad else None
-        return (grad_h, g_w, None, None, None, None, g_bg) + (None,) * 7 + (g_obj, None, None, None, None)
+        return (grad_h, g_w, None, None, None, None, g_bg) + (None,) * 7 + (g_obj, None, None, None, None, None)
 
 
 class _masked_norm(Function):
@@ -257,6 +274,20 @@ class _masked_norm(Function):
         return outside * coef, None
 
 
+def _unfused_distortion(weights, nears, fars, noise, N, T):
+    """The distortion of the training route without the fused tail: loss.ray_distortion on the head's weights [N*T], with the sample depths of
+    run() (torch's linspace and jitter expressions) and a ray that misses the box set to 0 like the tail kernels do."""
+    from .loss import ray_distortion
+    span = (fars - nears).unsqueeze(-1)
+    z = span * torch.linspace(0.0, 1.0, T, device=weights.device).unsqueeze(0)         # z - near
+    if noise is not None:
+        z = z + (noise.view(N, T) - 0.5) * (span / T)
+    delta = torch.cat([z[:, 1:] - z[:, :-1], span / T], dim=-1)
+    live = (fars > nears).unsqueeze(-1)
+    zero = torch.zeros_like(z)
+    return ray_distortion(torch.where(live, weights.view(N, T), zero), torch.where(live, z + 0.5 * delta, zero), torch.where(live, delta, zero))
+
+
 def _background(bg_color, N, dev):
     """bg_color None / scalar / tensor -> (per-ray [N,3] tensor or None, scalar)."""
     if bg_color is None:
@@ -269,9 +300,15 @@ def _background(bg_color, N, dev):
 
 
 def render_fixed_steps(model, rays_o, rays_d, yolo_details=None, num_steps=512, bg_color=None, perturb=False, weight_thresh=1e-10,
-                       return_fields=None, _out=None, **kwargs):
+                       return_fields=None, _out=None, distortion=False, **kwargs):
     """Drop-in for NeRFRenderer.run(..., upsample_steps=0) on a focnerf_amd NeRFNetwork (fp16 autocast semantics); same result
-    dictionary (`return_fields` None = on in eval mode, like the reference's run(), off in training)."""
+    dictionary (`return_fields` None = on in eval mode, like the reference's run(), off in training).
+
+    distortion=True adds `results['distortion']`, shaped like `depth`: the per-ray distortion of mip-NeRF 360 (loss.ray_distortion of the raw
+    weights, m = (z - near) + delta / 2, interval delta, world units; 0 on a ray that misses the box), differentiable — its mean is the
+    reference's loss.eff_distloss. On the fused training tail it comes out of the tail kernels; on the training route without the tail from
+    loss.ray_distortion on the head's weights. Without a gradient there are no weights to regularise: ValueError. Off (the default): every
+    call, buffer and value is that of the path without the keyword."""
     import time
     if return_fields is None:
         return_fields = not model.training
@@ -291,6 +328,9 @@ def render_fixed_steps(model, rays_o, rays_d, yolo_details=None, num_steps=512, 
         bg_color = model._background_colour(rays_o, rays_d, bg_color)
     want_tail = plan.tail and model.training and torch.is_grad_enabled()
     fused_infer = not torch.is_grad_enabled() and plan.infer
+    if distortion and not torch.is_grad_enabled():
+        raise ValueError("render_fixed_steps: distortion=True needs the training route (gradients enabled): the inference paths form no "
+                         "differentiable weights; call it under torch.enable_grad() with model.train()")
     rb = ray_block_default() if fused_infer else 0
     enc_in, _, ray_sh = fixed_sample(rays_o, rays_d, nears, fars, aabb, noise, T, model.bound, want_ray_sh=True) if want_tail else \
         fixed_sample(rays_o, rays_d, nears, fars, aabb, noise, T, model.bound, ray_block=rb) + (None,)
@@ -360,9 +400,10 @@ def render_fixed_steps(model, rays_o, rays_d, yolo_details=None, num_steps=512, 
             bg_ray, bg_scalar = _background(bg_color, N, dev)
             outs = _render_tail.apply(h, cweights, ray_sh, nears, fars, noise, bg_ray, bg_scalar, N, T, model.density_scale, weight_thresh,
                                       cn.num_layers, cn.activation, obj_feat, want_crit and yolo_details[0].numel() == N, c_pre,
-                                      wc16 if c_pre is not None else None, plan.colour_input_pad)
+                                      wc16 if c_pre is not None else None, plan.colour_input_pad, *((True,) if distortion else ()))
             image, weights_sum, depth, sigma, weights, c = outs[:6]
-            if len(outs) == 7:
+            ray_dist = outs[-1] if distortion else None
+            if len(outs) - bool(distortion) == 7:
                 # a per-ray mask: the samples' sum of sigma^2 comes out of the tail kernel (no [M]-sized torch expression, no boolean-mask
                 # indexing with its host sync); sigma here is the kernel's exp(h0) — density_scale == 1 in every FOC configuration, and the
                 # criterion is taken on trunc_exp(h0) itself like the reference's
@@ -371,6 +412,8 @@ def render_fixed_steps(model, rays_o, rays_d, yolo_details=None, num_steps=512, 
             weights, weights_sum, depth, sigma, cin = _density_head.apply(h, rays_d, nears, fars, noise, N, T, model.density_scale, obj_feat)
             if plan.colour_input_pad != 0:                                # the head kernel writes 0 in the last column (tinycudann layouts: the pad)
                 cin = torch.cat([cin[:, :-1], cin.new_full((cin.shape[0], 1), plan.colour_input_pad)], dim=1)
+            if distortion:
+                ray_dist = _unfused_distortion(weights, nears, fars, noise, N, T)
         if want_crit and criterion_outside_mask is None:
             from .activation import trunc_exp
             criterion_outside_mask = torch.norm(trunc_exp(h[:, 0]).view(N, T)[~yolo_details[0].squeeze(0)] - 0)
@@ -384,6 +427,8 @@ def render_fixed_steps(model, rays_o, rays_d, yolo_details=None, num_steps=512, 
 
     results = {'depth': depth.view(*prefix), 'image': image.view(*prefix, 3), 'weights_sum': weights_sum,
                'criterion_outside_mask': criterion_outside_mask, 'timing': [t_mid - t_start, time.time() - t_mid]}
+    if distortion:
+        results['distortion'] = ray_dist.view(*prefix)
     if return_fields:
         from .head import rgb_head
         c16 = c.detach()

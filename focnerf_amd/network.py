@@ -83,7 +83,7 @@ class NeRFNetwork(NeRFRenderer):
 
     def run(self, rays_o, rays_d, yolo_details=None, fused=False, **kwargs):
         """`fused=True`: the fixed-step path through csrc/fixedstep.hip (same image, depth and gradients as `NeRFRenderer.run`, which
-        stays the default)."""
+        stays the default). Keywords go through to either: `distortion=True` adds results['distortion'] on both routes."""
         if fused and kwargs.get("upsample_steps", 0) == 0 and self.bg_radius <= 0:
             from .fixedstep import render_fixed_steps
             kwargs.pop("upsample_steps", None)

@@ -19,6 +19,10 @@ ONE node, `_occ_train`, serves the three layouts of the colour input, and its co
     with a gradient (the colour head returns it), column 47 of the colour input is the plan's pad, and the tail can return the per-ray
     sums of sigma^2 that FOC's outside-mask criterion needs.
 Without an object feature the library calls, the buffers and the values are those of the plain node.
+
+`want_dist` (run_cuda(..., distortion=True)): the tail also returns the per-ray distortion of mip-NeRF 360 (foc_occ_tail_forward_dist /
+_backward_dist), differentiable. The one-call node and its structs do not carry it: with `want_dist` the node takes the call-by-call
+chain (`_native_plan` returns None) — the same kernels enqueued from Python; what that costs in host time per step is not measured.
 """
 import ctypes
 import os
@@ -52,12 +56,12 @@ def _no_jitter(n, dev):
 _mlp_bytes = {}
 
 
-def _native_plan(offsets, grid, L, M, sigma, colour, colour_in=32):
+def _native_plan(offsets, grid, L, M, sigma, colour, colour_in=32, want_dist=False):
     """(grid workspace bytes, MLP workspace bytes) when the node can run as ONE library call each way (include/focnerf.h FocOccTrainNode:
     the encoder's counted forward and binned backward must apply, the switches that take other paths must be at their defaults), else None.
     FOC_OCC_NATIVE_NODE=0: always the call-by-call chain below (the tests compare the two). colour_in 48: the object-conditioned head,
-    whose workspace starts with a 48-wide blob image."""
-    if os.environ.get("FOC_OCC_NATIVE_NODE", "1") == "0" or _gridencoder.precount_standalone():
+    whose workspace starts with a 48-wide blob image. want_dist: None — FocOccTrainNode has no place for the distortion buffers."""
+    if want_dist or os.environ.get("FOC_OCC_NATIVE_NODE", "1") == "0" or _gridencoder.precount_standalone():
         return None
     grid_bytes = _gridencoder.binned_workspace_bytes(offsets, M, 3, 2, L, grid.log2_scale, grid.base_resolution, grid.gridtype, FOC_F16,
                                                      count_ahead=True)
@@ -105,6 +109,7 @@ class OccTrainConfig:
     colour: MlpShape
     colour_input_pad: float             # the colour input's last column (plan.colour_input_pad): 31 of the 32-wide row, 47 with an object feature
     want_sumsq: bool                    # the tail also returns the per-ray sums of sigma^2 (an object-conditioned network with a ray mask)
+    want_dist: bool = False             # the tail also returns the per-ray distortion (call-by-call chain only)
 
 
 _NODE_FIELDS = frozenset(name for name, _ in FocOccTrainNode._fields_)
@@ -129,11 +134,13 @@ def _forward_node(cfg, n, M, grid_bytes, **buffers):
 
 
 class _occ_train(Function):
-    """(embeddings, sigma weights, colour weights, obj, ...) -> (image, weights_sum, depth, ray_sumsq or None). obj None: a plain network
+    """(embeddings, sigma weights, colour weights, obj, ...) -> (image, weights_sum, depth, ray_sumsq or None, ray_dist or None). obj None: a plain network
     (pad 0) or the legacy tinycudann layout (column 31 = pad). obj [16] (any float dtype): the 48-wide colour head with the encoded object
     feature, which is differentiable, column 47 = pad; with cfg.want_sumsq the tail also returns ray_sumsq [n] = the sum of sigma^2 over all
-    of a ray's samples (include/focnerf.h foc_occ_tail_forward_sumsq), differentiable too. Two routes: the one-call node
-    (foc_occ_train_forward / _backward, their _pad31 or _obj form) and the call-by-call chain (FOC_OCC_NATIVE_NODE=0, an unbudgeted list)."""
+    of a ray's samples (include/focnerf.h foc_occ_tail_forward_sumsq), differentiable too. With cfg.want_dist ray_dist [n] = the ray's distortion
+    (foc_occ_tail_forward_dist), differentiable, with or without ray_sumsq. Two routes: the one-call node
+    (foc_occ_train_forward / _backward, their _pad31 or _obj form) and the call-by-call chain (FOC_OCC_NATIVE_NODE=0, an unbudgeted list,
+    want_dist)."""
 
     @staticmethod
     def forward(ctx, emb, w_sigma, w_color, obj, o, d, aabb, bitfield, counter, bg_ray, cfg):
@@ -155,7 +162,9 @@ class _occ_train(Function):
         out = torch.empty(n * (9 if want_sumsq else 8), dtype=torch.float32, device=dev)
         ws, depth, image_raw, image = out[:n], out[n: 2 * n], out[2 * n: 5 * n].view(n, 3), out[5 * n: 8 * n].view(n, 3)
         sumsq = out[8 * n:] if want_sumsq else None
-        plan = _native_plan(offsets, grid, L, cap, sigma, colour, 32 if obj is None else 48) if (budgeted and cap > 0 and n > 0) else None
+        want_dist = cfg.want_dist
+        plan = _native_plan(offsets, grid, L, cap, sigma, colour, 32 if obj is None else 48, want_dist) if (budgeted and cap > 0 and n > 0) else None
+        dist = wm = None
         M = cap
         ctx.node = ctx.object = None
         if plan is not None:
@@ -198,12 +207,15 @@ class _occ_train(Function):
                 check(fn(ptr(h), ptr(sh), 1, ptr(wc16), M, 64, colour.num_layers, colour.activation, ptr(c), _C_WIDTH, ptr(obj16), *extra, st), "color_head_forward")
             tail = (ptr(h), ptr(c), _C_WIDTH, ptr(deltas), ptr(rays), M, n, cfg.T_thresh, cfg.density_scale, ptr(bg_ray), cfg.bg_scalar,
                     ptr(nears), ptr(fars), ptr(ws), ptr(image_raw), ptr(image), ptr(depth))
-            if want_sumsq:
+            if want_dist:
+                dist, wm = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
+                check(lib.foc_occ_tail_forward_dist(*tail, ptr(sumsq), ptr(dist), ptr(wm), st), "occ_tail_forward_dist")
+            elif want_sumsq:
                 check(lib.foc_occ_tail_forward_sumsq(*tail, ptr(sumsq), st), "occ_tail_forward_sumsq")
             else:
                 check(lib.foc_occ_tail_forward(*tail, st), "occ_tail_forward")
         ctx.save_for_backward(enc_in, emb16, ws16, wc16, offsets, planes, h, c, sh, deltas, rays, counter, ws, image_raw,
-                              bg_ray if bg_ray is not None else torch.empty(0, device=dev))
+                              bg_ray if bg_ray is not None else torch.empty(0, device=dev), *((dist, wm) if want_dist else ()))
         ctx.obj16 = obj16
         ctx.obj_like = (obj.dtype, obj.shape) if obj is not None else None
         ctx.bg_grad = bg_ray is not None and ctx.needs_input_grad[9]
@@ -213,12 +225,12 @@ class _occ_train(Function):
         ctx.ticket = ticket
         ctx.mark_non_differentiable(depth)
         ctx.set_materialize_grads(False)
-        return image, ws, depth, sumsq
+        return image, ws, depth, sumsq, dist
 
     @staticmethod
-    def backward(ctx, g_image, g_ws, _g_depth, g_sumsq):
+    def backward(ctx, g_image, g_ws, _g_depth, g_sumsq, g_dist=None):
         """-> the gradients of the embeddings, the two weight blobs, obj (in its dtype and shape) and a per-ray background."""
-        enc_in, emb16, ws16, wc16, offsets, planes, h, c, sh, deltas, rays, counter, ws, image_raw, bg_ray = ctx.saved_tensors
+        enc_in, emb16, ws16, wc16, offsets, planes, h, c, sh, deltas, rays, counter, ws, image_raw, bg_ray, *dist_wm = ctx.saved_tensors
         M, n, T_thresh, density_scale, bg_scalar, grid, sigma, colour, pad = ctx.cfg
         S, H, (gridtype, align_corners, interp) = grid.log2_scale, grid.base_resolution, grid.tail()
         obj16 = ctx.obj16
@@ -233,7 +245,7 @@ class _occ_train(Function):
 
         g_emb = torch.zeros_like(emb16)
         g_wsig, g_wcol = torch.empty_like(ws16), torch.empty_like(wc16)
-        if M == 0 or (g_image is None and g_ws is None and g_sumsq is None):
+        if M == 0 or (g_image is None and g_ws is None and g_sumsq is None and g_dist is None):
             g_bg = g_image * (1 - ws).unsqueeze(-1) if ctx.bg_grad and g_image is not None else None
             return result(g_emb, g_wsig.zero_(), g_wcol.zero_(), (torch.zeros(16, dtype=torch.float32, device=dev) if obj16 is not None else None), g_bg)
         g_image = g_image.contiguous().float() if g_image is not None else torch.zeros(n, 3, dtype=torch.float32, device=dev)
@@ -268,7 +280,10 @@ class _occ_train(Function):
         grad_c, grad_h0 = gblock[: M * _C_WIDTH].view(M, _C_WIDTH), gblock[M * _C_WIDTH:]
         tail = (ptr(g_image), ptr(g_ws), ptr(h), ptr(c), _C_WIDTH, ptr(deltas), ptr(rays), ptr(counter), ptr(ws), ptr(image_raw), M, n,
                 T_thresh, density_scale, ptr(bg_ray if ctx.has_bg else None), bg_scalar, ptr(grad_c), ptr(grad_h0))
-        if g_sumsq is not None:
+        if g_dist is not None:
+            dist, wm = dist_wm
+            check(lib.foc_occ_tail_backward_dist(*tail, ptr(g_sumsq), ptr(wm), ptr(dist), ptr(g_dist.contiguous().float()), st), "occ_tail_backward_dist")
+        elif g_sumsq is not None:
             check(lib.foc_occ_tail_backward_sumsq(*tail, ptr(g_sumsq), st), "occ_tail_backward_sumsq")
         else:
             check(lib.foc_occ_tail_backward(*tail, st), "occ_tail_backward")
@@ -292,8 +307,10 @@ def ray_mask(mask, n):
     return mask.reshape(n).bool()
 
 
-def render_occupancy_train(model, plan, o, d, counter, bg_color, perturb, force_all_rays, dt_gamma, max_steps, T_thresh, align, obj16=None, want_sumsq=False):
-    """o, d [n,3] fp32 contiguous, counter int32[2] (zeroed by the caller) -> (image [n,3], weights_sum [n], depth [n], ray_sumsq [n] or None)
+def render_occupancy_train(model, plan, o, d, counter, bg_color, perturb, force_all_rays, dt_gamma, max_steps, T_thresh, align, obj16=None, want_sumsq=False,
+                           want_dist=False):
+    """o, d [n,3] fp32 contiguous, counter int32[2] (zeroed by the caller) -> (image [n,3], weights_sum [n], depth [n], ray_sumsq [n] or None),
+    with want_dist a fifth entry ray_dist [n] (the ray's distortion, differentiable; the node then runs call by call, module docstring),
     for a network whose `field.field_plan` is `plan` (plan.occ; plan.occ_object with obj16 [16], the encoded object feature, which receives
     a gradient); the rays' box test against the model's training box (near_far_from_aabb, min_near) happens inside the march."""
     if want_sumsq and obj16 is None:
@@ -304,6 +321,7 @@ def render_occupancy_train(model, plan, o, d, counter, bg_color, perturb, force_
         bound=float(model.bound), cascade=int(model.cascade), grid_size=int(model.grid_size), mean_count=int(model.mean_count), perturb=bool(perturb),
         align=int(align), force_all_rays=bool(force_all_rays), dt_gamma=float(dt_gamma), max_steps=int(max_steps), T_thresh=float(T_thresh),
         density_scale=float(model.density_scale), bg_scalar=float(bg_scalar), min_near=float(model.min_near), offsets=enc.offsets, grid=plan.grid,
-        sigma=plan.sigma, colour=plan.colour, colour_input_pad=float(plan.colour_input_pad), want_sumsq=bool(want_sumsq))
-    return _occ_train.apply(enc.embeddings, fused_mlp(model, "sigma_net").weights, fused_mlp(model, "color_net").weights, obj16, o, d,
-                            model._aabb().contiguous().float(), model.density_bitfield, counter, bg_ray, cfg)
+        sigma=plan.sigma, colour=plan.colour, colour_input_pad=float(plan.colour_input_pad), want_sumsq=bool(want_sumsq), want_dist=bool(want_dist))
+    res = _occ_train.apply(enc.embeddings, fused_mlp(model, "sigma_net").weights, fused_mlp(model, "color_net").weights, obj16, o, d,
+                           model._aabb().contiguous().float(), model.density_bitfield, counter, bg_ray, cfg)
+    return res if want_dist else res[:4]

@@ -136,7 +136,7 @@ class NeRFRenderer(nn.Module):
 
     # ------------------------------------------------------------------ fixed number of samples per ray
     def run(self, rays_o, rays_d, yolo_details=None, num_steps=512, upsample_steps=0, bg_color=None, perturb=False, weight_thresh=1e-10,
-            return_fields=None, **kwargs):
+            return_fields=None, distortion=False, **kwargs):
         """`num_steps` equidistant samples between the box entry and exit of every ray, density at all of them, colour where the
         compositing weight exceeds `weight_thresh`, then alpha compositing with torch ops — the computation of nerf/renderer.py:126-238
         for `upsample_steps=0` (the only value FOC uses, main_nerf.py:31-32), in its order of operations.
@@ -144,7 +144,9 @@ class NeRFRenderer(nn.Module):
         yolo_details = (sample mask [1,N,T], box, object feature) from the trainer (nerf/utils.py:57-154): handed on to `color()`, and
         in training it yields `criterion_outside_mask`, the norm of the densities outside the mask (:163-165).
         Result: depth, image, weights_sum, criterion_outside_mask, timing (host seconds before / after the colour query) and, with
-        `return_fields` (default: only in eval mode), densities [N,T,1] and rgbs [N,T,3]."""
+        `return_fields` (default: only in eval mode), densities [N,T,1] and rgbs [N,T,3]. distortion=True adds 'distortion', shaped like
+        depth: loss.ray_distortion of the weights with m = (z - near) + step / 2 and the interval step (0 on a ray that misses the box) —
+        what the fused tail returns for the same keyword (fixedstep.render_fixed_steps)."""
         want_fields = (not self.training) if return_fields is None else return_fields
         started = time.time()
         o, d, lead = _flat_rays(rays_o, rays_d)
@@ -206,6 +208,11 @@ class NeRFRenderer(nn.Module):
 
         out = {'depth': depth.view(*lead), 'image': image.view(*lead, 3), 'weights_sum': opacity, 'criterion_outside_mask': outside,
                'timing': [queried - started, time.time() - queried]}
+        if distortion:
+            from .loss import ray_distortion
+            live, zero = far > near, torch.zeros_like(z)
+            out['distortion'] = ray_distortion(torch.where(live, weights, zero), torch.where(live, (z - near) + 0.5 * step, zero),
+                                               torch.where(live, step, zero)).view(*lead)
         if want_fields:
             out['densities'], out['rgbs'] = sigma.unsqueeze(-1), colour
         return out
@@ -223,13 +230,16 @@ class NeRFRenderer(nn.Module):
         return sigmas if self.density_scale == 1 else self.density_scale * sigmas      # x * 1 == x: no launch for the default scale
 
     def run_cuda(self, rays_o, rays_d, dt_gamma=0, bg_color=None, perturb=False, force_all_rays=False, max_steps=1024, T_thresh=1e-4,
-                 device_compaction=None, yolo_details=None, **kwargs):
+                 device_compaction=None, yolo_details=None, distortion=False, **kwargs):
         """Samples only where the occupancy bitfield is set (legacy/nerf/renderer.py:256-376). Training: one marching pass, one
         evaluation of the field, one compositing node. Inference: rays advance a few samples at a time and leave the list once they are
         opaque or out of the box.
         yolo_details = (ray mask or None, box, raw object feature) for an object-conditioned network (`uses_object_feature`): the colour
         network takes the encoded feature, and the result carries 'criterion_outside_mask' — in training with a mask sqrt(sum of sigma^2
-        over every sample the march emitted for the rays outside the mask), sigma before density_scale; else None. The mask is per ray."""
+        over every sample the march emitted for the rays outside the mask), sigma before density_scale; else None. The mask is per ray.
+        distortion=True (fused training node only) adds 'distortion' [rays]: the per-ray distortion of mip-NeRF 360 out of the tail kernels
+        (occtrain.render_occupancy_train want_dist: m = the running sum of deltas[:,1], interval deltas[:,0]); the node then runs call by
+        call. Every other route forms no per-sample weights and raises ValueError."""
         o, d, lead = _flat_rays(rays_o, rays_d)
         n, dev = o.shape[0], o.device
         out = {}
@@ -257,13 +267,19 @@ class NeRFRenderer(nn.Module):
                 self.local_step += 1
                 if obj16 is None and self.bg_radius > 0:          # the background model (plan.occ: network_linear.py, plan.background)
                     bg_color = self._background_colour(o, d, bg_color)
-                image, opacity, depth, sumsq = render_occupancy_train(self, plan, o.float(), d.float(), slot, bg_color, perturb, force_all_rays, dt_gamma, max_steps,
-                                                                      T_thresh, _MARCH_ALIGN, obj16, outside is not None)
+                res = render_occupancy_train(self, plan, o.float(), d.float(), slot, bg_color, perturb, force_all_rays, dt_gamma, max_steps, T_thresh,
+                                             _MARCH_ALIGN, obj16, outside is not None, **({"want_dist": True} if distortion else {}))
+                image, opacity, depth, sumsq = res[:4]
+                if distortion:
+                    out['distortion'] = res[4].view(*lead)
                 if sumsq is not None:
                     out['criterion_outside_mask'] = _masked_norm.apply(sumsq, outside.to(torch.float32))
                 out['weights_sum'] = opacity
                 out['image'], out['depth'] = image.view(*lead, 3), depth.view(*lead)
                 return out
+        if distortion:
+            raise ValueError("run_cuda: distortion=True needs the fused occupancy training node, which alone forms the per-sample weights: a CUDA "
+                             "device, model.train(), gradients and autocast enabled, a network that node serves, and FOC_FUSED_OCC unset or 1")
         near, far = raymarching.near_far_from_aabb(o, d, self._aabb(), self.min_near)
         background = self._background_colour(o, d, bg_color)
         if self.training:

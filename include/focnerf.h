@@ -733,6 +733,42 @@ int foc_occ_tail_backward_sumsq(const float *grad_image, const float *grad_ws, c
                                 const float *image_raw, uint32_t M, uint32_t N, float T_thresh, float density_scale,
                                 const float *bg_ray, float bg_scalar, void *grad_c, void *grad_h0, const float *grad_sumsq, void *stream);
 
+/* The four tails above with the per-ray DISTORTION of mip-NeRF 360 (the reference's loss.py eff_distloss without its division by the ray
+ * count), a differentiable output, from the weights the tails already form:
+ *   dist = sum_i (1/3) delta_i w_i^2 + 2 sum_i w_i (m_i W_<i - WM_<i),   W_<i = sum_{j<i} w_j,  WM_<i = sum_{j<i} w_j m_j
+ * fixed-step: m_i = (z_i - near) + delta_i / 2 and delta_i = the distance to the next sample (the last one: (far - near) / T), world units,
+ *   the raw weight (not the `w > thresh` colour mask); a ray with !(far > near) gets dist = 0, ray_wm = 0 and no distortion gradient (its
+ *   weights are 0 and its m may be non-finite).
+ * ragged: m_i = the running sum of deltas[:,1] including sample i (the depth's t), delta_i = deltas[:,0], w = the composite's weight: 0
+ *   behind the sample at which the ray stopped at T_thresh, that sample counts. A ray with count 0 or one that does not fit the list gets
+ *   0 and no gradient; rows behind a stop get no distortion gradient.
+ * m and delta carry no gradient; the only gradient is through w: G_i = d dist / d w_i = (2/3) delta_i w_i + 2 (m_i (W_<i - W_>i) + (WM_>i - WM_<i)).
+ * Forward: ray_dist [N] and ray_wm [N] (= sum_i w_i m_i, which the backward needs beside weights_sum), both required; ray_sumsq [N] may be
+ *   NULL (with or without the outside-mask criterion). Every other output is bit for bit the plain entry point's.
+ * Backward: grad_dist [N] = the gradient of ray_dist; NULL: the plain backward (ray_wm / ray_dist are then not read). Otherwise ray_wm
+ *   [N] and weights_sum [N] of the forward are required; grad_dist[ray] G_i joins the gradient of w_i — fixed-step: before the density
+ *   head's backward; ragged: grad_sigma_i gains dt0_i g (G_i T_after_i - sum_{j>i} G_j w_j), with sum_j G_j w_j = 2 dist taken from
+ *   ray_dist [N] (required there; the fixed-step backward walks from the ray's end, accepts ray_dist and does not read it). A ray whose
+ *   grad_dist is 0 gets the plain backward's bits. grad_sumsq [N] may be NULL. One wave per ray, wave scans only: the same bits on every run. */
+int foc_fixed_tail_forward_dist(const void *h, const void *c, const float *nears, const float *fars, const float *noise,
+                                const float *bg_ray, float bg_scalar, uint32_t N, uint32_t T, float density_scale, float thresh,
+                                float *sigma, float *trans, float *weights, float *weights_sum, float *depth, float *image,
+                                uint32_t c_width, float *ray_sumsq, float *ray_dist, float *ray_wm, void *stream);
+int foc_fixed_tail_backward_dist(const float *grad_image, const float *grad_ws, const float *grad_depth, const void *c,
+                                 const float *sigma, const float *trans, const float *weights, const float *weights_sum, const float *nears,
+                                 const float *fars, const float *noise, const float *bg_ray, float bg_scalar, uint32_t N,
+                                 uint32_t T, float density_scale, float thresh, void *grad_c, void *grad_h0, uint32_t c_width,
+                                 const float *grad_sumsq, const float *ray_wm, const float *ray_dist, const float *grad_dist, void *stream);
+int foc_occ_tail_forward_dist(const void *h, const void *c, uint32_t c_width, const float *deltas, const int32_t *rays,
+                              uint32_t M, uint32_t N, float T_thresh, float density_scale, const float *bg_ray, float bg_scalar,
+                              const float *nears, const float *fars, float *weights_sum, float *image_raw, float *image,
+                              float *depth, float *ray_sumsq, float *ray_dist, float *ray_wm, void *stream);
+int foc_occ_tail_backward_dist(const float *grad_image, const float *grad_ws, const void *h, const void *c, uint32_t c_width,
+                               const float *deltas, const int32_t *rays, const int32_t *counter, const float *weights_sum,
+                               const float *image_raw, uint32_t M, uint32_t N, float T_thresh, float density_scale,
+                               const float *bg_ray, float bg_scalar, void *grad_c, void *grad_h0, const float *grad_sumsq,
+                               const float *ray_wm, const float *ray_dist, const float *grad_dist, void *stream);
+
 /* The whole occupancy-grid TRAINING node as ONE call each way (csrc/occtrain.hip): what legacy/nerf/renderer.py:256-322 (`run_cuda`, training
  * branch, a fixed sample budget) + nerf/network_ff.py:51-75 do between the rays and the image, in the order
  *   forward:  foc_march_rays_train_field -> foc_grid_encode_forward_counted -> foc_ffmlp_forward_planar -> foc_color_head_forward -> foc_occ_tail_forward
