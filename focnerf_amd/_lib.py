@@ -71,6 +71,15 @@ class FocOccTrainObject(ctypes.Structure):
     ]
 
 
+class FocOccTrainTail(ctypes.Structure):
+    """include/focnerf.h `FocOccTrainTail`, field for field: the tail's optional per-ray buffers (distortion, depth_raw), beside the node."""
+    _fields_ = [
+        ("struct_bytes", u32),
+        ("ray_dist", c_vp), ("ray_wm", c_vp), ("depth_raw", c_vp),
+        ("grad_dist", c_vp), ("grad_depth", c_vp),
+    ]
+
+
 # name -> (restype, [argtypes]) — one entry per declaration in include/focnerf.h
 SIGNATURES = {
     "foc_abi_version": (i32, []),
@@ -104,6 +113,12 @@ SIGNATURES = {
                                         c_vp]),
     "foc_occ_tail_backward_dist": (i32, [c_vp, c_vp, c_vp, c_vp, u32, c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, f32, f32, c_vp, f32, c_vp, c_vp, c_vp, c_vp,
                                          c_vp, c_vp, c_vp]),
+    "foc_occ_tail_forward_depth": (i32, [c_vp, c_vp, u32, c_vp, c_vp, u32, u32, f32, f32, c_vp, f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                         c_vp, c_vp]),
+    "foc_occ_tail_backward_depth": (i32, [c_vp, c_vp, c_vp, c_vp, u32, c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, f32, f32, c_vp, f32, c_vp, c_vp, c_vp, c_vp,
+                                          c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "foc_occ_train_forward_tail": (i32, [ctypes.POINTER(FocOccTrainNode), ctypes.POINTER(FocOccTrainObject), f32, ctypes.POINTER(FocOccTrainTail), c_vp]),
+    "foc_occ_train_backward_tail": (i32, [ctypes.POINTER(FocOccTrainNode), ctypes.POINTER(FocOccTrainObject), f32, ctypes.POINTER(FocOccTrainTail), c_vp]),
     "foc_march_rays_train_scratch_bytes": (u64, [u32, u32]),
     "foc_composite_rays_train_forward": (i32, [c_vp, c_vp, c_vp, c_vp, u32, u32, f32, c_vp, c_vp, c_vp, c_vp]),
     "foc_composite_rays_train_backward": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, f32,

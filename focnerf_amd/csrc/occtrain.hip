@@ -16,8 +16,9 @@
 // the ray became opaque, zeros for a ray that did not fit the list), and the rows behind the last ray's range are zeroed by spare
 // waves — the colour network's backward reads all M rows, and the caller's zero fill of them was a launch of its own.
 //
-// Below the kernels: the whole training node as one call each way (foc_occ_train_forward / _backward and their _pad31 and _obj forms).
-// One forward and one backward sequence serve every layout of the colour input; the six entry points differ in their checks only.
+// Below the kernels: the whole training node as one call each way (foc_occ_train_forward / _backward, their _pad31 and _obj forms, and the
+// _tail pair that carries the distortion and depth buffers beside the node). One forward and one backward sequence serve every layout of
+// the colour input; the entry points differ in their checks only.
 #include "common.h"
 #include "sample_math.h"     // foc_sigmoid_h, foc_trunc_exp_bwd, foc_bg, h8
 #include "ragged.h"          // ot_ray, ot_step, ot_grad_acc: the composite, shared with k_composite_train_fwd / _bwd
@@ -29,14 +30,16 @@
 // which the composite stopped included (0 for a ray that did not fit): lane l sums samples l, l + 64, ... in order, then one wave_sum.
 // DIST (foc_occ_tail_forward_dist): also ray_dist[ray] = the ray's distortion and ray_wm[ray] = sum w m over the samples that count (ragged.h
 // ot_dist_fwd_step; both 0 for a ray that did not fit); every other output is the bits of the instantiation without it.
-template <bool CRIT, bool DIST>
+// DEPTH (foc_occ_tail_forward_depth): also depth_raw[ray] = sum w t, the `d` below before `depth` is normalised (0 for a ray that did not fit):
+// what the backward's depth term needs beside nears / fars.
+template <bool CRIT, bool DIST, bool DEPTH>
 __global__ void __launch_bounds__(256) k_occ_tail_fwd(const _Float16 *__restrict__ h, const _Float16 *__restrict__ c, uint32_t c_ld,
                                                       const float *__restrict__ deltas, const int32_t *__restrict__ rays, uint32_t M, uint32_t N,
                                                       float T_thresh, float density_scale, const float *__restrict__ bg_ray, float bg_scalar,
                                                       const float *__restrict__ nears, const float *__restrict__ fars,
                                                       float *__restrict__ weights_sum, float *__restrict__ image_raw, float *__restrict__ image,
                                                       float *__restrict__ depth, float *__restrict__ ray_sumsq, float *__restrict__ ray_dist,
-                                                      float *__restrict__ ray_wm) {
+                                                      float *__restrict__ ray_wm, float *__restrict__ depth_raw) {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t n = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (n >= N) return;
@@ -92,6 +95,7 @@ __global__ void __launch_bounds__(256) k_occ_tail_fwd(const _Float16 *__restrict
         depth[k] = (dd < 0.0f ? 0.0f : dd) / (fars[k] - nr);
         if constexpr (CRIT) ray_sumsq[k] = sq;
         if constexpr (DIST) { ray_dist[k] = dist.acc; ray_wm[k] = dist.WM; }
+        if constexpr (DEPTH) depth_raw[k] = d;
     }
 }
 
@@ -101,7 +105,11 @@ __global__ void __launch_bounds__(256) k_occ_tail_fwd(const _Float16 *__restrict
 // DIST (foc_occ_tail_backward_dist): grad_dist [N] is the gradient of the forward's ray_dist; with g = grad_dist[ray] and G_i = d dist / d w_i
 // (ragged.h ot_dist_bwd_step) grad_sigma_i gains dt0_i (g G_i T_after_i - g sum_{j>i} G_j w_j) on the samples that count. Rows behind a stop
 // and rays that did not fit get nothing from it; a ray whose grad_dist is 0 is the plain backward's bits.
-template <bool CRIT, bool DIST>
+// DEPTH (foc_occ_tail_backward_depth): grad_depth [N] is the gradient of the forward's normalised `depth`; with s = its share of depth_raw
+// (ragged.h ot_depth_scale: 0 on a clamped ray) grad_sigma_i gains dt0_i s (T_after_i t_i - (depth_raw - D_acc_i)) on the samples that count
+// (ot_depth_bwd_step). The dt1 load and the scan of t are DIST's when both are on. Rows behind a stop, rays that did not fit and rays with
+// s == 0 get nothing from it: such a ray is the bits of the instantiation without DEPTH.
+template <bool CRIT, bool DIST, bool DEPTH>
 __global__ void __launch_bounds__(256) k_occ_tail_bwd(const float *__restrict__ grad_image, const float *__restrict__ grad_ws,
                                                       const _Float16 *__restrict__ h, const _Float16 *__restrict__ c, uint32_t c_ld,
                                                       const float *__restrict__ deltas, const int32_t *__restrict__ rays, const int32_t *__restrict__ counter,
@@ -109,7 +117,9 @@ __global__ void __launch_bounds__(256) k_occ_tail_bwd(const float *__restrict__ 
                                                       float T_thresh, float density_scale, const float *__restrict__ bg_ray, float bg_scalar,
                                                       _Float16 *__restrict__ grad_c, _Float16 *__restrict__ grad_h0,
                                                       const float *__restrict__ grad_sumsq, const float *__restrict__ ray_wm,
-                                                      const float *__restrict__ ray_dist, const float *__restrict__ grad_dist) {
+                                                      const float *__restrict__ ray_dist, const float *__restrict__ grad_dist,
+                                                      const float *__restrict__ nears, const float *__restrict__ fars,
+                                                      const float *__restrict__ depth_raw, const float *__restrict__ grad_depth) {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t n = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (blockIdx.x >= (N + 3u) / 4u) {
@@ -153,6 +163,8 @@ __global__ void __launch_bounds__(256) k_occ_tail_bwd(const float *__restrict__ 
     float gdist = 0.0f, W_total = 0.0f, WM_total = 0.0f, dist2 = 0.0f, t_carry = 0.0f;
     OtDist dist = {0, 0, 0};
     if constexpr (DIST) { gdist = grad_dist[index]; W_total = weights_sum[index]; WM_total = ray_wm[index]; dist2 = 2.0f * ray_dist[index]; }
+    float sdep = 0.0f, d_total = 0.0f, D_carry = 0.0f;
+    if constexpr (DEPTH) { d_total = depth_raw[index]; sdep = ot_depth_scale(d_total, nears[index], fars[index], grad_depth[index]); }
     float T_carry = 1.0f;
     OtColour carry = {0, 0, 0};
     bool dead = false;                                         // wave-uniform: the ray became opaque in an earlier block of 64
@@ -166,7 +178,7 @@ __global__ void __launch_bounds__(256) k_occ_tail_bwd(const float *__restrict__ 
             const float x = (float)h[s * 16];
             e_raw = expf(x);
             sigma = density_scale != 1.0f ? density_scale * e_raw : e_raw;
-            if constexpr (DIST) { const float2 dl = *reinterpret_cast<const float2 *>(deltas + s * 2); dt0 = dl.x; dt1 = dl.y; }
+            if constexpr (DIST || DEPTH) { const float2 dl = *reinterpret_cast<const float2 *>(deltas + s * 2); dt0 = dl.x; dt1 = dl.y; }
             else dt0 = deltas[s * 2];
             const uint2 raw = *reinterpret_cast<const uint2 *>(c + s * c_ld);
             const _Float16 *cc = reinterpret_cast<const _Float16 *>(&raw);
@@ -176,12 +188,20 @@ __global__ void __launch_bounds__(256) k_occ_tail_bwd(const float *__restrict__ 
         const OtStep st = ot_step(valid, sigma, dt0, T_carry, T_thresh, lane);
         const OtColour acc = ot_running(carry, st.w, c0, c1, c2, lane);
         float dist_term = 0.0f;                                // g (G_i T_after_i - sum_{j>i} G_j w_j)
-        if constexpr (DIST) {
-            if (gdist != 0.0f) {                               // wave-uniform
+        float depth_term = 0.0f;                               // s (T_after_i t_i - sum_{j>i} w_j t_j)
+        if constexpr (DIST || DEPTH) {
+            if (gdist != 0.0f || sdep != 0.0f) {               // wave-uniform
                 const float tsum = t_carry + wave_incl_sum(dt1, (int)lane);        // the forward's running t
-                float Gw_incl;
-                const float G = ot_dist_bwd_step(dist, st.w, tsum, dt0, W_total, WM_total, lane, Gw_incl);
-                dist_term = gdist * (G * st.T_after - (dist2 - Gw_incl));
+                if constexpr (DIST) {
+                    if (gdist != 0.0f) {
+                        float Gw_incl;
+                        const float G = ot_dist_bwd_step(dist, st.w, tsum, dt0, W_total, WM_total, lane, Gw_incl);
+                        dist_term = gdist * (G * st.T_after - (dist2 - Gw_incl));
+                    }
+                }
+                if constexpr (DEPTH) {
+                    if (sdep != 0.0f) depth_term = ot_depth_bwd_step(D_carry, sdep, st.w, tsum, st.T_after, d_total, lane);
+                }
                 t_carry = __shfl(tsum, 63, 64);
             }
         }
@@ -189,6 +209,7 @@ __global__ void __launch_bounds__(256) k_occ_tail_bwd(const float *__restrict__ 
             // k_composite_train_bwd: grad_rgbs = g w; grad_sigmas = dt0 (...)
             float ga = ot_grad_acc(q, st.T_after, c0, c1, c2, acc);
             if constexpr (DIST) { if (gdist != 0.0f) ga += dist_term; }
+            if constexpr (DEPTH) { if (sdep != 0.0f) ga += depth_term; }
             float gs = dt0 * ga;
             if (density_scale != 1.0f) gs = density_scale * gs;       // through `density_scale * sigmas`
             if constexpr (CRIT) gs = fmaf(gsq2, e_raw, gs);
@@ -207,15 +228,20 @@ extern "C" {
 // ray_sumsq / grad_sumsq NULL: the plain kernels (foc_occ_tail_forward / _backward); `who` names the entry point in messages
 static int occ_tail_forward(const char *who, const void *h, const void *c, uint32_t c_width, const float *deltas, const int32_t *rays, uint32_t M, uint32_t N,
                             float T_thresh, float density_scale, const float *bg_ray, float bg_scalar, const float *nears, const float *fars,
-                            float *weights_sum, float *image_raw, float *image, float *depth, float *ray_sumsq, float *ray_dist, float *ray_wm, void *stream) {
+                            float *weights_sum, float *image_raw, float *image, float *depth, float *ray_sumsq, float *ray_dist, float *ray_wm, float *depth_raw,
+                            void *stream) {
     FocDeviceGuard foc_guard_(stream, h);
     if (N == 0) return FOC_OK;
     FOC_REQUIRE(c_width == 16 || c_width == 4, FOC_E_INVALID, "%s: c_width must be 16 or 4 (got %u)", who, c_width);
     FOC_REQUIRE(rays && nears && fars && weights_sum && image_raw && image && depth && (M == 0 || (h && c && deltas)), FOC_E_INVALID, "%s: null pointer", who);
-    auto kern = ray_dist ? (ray_sumsq ? k_occ_tail_fwd<true, true> : k_occ_tail_fwd<false, true>) : (ray_sumsq ? k_occ_tail_fwd<true, false> : k_occ_tail_fwd<false, false>);
+    static constexpr decltype(&k_occ_tail_fwd<false, false, false>) kerns[8] = {
+                               k_occ_tail_fwd<false, false, false>, k_occ_tail_fwd<true, false, false>, k_occ_tail_fwd<false, true, false>,
+                               k_occ_tail_fwd<true, true, false>,   k_occ_tail_fwd<false, false, true>, k_occ_tail_fwd<true, false, true>,
+                               k_occ_tail_fwd<false, true, true>,   k_occ_tail_fwd<true, true, true>};
+    auto kern = kerns[(ray_sumsq ? 1 : 0) + (ray_dist ? 2 : 0) + (depth_raw ? 4 : 0)];
     hipLaunchKernelGGL(kern, dim3(foc_div_up(N, 4)), dim3(256), 0, (hipStream_t)stream, (const _Float16 *)h,
                        (const _Float16 *)c, c_width, deltas, rays, M, N, T_thresh, density_scale, bg_ray, bg_scalar, nears, fars, weights_sum, image_raw, image, depth,
-                       ray_sumsq, ray_dist, ray_wm);
+                       ray_sumsq, ray_dist, ray_wm, depth_raw);
     FOC_CHECK_LAUNCH(who);
     return FOC_OK;
 }
@@ -223,15 +249,20 @@ static int occ_tail_forward(const char *who, const void *h, const void *c, uint3
 static int occ_tail_backward(const char *who, const float *grad_image, const float *grad_ws, const void *h, const void *c, uint32_t c_width, const float *deltas,
                              const int32_t *rays, const int32_t *counter, const float *weights_sum, const float *image_raw, uint32_t M, uint32_t N,
                              float T_thresh, float density_scale, const float *bg_ray, float bg_scalar, void *grad_c, void *grad_h0, const float *grad_sumsq,
-                             const float *ray_wm, const float *ray_dist, const float *grad_dist, void *stream) {
+                             const float *ray_wm, const float *ray_dist, const float *grad_dist, const float *nears, const float *fars,
+                             const float *depth_raw, const float *grad_depth, void *stream) {
     FocDeviceGuard foc_guard_(stream, grad_image);
     if (N == 0 || M == 0) return FOC_OK;
     FOC_REQUIRE(c_width == 16 || c_width == 4, FOC_E_INVALID, "%s: c_width must be 16 or 4 (got %u)", who, c_width);
     FOC_REQUIRE(grad_image && h && c && deltas && rays && counter && weights_sum && image_raw && grad_c && grad_h0, FOC_E_INVALID, "%s: null pointer", who);
-    auto kern = grad_dist ? (grad_sumsq ? k_occ_tail_bwd<true, true> : k_occ_tail_bwd<false, true>) : (grad_sumsq ? k_occ_tail_bwd<true, false> : k_occ_tail_bwd<false, false>);
+    static constexpr decltype(&k_occ_tail_bwd<false, false, false>) kerns[8] = {
+                               k_occ_tail_bwd<false, false, false>, k_occ_tail_bwd<true, false, false>, k_occ_tail_bwd<false, true, false>,
+                               k_occ_tail_bwd<true, true, false>,   k_occ_tail_bwd<false, false, true>, k_occ_tail_bwd<true, false, true>,
+                               k_occ_tail_bwd<false, true, true>,   k_occ_tail_bwd<true, true, true>};
+    auto kern = kerns[(grad_sumsq ? 1 : 0) + (grad_dist ? 2 : 0) + (grad_depth ? 4 : 0)];
     hipLaunchKernelGGL(kern, dim3(foc_div_up(N, 4) + OT_PAD_BLOCKS), dim3(256), 0, (hipStream_t)stream, grad_image,
                        grad_ws, (const _Float16 *)h, (const _Float16 *)c, c_width, deltas, rays, counter, weights_sum, image_raw, M, N, T_thresh, density_scale, bg_ray,
-                       bg_scalar, (_Float16 *)grad_c, (_Float16 *)grad_h0, grad_sumsq, ray_wm, ray_dist, grad_dist);
+                       bg_scalar, (_Float16 *)grad_c, (_Float16 *)grad_h0, grad_sumsq, ray_wm, ray_dist, grad_dist, nears, fars, depth_raw, grad_depth);
     FOC_CHECK_LAUNCH(who);
     return FOC_OK;
 }
@@ -240,14 +271,14 @@ int foc_occ_tail_forward(const void *h, const void *c, uint32_t c_width, const f
                          float T_thresh, float density_scale, const float *bg_ray, float bg_scalar, const float *nears, const float *fars,
                          float *weights_sum, float *image_raw, float *image, float *depth, void *stream) {
     return occ_tail_forward("occ_tail_forward", h, c, c_width, deltas, rays, M, N, T_thresh, density_scale, bg_ray, bg_scalar, nears, fars, weights_sum, image_raw,
-                            image, depth, nullptr, nullptr, nullptr, stream);
+                            image, depth, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int foc_occ_tail_backward(const float *grad_image, const float *grad_ws, const void *h, const void *c, uint32_t c_width, const float *deltas,
                           const int32_t *rays, const int32_t *counter, const float *weights_sum, const float *image_raw, uint32_t M, uint32_t N,
                           float T_thresh, float density_scale, const float *bg_ray, float bg_scalar, void *grad_c, void *grad_h0, void *stream) {
     return occ_tail_backward("occ_tail_backward", grad_image, grad_ws, h, c, c_width, deltas, rays, counter, weights_sum, image_raw, M, N, T_thresh, density_scale,
-                             bg_ray, bg_scalar, grad_c, grad_h0, nullptr, nullptr, nullptr, nullptr, stream);
+                             bg_ray, bg_scalar, grad_c, grad_h0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int foc_occ_tail_forward_sumsq(const void *h, const void *c, uint32_t c_width, const float *deltas, const int32_t *rays, uint32_t M, uint32_t N,
@@ -255,7 +286,7 @@ int foc_occ_tail_forward_sumsq(const void *h, const void *c, uint32_t c_width, c
                                float *weights_sum, float *image_raw, float *image, float *depth, float *ray_sumsq, void *stream) {
     FOC_REQUIRE(ray_sumsq || N == 0, FOC_E_INVALID, "occ_tail_forward_sumsq: null ray_sumsq");
     return occ_tail_forward("occ_tail_forward_sumsq", h, c, c_width, deltas, rays, M, N, T_thresh, density_scale, bg_ray, bg_scalar, nears, fars, weights_sum,
-                            image_raw, image, depth, ray_sumsq, nullptr, nullptr, stream);
+                            image_raw, image, depth, ray_sumsq, nullptr, nullptr, nullptr, stream);
 }
 
 int foc_occ_tail_backward_sumsq(const float *grad_image, const float *grad_ws, const void *h, const void *c, uint32_t c_width, const float *deltas,
@@ -264,7 +295,7 @@ int foc_occ_tail_backward_sumsq(const float *grad_image, const float *grad_ws, c
                                 const float *grad_sumsq, void *stream) {
     FOC_REQUIRE(grad_sumsq || N == 0 || M == 0, FOC_E_INVALID, "occ_tail_backward_sumsq: null grad_sumsq");
     return occ_tail_backward("occ_tail_backward_sumsq", grad_image, grad_ws, h, c, c_width, deltas, rays, counter, weights_sum, image_raw, M, N, T_thresh,
-                             density_scale, bg_ray, bg_scalar, grad_c, grad_h0, grad_sumsq, nullptr, nullptr, nullptr, stream);
+                             density_scale, bg_ray, bg_scalar, grad_c, grad_h0, grad_sumsq, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 // the two tails with the ray distortion (include/focnerf.h); ray_sumsq / grad_sumsq may be NULL: with or without the criterion
@@ -273,7 +304,7 @@ int foc_occ_tail_forward_dist(const void *h, const void *c, uint32_t c_width, co
                               float *weights_sum, float *image_raw, float *image, float *depth, float *ray_sumsq, float *ray_dist, float *ray_wm, void *stream) {
     FOC_REQUIRE((ray_dist && ray_wm) || N == 0, FOC_E_INVALID, "occ_tail_forward_dist: null ray_dist / ray_wm");
     return occ_tail_forward("occ_tail_forward_dist", h, c, c_width, deltas, rays, M, N, T_thresh, density_scale, bg_ray, bg_scalar, nears, fars, weights_sum,
-                            image_raw, image, depth, ray_sumsq, ray_dist, ray_wm, stream);
+                            image_raw, image, depth, ray_sumsq, ray_dist, ray_wm, nullptr, stream);
 }
 
 int foc_occ_tail_backward_dist(const float *grad_image, const float *grad_ws, const void *h, const void *c, uint32_t c_width, const float *deltas,
@@ -282,7 +313,29 @@ int foc_occ_tail_backward_dist(const float *grad_image, const float *grad_ws, co
                                const float *grad_sumsq, const float *ray_wm, const float *ray_dist, const float *grad_dist, void *stream) {
     FOC_REQUIRE(!grad_dist || (ray_wm && ray_dist) || N == 0 || M == 0, FOC_E_INVALID, "occ_tail_backward_dist: grad_dist needs ray_wm and ray_dist");
     return occ_tail_backward("occ_tail_backward_dist", grad_image, grad_ws, h, c, c_width, deltas, rays, counter, weights_sum, image_raw, M, N, T_thresh,
-                             density_scale, bg_ray, bg_scalar, grad_c, grad_h0, grad_sumsq, ray_wm, ray_dist, grad_dist, stream);
+                             density_scale, bg_ray, bg_scalar, grad_c, grad_h0, grad_sumsq, ray_wm, ray_dist, grad_dist, nullptr, nullptr, nullptr, nullptr, stream);
+}
+
+// the supersets of the pairs above (include/focnerf.h): every extra output / incoming gradient optional, the depth's among them
+int foc_occ_tail_forward_depth(const void *h, const void *c, uint32_t c_width, const float *deltas, const int32_t *rays, uint32_t M, uint32_t N,
+                               float T_thresh, float density_scale, const float *bg_ray, float bg_scalar, const float *nears, const float *fars,
+                               float *weights_sum, float *image_raw, float *image, float *depth, float *ray_sumsq, float *ray_dist, float *ray_wm,
+                               float *depth_raw, void *stream) {
+    FOC_REQUIRE((ray_dist != nullptr) == (ray_wm != nullptr), FOC_E_INVALID, "occ_tail_forward_depth: ray_dist and ray_wm come together");
+    return occ_tail_forward("occ_tail_forward_depth", h, c, c_width, deltas, rays, M, N, T_thresh, density_scale, bg_ray, bg_scalar, nears, fars, weights_sum,
+                            image_raw, image, depth, ray_sumsq, ray_dist, ray_wm, depth_raw, stream);
+}
+
+int foc_occ_tail_backward_depth(const float *grad_image, const float *grad_ws, const void *h, const void *c, uint32_t c_width, const float *deltas,
+                                const int32_t *rays, const int32_t *counter, const float *weights_sum, const float *image_raw, uint32_t M, uint32_t N,
+                                float T_thresh, float density_scale, const float *bg_ray, float bg_scalar, void *grad_c, void *grad_h0,
+                                const float *grad_sumsq, const float *ray_wm, const float *ray_dist, const float *grad_dist, const float *nears,
+                                const float *fars, const float *depth_raw, const float *grad_depth, void *stream) {
+    FOC_REQUIRE(!grad_dist || (ray_wm && ray_dist) || N == 0 || M == 0, FOC_E_INVALID, "occ_tail_backward_depth: grad_dist needs ray_wm and ray_dist");
+    FOC_REQUIRE(!grad_depth || (depth_raw && nears && fars) || N == 0 || M == 0, FOC_E_INVALID,
+                "occ_tail_backward_depth: grad_depth needs depth_raw, nears and fars");
+    return occ_tail_backward("occ_tail_backward_depth", grad_image, grad_ws, h, c, c_width, deltas, rays, counter, weights_sum, image_raw, M, N, T_thresh,
+                             density_scale, bg_ray, bg_scalar, grad_c, grad_h0, grad_sumsq, ray_wm, ray_dist, grad_dist, nears, fars, depth_raw, grad_depth, stream);
 }
 
 // ---------------------------------------------------------------- the node as one call each way
@@ -328,8 +381,9 @@ static int ot_check_object(const FocOccTrainNode *n, const FocOccTrainObject *ob
 }
 
 // march -> counted encode -> both networks (one kernel, or sigma MLP + colour head) -> tail. ray_sumsq [n_rays] or NULL: the tail that
-// also sums sigma^2 per ray.
-static int occ_train_forward(const FocOccTrainNode *n, const void *obj_feat, float input_pad, bool pad31, float *ray_sumsq, void *stream) {
+// also sums sigma^2 per ray. tail (FocOccTrainTail beside the node) or NULL: the tail that also returns the distortion and / or depth_raw.
+static int occ_train_forward(const FocOccTrainNode *n, const void *obj_feat, float input_pad, bool pad31, float *ray_sumsq, const FocOccTrainTail *tail,
+                             void *stream) {
     const uint32_t M = n->cap;
     int rc = foc_march_rays_train_field(n->rays_o, n->rays_d, n->bitfield, n->bound, n->dt_gamma, n->max_steps, n->n_rays, n->cascade, n->grid_size, M, n->nears,
                                         n->fars, n->enc_in, n->sh_rows, n->deltas, n->rays, n->counter, n->jitter, n->march_scratch, n->pad_align, n->aabb, n->min_near,
@@ -352,18 +406,21 @@ static int occ_train_forward(const FocOccTrainNode *n, const void *obj_feat, flo
                                 stream);
         if (rc != FOC_OK) return rc;
     }
-    return occ_tail_forward(ray_sumsq ? "occ_tail_forward_sumsq" : "occ_tail_forward", n->h, n->c, n->c_width, n->deltas, n->rays, M, n->n_rays, n->T_thresh,
-                            n->density_scale, n->bg_ray, n->bg_scalar, n->nears, n->fars, n->weights_sum, n->image_raw, n->image, n->depth, ray_sumsq, nullptr, nullptr,
-                            stream);
+    return occ_tail_forward(tail ? "occ_tail_forward_depth" : ray_sumsq ? "occ_tail_forward_sumsq" : "occ_tail_forward", n->h, n->c, n->c_width, n->deltas, n->rays,
+                            M, n->n_rays, n->T_thresh, n->density_scale, n->bg_ray, n->bg_scalar, n->nears, n->fars, n->weights_sum, n->image_raw, n->image, n->depth,
+                            ray_sumsq, tail ? tail->ray_dist : nullptr, tail ? tail->ray_wm : nullptr, tail ? tail->depth_raw : nullptr, stream);
 }
 
 // tail -> colour head -> sigma MLP -> binned encoder backward. grad_sumsq [n_rays] or NULL: the gradient of the forward's ray_sumsq;
-// grad_obj [16] fp32 or NULL: the object feature's gradient.
-static int occ_train_backward(const FocOccTrainNode *n, const void *obj_feat, float input_pad, bool pad31, const float *grad_sumsq, float *grad_obj, void *stream) {
+// grad_obj [16] fp32 or NULL: the object feature's gradient. tail or NULL: the gradients of the distortion and / or the depth.
+static int occ_train_backward(const FocOccTrainNode *n, const void *obj_feat, float input_pad, bool pad31, const float *grad_sumsq, float *grad_obj,
+                              const FocOccTrainTail *tail, void *stream) {
     const uint32_t M = n->cap;
-    int rc = occ_tail_backward(grad_sumsq ? "occ_tail_backward_sumsq" : "occ_tail_backward", n->grad_image, n->grad_ws, n->h, n->c, n->c_width, n->deltas, n->rays,
-                               n->counter, n->weights_sum, n->image_raw, M, n->n_rays, n->T_thresh, n->density_scale, n->bg_ray, n->bg_scalar, n->grad_c, n->grad_h0,
-                               grad_sumsq, nullptr, nullptr, nullptr, stream);
+    const float *grad_dist = tail ? tail->grad_dist : nullptr, *grad_depth = tail ? tail->grad_depth : nullptr;
+    int rc = occ_tail_backward(tail ? "occ_tail_backward_depth" : grad_sumsq ? "occ_tail_backward_sumsq" : "occ_tail_backward", n->grad_image, n->grad_ws, n->h, n->c,
+                               n->c_width, n->deltas, n->rays, n->counter, n->weights_sum, n->image_raw, M, n->n_rays, n->T_thresh, n->density_scale, n->bg_ray,
+                               n->bg_scalar, n->grad_c, n->grad_h0, grad_sumsq, grad_dist ? tail->ray_wm : nullptr, grad_dist ? tail->ray_dist : nullptr, grad_dist,
+                               grad_depth ? n->nears : nullptr, grad_depth ? n->fars : nullptr, grad_depth ? tail->depth_raw : nullptr, grad_depth, stream);
     if (rc != FOC_OK) return rc;
     rc = color_head_backward(n->grad_c, n->h, n->sh_rows, 1, n->grad_h0, n->w_color, M, n->color_hidden, n->color_layers, n->color_activation, n->grad_h,
                              n->grad_w_color, n->mlp_workspace, n->mlp_workspace_bytes, n->c_width, obj_feat, grad_obj, input_pad, pad31, stream);
@@ -378,31 +435,31 @@ static int occ_train_backward(const FocOccTrainNode *n, const void *obj_feat, fl
 
 int foc_occ_train_forward(const FocOccTrainNode *n, void *stream) {
     const int rc = ot_check_node(n, "occ_train_forward");
-    return rc != FOC_OK ? rc : occ_train_forward(n, nullptr, 0.0f, false, nullptr, stream);
+    return rc != FOC_OK ? rc : occ_train_forward(n, nullptr, 0.0f, false, nullptr, nullptr, stream);
 }
 
 int foc_occ_train_backward(const FocOccTrainNode *n, void *stream) {
     const int rc = ot_check_node(n, "occ_train_backward");
-    return rc != FOC_OK ? rc : occ_train_backward(n, nullptr, 0.0f, false, nullptr, nullptr, stream);
+    return rc != FOC_OK ? rc : occ_train_backward(n, nullptr, 0.0f, false, nullptr, nullptr, nullptr, stream);
 }
 
 // column 31 of the 32-wide colour input holds input_pad (the legacy tinycudann layout)
 int foc_occ_train_forward_pad31(const FocOccTrainNode *n, float input_pad, void *stream) {
     int rc = ot_check_node(n, "occ_train_forward_pad31");
     if (rc == FOC_OK) rc = ot_check_pad31(n, input_pad, "occ_train_forward_pad31");
-    return rc != FOC_OK ? rc : occ_train_forward(n, nullptr, input_pad, true, nullptr, stream);
+    return rc != FOC_OK ? rc : occ_train_forward(n, nullptr, input_pad, true, nullptr, nullptr, stream);
 }
 
 int foc_occ_train_backward_pad31(const FocOccTrainNode *n, float input_pad, void *stream) {
     int rc = ot_check_node(n, "occ_train_backward_pad31");
     if (rc == FOC_OK) rc = ot_check_pad31(n, input_pad, "occ_train_backward_pad31");
-    return rc != FOC_OK ? rc : occ_train_backward(n, nullptr, input_pad, true, nullptr, nullptr, stream);
+    return rc != FOC_OK ? rc : occ_train_backward(n, nullptr, input_pad, true, nullptr, nullptr, nullptr, stream);
 }
 
 // the 48-wide colour head of an object-conditioned network: the feature, its pad (column 47) and the sums of sigma^2 travel in `ob`
 int foc_occ_train_forward_obj(const FocOccTrainNode *n, const FocOccTrainObject *ob, void *stream) {
     const int rc = ot_check_object(n, ob, "occ_train_forward_obj");
-    return rc != FOC_OK ? rc : occ_train_forward(n, ob->obj_feat, ob->input_pad, false, ob->ray_sumsq, stream);
+    return rc != FOC_OK ? rc : occ_train_forward(n, ob->obj_feat, ob->input_pad, false, ob->ray_sumsq, nullptr, stream);
 }
 
 int foc_occ_train_backward_obj(const FocOccTrainNode *n, const FocOccTrainObject *ob, void *stream) {
@@ -411,7 +468,39 @@ int foc_occ_train_backward_obj(const FocOccTrainNode *n, const FocOccTrainObject
     FOC_REQUIRE(n->mlp_workspace_bytes >= foc_ffmlp_backward_workspace_bytes(48, 64, n->color_layers), FOC_E_INVALID,
                 "occ_train_backward_obj: MLP workspace of %llu bytes, the 48-wide colour head asks for foc_ffmlp_backward_workspace_bytes(48, 64, %u) = %llu",
                 (unsigned long long)n->mlp_workspace_bytes, n->color_layers, (unsigned long long)foc_ffmlp_backward_workspace_bytes(48, 64, n->color_layers));
-    return occ_train_backward(n, ob->obj_feat, ob->input_pad, false, ob->grad_sumsq, ob->grad_obj, stream);
+    return occ_train_backward(n, ob->obj_feat, ob->input_pad, false, ob->grad_sumsq, ob->grad_obj, nullptr, stream);
+}
+
+// The node with the tail's optional per-ray outputs (FocOccTrainTail beside it): one pair for the three layouts. object NULL: the plain
+// layout (input_pad 0) or column 31 = input_pad; else the object's own pad, input_pad is not read.
+static int ot_check_tail(const FocOccTrainNode *n, const FocOccTrainObject *ob, float input_pad, const FocOccTrainTail *tail, const char *who) {
+    int rc = ob ? ot_check_object(n, ob, who) : ot_check_node(n, who);
+    if (rc == FOC_OK && !ob) rc = ot_check_pad31(n, input_pad, who);
+    if (rc != FOC_OK) return rc;
+    FOC_REQUIRE(tail != nullptr, FOC_E_INVALID, "%s: null tail (a node without the tail's extra outputs takes foc_occ_train_forward / _backward and their twins)", who);
+    FOC_REQUIRE(tail->struct_bytes == (uint32_t)sizeof(FocOccTrainTail), FOC_E_INVALID, "%s: tail of %u bytes, this library's FocOccTrainTail has %zu", who,
+                tail->struct_bytes, sizeof(FocOccTrainTail));
+    FOC_REQUIRE((tail->ray_dist != nullptr) == (tail->ray_wm != nullptr), FOC_E_INVALID, "%s: ray_dist and ray_wm come together", who);
+    return FOC_OK;
+}
+
+int foc_occ_train_forward_tail(const FocOccTrainNode *n, const FocOccTrainObject *ob, float input_pad, const FocOccTrainTail *tail, void *stream) {
+    const int rc = ot_check_tail(n, ob, input_pad, tail, "occ_train_forward_tail");
+    if (rc != FOC_OK) return rc;
+    return ob ? occ_train_forward(n, ob->obj_feat, ob->input_pad, false, ob->ray_sumsq, tail, stream)
+              : occ_train_forward(n, nullptr, input_pad, input_pad != 0.0f, nullptr, tail, stream);
+}
+
+int foc_occ_train_backward_tail(const FocOccTrainNode *n, const FocOccTrainObject *ob, float input_pad, const FocOccTrainTail *tail, void *stream) {
+    const int rc = ot_check_tail(n, ob, input_pad, tail, "occ_train_backward_tail");
+    if (rc != FOC_OK) return rc;
+    FOC_REQUIRE(!tail->grad_dist || tail->ray_dist, FOC_E_INVALID, "occ_train_backward_tail: grad_dist needs ray_wm and ray_dist");
+    FOC_REQUIRE(!tail->grad_depth || (tail->depth_raw && n->nears && n->fars), FOC_E_INVALID, "occ_train_backward_tail: grad_depth needs depth_raw, nears and fars");
+    if (!ob) return occ_train_backward(n, nullptr, input_pad, input_pad != 0.0f, nullptr, nullptr, tail, stream);
+    FOC_REQUIRE(n->mlp_workspace_bytes >= foc_ffmlp_backward_workspace_bytes(48, 64, n->color_layers), FOC_E_INVALID,
+                "occ_train_backward_tail: MLP workspace of %llu bytes, the 48-wide colour head asks for foc_ffmlp_backward_workspace_bytes(48, 64, %u) = %llu",
+                (unsigned long long)n->mlp_workspace_bytes, n->color_layers, (unsigned long long)foc_ffmlp_backward_workspace_bytes(48, 64, n->color_layers));
+    return occ_train_backward(n, ob->obj_feat, ob->input_pad, false, ob->grad_sumsq, ob->grad_obj, tail, stream);
 }
 
 } // extern "C"

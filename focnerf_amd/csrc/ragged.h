@@ -84,3 +84,17 @@ __device__ __forceinline__ float ot_dist_bwd_step(OtDist &d, float w, float m, f
     d.acc = __shfl(Gw_incl, 63, 64);
     return G;
 }
+
+// ---------------------------------------------------------------- depth gradient (include/focnerf.h foc_occ_tail_backward_depth)
+// depth = clamp(depth_raw - near, 0) / (far - near), depth_raw = sum_i w_i t_i over the samples that count (t_i = the forward's tsum). Per ray
+// s = d loss / d depth_raw: the forward's own clamp branch (the gradient passes at exactly 0, as torch.clamp(min=0) does), 0 on a ray with
+// !(far > near). Per sample grad_sigma_i / dt0_i gains s (T_after_i t_i - (depth_raw - D_acc_i)), D_acc_i = sum_{j<=i} w_j t_j: the colour
+// term of ot_grad_acc with t in the colour's place, one wave scan and a carry (D_carry: the sum in front of the step, moved behind it).
+__device__ __forceinline__ float ot_depth_scale(float depth_raw, float near, float far, float grad_depth) {
+    return (depth_raw - near < 0.0f || !(far > near)) ? 0.0f : grad_depth / (far - near);
+}
+__device__ __forceinline__ float ot_depth_bwd_step(float &D_carry, float s, float w, float t, float T_after, float depth_raw, uint32_t lane) {
+    const float D_acc = D_carry + wave_incl_sum(w * t, (int)lane);
+    D_carry = __shfl(D_acc, 63, 64);
+    return s * fmaf(T_after, t, -(depth_raw - D_acc));
+}

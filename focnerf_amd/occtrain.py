@@ -21,8 +21,10 @@ ONE node, `_occ_train`, serves the three layouts of the colour input, and its co
 Without an object feature the library calls, the buffers and the values are those of the plain node.
 
 `want_dist` (run_cuda(..., distortion=True)): the tail also returns the per-ray distortion of mip-NeRF 360 (foc_occ_tail_forward_dist /
-_backward_dist), differentiable. The one-call node and its structs do not carry it: with `want_dist` the node takes the call-by-call
-chain (`_native_plan` returns None) — the same kernels enqueued from Python; what that costs in host time per step is not measured.
+_backward_dist), differentiable. `want_depth_grad` (run_cuda(..., depth_grad=True)): `depth` carries a gradient (the tail also keeps
+depth_raw = sum w t, foc_occ_tail_forward_depth / _backward_depth); without it `depth` is marked non-differentiable, as the reference's
+composite ignores grad_depth. The buffers of both travel beside the node in a FocOccTrainTail, and with either keyword the one-call route is
+foc_occ_train_forward_tail / _backward_tail for every layout; the call-by-call chain calls the tail entry points itself.
 """
 import ctypes
 import os
@@ -31,7 +33,7 @@ from dataclasses import dataclass
 import torch
 from torch.autograd import Function
 
-from ._lib import lib, ptr, stream_of, check, FocOccTrainNode, FocOccTrainObject, FOC_F16
+from ._lib import lib, ptr, stream_of, check, FocOccTrainNode, FocOccTrainObject, FocOccTrainTail, FOC_F16
 from .backend import _gridencoder, _ffmlp, _scratch
 from .field import MlpShape, _half_of, fused_mlp, object_feature_half, pad_twin
 from .fixedstep import _C_WIDTH, _background
@@ -56,12 +58,12 @@ def _no_jitter(n, dev):
 _mlp_bytes = {}
 
 
-def _native_plan(offsets, grid, L, M, sigma, colour, colour_in=32, want_dist=False):
+def _native_plan(offsets, grid, L, M, sigma, colour, colour_in=32):
     """(grid workspace bytes, MLP workspace bytes) when the node can run as ONE library call each way (include/focnerf.h FocOccTrainNode:
     the encoder's counted forward and binned backward must apply, the switches that take other paths must be at their defaults), else None.
     FOC_OCC_NATIVE_NODE=0: always the call-by-call chain below (the tests compare the two). colour_in 48: the object-conditioned head,
-    whose workspace starts with a 48-wide blob image. want_dist: None — FocOccTrainNode has no place for the distortion buffers."""
-    if want_dist or os.environ.get("FOC_OCC_NATIVE_NODE", "1") == "0" or _gridencoder.precount_standalone():
+    whose workspace starts with a 48-wide blob image."""
+    if os.environ.get("FOC_OCC_NATIVE_NODE", "1") == "0" or _gridencoder.precount_standalone():
         return None
     grid_bytes = _gridencoder.binned_workspace_bytes(offsets, M, 3, 2, L, grid.log2_scale, grid.base_resolution, grid.gridtype, FOC_F16,
                                                      count_ahead=True)
@@ -109,7 +111,8 @@ class OccTrainConfig:
     colour: MlpShape
     colour_input_pad: float             # the colour input's last column (plan.colour_input_pad): 31 of the 32-wide row, 47 with an object feature
     want_sumsq: bool                    # the tail also returns the per-ray sums of sigma^2 (an object-conditioned network with a ray mask)
-    want_dist: bool = False             # the tail also returns the per-ray distortion (call-by-call chain only)
+    want_dist: bool = False             # the tail also returns the per-ray distortion
+    want_depth_grad: bool = False       # `depth` carries a gradient (the tail also keeps depth_raw)
 
 
 _NODE_FIELDS = frozenset(name for name, _ in FocOccTrainNode._fields_)
@@ -138,9 +141,10 @@ class _occ_train(Function):
     (pad 0) or the legacy tinycudann layout (column 31 = pad). obj [16] (any float dtype): the 48-wide colour head with the encoded object
     feature, which is differentiable, column 47 = pad; with cfg.want_sumsq the tail also returns ray_sumsq [n] = the sum of sigma^2 over all
     of a ray's samples (include/focnerf.h foc_occ_tail_forward_sumsq), differentiable too. With cfg.want_dist ray_dist [n] = the ray's distortion
-    (foc_occ_tail_forward_dist), differentiable, with or without ray_sumsq. Two routes: the one-call node
-    (foc_occ_train_forward / _backward, their _pad31 or _obj form) and the call-by-call chain (FOC_OCC_NATIVE_NODE=0, an unbudgeted list,
-    want_dist)."""
+    (foc_occ_tail_forward_dist), differentiable, with or without ray_sumsq. With cfg.want_depth_grad `depth` is differentiable
+    (foc_occ_tail_backward_depth), else marked non-differentiable. Two routes: the one-call node (foc_occ_train_forward / _backward, their
+    _pad31 or _obj form; with want_dist or want_depth_grad the _tail pair) and the call-by-call chain (FOC_OCC_NATIVE_NODE=0, an
+    unbudgeted list)."""
 
     @staticmethod
     def forward(ctx, emb, w_sigma, w_color, obj, o, d, aabb, bitfield, counter, bg_ray, cfg):
@@ -162,11 +166,13 @@ class _occ_train(Function):
         out = torch.empty(n * (9 if want_sumsq else 8), dtype=torch.float32, device=dev)
         ws, depth, image_raw, image = out[:n], out[n: 2 * n], out[2 * n: 5 * n].view(n, 3), out[5 * n: 8 * n].view(n, 3)
         sumsq = out[8 * n:] if want_sumsq else None
-        want_dist = cfg.want_dist
-        plan = _native_plan(offsets, grid, L, cap, sigma, colour, 32 if obj is None else 48, want_dist) if (budgeted and cap > 0 and n > 0) else None
-        dist = wm = None
+        want_dist, want_depth = cfg.want_dist, cfg.want_depth_grad
+        plan = _native_plan(offsets, grid, L, cap, sigma, colour, 32 if obj is None else 48) if (budgeted and cap > 0 and n > 0) else None
+        rays_out = torch.empty((2 * want_dist + want_depth) * n, dtype=torch.float32, device=dev) if (want_dist or want_depth) else None
+        dist, wm = (rays_out[:n], rays_out[n: 2 * n]) if want_dist else (None, None)
+        draw = rays_out[2 * n * want_dist:] if want_depth else None          # depth_raw: the composite's depth before its normalisation
         M = cap
-        ctx.node = ctx.object = None
+        ctx.node = ctx.object = ctx.tail = None
         if plan is not None:
             # the whole forward as one library call (csrc/occtrain.hip foc_occ_train_forward): the same five entry points in the same order,
             # enqueued from C — the step's host time no longer depends on nine trips through the binding
@@ -177,9 +183,16 @@ class _occ_train(Function):
             nd = _forward_node(cfg, n, M, plan[0], rays_o=o, rays_d=d, aabb=aabb, jitter=jitter, bitfield=bitfield, nears=nears, fars=fars, enc_in=enc_in,
                                deltas=deltas, sh_rows=sh, rays=rays, counter=counter, march_scratch=scratch, embeddings=emb16, planes=planes, grid_workspace=gws,
                                w_sigma=ws16, w_color=wc16, h=h, c=c, bg_ray=bg_ray, weights_sum=ws, image_raw=image_raw, image=image, depth=depth)
+            ob = None
             if obj is not None:                             # what the object adds travels beside the node
                 ob = ctx.object = FocOccTrainObject()
                 ob.struct_bytes, ob.input_pad, ob.obj_feat, ob.ray_sumsq = ctypes.sizeof(FocOccTrainObject), float(pad), _a(obj16), _a(sumsq)
+            if rays_out is not None:                        # so do the tail's optional outputs: one entry point for the three layouts
+                tl = ctx.tail = FocOccTrainTail()
+                tl.struct_bytes, tl.ray_dist, tl.ray_wm, tl.depth_raw = ctypes.sizeof(FocOccTrainTail), _a(dist), _a(wm), _a(draw)
+                check(lib.foc_occ_train_forward_tail(ctypes.byref(nd), ctypes.byref(ob) if ob is not None else None, pad, ctypes.byref(tl), st),
+                      "occ_train_forward_tail")
+            elif ob is not None:
                 check(lib.foc_occ_train_forward_obj(ctypes.byref(nd), ctypes.byref(ob), st), "occ_train_forward_obj")
             elif pad != 0:                                  # column 31 of the colour input = pad: the node's twin, the pad beside the node
                 check(lib.foc_occ_train_forward_pad31(ctypes.byref(nd), pad, st), "occ_train_forward_pad31")
@@ -207,15 +220,17 @@ class _occ_train(Function):
                 check(fn(ptr(h), ptr(sh), 1, ptr(wc16), M, 64, colour.num_layers, colour.activation, ptr(c), _C_WIDTH, ptr(obj16), *extra, st), "color_head_forward")
             tail = (ptr(h), ptr(c), _C_WIDTH, ptr(deltas), ptr(rays), M, n, cfg.T_thresh, cfg.density_scale, ptr(bg_ray), cfg.bg_scalar,
                     ptr(nears), ptr(fars), ptr(ws), ptr(image_raw), ptr(image), ptr(depth))
-            if want_dist:
-                dist, wm = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
+            if want_depth:
+                check(lib.foc_occ_tail_forward_depth(*tail, ptr(sumsq), ptr(dist), ptr(wm), ptr(draw), st), "occ_tail_forward_depth")
+            elif want_dist:
                 check(lib.foc_occ_tail_forward_dist(*tail, ptr(sumsq), ptr(dist), ptr(wm), st), "occ_tail_forward_dist")
             elif want_sumsq:
                 check(lib.foc_occ_tail_forward_sumsq(*tail, ptr(sumsq), st), "occ_tail_forward_sumsq")
             else:
                 check(lib.foc_occ_tail_forward(*tail, st), "occ_tail_forward")
         ctx.save_for_backward(enc_in, emb16, ws16, wc16, offsets, planes, h, c, sh, deltas, rays, counter, ws, image_raw,
-                              bg_ray if bg_ray is not None else torch.empty(0, device=dev), *((dist, wm) if want_dist else ()))
+                              bg_ray if bg_ray is not None else torch.empty(0, device=dev), *((rays_out,) if rays_out is not None else ()))
+        ctx.want = (want_dist, want_depth)
         ctx.obj16 = obj16
         ctx.obj_like = (obj.dtype, obj.shape) if obj is not None else None
         ctx.bg_grad = bg_ray is not None and ctx.needs_input_grad[9]
@@ -223,20 +238,26 @@ class _occ_train(Function):
         ctx.nears_fars = nf
         ctx.cfg = (M, n, cfg.T_thresh, cfg.density_scale, cfg.bg_scalar, grid, sigma, colour, pad)
         ctx.ticket = ticket
-        ctx.mark_non_differentiable(depth)
+        if not want_depth:
+            ctx.mark_non_differentiable(depth)
         ctx.set_materialize_grads(False)
         return image, ws, depth, sumsq, dist
 
     @staticmethod
-    def backward(ctx, g_image, g_ws, _g_depth, g_sumsq, g_dist=None):
+    def backward(ctx, g_image, g_ws, g_depth, g_sumsq, g_dist=None):
         """-> the gradients of the embeddings, the two weight blobs, obj (in its dtype and shape) and a per-ray background."""
-        enc_in, emb16, ws16, wc16, offsets, planes, h, c, sh, deltas, rays, counter, ws, image_raw, bg_ray, *dist_wm = ctx.saved_tensors
+        enc_in, emb16, ws16, wc16, offsets, planes, h, c, sh, deltas, rays, counter, ws, image_raw, bg_ray, *rays_out = ctx.saved_tensors
         M, n, T_thresh, density_scale, bg_scalar, grid, sigma, colour, pad = ctx.cfg
         S, H, (gridtype, align_corners, interp) = grid.log2_scale, grid.base_resolution, grid.tail()
         obj16 = ctx.obj16
         dev = h.device
         st = stream_of(h)
         L = offsets.shape[0] - 1
+        want_dist, want_depth = ctx.want
+        if not want_depth:
+            g_depth = None                                      # the reference's composite ignores grad_depth (raymarching.cu:601-693)
+        dist, wm = (rays_out[0][:n], rays_out[0][n: 2 * n]) if want_dist else (None, None)
+        draw = rays_out[0][2 * n * want_dist:] if want_depth else None
 
         def result(g_emb, g_wsig, g_wcol, g_obj, g_bg):
             if g_obj is not None:
@@ -245,12 +266,14 @@ class _occ_train(Function):
 
         g_emb = torch.zeros_like(emb16)
         g_wsig, g_wcol = torch.empty_like(ws16), torch.empty_like(wc16)
-        if M == 0 or (g_image is None and g_ws is None and g_sumsq is None and g_dist is None):
+        if M == 0 or (g_image is None and g_ws is None and g_sumsq is None and g_dist is None and g_depth is None):
             g_bg = g_image * (1 - ws).unsqueeze(-1) if ctx.bg_grad and g_image is not None else None
             return result(g_emb, g_wsig.zero_(), g_wcol.zero_(), (torch.zeros(16, dtype=torch.float32, device=dev) if obj16 is not None else None), g_bg)
         g_image = g_image.contiguous().float() if g_image is not None else torch.zeros(n, 3, dtype=torch.float32, device=dev)
         g_ws = g_ws.contiguous().float() if g_ws is not None else None
         g_sumsq = g_sumsq.contiguous().float() if g_sumsq is not None else None
+        g_dist = g_dist.contiguous().float() if g_dist is not None else None
+        g_depth = g_depth.contiguous().float() if g_depth is not None else None
         # a learned background (network_linear.py): image = raw + (1 - ws) bg
         g_bg = g_image * (1 - ws).unsqueeze(-1) if ctx.bg_grad else None
         g_obj = torch.empty(16, dtype=torch.float32, device=dev) if obj16 is not None else None
@@ -266,23 +289,31 @@ class _occ_train(Function):
             nd.grad_planes, nd.grad_w_color, nd.grad_w_sigma, nd.grad_embeddings = _a(g_planes), _a(g_wcol), _a(g_wsig), _a(g_emb)
             nd.mlp_workspace, nd.mlp_workspace_bytes, nd.grid_workspace, nd.grid_workspace_bytes = _a(mws), mws.numel(), _a(gws), ctx.plan[0]
             nd.precounted = int(_gridencoder._precount_valid(ctx.ticket, enc_in, M, L, FOC_F16, gws))
-            ob = ctx.object
+            ob, tl = ctx.object, ctx.tail
             if ob is not None:
                 ob.grad_sumsq, ob.grad_obj = _a(g_sumsq), _a(g_obj)
+            if tl is not None:
+                tl.grad_dist, tl.grad_depth = _a(g_dist), _a(g_depth)
+                check(lib.foc_occ_train_backward_tail(ctypes.byref(nd), ctypes.byref(ob) if ob is not None else None, pad, ctypes.byref(tl), st),
+                      "occ_train_backward_tail")
+            elif ob is not None:
                 check(lib.foc_occ_train_backward_obj(ctypes.byref(nd), ctypes.byref(ob), st), "occ_train_backward_obj")
             elif pad != 0:
                 check(lib.foc_occ_train_backward_pad31(ctypes.byref(nd), pad, st), "occ_train_backward_pad31")
             else:
                 check(lib.foc_occ_train_backward(ctypes.byref(nd), st), "occ_train_backward")
             _gridencoder._invalidate_precount(dev)              # the header now belongs to this pass (and a used ticket is spent)
-            ctx.node = ctx.object = None
+            ctx.node = ctx.object = ctx.tail = None
             return result(g_emb, g_wsig, g_wcol, g_obj, g_bg)
         grad_c, grad_h0 = gblock[: M * _C_WIDTH].view(M, _C_WIDTH), gblock[M * _C_WIDTH:]
         tail = (ptr(g_image), ptr(g_ws), ptr(h), ptr(c), _C_WIDTH, ptr(deltas), ptr(rays), ptr(counter), ptr(ws), ptr(image_raw), M, n,
                 T_thresh, density_scale, ptr(bg_ray if ctx.has_bg else None), bg_scalar, ptr(grad_c), ptr(grad_h0))
-        if g_dist is not None:
-            dist, wm = dist_wm
-            check(lib.foc_occ_tail_backward_dist(*tail, ptr(g_sumsq), ptr(wm), ptr(dist), ptr(g_dist.contiguous().float()), st), "occ_tail_backward_dist")
+        if want_depth:
+            nf = ctx.nears_fars
+            check(lib.foc_occ_tail_backward_depth(*tail, ptr(g_sumsq), ptr(wm), ptr(dist), ptr(g_dist), ptr(nf[0]), ptr(nf[1]), ptr(draw), ptr(g_depth), st),
+                  "occ_tail_backward_depth")
+        elif g_dist is not None:
+            check(lib.foc_occ_tail_backward_dist(*tail, ptr(g_sumsq), ptr(wm), ptr(dist), ptr(g_dist), st), "occ_tail_backward_dist")
         elif g_sumsq is not None:
             check(lib.foc_occ_tail_backward_sumsq(*tail, ptr(g_sumsq), st), "occ_tail_backward_sumsq")
         else:
@@ -308,9 +339,10 @@ def ray_mask(mask, n):
 
 
 def render_occupancy_train(model, plan, o, d, counter, bg_color, perturb, force_all_rays, dt_gamma, max_steps, T_thresh, align, obj16=None, want_sumsq=False,
-                           want_dist=False):
+                           want_dist=False, want_depth_grad=False):
     """o, d [n,3] fp32 contiguous, counter int32[2] (zeroed by the caller) -> (image [n,3], weights_sum [n], depth [n], ray_sumsq [n] or None),
-    with want_dist a fifth entry ray_dist [n] (the ray's distortion, differentiable; the node then runs call by call, module docstring),
+    with want_dist a fifth entry ray_dist [n] (the ray's distortion, differentiable); with want_depth_grad `depth` carries a gradient
+    (module docstring),
     for a network whose `field.field_plan` is `plan` (plan.occ; plan.occ_object with obj16 [16], the encoded object feature, which receives
     a gradient); the rays' box test against the model's training box (near_far_from_aabb, min_near) happens inside the march."""
     if want_sumsq and obj16 is None:
@@ -321,7 +353,8 @@ def render_occupancy_train(model, plan, o, d, counter, bg_color, perturb, force_
         bound=float(model.bound), cascade=int(model.cascade), grid_size=int(model.grid_size), mean_count=int(model.mean_count), perturb=bool(perturb),
         align=int(align), force_all_rays=bool(force_all_rays), dt_gamma=float(dt_gamma), max_steps=int(max_steps), T_thresh=float(T_thresh),
         density_scale=float(model.density_scale), bg_scalar=float(bg_scalar), min_near=float(model.min_near), offsets=enc.offsets, grid=plan.grid,
-        sigma=plan.sigma, colour=plan.colour, colour_input_pad=float(plan.colour_input_pad), want_sumsq=bool(want_sumsq), want_dist=bool(want_dist))
+        sigma=plan.sigma, colour=plan.colour, colour_input_pad=float(plan.colour_input_pad), want_sumsq=bool(want_sumsq), want_dist=bool(want_dist),
+        want_depth_grad=bool(want_depth_grad))
     res = _occ_train.apply(enc.embeddings, fused_mlp(model, "sigma_net").weights, fused_mlp(model, "color_net").weights, obj16, o, d,
                            model._aabb().contiguous().float(), model.density_bitfield, counter, bg_ray, cfg)
     return res if want_dist else res[:4]

@@ -146,7 +146,8 @@ class NeRFRenderer(nn.Module):
         Result: depth, image, weights_sum, criterion_outside_mask, timing (host seconds before / after the colour query) and, with
         `return_fields` (default: only in eval mode), densities [N,T,1] and rgbs [N,T,3]. distortion=True adds 'distortion', shaped like
         depth: loss.ray_distortion of the weights with m = (z - near) + step / 2 and the interval step (0 on a ray that misses the box) —
-        what the fused tail returns for the same keyword (fixedstep.render_fixed_steps)."""
+        what the fused tail returns for the same keyword (fixedstep.render_fixed_steps). `depth` is differentiable on this route, fused or
+        not: run_cuda's `depth_grad` keyword arrives in **kwargs and is ignored, so one call site serves both routes."""
         want_fields = (not self.training) if return_fields is None else return_fields
         started = time.time()
         o, d, lead = _flat_rays(rays_o, rays_d)
@@ -230,7 +231,7 @@ class NeRFRenderer(nn.Module):
         return sigmas if self.density_scale == 1 else self.density_scale * sigmas      # x * 1 == x: no launch for the default scale
 
     def run_cuda(self, rays_o, rays_d, dt_gamma=0, bg_color=None, perturb=False, force_all_rays=False, max_steps=1024, T_thresh=1e-4,
-                 device_compaction=None, yolo_details=None, distortion=False, **kwargs):
+                 device_compaction=None, yolo_details=None, distortion=False, depth_grad=False, **kwargs):
         """Samples only where the occupancy bitfield is set (legacy/nerf/renderer.py:256-376). Training: one marching pass, one
         evaluation of the field, one compositing node. Inference: rays advance a few samples at a time and leave the list once they are
         opaque or out of the box.
@@ -238,8 +239,11 @@ class NeRFRenderer(nn.Module):
         network takes the encoded feature, and the result carries 'criterion_outside_mask' — in training with a mask sqrt(sum of sigma^2
         over every sample the march emitted for the rays outside the mask), sigma before density_scale; else None. The mask is per ray.
         distortion=True (fused training node only) adds 'distortion' [rays]: the per-ray distortion of mip-NeRF 360 out of the tail kernels
-        (occtrain.render_occupancy_train want_dist: m = the running sum of deltas[:,1], interval deltas[:,0]); the node then runs call by
-        call. Every other route forms no per-sample weights and raises ValueError."""
+        (occtrain.render_occupancy_train want_dist: m = the running sum of deltas[:,1], interval deltas[:,0]). Every other route forms no
+        per-sample weights and raises ValueError.
+        depth_grad=True (fused training node only) makes 'depth' differentiable (want_depth_grad: the tail's backward takes its gradient, as
+        the fixed-step tail's does); the default keeps the reference's semantics, whose composite ignores grad_depth: 'depth' then carries
+        no gradient. Every other route raises ValueError."""
         o, d, lead = _flat_rays(rays_o, rays_d)
         n, dev = o.shape[0], o.device
         out = {}
@@ -268,7 +272,8 @@ class NeRFRenderer(nn.Module):
                 if obj16 is None and self.bg_radius > 0:          # the background model (plan.occ: network_linear.py, plan.background)
                     bg_color = self._background_colour(o, d, bg_color)
                 res = render_occupancy_train(self, plan, o.float(), d.float(), slot, bg_color, perturb, force_all_rays, dt_gamma, max_steps, T_thresh,
-                                             _MARCH_ALIGN, obj16, outside is not None, **({"want_dist": True} if distortion else {}))
+                                             _MARCH_ALIGN, obj16, outside is not None, **({"want_dist": True} if distortion else {}),
+                                             **({"want_depth_grad": True} if depth_grad else {}))
                 image, opacity, depth, sumsq = res[:4]
                 if distortion:
                     out['distortion'] = res[4].view(*lead)
@@ -279,6 +284,9 @@ class NeRFRenderer(nn.Module):
                 return out
         if distortion:
             raise ValueError("run_cuda: distortion=True needs the fused occupancy training node, which alone forms the per-sample weights: a CUDA "
+                             "device, model.train(), gradients and autocast enabled, a network that node serves, and FOC_FUSED_OCC unset or 1")
+        if depth_grad:
+            raise ValueError("run_cuda: depth_grad=True needs the fused occupancy training node, whose tail alone takes the depth's gradient: a CUDA "
                              "device, model.train(), gradients and autocast enabled, a network that node serves, and FOC_FUSED_OCC unset or 1")
         near, far = raymarching.near_far_from_aabb(o, d, self._aabb(), self.min_near)
         background = self._background_colour(o, d, bg_color)

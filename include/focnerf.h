@@ -768,6 +768,30 @@ int foc_occ_tail_backward_dist(const float *grad_image, const float *grad_ws, co
                                const float *image_raw, uint32_t M, uint32_t N, float T_thresh, float density_scale,
                                const float *bg_ray, float bg_scalar, void *grad_c, void *grad_h0, const float *grad_sumsq,
                                const float *ray_wm, const float *ray_dist, const float *grad_dist, void *stream);
+/* The ragged tails with a DIFFERENTIABLE depth: supersets of the _dist pair above. The reference's composite ignores grad_depth
+ * (raymarching.cu:601-693) and foc_occ_tail_backward keeps doing so; these carry it, as foc_fixed_tail_backward does on the fixed-step path.
+ * Forward: depth_raw [N] (may be NULL) = sum_i w_i t_i over the samples that count, t_i = the running sum of deltas[:,1] including sample
+ *   i — the composite's own depth before depth = clamp(depth_raw - near, 0) / (far - near); exactly 0 for a ray with count 0 or one that
+ *   does not fit the list. ray_sumsq [N] may be NULL; ray_dist and ray_wm [N] may be NULL together (one without the other is refused).
+ *   Every other output is bit for bit the plain / _sumsq / _dist entry point's; with all four NULL this is foc_occ_tail_forward.
+ * Backward: grad_depth [N] (may be NULL) = the gradient of the NORMALISED depth. Per ray
+ *     s = (depth_raw - near < 0 || !(far > near)) ? 0 : grad_depth / (far - near)
+ *   — the forward's own clamp branch, which passes the gradient at exactly 0 as torch.clamp(min=0) does — and on the samples that count
+ *     grad_sigma_i += dt0_i s (T_after_i t_i - (depth_raw - D_acc_i)),    D_acc_i = sum_{j<=i} w_j t_j.
+ *   t carries no gradient (deltas are inputs). Rows behind a stop, rays that do not fit, clamped rays and rays whose grad_depth is 0 get
+ *   nothing from it: the plain backward's bits. grad_depth needs depth_raw, nears and fars (refused otherwise; without grad_depth none of
+ *   the three is read); grad_dist needs ray_wm and ray_dist as above; grad_sumsq, grad_dist, grad_depth NULL = absent, in any combination.
+ *   One wave per ray, wave scans only, no atomics: the same bits on every run. */
+int foc_occ_tail_forward_depth(const void *h, const void *c, uint32_t c_width, const float *deltas, const int32_t *rays,
+                               uint32_t M, uint32_t N, float T_thresh, float density_scale, const float *bg_ray, float bg_scalar,
+                               const float *nears, const float *fars, float *weights_sum, float *image_raw, float *image,
+                               float *depth, float *ray_sumsq, float *ray_dist, float *ray_wm, float *depth_raw, void *stream);
+int foc_occ_tail_backward_depth(const float *grad_image, const float *grad_ws, const void *h, const void *c, uint32_t c_width,
+                                const float *deltas, const int32_t *rays, const int32_t *counter, const float *weights_sum,
+                                const float *image_raw, uint32_t M, uint32_t N, float T_thresh, float density_scale,
+                                const float *bg_ray, float bg_scalar, void *grad_c, void *grad_h0, const float *grad_sumsq,
+                                const float *ray_wm, const float *ray_dist, const float *grad_dist, const float *nears,
+                                const float *fars, const float *depth_raw, const float *grad_depth, void *stream);
 
 /* The whole occupancy-grid TRAINING node as ONE call each way (csrc/occtrain.hip): what legacy/nerf/renderer.py:256-322 (`run_cuda`, training
  * branch, a fixed sample budget) + nerf/network_ff.py:51-75 do between the rays and the image, in the order
@@ -842,6 +866,24 @@ typedef struct FocOccTrainObject {
 } FocOccTrainObject;
 int foc_occ_train_forward_obj(const FocOccTrainNode *node, const FocOccTrainObject *object, void *stream);
 int foc_occ_train_backward_obj(const FocOccTrainNode *node, const FocOccTrainObject *object, void *stream);
+/* The node whose tail also returns the per-ray distortion and / or a differentiable depth (foc_occ_tail_forward_depth / _backward_depth in
+ * the tail's place). FocOccTrainNode and FocOccTrainObject keep their layouts; the tail's optional buffers travel beside them in
+ * FocOccTrainTail, as the object's do. ONE pair serves the three layouts of the colour input: object NULL and input_pad 0 = the sequence of
+ * foc_occ_train_forward / _backward; object NULL and input_pad != 0 = the _pad31 pair; an object = the _obj pair (the pad is the object's,
+ * `input_pad` is not read) — the same checks, all before the first launch. Forward: ray_dist and ray_wm [n_rays] (NULL together),
+ * depth_raw [n_rays] (may be NULL). Backward: grad_dist [n_rays] (may be NULL; needs the forward's ray_dist / ray_wm), grad_depth [n_rays]
+ * (may be NULL; needs depth_raw and the node's nears / fars). `struct_bytes` = sizeof(FocOccTrainTail). Refused: a NULL tail, a wrong
+ * struct_bytes, ray_dist without ray_wm or the reverse, a gradient without its forward buffers. */
+typedef struct FocOccTrainTail {
+    uint32_t struct_bytes;
+    float *ray_dist, *ray_wm, *depth_raw;
+    /* backward only */
+    const float *grad_dist, *grad_depth;
+} FocOccTrainTail;
+int foc_occ_train_forward_tail(const FocOccTrainNode *node, const FocOccTrainObject *object, float input_pad,
+                               const FocOccTrainTail *tail, void *stream);
+int foc_occ_train_backward_tail(const FocOccTrainNode *node, const FocOccTrainObject *object, float input_pad,
+                                const FocOccTrainTail *tail, void *stream);
 
 /* Extension (no reference binding; focnerf_amd/rayorder.py): perm [N] int64 = the order in which a staged render walks a view's rays —
  * tile_h x tile_w pixel tiles when rays_d [N,3] fp32 is a row-major H x W pixel grid (recognised from the directions: W >= 16, H >= 8),
