@@ -5,6 +5,7 @@ include/focnerf.h); importing this package fails loudly if that library is missi
 from . import _lib  # noqa: F401  (raises ImportError when libfocnerf_hip.so is absent)
 from .determinism import use_deterministic, is_deterministic, deterministic  # noqa: F401  (FOC_DETERMINISTIC: bit-reproducible training steps)
 from .combine import Attribution  # noqa: F401  (per-object mattes, depths and the instance map of a combined render)
+from .placement import Placement  # noqa: F401  (rotation, uniform scale and translation of an object in the combined render)
 
 __all__ = ["raymarching", "gridencoder", "freqencoder", "ffmlp", "activation", "encoding", "shencoder",
-           "renderer", "network", "combine", "fixedcull", "use_deterministic", "is_deterministic", "deterministic", "Attribution"]
+           "renderer", "network", "combine", "fixedcull", "use_deterministic", "is_deterministic", "deterministic", "Attribution", "placement", "Placement"]

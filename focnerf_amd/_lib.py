@@ -180,6 +180,9 @@ SIGNATURES = {
     "foc_fixed_cull": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, f32, c_vp, u32, u32, c_vp, c_vp, c_vp, c_vp, u64, c_vp]),
     "foc_fixed_cull_emit": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, f32, c_vp, c_vp, u32, c_vp, c_vp, c_vp]),
     "foc_fixed_field_pack_culled": (i32, [c_vp, c_vp, c_vp, c_vp, u32, c_vp, c_vp, u32, u32, f32, f32, c_vp, c_vp]),
+    "foc_fixed_cull_placed": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, c_vp, c_vp, f32, c_vp, u32, u32, c_vp, c_vp, c_vp, c_vp, u64, c_vp]),
+    "foc_fixed_cull_emit_placed": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, c_vp, f32, f32, c_vp, c_vp, u32, c_vp, c_vp, c_vp]),
+    "foc_fixed_field_pack_culled_gain": (i32, [c_vp, c_vp, c_vp, c_vp, u32, c_vp, c_vp, u32, u32, f32, f32, f32, c_vp, c_vp]),
     "foc_composite_fixed_steps":(i32, [c_vp, c_vp, c_vp, c_vp, u32, u32, f32, c_vp, c_vp, c_vp]),
     "foc_fixed_sample": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, f32, c_vp, c_vp, c_vp, u32, c_vp]),
     "foc_fixed_tail_forward": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, f32, u32, u32, f32, f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, u32, c_vp, c_vp]),

@@ -257,6 +257,46 @@ def combine_packed(fields4, nears, fars, bgs=(1.0, 0.0), want_merged=False, ops=
     return ops.select_composite(fields4, nears.contiguous().float(), fars.contiguous().float(), tuple(bgs), want_merged)
 
 
+def placed_field_fns(models, occupancies, placements, rays_o, rays_d, T, scene_aabb, yolo_details=None, weight_thresh=1e-10):
+    """Objects placed in one scene, ready for the combiner: -> (field_fns, nears, fars) for `ObjectCombiner.render_view(field_fns, N, nears,
+    fars, T, ...)` and `combine_packed`. Entry k is `models[k]` with its `occupancies[k]` (a `fixedcull.Occupancy`) under `placements[k]`
+    (a `Placement`; None = the identity) — the same model may appear more than once with different placements, and hiding an object
+    means leaving it out. rays_o / rays_d [N,3]: the view's rays; scene_aabb: float32 [6] tensor on their device. nears / fars [N] are
+    those of the view's rays against the scene's box (the first model's `min_near`, which all must share): every field is built along
+    them, and the composite must run along the same. yolo_details: None, or one entry per object."""
+    from . import raymarching
+    from .field import field_plan
+    from .fixedcull import _check_culled, _scene_box, culled_field4
+    from .placement import Placement
+    models, occupancies = list(models), list(occupancies)
+    placements = [Placement() if p is None else p for p in placements]
+    yolos = [None] * len(models) if yolo_details is None else list(yolo_details)
+    if not (len(models) == len(occupancies) == len(placements) == len(yolos)) or not models:
+        raise ValueError(f"placed_field_fns: {len(models)} models, {len(occupancies)} occupancies, {len(placements)} placements, {len(yolos)} "
+                         "yolo_details: one of each per object, at least one object")
+    rays_o = rays_o.contiguous().view(-1, 3).float()
+    rays_d = rays_d.contiguous().view(-1, 3).float()
+    T = int(T)
+    plans = [field_plan(m) for m in models]
+    for m, plan, occ, p in zip(models, plans, occupancies, placements):
+        if not isinstance(p, Placement):
+            raise ValueError("placed_field_fns: placements must be focnerf_amd.Placement objects (or None for the identity)")
+        _check_culled(m, plan, occ)
+        if float(m.min_near) != float(models[0].min_near):
+            raise ValueError(f"placed_field_fns: the objects must share min_near (one near / far per ray): {float(m.min_near)} and "
+                             f"{float(models[0].min_near)}")
+    box = _scene_box(scene_aabb, models[0], rays_o.device)
+    nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, box, models[0].min_near)
+
+    def make(m, plan, occ, p, yolo):
+        def fn(lo, hi, out=None):
+            if out is None:
+                out = torch.empty(hi - lo, T, 4, dtype=torch.float32, device=rays_o.device)
+            return culled_field4(m, plan, rays_o[lo:hi], rays_d[lo:hi], nears[lo:hi], fars[lo:hi], box, T, weight_thresh, yolo, out, occ, p)
+        return fn
+    return [make(*args) for args in zip(models, plans, occupancies, placements, yolos)], nears, fars
+
+
 class ObjectCombiner:
     """One object per rank. All tensors live on the rank's device; collectives go over `group`
     (backend nccl == RCCL on ROCm, gloo in the CPU tests)."""

@@ -9,6 +9,7 @@ such samples is slightly higher, and a sample whose own weight stood at the 1e-1
     occ = Occupancy.of(model)            # a cuda_ray network: its trained density_bitfield, no copy
     occ = Occupancy.estimate(model)      # any network with density(x): the full-grid passes of update_extra_state on own buffers
     render_field4(model, rays_o, rays_d, num_steps=T, out=buf, occupancy=occ)
+    render_field4(model, rays_o, rays_d, num_steps=T, out=buf, occupancy=occ, placement=P, scene_aabb=box)     # placement.py
 """
 import torch
 
@@ -65,9 +66,28 @@ class Occupancy:
         return cls(bits, C, H, model.bound)
 
 
-def fixed_cull(rays_o, rays_d, nears, fars, aabb, T, occ):
+def _host_floats(values, n, what):
+    """`n` floats for a kernel argument block (ctypes array). A tensor is read on the host ONCE and remembered on the tensor object (a
+    model's box never changes; an in-place write shows in `_version` and reads it again) — no synchronisation per call."""
+    import ctypes
+    if torch.is_tensor(values):
+        kept = getattr(values, "_foc_host_floats", None)
+        if kept is None or kept[0] != values._version:
+            kept = (values._version, [float(v) for v in values.detach().reshape(-1).tolist()])
+            values._foc_host_floats = kept
+        values = kept[1]
+    values = [float(v) for v in values]
+    if len(values) != n:
+        raise ValueError(f"{what}: {n} values expected, got {len(values)}")
+    return (ctypes.c_float * n)(*values)
+
+
+def fixed_cull(rays_o, rays_d, nears, fars, aabb, T, occ, placement=None, obj_aabb=None):
     """The cull pass for N rays x T fixed steps: -> (mask uint64-as-int64 [R], offsets uint32-as-int32 [R + 1], count int32 [1]) with
-    R = ceil(N/64) * T rows of the block-interleaved order (include/focnerf.h). No host synchronisation."""
+    R = ceil(N/64) * T rows of the block-interleaved order (include/focnerf.h). No host synchronisation.
+    placement (a `Placement`, default None = the unplaced entry point): `aabb` is then the SCENE's box (the samples are the view's
+    against it), each sample is mapped into the object's frame and tested against `obj_aabb` (6 floats or a tensor: the object's own
+    box, lo then hi; default the cube of the grid's bound) before its cell is looked up (foc_fixed_cull_placed)."""
     N, dev = rays_o.shape[0], rays_o.device
     R = -(-N // 64) * T
     mask = torch.empty(R, dtype=torch.int64, device=dev)
@@ -75,26 +95,37 @@ def fixed_cull(rays_o, rays_d, nears, fars, aabb, T, occ):
     count = torch.empty(1, dtype=torch.int32, device=dev)
     nbytes = lib.foc_fixed_cull_scratch_bytes(N, T)
     scratch = _scratch.get("fixed_cull", nbytes, dev)
+    if placement is not None:
+        w2o = _host_floats(placement.world_to_object(), 12, "fixed_cull: placement.world_to_object()")
+        box = _host_floats([-occ.bound] * 3 + [occ.bound] * 3 if obj_aabb is None else obj_aabb, 6, "fixed_cull: obj_aabb")
+        check(lib.foc_fixed_cull_placed(ptr(rays_o), ptr(rays_d), ptr(nears), ptr(fars), ptr(aabb), N, T, w2o, box, occ.bound, ptr(occ.bitfield),
+                                        occ.cascade, occ.grid_size, ptr(mask), ptr(offsets), ptr(count), ptr(scratch), nbytes, stream_of(rays_o)),
+              "fixed_cull_placed")
+        return mask, offsets, count
+    if obj_aabb is not None:
+        raise ValueError("fixed_cull: obj_aabb belongs to a placement; without one the samples are tested in the box they were clamped to")
     check(lib.foc_fixed_cull(ptr(rays_o), ptr(rays_d), ptr(nears), ptr(fars), ptr(aabb), N, T, occ.bound, ptr(occ.bitfield), occ.cascade, occ.grid_size,
                              ptr(mask), ptr(offsets), ptr(count), ptr(scratch), nbytes, stream_of(rays_o)), "fixed_cull")
     return mask, offsets, count
 
 
-def fixed_cull_emit(rays_o, rays_d, nears, fars, aabb, T, bound, mask, offsets, m_occ):
-    """-> enc_in_c [m_occ,3] (normalised positions of the occupied samples), dirs_c [m_occ,3] (their rays' directions)."""
+def fixed_cull_emit(rays_o, rays_d, nears, fars, aabb, T, bound, mask, offsets, m_occ, placement=None):
+    """-> enc_in_c [m_occ,3] (normalised positions of the occupied samples), dirs_c [m_occ,3] (their rays' directions). With a
+    placement: the positions in the object's frame and the turned directions (foc_fixed_cull_emit_placed)."""
     N, dev = rays_o.shape[0], rays_o.device
     enc_in_c = torch.empty(m_occ, 3, dtype=torch.float32, device=dev)
     dirs_c = torch.empty(m_occ, 3, dtype=torch.float32, device=dev)
+    if placement is not None:
+        w2o = _host_floats(placement.world_to_object(), 12, "fixed_cull_emit: placement.world_to_object()")
+        check(lib.foc_fixed_cull_emit_placed(ptr(rays_o), ptr(rays_d), ptr(nears), ptr(fars), ptr(aabb), N, T, w2o, float(placement.dir_scale), float(bound),
+                                             ptr(mask), ptr(offsets), m_occ, ptr(enc_in_c), ptr(dirs_c), stream_of(rays_o)), "fixed_cull_emit_placed")
+        return enc_in_c, dirs_c
     check(lib.foc_fixed_cull_emit(ptr(rays_o), ptr(rays_d), ptr(nears), ptr(fars), ptr(aabb), N, T, float(bound), ptr(mask), ptr(offsets), m_occ,
                                   ptr(enc_in_c), ptr(dirs_c), stream_of(rays_o)), "fixed_cull_emit")
     return enc_in_c, dirs_c
 
 
-def render_field4_culled(model, plan, rays_o, rays_d, T, weight_thresh, yolo_details, out, occ):
-    """`render_field4` with an Occupancy (rays_o / rays_d [N,3] fp32 contiguous, out [N,T,4]): near_far -> cull -> ONE host read of the
-    count -> encoder + whole-field kernel on the occupied samples -> culled pack."""
-    from . import raymarching
-    from .field import field_infer
+def _check_culled(model, plan, occ):
     if not isinstance(occ, Occupancy):
         raise ValueError("render_field4: occupancy must be a focnerf_amd.fixedcull.Occupancy")
     if not (plan.infer and model.bg_radius <= 0):
@@ -102,20 +133,68 @@ def render_field4_culled(model, plan, rays_o, rays_d, T, weight_thresh, yolo_det
                          "model; this one would have to render dense")
     if occ.bound != float(model.bound):
         raise ValueError(f"render_field4: the occupancy grid covers bound {occ.bound}, the model bound {float(model.bound)}")
+
+
+def culled_field4(model, plan, rays_o, rays_d, nears, fars, aabb, T, weight_thresh, yolo_details, out, occ, placement=None):
+    """The culled field along GIVEN nears / fars [N] (of the rays against `aabb`): cull -> ONE host read of the count -> encoder +
+    whole-field kernel on the occupied samples -> culled pack. With a placement, `aabb` is the scene's box, the object's own box is
+    the model's, and the pack applies the placement's sigma gain."""
+    from .field import field_infer
     N, dev = rays_o.shape[0], rays_o.device
     if N == 0:
         return out
     if occ.bitfield.device != dev:
         raise ValueError(f"render_field4: the occupancy bitfield is on {occ.bitfield.device}, the rays on {dev}")
-    aabb = model.aabb_train if model.training else model.aabb_infer
-    nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, aabb, model.min_near)
-    mask, offsets, count = fixed_cull(rays_o, rays_d, nears, fars, aabb, T, occ)
+    obj_aabb = None if placement is None else (model.aabb_train if model.training else model.aabb_infer)
+    mask, offsets, count = fixed_cull(rays_o, rays_d, nears, fars, aabb, T, occ, placement, obj_aabb)
     m_occ = int(count.item())                                   # the host read: sizes the compact arrays and the field launch
     sigma = rgb = None
     if m_occ:
-        enc_in_c, dirs_c = fixed_cull_emit(rays_o, rays_d, nears, fars, aabb, T, model.bound, mask, offsets, m_occ)
+        enc_in_c, dirs_c = fixed_cull_emit(rays_o, rays_d, nears, fars, aabb, T, model.bound, mask, offsets, m_occ, placement)
         obj_feat = model.encode_object_feature(yolo_details, dev) if plan.uses_object_feature else None
         sigma, rgb = field_infer(model, enc_in_c, dirs_c, dir_div=1, dir_block=0, obj_feat=obj_feat)
+    if placement is not None:
+        check(lib.foc_fixed_field_pack_culled_gain(ptr(sigma), ptr(rgb), ptr(mask), ptr(offsets), m_occ, ptr(nears), ptr(fars), N, T,
+                                                   float(model.density_scale), float(weight_thresh), float(placement.sigma_gain), ptr(out),
+                                                   stream_of(out)), "fixed_field_pack_culled_gain")
+        return out
     check(lib.foc_fixed_field_pack_culled(ptr(sigma), ptr(rgb), ptr(mask), ptr(offsets), m_occ, ptr(nears), ptr(fars), N, T, float(model.density_scale),
                                           float(weight_thresh), ptr(out), stream_of(out)), "fixed_field_pack_culled")
     return out
+
+
+def render_field4_culled(model, plan, rays_o, rays_d, T, weight_thresh, yolo_details, out, occ):
+    """`render_field4` with an Occupancy (rays_o / rays_d [N,3] fp32 contiguous, out [N,T,4]): near_far -> cull -> ONE host read of the
+    count -> encoder + whole-field kernel on the occupied samples -> culled pack."""
+    from . import raymarching
+    _check_culled(model, plan, occ)
+    if rays_o.shape[0] == 0:
+        return out
+    aabb = model.aabb_train if model.training else model.aabb_infer
+    nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, aabb, model.min_near)
+    return culled_field4(model, plan, rays_o, rays_d, nears, fars, aabb, T, weight_thresh, yolo_details, out, occ)
+
+
+def _scene_box(scene_aabb, model, dev):
+    if scene_aabb is None:
+        return model.aabb_train if model.training else model.aabb_infer
+    if not torch.is_tensor(scene_aabb) or scene_aabb.dtype != torch.float32 or scene_aabb.numel() != 6:
+        raise ValueError("render_field4: scene_aabb must be a float32 tensor of 6 values (lo, then hi)")
+    if scene_aabb.device != dev:
+        raise ValueError(f"render_field4: scene_aabb is on {scene_aabb.device}, the rays on {dev}")
+    return scene_aabb.contiguous().view(-1)
+
+
+def render_field4_placed(model, plan, rays_o, rays_d, T, weight_thresh, yolo_details, out, occ, placement, scene_aabb=None):
+    """`render_field4` with an Occupancy and a Placement: near / far of the view's rays against the SCENE's box (default: the model's),
+    then the sequence of `render_field4_culled` through the placed entry points."""
+    from . import raymarching
+    from .placement import Placement
+    if not isinstance(placement, Placement):
+        raise ValueError("render_field4: placement must be a focnerf_amd.Placement")
+    _check_culled(model, plan, occ)
+    if rays_o.shape[0] == 0:
+        return out
+    aabb = _scene_box(scene_aabb, model, rays_o.device)
+    nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, aabb, model.min_near)
+    return culled_field4(model, plan, rays_o, rays_d, nears, fars, aabb, T, weight_thresh, yolo_details, out, occ, placement)

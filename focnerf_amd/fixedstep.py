@@ -441,7 +441,8 @@ def render_fixed_steps(model, rays_o, rays_d, yolo_details=None, num_steps=512, 
 
 
 @torch.no_grad()
-def render_field4(model, rays_o, rays_d, num_steps=512, weight_thresh=1e-10, yolo_details=None, out=None, occupancy=None):
+def render_field4(model, rays_o, rays_d, num_steps=512, weight_thresh=1e-10, yolo_details=None, out=None, occupancy=None, placement=None,
+                  scene_aabb=None):
     """What the combiner needs from one object for a chunk of rays — COMBINED.py's `run` (:451-534 with upsample_steps=0, perturb off):
     `densities` [N,T] and `rgbs` [N,T,3] (zero where the object's own compositing weight is <= 1e-10) — PACKED as field4 [N,T,4] fp32
     (sigma, r, g, b), written into `out` when given. Fused path: sample -> encoder -> whole-field kernel -> weights + mask + pack
@@ -453,8 +454,18 @@ def render_field4(model, rays_o, rays_d, num_steps=512, weight_thresh=1e-10, yol
     It is the approximation `run_cuda` makes: densities below the grid's threshold are dropped, so the transmittance behind such
     samples is slightly higher and a sample's own-weight mask can flip. The host read makes a call with `occupancy` uncapturable in a
     HIP graph (the dense path is as capturable as before). Needs a network the fused inference serves and no background model
-    (ValueError otherwise: it never falls back to rendering dense), and a grid over the model's `bound`."""
+    (ValueError otherwise: it never falls back to rendering dense), and a grid over the model's `bound`.
+
+    placement (a `Placement`, default None = the paths above, unchanged; needs `occupancy`): the object stands rotated, scaled and moved
+    in a scene. The T positions are those of the view's rays against `scene_aabb` (float32 [6] tensor, default the model's box); each is
+    mapped into the object's frame, samples outside the object's own box are empty, and sigma is rescaled by 1 / scale
+    (include/focnerf.h foc_fixed_cull_placed)."""
     from .field import field_plan, field_infer
+    if placement is None and scene_aabb is not None:
+        raise ValueError("render_field4: scene_aabb belongs to a placement; without one the object is rendered in its own box")
+    if placement is not None and occupancy is None:
+        raise ValueError("render_field4: placement needs occupancy= (the placed path is the occupancy-culled one): pass "
+                         "fixedcull.Occupancy.of(model) for a cuda_ray network or fixedcull.Occupancy.estimate(model) for any other")
     rays_o = rays_o.contiguous().view(-1, 3).float()
     rays_d = rays_d.contiguous().view(-1, 3).float()
     N, T = rays_o.shape[0], int(num_steps)
@@ -463,6 +474,9 @@ def render_field4(model, rays_o, rays_d, num_steps=512, weight_thresh=1e-10, yol
         out = torch.empty(N, T, 4, dtype=torch.float32, device=dev)
     assert out.shape == (N, T, 4) and out.dtype == torch.float32 and out.is_contiguous()
     plan = field_plan(model)
+    if placement is not None:
+        from .fixedcull import render_field4_placed
+        return render_field4_placed(model, plan, rays_o, rays_d, T, weight_thresh, yolo_details, out, occupancy, placement, scene_aabb)
     if occupancy is not None:
         from .fixedcull import render_field4_culled
         return render_field4_culled(model, plan, rays_o, rays_d, T, weight_thresh, yolo_details, out, occupancy)

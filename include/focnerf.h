@@ -962,6 +962,37 @@ int foc_fixed_field_pack_culled(const float *sigma_c, const float *rgb_c, const 
                                 uint32_t m_occ, const float *nears, const float *fars, uint32_t N, uint32_t T,
                                 float density_scale, float thresh, float *field4, void *stream);
 
+/* The three calls above for an object PLACED in a scene: object -> world is x_world = s R (x_obj - pivot) + pivot + translation with a
+ * rotation R and a uniform scale s > 0; the calls take its inverse, world_to_object = 12 floats IN HOST MEMORY: A = R^T / s row-major,
+ * then b (q = A x + b). obj_aabb: 6 floats in host memory, the object's own box (lo, then hi). Both travel by value in the kernel
+ * argument block. scene_aabb [6] is device memory like foc_fixed_cull's aabb.
+ *   World sample.  Exactly the point foc_fixed_sample(noise = NULL, ray_block = 64) produces for (rays_o, rays_d, nears, fars,
+ *                  scene_aabb): clamped to scene_aabb, the same bits. nears / fars belong to the view's rays against the scene box and
+ *                  are passed in.
+ *   Object-frame point.  Per axis k: q_k = ((A_k0 x + A_k1 y) + A_k2 z) + b_k — this operation order, no contraction. q is not clamped.
+ *   Inside.        obj_aabb_lo <= q <= obj_aabb_hi on all three axes. occupied = inside && bit(cell(q)), cell = foc_fixed_cull's on q
+ *                  with the object's bound / cascade / grid_size.
+ *   Emit.          enc_in_c = (q + bound) / (2 bound); dirs_c = dir_scale * ((A_k0 dx + A_k1 dy) + A_k2 dz), computed per ray and not
+ *                  renormalised (dir_scale = s gives the turned direction at its original length).
+ *   Pack with gain.  The sample's sigma is sigma_c[slot] * sigma_gain, one fp32 multiply (sigma_gain = 1 / s: the object's density per
+ *                  unit of WORLD length); that value goes into field4.x and into the own-weight mask. sigma_gain finite and > 0. With
+ *                  sigma_gain == 1 the bits are those of foc_fixed_field_pack_culled.
+ *   Everything else as foc_fixed_cull: mask / offsets layout, slots by prefix sum, refusals (plus: null or non-finite host arrays),
+ *                  N = 0, the 2^31 limit, no synchronisation.
+ *   Identity case. With A = I, b = 0, dir_scale = 1 and obj_aabb = scene_aabb, mask, offsets, enc_in_c and dirs_c equal the unplaced
+ *                  entry points' bit for bit. */
+int foc_fixed_cull_placed(const float *rays_o, const float *rays_d, const float *nears, const float *fars, const float *scene_aabb,
+                          uint32_t N, uint32_t T, const float *world_to_object, const float *obj_aabb, float bound,
+                          const uint8_t *bitfield, uint32_t cascade, uint32_t grid_size, uint64_t *mask, uint32_t *offsets,
+                          uint32_t *count, void *scratch, uint64_t scratch_bytes, void *stream);
+int foc_fixed_cull_emit_placed(const float *rays_o, const float *rays_d, const float *nears, const float *fars,
+                               const float *scene_aabb, uint32_t N, uint32_t T, const float *world_to_object, float dir_scale,
+                               float bound, const uint64_t *mask, const uint32_t *offsets, uint32_t m_occ, float *enc_in_c,
+                               float *dirs_c, void *stream);
+int foc_fixed_field_pack_culled_gain(const float *sigma_c, const float *rgb_c, const uint64_t *mask, const uint32_t *offsets,
+                                     uint32_t m_occ, const float *nears, const float *fars, uint32_t N, uint32_t T,
+                                     float density_scale, float thresh, float sigma_gain, float *field4, void *stream);
+
 /* ---------------------------------------------------------------------------
  * Per-sample network glue for callers with arbitrary sample lists (the occupancy-grid paths): the torch
  * expressions of nerf/network_ff.py:51-75 between the sigma network, the SH-encoded direction and the
