@@ -9,6 +9,15 @@
 //     coalesced, transmittance is a wave product-scan (DPP shuffles), early termination
 //     is a ballot, the per-ray sums are wave reductions — instead of the reference's one
 //     thread walking its own ray segment (uncoalesced, 128 rays per block).
+// Every form of the march (one ray per lane, one wave per ray, 16 lanes per ray, two phases, staged in LDS) has to emit the reference's
+// samples bit for bit, so what they share is defined once and they are written in terms of it:
+//   RmRay / rm_load_ray (o, d, 1 / d); rm_dt, rm_start (the step clamp(t dt_gamma, dt_min, dt_max), the jittered start of a walk); rm_pos,
+//   rm_cell, rm_skip_target, rm_skip (clamped position, cell lookup, voxel exit, the walk over an empty cell); rm_train_range (near / far of a
+//   training ray, both count kernels); rm_lattice<DPP, COUNT, MED3> (the general step of the t lattice on 64 lanes, k_march_count_wave's slow
+//   path, or on 16, rm_row_walk); rm_lane_walk<BAIL, DIRS> (THE serial loop: k_march_rays, k_march_rays_first, k_march_walkers and, into LDS,
+//   k_march_rays_staged); RmSlots / rm_put_sample (where a walk's samples go, the record of one); rm_zero_row (k_march_emit); RmAcc,
+//   rm_acc_load, rm_composite_sample, rm_composite_finish (k_composite_rays, k_composite_rays_pre); rm_scan_1024 (k_march_scan, k_compact_scan);
+//   on the host rm_check_grid, rm_launch_row, rm_launch_lane (the grid refusals and the two launches the R9 entry points share).
 // Floating-point policy: compiled with -ffp-contract=off; fused multiply-adds are written
 // as explicit fmaf() exactly where oracle/oracle.c has them, so the marching control flow
 // (and therefore every sample index and position) is bit-identical to the oracle.
@@ -137,12 +146,29 @@ struct RmParams {
 // position of an emitted sample as it is stored (the native render step asks for the normalised form: csrc/occrender.hip)
 __device__ __forceinline__ float rm_out(const RmParams &p, float x) { return p.norm_inv != 0.0f ? (x + p.bound) * p.norm_inv : x; }
 
-__device__ __forceinline__ bool rm_cell(const uint8_t *__restrict__ grid, const RmParams &p, float ox, float oy, float oz,
-                                        float dx, float dy, float dz, float t, RmCell &c) {
-    c.x = rm_clamp(fmaf(t, dx, ox), -p.bound, p.bound);
-    c.y = rm_clamp(fmaf(t, dy, oy), -p.bound, p.bound);
-    c.z = rm_clamp(fmaf(t, dz, oz), -p.bound, p.bound);
-    c.dt = rm_clamp(t * p.dt_gamma, p.dt_min, p.dt_max);
+// One ray as every walk holds it: origin, direction, 1 / direction (the voxel exit needs it; where no walk skips, as in k_march_emit, the compiler drops it).
+struct RmRay { float ox, oy, oz, dx, dy, dz, rdx, rdy, rdz; };
+template <typename I>                                      // (the row index keeps its caller's type: uint32_t ray number or int list entry)
+__device__ __forceinline__ RmRay rm_load_ray(const float *__restrict__ rays_o, const float *__restrict__ rays_d, I i) {
+    RmRay r;
+    r.ox = rays_o[i * 3]; r.oy = rays_o[i * 3 + 1]; r.oz = rays_o[i * 3 + 2];
+    r.dx = rays_d[i * 3]; r.dy = rays_d[i * 3 + 1]; r.dz = rays_d[i * 3 + 2];
+    r.rdx = 1 / r.dx; r.rdy = 1 / r.dy; r.rdz = 1 / r.dz;
+    return r;
+}
+// the step at t (raymarching.cu:371 == :385 == :397) and the jittered start of a walk (:357)
+__device__ __forceinline__ float rm_dt(const RmParams &p, float t) { return rm_clamp(t * p.dt_gamma, p.dt_min, p.dt_max); }
+__device__ __forceinline__ float rm_start(const RmParams &p, float t, float noise) { return fmaf(rm_dt(p, t), noise, t); }
+// clamped position of the ray at t
+__device__ __forceinline__ void rm_pos(const RmParams &p, const RmRay &r, float t, float &x, float &y, float &z) {
+    x = rm_clamp(fmaf(t, r.dx, r.ox), -p.bound, p.bound);
+    y = rm_clamp(fmaf(t, r.dy, r.oy), -p.bound, p.bound);
+    z = rm_clamp(fmaf(t, r.dz, r.oz), -p.bound, p.bound);
+}
+
+__device__ __forceinline__ bool rm_cell(const uint8_t *__restrict__ grid, const RmParams &p, const RmRay &r, float t, RmCell &c) {
+    rm_pos(p, r, t, c.x, c.y, c.z);
+    c.dt = rm_dt(p, t);
     // mip_from_pos / mip_from_dt (:42-54): float min/max, then truncation
     const int l1 = rm_mip_from_pos(c.x, c.y, c.z, p.Cf);
     const float mdt = (float)((double)(c.dt * p.Hf) * 0.5);
@@ -152,18 +178,16 @@ __device__ __forceinline__ bool rm_cell(const uint8_t *__restrict__ grid, const 
 }
 
 // Empty cell: jump to the voxel exit (:389-398).
-__device__ __forceinline__ float rm_skip_target(const RmParams &p, const RmCell &c, float t, float dx, float dy, float dz,
-                                                float rdx, float rdy, float rdz) {
-    const float tx = fmaf(fmaf(fmaf(0.5f, rm_sign(dx), (float)c.nx + 0.5f) * p.rH, 2.0f, -1.0f), c.mip_bound, -c.x) * rdx;
-    const float ty = fmaf(fmaf(fmaf(0.5f, rm_sign(dy), (float)c.ny + 0.5f) * p.rH, 2.0f, -1.0f), c.mip_bound, -c.y) * rdy;
-    const float tz = fmaf(fmaf(fmaf(0.5f, rm_sign(dz), (float)c.nz + 0.5f) * p.rH, 2.0f, -1.0f), c.mip_bound, -c.z) * rdz;
+__device__ __forceinline__ float rm_skip_target(const RmParams &p, const RmCell &c, float t, const RmRay &r) {
+    const float tx = fmaf(fmaf(fmaf(0.5f, rm_sign(r.dx), (float)c.nx + 0.5f) * p.rH, 2.0f, -1.0f), c.mip_bound, -c.x) * r.rdx;
+    const float ty = fmaf(fmaf(fmaf(0.5f, rm_sign(r.dy), (float)c.ny + 0.5f) * p.rH, 2.0f, -1.0f), c.mip_bound, -c.y) * r.rdy;
+    const float tz = fmaf(fmaf(fmaf(0.5f, rm_sign(r.dz), (float)c.nz + 0.5f) * p.rH, 2.0f, -1.0f), c.mip_bound, -c.z) * r.rdz;
     return t + fmaxf(0.0f, fminf(tx, fminf(ty, tz)));
 }
 
-__device__ __forceinline__ float rm_skip(const RmParams &p, const RmCell &c, float t, float dx, float dy, float dz,
-                                         float rdx, float rdy, float rdz) {
-    const float tt = rm_skip_target(p, c, t, dx, dy, dz, rdx, rdy, rdz);
-    do { t += rm_clamp(t * p.dt_gamma, p.dt_min, p.dt_max); } while (t < tt);
+__device__ __forceinline__ float rm_skip(const RmParams &p, const RmCell &c, float t, const RmRay &r) {
+    const float tt = rm_skip_target(p, c, t, r);
+    do { t += rm_dt(p, t); } while (t < tt);
     return t;
 }
 
@@ -184,8 +208,33 @@ static RmParams rm_make_params(float bound, float dt_gamma, uint32_t max_steps, 
     return p;
 }
 
+// The range of training ray n (both count kernels). aabb != NULL: nears / fars are OUTPUTS — the ray's slab test (k_near_far_from_aabb's
+// expressions) is done here and written by the lanes with `writer` set.
+__device__ __forceinline__ void rm_train_range(const RmRay &r, uint32_t n, const float *__restrict__ aabb, float min_near, bool writer,
+                                               float *__restrict__ nears, float *__restrict__ fars, float &near, float &far) {
+    if (aabb) {
+        rm_near_far(r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, aabb[0], aabb[1], aabb[2], aabb[3], aabb[4], aabb[5], min_near, near, far);
+        if (writer) { nears[n] = near; fars[n] = far; }
+    } else { near = nears[n]; far = fars[n]; }
+}
+
+// The general step of the lattice t_{j+1} = t_j + clamp(t_j dt_gamma, dt_min, dt_max) on COUNT lanes: every lane runs the recurrence from t_cur,
+// each new value enters at the last lane of the wave (DPP 0x130, wave_shl:1) or of the 16-lane row (0x101, row_shl:1) while the earlier ones
+// move down one lane, so after COUNT steps lane j holds T = t_j and every lane t_next = t_COUNT. MED3 (dt_min <= dt_max, any real setting):
+// the clamp is one v_med3_f32 — for ordered operands the median IS fminf(hi, fmaxf(lo, x)), bit for bit.
+template <int DPP, uint32_t COUNT, bool MED3>
+__device__ __forceinline__ void rm_lattice(const RmParams &p, float t_cur, float &T, float &t_next) {
+    constexpr uint32_t UNROLL = COUNT > 16u ? 8u : COUNT;
+    T = t_cur; t_next = t_cur;
+#pragma unroll UNROLL
+    for (uint32_t j = 0; j < COUNT; j++) {
+        T = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, t_next), __builtin_bit_cast(int, T), DPP, 0xf, 0xf, false));
+        const float raw = t_next * p.dt_gamma;
+        t_next += MED3 ? __builtin_amdgcn_fmed3f(raw, p.dt_min, p.dt_max) : rm_clamp(raw, p.dt_min, p.dt_max);
+    }
+}
+
 // ---------------------------------------------------------------- R6 pass 1: count (raymarching.cu:348-400)
-// aabb != NULL (both count kernels): nears / fars are OUTPUTS — the ray's slab test (k_near_far_from_aabb's expressions) is done here
 __global__ void __launch_bounds__(64) k_march_count(const float *__restrict__ rays_o, const float *__restrict__ rays_d,
                               const uint8_t *__restrict__ grid, RmParams p, uint32_t max_steps, uint32_t N,
                               float *__restrict__ nears, float *__restrict__ fars,
@@ -193,16 +242,10 @@ __global__ void __launch_bounds__(64) k_march_count(const float *__restrict__ ra
                               const float *__restrict__ aabb, float min_near) {
     const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N) return;
-    const float ox = rays_o[n * 3], oy = rays_o[n * 3 + 1], oz = rays_o[n * 3 + 2];
-    const float dx = rays_d[n * 3], dy = rays_d[n * 3 + 1], dz = rays_d[n * 3 + 2];
-    const float rdx = 1 / dx, rdy = 1 / dy, rdz = 1 / dz;
+    const RmRay r = rm_load_ray(rays_o, rays_d, n);
     float near_n, far;
-    if (aabb) {
-        rm_near_far(ox, oy, oz, dx, dy, dz, aabb[0], aabb[1], aabb[2], aabb[3], aabb[4], aabb[5], min_near, near_n, far);
-        nears[n] = near_n; fars[n] = far;
-    } else { near_n = nears[n]; far = fars[n]; }
-    float t = near_n;
-    t = fmaf(rm_clamp(t * p.dt_gamma, p.dt_min, p.dt_max), noises[n], t);
+    rm_train_range(r, n, aabb, min_near, true, nears, fars, near_n, far);
+    float t = rm_start(p, near_n, noises[n]);
     uint32_t num_steps = 0;
     RmCell c;
     // The marching loop is a chain of dependent L2 lookups: running it a second time to write the samples (as the reference does,
@@ -210,8 +253,8 @@ __global__ void __launch_bounds__(64) k_march_count(const float *__restrict__ ra
     // (max_steps floats per ray), from which k_march_emit rebuilds position, dt and the two deltas with the loop's own expressions.
     float *strip = tstrip + (uint64_t)n * max_steps;
     while (t < far && num_steps < max_steps) {
-        if (rm_cell(grid, p, ox, oy, oz, dx, dy, dz, t, c)) { strip[num_steps] = t; num_steps++; t += c.dt; }
-        else t = rm_skip(p, c, t, dx, dy, dz, rdx, rdy, rdz);
+        if (rm_cell(grid, p, r, t, c)) { strip[num_steps] = t; num_steps++; t += c.dt; }
+        else t = rm_skip(p, c, t, r);
     }
     counts[n] = (int32_t)num_steps;
 }
@@ -237,16 +280,10 @@ __global__ void __launch_bounds__(256) k_march_count_wave(const float *__restric
     // the emit pass does the slot reservation itself (k_march_emit<.., true>): it takes the counter's entry values from a snapshot behind the
     // counts, because its last workgroup overwrites the counter while others may not have started
     if (counter_in && n == 0 && lane == 0) { counts[N] = counter_in[0]; counts[N + 1] = counter_in[1]; }
-    const float ox = rays_o[n * 3], oy = rays_o[n * 3 + 1], oz = rays_o[n * 3 + 2];
-    const float dx = rays_d[n * 3], dy = rays_d[n * 3 + 1], dz = rays_d[n * 3 + 2];
-    const float rdx = 1 / dx, rdy = 1 / dy, rdz = 1 / dz;
+    const RmRay r = rm_load_ray(rays_o, rays_d, n);
     float near_n, far;
-    if (aabb) {                                            // wave-uniform
-        rm_near_far(ox, oy, oz, dx, dy, dz, aabb[0], aabb[1], aabb[2], aabb[3], aabb[4], aabb[5], min_near, near_n, far);
-        if (lane == 0) { nears[n] = near_n; fars[n] = far; }
-    } else { near_n = nears[n]; far = fars[n]; }
-    float t_cur = near_n;
-    t_cur = fmaf(rm_clamp(t_cur * p.dt_gamma, p.dt_min, p.dt_max), noises[n], t_cur);
+    rm_train_range(r, n, aabb, min_near, lane == 0, nears, fars, near_n, far);        // (wave-uniform but for the writer)
+    float t_cur = rm_start(p, near_n, noises[n]);
     float *strip = tstrip + (uint64_t)n * max_steps;
     uint32_t num_steps = 0;
     bool skipping = false;                                 // inside the do-while of an empty cell whose exit `skip_to` lies beyond the last 64 points
@@ -289,15 +326,7 @@ __global__ void __launch_bounds__(256) k_march_count_wave(const float *__restric
             const float raw63 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, T), 63)) * p.dt_gamma;
             fast = regime == 0 ? raw63 <= p.dt_min : (regime == 2 ? true : raw63 <= p.dt_max);
         }
-        if (!fast) {
-            T = t_cur; t_next = t_cur;
-#pragma unroll 8
-            for (uint32_t j = 0; j < 64; j++) {
-                T = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, t_next), __builtin_bit_cast(int, T), 0x130, 0xf, 0xf, false));
-                const float raw = t_next * p.dt_gamma;             // for ordered operands the median IS fminf(hi, fmaxf(lo, x)), bit for bit
-                t_next += MED3 ? __builtin_amdgcn_fmed3f(raw, p.dt_min, p.dt_max) : rm_clamp(raw, p.dt_min, p.dt_max);
-            }
-        }
+        if (!fast) rm_lattice<0x130, 64u, MED3>(p, t_cur, T, t_next);
         const uint64_t in_range = __ballot(T < far);
         uint32_t k = 0;                                    // lane of the lattice point the loop is at
         if (skipping) {
@@ -311,8 +340,8 @@ __global__ void __launch_bounds__(256) k_march_count_wave(const float *__restric
             skipping = false;
         }
         RmCell c;
-        const bool occupied_here = rm_cell(grid, p, ox, oy, oz, dx, dy, dz, T, c);
-        const float exit_here = rm_skip_target(p, c, T, dx, dy, dz, rdx, rdy, rdz);
+        const bool occupied_here = rm_cell(grid, p, r, T, c);
+        const float exit_here = rm_skip_target(p, c, T, r);
         const uint64_t emit_ok = __ballot(occupied_here) & in_range;
         uint64_t emitted = 0ull;
         uint32_t room = (uint32_t)__builtin_amdgcn_readfirstlane((int)(max_steps - num_steps));
@@ -381,36 +410,45 @@ __global__ void __launch_bounds__(256) k_march_count_wave(const float *__restric
 // One 1024-thread workgroup scans the N counts in ray order (each thread owns a contiguous
 // chunk), writes rays[n] = (n, base + exclusive_prefix, count) and bumps the two counters —
 // the deterministic stand-in for the atomicAdd pair of raymarching.cu:405-413.
-__global__ void __launch_bounds__(1024) k_march_scan(const int32_t *__restrict__ counts, uint32_t N,
-                                                     int32_t *__restrict__ rays, int32_t *__restrict__ counter) {
+// (the scan itself: rm_scan_1024, shared with the compaction's k_compact_scan)
+struct RmScan { uint32_t lo, hi; int base; };              // this thread's chunk [lo, hi) of the values and the sum of all values before it
+__device__ __forceinline__ RmScan rm_scan_1024(const int32_t *v, uint32_t n, int *total) {
     __shared__ int s_wave[16];
-    __shared__ int s_total;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t per = (N + 1023) / 1024;
-    const uint32_t lo = tid * per, hi = min(N, lo + per);
+    const uint32_t per = (n + 1023) / 1024;
+    RmScan sc;
+    sc.lo = tid * per; sc.hi = min(n, sc.lo + per);
     int local = 0;
-    for (uint32_t i = lo; i < hi; i++) local += counts[i];
+    for (uint32_t i = sc.lo; i < sc.hi; i++) local += v[i];
     const int incl = wave_incl_sum_i(local, (int)lane);
     if (lane == 63) s_wave[wave] = incl;
     __syncthreads();
     if (wave == 0) {
-        int v = lane < 16 ? s_wave[lane] : 0;
-        const int vi = wave_incl_sum_i(v, (int)lane);
-        if (lane < 16) s_wave[lane] = vi - v;   // exclusive base per wave
-        if (lane == 15) s_total = vi;
+        int w = lane < 16 ? s_wave[lane] : 0;
+        const int wi = wave_incl_sum_i(w, (int)lane);
+        if (lane < 16) s_wave[lane] = wi - w;   // exclusive base per wave
+        if (lane == 15) *total = wi;            // (one thread writes the sum of all values: to LDS or to memory, as the caller needs it)
     }
     __syncthreads();
+    sc.base = s_wave[wave] + (incl - local);
+    return sc;
+}
+
+__global__ void __launch_bounds__(1024) k_march_scan(const int32_t *__restrict__ counts, uint32_t N,
+                                                     int32_t *__restrict__ rays, int32_t *__restrict__ counter) {
+    __shared__ int s_total;
+    const RmScan sc = rm_scan_1024(counts, N, &s_total);
     const int base0 = counter[0];
     const int ray0 = counter[1];
-    int run = base0 + s_wave[wave] + (incl - local);
-    for (uint32_t i = lo; i < hi; i++) {
+    int run = base0 + sc.base;
+    for (uint32_t i = sc.lo; i < sc.hi; i++) {
         const int c = counts[i];
         const uint32_t r = i;   // rows in ray order; a non-zero counter[1] would index past rays[N,3] in the reference
         rays[r * 3] = (int32_t)i; rays[r * 3 + 1] = run; rays[r * 3 + 2] = c;
         run += c;
     }
     __syncthreads();
-    if (tid == 0) { counter[0] = base0 + s_total; counter[1] = ray0 + (int32_t)N; }
+    if (threadIdx.x == 0) { counter[0] = base0 + s_total; counter[1] = ray0 + (int32_t)N; }
 }
 
 // ---------------------------------------------------------------- R6 pass 3: emit (raymarching.cu:415-479)
@@ -423,6 +461,12 @@ __global__ void __launch_bounds__(1024) k_march_scan(const int32_t *__restrict__
 // a ray, all equal. Every row of both arrays is written — rays that do not fit the list and the rows behind the last ray get zeros
 // (spare workgroups; `counter` from k_march_scan) — so the caller needs no zero fill.
 #define RM_PAD_BLOCKS 64u
+// row s of the FIELD list that holds no sample
+__device__ __forceinline__ void rm_zero_row(float *__restrict__ xyzs, float *__restrict__ deltas, _Float16 *__restrict__ sh, uint64_t s) {
+    xyzs[s * 3] = 0.0f; xyzs[s * 3 + 1] = 0.0f; xyzs[s * 3 + 2] = 0.0f;
+    deltas[s * 2] = 0.0f; deltas[s * 2 + 1] = 0.0f;
+    *reinterpret_cast<uint4 *>(sh + s * 16) = make_uint4(0u, 0u, 0u, 0u); *reinterpret_cast<uint4 *>(sh + s * 16 + 8) = make_uint4(0u, 0u, 0u, 0u);
+}
 // SCAN (round 5): the ordered slot reservation of k_march_scan done HERE, by every workgroup for itself — a workgroup's rays start at the sum
 // of the counts of all rays before them, 256 threads add those up (at most 16 384 ints, L2 resident) and the wave of ray n adds the counts of
 // the workgroup's earlier rays: the same integers as the one-workgroup scan, with no launch of its own (8.6 us + a launch gap of the configs[2]
@@ -467,11 +511,7 @@ __global__ void __launch_bounds__(256) k_march_emit(const float *__restrict__ ra
             // pad_align > 0: the caller cuts the list to the samples marched, rounded up like raymarching.py:226 — nothing behind that is read
             const uint32_t total = SCAN ? scan_total : (uint32_t)counter[0], pb = blockIdx.x - (N + 3u) / 4u;
             const uint64_t end = pad_align ? min((uint64_t)M, (uint64_t)total + (pad_align - total % pad_align)) : (uint64_t)M;
-            for (uint64_t s = (uint64_t)total + pb * 256u + threadIdx.x; s < end; s += (uint64_t)RM_PAD_BLOCKS * 256u) {
-                xyzs[s * 3] = 0.0f; xyzs[s * 3 + 1] = 0.0f; xyzs[s * 3 + 2] = 0.0f;
-                deltas[s * 2] = 0.0f; deltas[s * 2 + 1] = 0.0f;
-                *reinterpret_cast<uint4 *>(sh + s * 16) = make_uint4(0u, 0u, 0u, 0u); *reinterpret_cast<uint4 *>(sh + s * 16 + 8) = make_uint4(0u, 0u, 0u, 0u);
-            }
+            for (uint64_t s = (uint64_t)total + pb * 256u + threadIdx.x; s < end; s += (uint64_t)RM_PAD_BLOCKS * 256u) rm_zero_row(xyzs, deltas, sh, s);
             return;
         }
     }
@@ -482,32 +522,26 @@ __global__ void __launch_bounds__(256) k_march_emit(const float *__restrict__ ra
     if (point_index + num_steps > M) {                             // raymarching.cu:413
         if constexpr (FIELD) {
             const uint64_t end = min((uint64_t)point_index + num_steps, (uint64_t)M);
-            for (uint64_t s = (uint64_t)point_index + lane; s < end; s += 64) {
-                xyzs[s * 3] = 0.0f; xyzs[s * 3 + 1] = 0.0f; xyzs[s * 3 + 2] = 0.0f;
-                deltas[s * 2] = 0.0f; deltas[s * 2 + 1] = 0.0f;
-                *reinterpret_cast<uint4 *>(sh + s * 16) = make_uint4(0u, 0u, 0u, 0u); *reinterpret_cast<uint4 *>(sh + s * 16 + 8) = make_uint4(0u, 0u, 0u, 0u);
-            }
+            for (uint64_t s = (uint64_t)point_index + lane; s < end; s += 64) rm_zero_row(xyzs, deltas, sh, s);
         }
         return;
     }
-    const float ox = rays_o[n * 3], oy = rays_o[n * 3 + 1], oz = rays_o[n * 3 + 2];
-    const float dx = rays_d[n * 3], dy = rays_d[n * 3 + 1], dz = rays_d[n * 3 + 2];
-    float t0 = nears[n];
-    t0 = fmaf(rm_clamp(t0 * p.dt_gamma, p.dt_min, p.dt_max), noises[n], t0);
+    const RmRay r = rm_load_ray(rays_o, rays_d, n);        // (1 / d is not used here and not computed)
+    const float t0 = rm_start(p, nears[n], noises[n]);
     const float *strip = tstrip + (uint64_t)n * max_steps;
     h8 sh0, sh1;
-    if constexpr (FIELD) foc_sh16_h(dx, dy, dz, sh0, sh1);
+    if constexpr (FIELD) foc_sh16_h(r.dx, r.dy, r.dz, sh0, sh1);
     for (uint32_t k = lane; k < num_steps; k += 64) {
         const float t = strip[k];
-        const float dt = rm_clamp(t * p.dt_gamma, p.dt_min, p.dt_max);
+        const float dt = rm_dt(p, t);
         float last_t = t0;
-        if (k > 0) { const float tp = strip[k - 1]; last_t = tp + rm_clamp(tp * p.dt_gamma, p.dt_min, p.dt_max); }
+        if (k > 0) { const float tp = strip[k - 1]; last_t = tp + rm_dt(p, tp); }
         const uint64_t s = (uint64_t)point_index + k;
-        xyzs[s * 3] = rm_out(p, rm_clamp(fmaf(t, dx, ox), -p.bound, p.bound));
-        xyzs[s * 3 + 1] = rm_out(p, rm_clamp(fmaf(t, dy, oy), -p.bound, p.bound));
-        xyzs[s * 3 + 2] = rm_out(p, rm_clamp(fmaf(t, dz, oz), -p.bound, p.bound));
+        float x, y, z;
+        rm_pos(p, r, t, x, y, z);
+        xyzs[s * 3] = rm_out(p, x); xyzs[s * 3 + 1] = rm_out(p, y); xyzs[s * 3 + 2] = rm_out(p, z);
         if constexpr (FIELD) { *reinterpret_cast<h8 *>(sh + s * 16) = sh0; *reinterpret_cast<h8 *>(sh + s * 16 + 8) = sh1; }
-        else { dirs[s * 3] = dx; dirs[s * 3 + 1] = dy; dirs[s * 3 + 2] = dz; }
+        else { dirs[s * 3] = r.dx; dirs[s * 3 + 1] = r.dy; dirs[s * 3 + 2] = r.dz; }
         deltas[s * 2] = dt;
         deltas[s * 2 + 1] = (t + dt) - last_t;
     }
@@ -594,38 +628,51 @@ __global__ void __launch_bounds__(256) k_composite_train_bwd(const float *__rest
 }
 
 // ---------------------------------------------------------------- R9 (raymarching.cu:700-805)
-// The serial loop of one list entry n (ray `index`). BAIL: stop at the first empty cell and report it (the two-phase form below: such a
-// ray is a "walker" and is marched again, from its start, by the walkers' kernel).
-template <bool BAIL>
-__device__ __forceinline__ bool rm_lane_walk(uint32_t n, int index, uint32_t n_step, const float *__restrict__ rays_t, const float *__restrict__ rays_o,
-                                             const float *__restrict__ rays_d, const uint8_t *__restrict__ grid, const RmParams &p, const float *__restrict__ fars,
-                                             float *__restrict__ xyzs, float *__restrict__ dirs, float *__restrict__ deltas, const float *__restrict__ noises) {
-    const float ox = rays_o[index * 3], oy = rays_o[index * 3 + 1], oz = rays_o[index * 3 + 2];
-    const float dx = rays_d[index * 3], dy = rays_d[index * 3 + 1], dz = rays_d[index * 3 + 2];
-    const float rdx = 1 / dx, rdy = 1 / dy, rdz = 1 / dz;
-    float *px = xyzs + (uint64_t)n * n_step * 3, *pd = dirs + (uint64_t)n * n_step * 3, *pl = deltas + (uint64_t)n * n_step * 2;
+// Where a walk puts its samples: position [3], direction [3] and (dt, span) [2] per slot. The global arrays carry a direction per sample (DIRS);
+// an LDS record does not — the flush adds it.
+struct RmSlots { float *px, *pd, *pl; };
+__device__ __forceinline__ RmSlots rm_slots_global(float *__restrict__ xyzs, float *__restrict__ dirs, float *__restrict__ deltas, uint32_t n, uint32_t n_step) {
+    return RmSlots{xyzs + (uint64_t)n * n_step * 3, dirs + (uint64_t)n * n_step * 3, deltas + (uint64_t)n * n_step * 2};
+}
+__device__ __forceinline__ RmSlots rm_slots_lds(float *rec, uint32_t n_step) { return RmSlots{rec, nullptr, rec + 3u * n_step}; }
+// The record of one emitted sample (raymarching.cu:776-787): the position as it is stored, the direction, dt and the span since the previous sample's end.
+template <bool DIRS>
+__device__ __forceinline__ void rm_put_sample(const RmSlots &o, uint32_t slot, const RmParams &p, const RmCell &c, const RmRay &r, float span) {
+    o.px[slot * 3] = rm_out(p, c.x); o.px[slot * 3 + 1] = rm_out(p, c.y); o.px[slot * 3 + 2] = rm_out(p, c.z);
+    if (DIRS) { o.pd[slot * 3] = r.dx; o.pd[slot * 3 + 1] = r.dy; o.pd[slot * 3 + 2] = r.dz; }
+    o.pl[slot * 2] = c.dt; o.pl[slot * 2 + 1] = span;
+}
+
+// The serial loop of one list entry n (ray `index`), its samples into `o` from slot 0 on. BAIL: stop at the first empty cell and report it (the
+// two-phase form below: such a ray is a "walker" and is marched again, from its start, by the walkers' kernel). The number of samples emitted
+// and the ray's direction come back for a caller that writes the samples out itself (k_march_rays_staged).
+struct RmWalked { uint32_t step; bool bailed; float dx, dy, dz; };
+template <bool BAIL, bool DIRS>
+__device__ __forceinline__ RmWalked rm_lane_walk(uint32_t n, int index, uint32_t n_step, const float *__restrict__ rays_t, const float *__restrict__ rays_o,
+                                                 const float *__restrict__ rays_d, const uint8_t *__restrict__ grid, const RmParams &p, const float *__restrict__ fars,
+                                                 const float *__restrict__ noises, RmSlots o) {
+    const RmRay r = rm_load_ray(rays_o, rays_d, index);
     float t = rays_t[index];
     const float far = fars[index];
-    t = fmaf(rm_clamp(t * p.dt_gamma, p.dt_min, p.dt_max), noises[n], t);
+    t = rm_start(p, t, noises[n]);
     float last_t = t;
-    uint32_t step = 0;
+    RmWalked w = {0u, false, r.dx, r.dy, r.dz};
     RmCell c;
-    while (t < far && step < n_step) {
-        if (rm_cell(grid, p, ox, oy, oz, dx, dy, dz, t, c)) {
-            px[0] = rm_out(p, c.x); px[1] = rm_out(p, c.y); px[2] = rm_out(p, c.z);
-            pd[0] = dx; pd[1] = dy; pd[2] = dz;
+    while (t < far && w.step < n_step) {
+        if (rm_cell(grid, p, r, t, c)) {
             t += c.dt;
             const float span = t - last_t;
-            pl[0] = c.dt; pl[1] = span;
+            rm_put_sample<DIRS>(o, 0u, p, c, r, span);
             if (p.rederive) t = last_t + span;
             last_t = t;
-            px += 3; pd += 3; pl += 2; step++;
+            o.px += 3; o.pl += 2; w.step++;
+            if (DIRS) o.pd += 3;
         } else {
-            if (BAIL) return true;
-            t = rm_skip(p, c, t, dx, dy, dz, rdx, rdy, rdz);
+            if (BAIL) { w.bailed = true; return w; }
+            t = rm_skip(p, c, t, r);
         }
     }
-    return false;
+    return w;
 }
 
 __global__ void __launch_bounds__(64) k_march_rays(uint32_t n_alive, uint32_t n_step, const int32_t *__restrict__ rays_alive,
@@ -637,14 +684,14 @@ __global__ void __launch_bounds__(64) k_march_rays(uint32_t n_alive, uint32_t n_
     if (n >= n_alive) return;
     const int index = rays_alive[n];
     if (index < 0) return;             // a list entry marked dead (-1, as composite_rays leaves them): its slots stay zero = "terminated"
-    (void)rm_lane_walk<false>(n, index, n_step, rays_t, rays_o, rays_d, grid, p, fars, xyzs, dirs, deltas, noises);
+    (void)rm_lane_walk<false, true>(n, index, n_step, rays_t, rays_o, rays_d, grid, p, fars, noises, rm_slots_global(xyzs, dirs, deltas, n, n_step));
 }
 
 // ---------------------------------------------------------------- R9, one ray per lane, the wave's samples staged in LDS
 // k_march_rays writes a ray's samples as single dwords at a 32 n_step-byte lane stride (a burst of 8: 64 stores per lane, each touching 64
 // cache lines) and relies on the caller for the zeros of the slots a ray does not fill. Here a lane collects its ray's burst in LDS
 // ([3 n_step] positions | [2 n_step] deltas | samples filled, direction) and the wave then writes the three arrays of its 64 list entries as
-// runs of consecutive floats, zeros included: every slot of every entry is written, whole cache lines at a time. Same loop, same bits.
+// runs of consecutive floats, zeros included: every slot of every entry is written, whole cache lines at a time. The loop is rm_lane_walk's.
 __global__ void __launch_bounds__(64) k_march_rays_staged(uint32_t n_alive, uint32_t n_step, const int32_t *__restrict__ rays_alive,
                              const float *__restrict__ rays_t, const float *__restrict__ rays_o, const float *__restrict__ rays_d,
                              const uint8_t *__restrict__ grid, RmParams p, const float *__restrict__ fars,
@@ -655,32 +702,10 @@ __global__ void __launch_bounds__(64) k_march_rays_staged(uint32_t n_alive, uint
     const uint32_t stride = 5u * n_step + 4u;
     float *mine = rm_stage + lane * stride;
     const int index = n < n_alive ? rays_alive[n] : -1;
-    uint32_t step = 0;
-    float dx = 0.0f, dy = 0.0f, dz = 0.0f;
-    if (index >= 0) {
-        const float ox = rays_o[index * 3], oy = rays_o[index * 3 + 1], oz = rays_o[index * 3 + 2];
-        dx = rays_d[index * 3]; dy = rays_d[index * 3 + 1]; dz = rays_d[index * 3 + 2];
-        const float rdx = 1 / dx, rdy = 1 / dy, rdz = 1 / dz;
-        float t = rays_t[index];
-        const float far = fars[index];
-        t = fmaf(rm_clamp(t * p.dt_gamma, p.dt_min, p.dt_max), noises[n], t);
-        float last_t = t;
-        float *px = mine, *pl = mine + 3u * n_step;
-        RmCell c;
-        while (t < far && step < n_step) {
-            if (rm_cell(grid, p, ox, oy, oz, dx, dy, dz, t, c)) {
-                px[0] = rm_out(p, c.x); px[1] = rm_out(p, c.y); px[2] = rm_out(p, c.z);
-                t += c.dt;
-                const float span = t - last_t;
-                pl[0] = c.dt; pl[1] = span;
-                if (p.rederive) t = last_t + span;
-                last_t = t;
-                px += 3; pl += 2; step++;
-            } else t = rm_skip(p, c, t, dx, dy, dz, rdx, rdy, rdz);
-        }
-    }
+    RmWalked w = {0u, false, 0.0f, 0.0f, 0.0f};
+    if (index >= 0) w = rm_lane_walk<false, false>(n, index, n_step, rays_t, rays_o, rays_d, grid, p, fars, noises, rm_slots_lds(mine, n_step));
     float *tail = mine + 5u * n_step;
-    tail[0] = __builtin_bit_cast(float, step); tail[1] = dx; tail[2] = dy; tail[3] = dz;
+    tail[0] = __builtin_bit_cast(float, w.step); tail[1] = w.dx; tail[2] = w.dy; tail[3] = w.dz;
     __syncthreads();                                       // one wave per workgroup: orders the LDS traffic, costs nothing
     const uint32_t cnt = min(64u, n_alive - n0);           // list entries of this wave (n0 < n_alive by the launch)
     if (sample_major) {
@@ -735,39 +760,30 @@ __global__ void __launch_bounds__(64) k_march_rays_staged(uint32_t n_alive, uint
 // (one DPP row, 4 rays per wave) generates what a burst of 8 typically consumes in one or two rounds.
 #define RM_ROW_MAX_ROUNDS (1u << 14)                       // x 16 lattice points: far beyond any real ray; makes the loop finite whatever the inputs
 // all 64 lanes of a wave call this together; `have`, `n`, `index` are uniform over each 16-lane group
-// STAGE: the samples of a ray are collected in LDS (`stage`: 5 n_step floats per 16-lane group) and leave in rm_row_flush — whole runs of
-// consecutive floats per group, zeros in the slots the ray did not fill — instead of as single dwords at a 32 n_step-byte lane stride.
-template <bool MED3, bool STAGE = false>
+// The samples go to `o`: the ray's slots of the global arrays (DIRS), or its LDS record (rm_slots_lds: 5 n_step floats per 16-lane group), which
+// leaves in rm_row_flush — whole runs of consecutive floats per group, zeros in the slots the ray did not fill — instead of as single dwords at
+// a 32 n_step-byte lane stride.
+template <bool MED3, bool DIRS>
 __device__ __forceinline__ uint32_t rm_row_walk(bool have, uint32_t n, int index, uint32_t n_step, const float *__restrict__ rays_t, const float *__restrict__ rays_o,
                                             const float *__restrict__ rays_d, const uint8_t *__restrict__ grid, const RmParams &p, const float *__restrict__ fars,
-                                            float *__restrict__ xyzs, float *__restrict__ dirs, float *__restrict__ deltas, const float *__restrict__ noises,
-                                            float *stage = nullptr) {
+                                            const float *__restrict__ noises, const RmSlots o) {
     constexpr uint32_t G = 16u;
     const uint32_t lane = threadIdx.x & 63u, sub = lane & (G - 1u), gbase = lane & ~(G - 1u), gshift = gbase;
-    const float ox = rays_o[index * 3], oy = rays_o[index * 3 + 1], oz = rays_o[index * 3 + 2];
-    const float dx = rays_d[index * 3], dy = rays_d[index * 3 + 1], dz = rays_d[index * 3 + 2];
-    const float rdx = 1 / dx, rdy = 1 / dy, rdz = 1 / dz;
+    const RmRay r = rm_load_ray(rays_o, rays_d, index);
     const float far = fars[index];
-    float t_cur = rays_t[index];
-    t_cur = fmaf(rm_clamp(t_cur * p.dt_gamma, p.dt_min, p.dt_max), noises[have ? n : 0u], t_cur);
+    float t_cur = rm_start(p, rays_t[index], noises[have ? n : 0u]);
     float last_t = t_cur;
-    float *px = xyzs + (uint64_t)n * n_step * 3, *pd = dirs + (uint64_t)n * n_step * 3, *pl = deltas + (uint64_t)n * n_step * 2;
     uint32_t step = 0;
     bool skipping = false, live = have;                    // live: this ray's loop has not ended (uniform over the ray's G lanes)
     float skip_to = 0.0f;
     const uint32_t below = (1u << sub) - 1u;
     for (uint32_t round = 0; round < RM_ROW_MAX_ROUNDS && __builtin_amdgcn_ballot_w64(live) != 0ull; round++) {
-        float T = t_cur, t_next = t_cur;
-#pragma unroll
-        for (uint32_t j = 0; j < G; j++) {
-            T = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, t_next), __builtin_bit_cast(int, T), 0x101, 0xf, 0xf, false));
-            const float raw = t_next * p.dt_gamma;
-            t_next += MED3 ? __builtin_amdgcn_fmed3f(raw, p.dt_min, p.dt_max) : rm_clamp(raw, p.dt_min, p.dt_max);
-        }
+        float T, t_next;
+        rm_lattice<0x101, G, MED3>(p, t_cur, T, t_next);
         // every lane of the wave evaluates its lattice point (rays that have ended idle along: their results are not looked at)
         RmCell c;
-        const bool occupied_here = rm_cell(grid, p, ox, oy, oz, dx, dy, dz, T, c);
-        const float exit_here = rm_skip_target(p, c, T, dx, dy, dz, rdx, rdy, rdz);
+        const bool occupied_here = rm_cell(grid, p, r, T, c);
+        const float exit_here = rm_skip_target(p, c, T, r);
         const float t_new = T + c.dt;                      // the loop's `t += dt` of an emitting visit (== the next lattice point)
         const uint32_t in_range = (uint32_t)(__ballot(T < far) >> gshift) & 0xFFFFu;
         const uint32_t occ = (uint32_t)(__ballot(occupied_here) >> gshift) & 0xFFFFu;
@@ -806,17 +822,7 @@ __device__ __forceinline__ uint32_t rm_row_walk(bool have, uint32_t n, int index
         const uint32_t before = emitted & below;
         const int prev_lane = before ? (int)(gbase + 31u - (uint32_t)__builtin_clz(before)) : (int)lane;
         const float prev_end = __shfl(t_new, prev_lane, 64);
-        if ((emitted >> sub) & 1u) {
-            const uint32_t slot = step + (uint32_t)__builtin_popcount(before);
-            if (STAGE) {
-                stage[slot * 3] = rm_out(p, c.x); stage[slot * 3 + 1] = rm_out(p, c.y); stage[slot * 3 + 2] = rm_out(p, c.z);
-                stage[3 * n_step + slot * 2] = c.dt; stage[3 * n_step + slot * 2 + 1] = t_new - (before ? prev_end : last_t);
-            } else {
-                px[slot * 3] = rm_out(p, c.x); px[slot * 3 + 1] = rm_out(p, c.y); px[slot * 3 + 2] = rm_out(p, c.z);
-                pd[slot * 3] = dx; pd[slot * 3 + 1] = dy; pd[slot * 3 + 2] = dz;
-                pl[slot * 2] = c.dt; pl[slot * 2 + 1] = t_new - (before ? prev_end : last_t);
-            }
-        }
+        if ((emitted >> sub) & 1u) rm_put_sample<DIRS>(o, step + (uint32_t)__builtin_popcount(before), p, c, r, t_new - (before ? prev_end : last_t));
         const int top_lane = emitted ? (int)(gbase + 31u - (uint32_t)__builtin_clz(emitted)) : (int)lane;
         const float top_end = __shfl(t_new, top_lane, 64);
         if (emitted) last_t = top_end;
@@ -852,7 +858,7 @@ __global__ void __launch_bounds__(256) k_march_rays_row(uint32_t n_alive, uint32
     const int listed = n < n_alive ? rays_alive[n] : -1;
     const bool have = listed >= 0;     // beyond the list, or an entry marked dead (-1): nothing to march
     float *mine = stage[threadIdx.x >> 4];
-    const uint32_t filled = rm_row_walk<MED3, true>(have, n, have ? listed : 0, n_step, rays_t, rays_o, rays_d, grid, p, fars, xyzs, dirs, deltas, noises, mine);
+    const uint32_t filled = rm_row_walk<MED3, false>(have, n, have ? listed : 0, n_step, rays_t, rays_o, rays_d, grid, p, fars, noises, rm_slots_lds(mine, n_step));
     __syncthreads();
     // every entry of the list leaves with all of its slots written (a dead one: zeros = "terminated"), so the caller need not have zeroed them
     if (n < n_alive) rm_row_flush(n, have ? listed : 0, n_step, have ? filled : 0u, rays_d, mine, xyzs, dirs, deltas);
@@ -875,7 +881,7 @@ __global__ void __launch_bounds__(256) k_march_rays_first(uint32_t n_alive, uint
     bool walker = false;
     if (n < n_alive) {
         const int index = rays_alive[n];
-        if (index >= 0) walker = rm_lane_walk<true>(n, index, n_step, rays_t, rays_o, rays_d, grid, p, fars, xyzs, dirs, deltas, noises);
+        if (index >= 0) walker = rm_lane_walk<true, true>(n, index, n_step, rays_t, rays_o, rays_d, grid, p, fars, noises, rm_slots_global(xyzs, dirs, deltas, n, n_step)).bailed;
     }
     const uint64_t mask = __ballot(walker);
     if (mask != 0ull) {
@@ -901,12 +907,12 @@ __global__ void __launch_bounds__(256) k_march_walkers(uint32_t n_alive, uint32_
             const uint32_t i = base + ((threadIdx.x & 63u) >> 4);
             const bool have = i < count;
             const uint32_t n = have ? (uint32_t)worklist[i] : 0u;
-            rm_row_walk<MED3>(have, n, have ? rays_alive[n] : 0, n_step, rays_t, rays_o, rays_d, grid, p, fars, xyzs, dirs, deltas, noises);
+            rm_row_walk<MED3, true>(have, n, have ? rays_alive[n] : 0, n_step, rays_t, rays_o, rays_d, grid, p, fars, noises, rm_slots_global(xyzs, dirs, deltas, n, n_step));
         }
     } else {
         for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < count; i += gridDim.x * 256u) {
             const uint32_t n = (uint32_t)worklist[i];
-            (void)rm_lane_walk<false>(n, rays_alive[n], n_step, rays_t, rays_o, rays_d, grid, p, fars, xyzs, dirs, deltas, noises);
+            (void)rm_lane_walk<false, true>(n, rays_alive[n], n_step, rays_t, rays_o, rays_d, grid, p, fars, noises, rm_slots_global(xyzs, dirs, deltas, n, n_step));
         }
     }
 }
@@ -930,8 +936,47 @@ __device__ __forceinline__ void rm_record_deaths(const RmDeaths &dh, bool died, 
 }
 
 // ---------------------------------------------------------------- R10 (raymarching.cu:818-905)
+// What a ray accumulates over the calls of a view, and the three pieces both composite kernels are made of.
+struct RmAcc { float t, weight_sum, d, r, g, b; };
+__device__ __forceinline__ RmAcc rm_acc_load(int index, const float *__restrict__ rays_t, const float *__restrict__ weights_sum, const float *__restrict__ depth,
+                                             const float *__restrict__ image) {
+    return RmAcc{rays_t[index], weights_sum[index], depth[index], image[index * 3], image[index * 3 + 1], image[index * 3 + 2]};
+}
+// one sample (:862-896) -> the ray ends here: the slot holds no sample (dt0 == 0), or the transmittance before it was below T_thresh.
+// Not free: k_composite_rays compiles to 153 / 218 instructions (COUNT off / on) through this function and rm_composite_finish, to 140 / 203 with
+// both spelled out in it (scalar control flow; registers, occupancy and the burst-1 view's time are unchanged): NOTEBOOK "One definition of the
+// occupancy march". Compare the counts again when changing either function.
+__device__ __forceinline__ bool rm_composite_sample(RmAcc &a, float sigma, float dt0, float dt1, float c0, float c1, float c2, float T_thresh) {
+    if (dt0 == 0) return true;
+    const float alpha = 1.0f - __expf(-sigma * dt0);
+    const float T = 1 - a.weight_sum;
+    const float weight = alpha * T;
+    a.weight_sum += weight;
+    a.t += dt1;
+    a.d = fmaf(weight, a.t, a.d);
+    a.r = fmaf(weight, c0, a.r); a.g = fmaf(weight, c1, a.g); a.b = fmaf(weight, c2, a.b);
+    return T < T_thresh;
+}
+// List entry n after its burst: ended at slot `ended_at` (marked dead) or still going (its t is kept for the next call); the accumulators go back.
+// Every lane of the wave comes here — `index` < 0: beyond the list or already marked dead (stays dead, nothing to accumulate).
 // COUNT: the wave also adds its number of surviving entries to block_counts[n / 1024] (zeroed by the caller) — the first pass of the ordered
-// compaction that follows in the native render step (k_compact_count otherwise)
+// compaction that follows in the native render step (k_compact_count otherwise) — and records where its rays died.
+template <bool COUNT>
+__device__ __forceinline__ void rm_composite_finish(uint32_t n, int index, const RmAcc &a, bool ended, uint32_t ended_at, uint32_t n_step,
+                                                    int32_t *__restrict__ rays_alive, float *__restrict__ rays_t, float *__restrict__ weights_sum,
+                                                    float *__restrict__ depth, float *__restrict__ image, int32_t *__restrict__ block_counts, const RmDeaths &dh) {
+    if (index >= 0) {
+        if (ended) rays_alive[n] = -1; else rays_t[index] = a.t;
+        weights_sum[index] = a.weight_sum; depth[index] = a.d;
+        image[index * 3] = a.r; image[index * 3 + 1] = a.g; image[index * 3 + 2] = a.b;
+    }
+    if (COUNT) {
+        const uint64_t alive = __ballot(index >= 0 && !ended);
+        if ((threadIdx.x & 63u) == 0u && alive != 0ull) atomicAdd(&block_counts[n >> 10], (int)__builtin_popcountll(alive));
+        rm_record_deaths(dh, index >= 0 && ended, ended_at, n_step, n);
+    }
+}
+
 template <bool COUNT>
 __global__ void __launch_bounds__(64) k_composite_rays(uint32_t n_alive, uint32_t n_step, float T_thresh,
                                  int32_t *__restrict__ rays_alive, float *__restrict__ rays_t,
@@ -940,37 +985,19 @@ __global__ void __launch_bounds__(64) k_composite_rays(uint32_t n_alive, uint32_
                                  RmDeaths dh) {
     const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
     const int index = n < n_alive ? rays_alive[n] : -1;
-    bool survives = false, died = false;
-    uint32_t died_at = 0;
-    if (index >= 0) {                  // beyond the list or already marked dead (stays dead, nothing to accumulate)
-    // ray-major [n_alive][n_step] (the reference's layout) or sample-major [n_step][n_alive] (dh.sample_major: the native render step)
-    const uint64_t first = dh.sample_major ? (uint64_t)n : (uint64_t)n * n_step, hop = dh.sample_major ? (uint64_t)n_alive : 1ull;
-    const float *s = sigmas + first, *c = rgbs + first * 3, *dl = deltas + first * 2;
-    float t = rays_t[index];
-    float weight_sum = weights_sum[index], d = depth[index];
-    float r = image[index * 3], g = image[index * 3 + 1], b = image[index * 3 + 2];
+    RmAcc a = {};
     uint32_t step = 0;
-    while (step < n_step) {
-        if (dl[0] == 0) break;
-        const float alpha = 1.0f - __expf(-s[0] * dl[0]);
-        const float T = 1 - weight_sum;
-        const float weight = alpha * T;
-        weight_sum += weight;
-        t += dl[1];
-        d = fmaf(weight, t, d);
-        r = fmaf(weight, c[0], r); g = fmaf(weight, c[1], g); b = fmaf(weight, c[2], b);
-        if (T < T_thresh) break;
-        s += hop; c += 3 * hop; dl += 2 * hop; step++;
+    if (index >= 0) {
+        // ray-major [n_alive][n_step] (the reference's layout) or sample-major [n_step][n_alive] (dh.sample_major: the native render step)
+        const uint64_t first = dh.sample_major ? (uint64_t)n : (uint64_t)n * n_step, hop = dh.sample_major ? (uint64_t)n_alive : 1ull;
+        const float *s = sigmas + first, *c = rgbs + first * 3, *dl = deltas + first * 2;
+        a = rm_acc_load(index, rays_t, weights_sum, depth, image);
+        while (step < n_step) {
+            if (rm_composite_sample(a, s[0], dl[0], dl[1], c[0], c[1], c[2], T_thresh)) break;
+            s += hop; c += 3 * hop; dl += 2 * hop; step++;
+        }
     }
-    if (step < n_step) { rays_alive[n] = -1; died = true; died_at = step; } else { rays_t[index] = t; survives = true; }
-    weights_sum[index] = weight_sum; depth[index] = d;
-    image[index * 3] = r; image[index * 3 + 1] = g; image[index * 3 + 2] = b;
-    }
-    if (COUNT) {
-        const uint64_t alive = __ballot(survives);
-        if ((threadIdx.x & 63u) == 0u && alive != 0ull) atomicAdd(&block_counts[n >> 10], (int)__builtin_popcountll(alive));
-        rm_record_deaths(dh, died, died_at, n_step, n);
-    }
+    rm_composite_finish<COUNT>(n, index, a, step < n_step, step, n_step, rays_alive, rays_t, weights_sum, depth, image, block_counts, dh);
 }
 
 // The same with a compile-time burst length that is a multiple of 4: the lane first loads ALL of its ray's sigmas / colours / deltas with
@@ -985,8 +1012,9 @@ __global__ void __launch_bounds__(64) k_composite_rays_pre(uint32_t n_alive, flo
     static_assert(NS % 4 == 0, "whole float4 loads");
     const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
     const int index = n < n_alive ? rays_alive[n] : -1;
-    bool survives = false, died = false;
-    uint32_t died_at = 0;
+    RmAcc a = {};
+    bool ended = false;
+    uint32_t ended_at = 0;
     if (index >= 0) {
         float sg[NS], cl[3 * NS], dl[2 * NS];
         if (dh.sample_major) {             // [NS][n_alive]: consecutive lanes read consecutive rays of one slot
@@ -1009,54 +1037,32 @@ __global__ void __launch_bounds__(64) k_composite_rays_pre(uint32_t n_alive, flo
 #pragma unroll
         for (int i = 0; i < 2 * NS / 4; i++) { const float4 v = pd[i]; dl[4 * i] = v.x; dl[4 * i + 1] = v.y; dl[4 * i + 2] = v.z; dl[4 * i + 3] = v.w; }
         }
-        float t = rays_t[index];
-        float weight_sum = weights_sum[index], d = depth[index];
-        float r = image[index * 3], g = image[index * 3 + 1], b = image[index * 3 + 2];
-        bool ended = false;
-        uint32_t ended_at = 0;
+        a = rm_acc_load(index, rays_t, weights_sum, depth, image);
 #pragma unroll
         for (int step = 0; step < NS; step++) {
             if (!ended) {
                 ended_at = (uint32_t)step;
-                if (dl[2 * step] == 0) ended = true;
-                else {
-                    const float alpha = 1.0f - __expf(-sg[step] * dl[2 * step]);
-                    const float T = 1 - weight_sum;
-                    const float weight = alpha * T;
-                    weight_sum += weight;
-                    t += dl[2 * step + 1];
-                    d = fmaf(weight, t, d);
-                    r = fmaf(weight, cl[3 * step], r); g = fmaf(weight, cl[3 * step + 1], g); b = fmaf(weight, cl[3 * step + 2], b);
-                    if (T < T_thresh) ended = true;
-                }
+                ended = rm_composite_sample(a, sg[step], dl[2 * step], dl[2 * step + 1], cl[3 * step], cl[3 * step + 1], cl[3 * step + 2], T_thresh);
             }
         }
-        if (ended) { rays_alive[n] = -1; died = true; died_at = ended_at; } else { rays_t[index] = t; survives = true; }
-        weights_sum[index] = weight_sum; depth[index] = d;
-        image[index * 3] = r; image[index * 3 + 1] = g; image[index * 3 + 2] = b;
     }
-    if (COUNT) {
-        const uint64_t alive = __ballot(survives);
-        if ((threadIdx.x & 63u) == 0u && alive != 0ull) atomicAdd(&block_counts[n >> 10], (int)__builtin_popcountll(alive));
-        rm_record_deaths(dh, died, died_at, (uint32_t)NS, n);
-    }
+    rm_composite_finish<COUNT>(n, index, a, ended, ended_at, (uint32_t)NS, rays_alive, rays_t, weights_sum, depth, image, block_counts, dh);
 }
 
 template <bool COUNT>
 static void rm_launch_composite(uint32_t n_alive, uint32_t n_step, float T_thresh, int32_t *rays_alive, float *rays_t, const float *sigmas, const float *rgbs,
                                 const float *deltas, float *weights_sum, float *depth, float *image, int32_t *block_counts, hipStream_t st,
                                 RmDeaths dh = RmDeaths{nullptr, 0u, 1u, 0}) {
-    const dim3 grid(foc_div_up(n_alive, 64)), block(64);
     const bool aligned = ((reinterpret_cast<uintptr_t>(sigmas) | reinterpret_cast<uintptr_t>(rgbs) | reinterpret_cast<uintptr_t>(deltas)) & 15u) == 0;
-    if (aligned && n_step == 4u)
-        hipLaunchKernelGGL((k_composite_rays_pre<4, COUNT>), grid, block, 0, st, n_alive, T_thresh, rays_alive, rays_t, sigmas, rgbs, deltas, weights_sum, depth, image, block_counts, dh);
-    else if (aligned && n_step == 8u)
-        hipLaunchKernelGGL((k_composite_rays_pre<8, COUNT>), grid, block, 0, st, n_alive, T_thresh, rays_alive, rays_t, sigmas, rgbs, deltas, weights_sum, depth, image, block_counts, dh);
-    else if (aligned && n_step == 16u)
-        hipLaunchKernelGGL((k_composite_rays_pre<16, COUNT>), grid, block, 0, st, n_alive, T_thresh, rays_alive, rays_t, sigmas, rgbs, deltas, weights_sum, depth, image, block_counts, dh);
-    else
-        hipLaunchKernelGGL(k_composite_rays<COUNT>, grid, block, 0, st, n_alive, n_step, T_thresh, rays_alive, rays_t, sigmas, rgbs, deltas, weights_sum, depth, image,
-                           block_counts, dh);
+    // (`burst`: the run-time n_step argument of the general kernel; the others have it in their name)
+    const auto launch = [&](auto kernel, auto... burst) {
+        hipLaunchKernelGGL(kernel, dim3(foc_div_up(n_alive, 64)), dim3(64), 0, st, n_alive, burst..., T_thresh, rays_alive, rays_t, sigmas, rgbs, deltas, weights_sum, depth,
+                           image, block_counts, dh);
+    };
+    if (aligned && n_step == 4u) launch(k_composite_rays_pre<4, COUNT>);
+    else if (aligned && n_step == 8u) launch(k_composite_rays_pre<8, COUNT>);
+    else if (aligned && n_step == 16u) launch(k_composite_rays_pre<16, COUNT>);
+    else launch(k_composite_rays<COUNT>, n_step);
 }
 
 // ---------------------------------------------------------------- ordered compaction of rays_alive >= 0
@@ -1071,24 +1077,9 @@ __global__ void __launch_bounds__(1024) k_compact_count(const int32_t *__restric
 }
 __global__ void __launch_bounds__(1024) k_compact_scan(int32_t *__restrict__ block_counts, uint32_t nb, int32_t *__restrict__ n_out) {
     // single workgroup: exclusive scan of nb block counts in place
-    __shared__ int s_wave[16];
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t per = (nb + 1023) / 1024;
-    const uint32_t lo = tid * per, hi = min(nb, lo + per);
-    int local = 0;
-    for (uint32_t i = lo; i < hi; i++) local += block_counts[i];
-    const int incl = wave_incl_sum_i(local, (int)lane);
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    if (wave == 0) {
-        int v = lane < 16 ? s_wave[lane] : 0;
-        const int vi = wave_incl_sum_i(v, (int)lane);
-        if (lane < 16) s_wave[lane] = vi - v;
-        if (lane == 15) n_out[0] = vi;
-    }
-    __syncthreads();
-    int run = s_wave[wave] + (incl - local);
-    for (uint32_t i = lo; i < hi; i++) { const int c = block_counts[i]; block_counts[i] = run; run += c; }
+    const RmScan sc = rm_scan_1024(block_counts, nb, n_out);
+    int run = sc.base;
+    for (uint32_t i = sc.lo; i < sc.hi; i++) { const int c = block_counts[i]; block_counts[i] = run; run += c; }
 }
 __global__ void __launch_bounds__(1024) k_compact_scatter(const int32_t *__restrict__ in, uint32_t n, const int32_t *__restrict__ block_base,
                                                           int32_t *__restrict__ out) {
@@ -1165,6 +1156,17 @@ int foc_packbits(const float *grid, uint32_t N, float density_thresh, uint8_t *b
     return FOC_OK;
 }
 
+// what every marching entry point refuses: a grid the kernels are not written for
+// (`n_step_max` != 0: the entry point marches bursts of 1 .. n_step_max samples and names n_step in its refusal)
+static int rm_check_grid(const char *who, uint32_t C, uint32_t H, uint32_t max_steps, uint32_t n_step_max = 0, uint32_t n_step = 1) {
+    const bool ok = C >= 1 && C <= 8 && H >= 2 && H <= 512 && max_steps >= 1;
+    if (n_step_max) FOC_REQUIRE(ok && n_step >= 1 && n_step <= n_step_max, FOC_E_INVALID, "%s: unsupported C=%u H=%u max_steps=%u n_step=%u", who, C, H, max_steps, n_step);
+    FOC_REQUIRE(ok, FOC_E_INVALID, "%s: unsupported C=%u H=%u max_steps=%u", who, C, H, max_steps);
+    // the float index `level*H^3 + morton` of raymarching.cu:378 is exact only below 2^24
+    FOC_REQUIRE((uint64_t)C * H * H * H <= (1ull << 24), FOC_E_INVALID, "%s: C*H^3 exceeds 2^24", who);
+    return FOC_OK;
+}
+
 // counts [N] (+ pad), then the per-ray strips of sample positions [N, max_steps]
 static uint64_t rm_strip_offset(uint32_t N) { return (((uint64_t)N + 64) * sizeof(int32_t) + 255) & ~(uint64_t)255; }
 uint64_t foc_march_rays_train_scratch_bytes(uint32_t N, uint32_t max_steps) { return rm_strip_offset(N) + (uint64_t)N * max_steps * sizeof(float); }
@@ -1178,10 +1180,7 @@ static int rm_march_train(const float *rays_o, const float *rays_d, const uint8_
     FOC_REQUIRE(rays_o && rays_d && grid && nears && fars && rays && counter && noises && scratch, FOC_E_INVALID,
                 "march_rays_train: null pointer");
     FOC_REQUIRE(M == 0 || (xyzs && deltas && (field ? sh_rows != nullptr : dirs != nullptr)), FOC_E_INVALID, "march_rays_train: null output with M > 0");
-    FOC_REQUIRE(C >= 1 && C <= 8 && H >= 2 && H <= 512 && max_steps >= 1, FOC_E_INVALID,
-                "march_rays_train: unsupported C=%u H=%u max_steps=%u", C, H, max_steps);
-    // the float index `level*H^3 + morton` of raymarching.cu:378 is exact only below 2^24
-    FOC_REQUIRE((uint64_t)C * H * H * H <= (1ull << 24), FOC_E_INVALID, "march_rays_train: C*H^3 exceeds 2^24");
+    if (const int bad = rm_check_grid("march_rays_train", C, H, max_steps)) return bad;
     RmParams p = rm_make_params(bound, dt_gamma, max_steps, C, H);
     hipStream_t st = (hipStream_t)stream;
     float *tstrip = reinterpret_cast<float *>(reinterpret_cast<char *>(scratch) + rm_strip_offset(N));
@@ -1270,6 +1269,18 @@ int foc_composite_rays_train_backward(const float *grad_weights_sum, const float
     return FOC_OK;
 }
 
+// the 16-lanes-per-ray and the one-ray-per-lane launch of R9 (foc_march_rays and foc_march_rays_two_phase)
+static void rm_launch_row(uint32_t n_alive, uint32_t n_step, const int32_t *rays_alive, const float *rays_t, const float *rays_o, const float *rays_d,
+                          const uint8_t *grid, const RmParams &p, const float *fars, float *xyzs, float *dirs, float *deltas, const float *noises, hipStream_t st) {
+    hipLaunchKernelGGL(p.dt_min <= p.dt_max ? k_march_rays_row<true> : k_march_rays_row<false>, dim3(foc_div_up((uint64_t)n_alive * 16u, 256)), dim3(256), 0, st,
+                       n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, grid, p, fars, xyzs, dirs, deltas, noises);
+}
+static void rm_launch_lane(uint32_t n_alive, uint32_t n_step, const int32_t *rays_alive, const float *rays_t, const float *rays_o, const float *rays_d,
+                           const uint8_t *grid, const RmParams &p, const float *fars, float *xyzs, float *dirs, float *deltas, const float *noises, hipStream_t st) {
+    hipLaunchKernelGGL(k_march_rays, dim3(foc_div_up(n_alive, 64)), dim3(64), 0, st, n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, grid, p, fars, xyzs, dirs,
+                       deltas, noises);
+}
+
 int foc_march_rays(uint32_t n_alive, uint32_t n_step, const int32_t *rays_alive, const float *rays_t, const float *rays_o,
                    const float *rays_d, float bound, float dt_gamma, uint32_t max_steps, uint32_t C, uint32_t H,
                    const uint8_t *grid, const float *nears, const float *fars, float *xyzs, float *dirs, float *deltas,
@@ -1279,9 +1290,7 @@ int foc_march_rays(uint32_t n_alive, uint32_t n_step, const int32_t *rays_alive,
     if (n_alive == 0) return FOC_OK;
     FOC_REQUIRE(rays_alive && rays_t && rays_o && rays_d && grid && fars && xyzs && dirs && deltas && noises, FOC_E_INVALID,
                 "march_rays: null pointer");
-    FOC_REQUIRE(C >= 1 && C <= 8 && H >= 2 && H <= 512 && max_steps >= 1 && n_step >= 1, FOC_E_INVALID,
-                "march_rays: unsupported C=%u H=%u max_steps=%u n_step=%u", C, H, max_steps, n_step);
-    FOC_REQUIRE((uint64_t)C * H * H * H <= (1ull << 24), FOC_E_INVALID, "march_rays: C*H^3 exceeds 2^24");
+    if (const int bad = rm_check_grid("march_rays", C, H, max_steps, ~0u, n_step)) return bad;
     const RmParams p = rm_make_params(bound, dt_gamma, max_steps, C, H);
     // 16 lanes per ray (k_march_rays_row) while the launch is latency-bound, one ray per lane beyond (FOC_MARCH_RAYS_ROW_MAX = most rays
     // the row form takes; 0 = never). Measured on the 800 x 800 occupancy render (profiles/, tools/quick_render_stats.sh; 549 launches,
@@ -1290,12 +1299,8 @@ int foc_march_rays(uint32_t n_alive, uint32_t n_step, const int32_t *rays_alive,
     // 549) against ~40 us. A lane form looking 8 lattice points ahead measured 53.8 us against 48.1 (round 3; removed): with
     // ~10 waves per SIMD the big launches are bound by the divergent walks' instruction count, not by their lookup chains.
     const long row_max = foc_opt(FOC_OPT_MARCH_RAYS_ROW_MAX);
-    if ((long)n_alive <= row_max && n_step <= 16u)
-        hipLaunchKernelGGL(p.dt_min <= p.dt_max ? k_march_rays_row<true> : k_march_rays_row<false>, dim3(foc_div_up((uint64_t)n_alive * 16u, 256)), dim3(256), 0,
-                           (hipStream_t)stream, n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, grid, p, fars, xyzs, dirs, deltas, noises);
-    else
-        hipLaunchKernelGGL(k_march_rays, dim3(foc_div_up(n_alive, 64)), dim3(64), 0, (hipStream_t)stream, n_alive, n_step, rays_alive,
-                           rays_t, rays_o, rays_d, grid, p, fars, xyzs, dirs, deltas, noises);
+    if ((long)n_alive <= row_max && n_step <= 16u) rm_launch_row(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, grid, p, fars, xyzs, dirs, deltas, noises, (hipStream_t)stream);
+    else rm_launch_lane(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, grid, p, fars, xyzs, dirs, deltas, noises, (hipStream_t)stream);
     FOC_CHECK_LAUNCH("march_rays");
     return FOC_OK;
 }
@@ -1328,9 +1333,7 @@ int foc_march_rays_two_phase(uint32_t n_alive, uint32_t n_step, const int32_t *r
     if (n_alive == 0) return FOC_OK;
     FOC_REQUIRE(rays_alive && rays_t && rays_o && rays_d && grid && fars && xyzs && dirs && deltas && noises && scratch, FOC_E_INVALID,
                 "march_rays_two_phase: null pointer");
-    FOC_REQUIRE(C >= 1 && C <= 8 && H >= 2 && H <= 512 && max_steps >= 1 && n_step >= 1 && n_step <= 16, FOC_E_INVALID,
-                "march_rays_two_phase: unsupported C=%u H=%u max_steps=%u n_step=%u", C, H, max_steps, n_step);
-    FOC_REQUIRE((uint64_t)C * H * H * H <= (1ull << 24), FOC_E_INVALID, "march_rays_two_phase: C*H^3 exceeds 2^24");
+    if (const int bad = rm_check_grid("march_rays_two_phase", C, H, max_steps, 16u, n_step)) return bad;
     RmParams p = rm_make_params(bound, dt_gamma, max_steps, C, H);
     if (normalised & 1) p.norm_inv = 1.0f / (2.0f * bound);    // `xyzs` receives (x + bound) / (2 bound) as torch evaluates it: times the reciprocal (grid.py:149)
     p.rederive = (normalised & 2) ? 1 : 0;
@@ -1340,21 +1343,17 @@ int foc_march_rays_two_phase(uint32_t n_alive, uint32_t n_step, const int32_t *r
     // 16 lanes per ray when few rays are left ("row"); FOC_OCC_MARCH_FORM = two | row | lane | staged overrides the choice (A/B runs, tests).
     const int form = rm_burst_form(n_step, n_alive, p.rederive != 0);
     if (form == 1) {
-        hipLaunchKernelGGL(p.dt_min <= p.dt_max ? k_march_rays_row<true> : k_march_rays_row<false>, dim3(foc_div_up((uint64_t)n_alive * 16u, 256)), dim3(256), 0, st,
-                           n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, grid, p, fars, xyzs, dirs, deltas, noises);
+        rm_launch_row(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, grid, p, fars, xyzs, dirs, deltas, noises, st);
         FOC_CHECK_LAUNCH("march_rays(row form)");
         return FOC_OK;
-    }
-    if (form == 3) {
+    } else if (form == 2) {
+        rm_launch_lane(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, grid, p, fars, xyzs, dirs, deltas, noises, st);
+        FOC_CHECK_LAUNCH("march_rays(lane form)");
+        return FOC_OK;
+    } else if (form == 3) {
         hipLaunchKernelGGL(k_march_rays_staged, dim3(foc_div_up(n_alive, 64)), dim3(64), 64u * (5u * n_step + 4u) * sizeof(float), st, n_alive, n_step, rays_alive, rays_t,
                            rays_o, rays_d, grid, p, fars, xyzs, dirs, deltas, noises, (normalised & 4) ? 1 : 0);
         FOC_CHECK_LAUNCH("march_rays(staged lane form)");
-        return FOC_OK;
-    }
-    if (form == 2) {
-        hipLaunchKernelGGL(k_march_rays, dim3(foc_div_up(n_alive, 64)), dim3(64), 0, st, n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, grid, p, fars, xyzs,
-                           dirs, deltas, noises);
-        FOC_CHECK_LAUNCH("march_rays(lane form)");
         return FOC_OK;
     }
     int32_t *wl_count = scratch, *worklist = scratch + 4;

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""tools/output_digest.py [out.json] [--sections a,b] [--root DIR]: sha256 of every output of the per-sample, ragged-composite, fixed-step
-and combine kernels on seeded inputs, and of the occupancy node driven from Python, as one JSON object {case: {output: digest}} — the bits
+"""tools/output_digest.py [out.json] [--sections a,b] [--root DIR]: sha256 of every output of the per-sample, ragged-composite, fixed-step,
+combine and marching kernels on seeded inputs, and of the occupancy node driven from Python, as one JSON object {case: {output: digest}} — the bits
 of one build — printed, or written to out.json with a one-line summary printed instead. Run it once per build on the same GPU
 (FOCNERF_LIB_PATH selects the library) and compare the two objects: equal = the same bits on every case.
---sections: of per_sample, ragged, fixed, combine, node (default: all). --root DIR: the checkout whose focnerf_amd package (and library)
+--sections: of per_sample, ragged, fixed, combine, march, node (default: all). --root DIR: the checkout whose focnerf_amd package (and library)
 is imported instead of this one's — the `node` section runs the package's Python, so one copy of this tool serves both commits of a
 comparison.
 
@@ -18,6 +18,16 @@ scalar and per-ray backgrounds, the object networks with and without a ray mask,
 weights_sum, the criterion (the masked norm of ray_sumsq), the marched counts and every parameter gradient. Then one evaluation view per
 kind through the native render loop. Run a build twice before comparing two builds: an output that differs between the two runs of one
 build (an fp32 atomic of torch's own backward) says nothing about the builds.
+
+`march` (raymarching.hip's entry points called through `_lib`, outputs only — scratch, worklists and block counts are left out; every walker
+writes its own slots and the atomics involved are integer adds, so every digested output is deterministic): a random bitfield of fill 0.5 at
+H = 32, bound 1 and 2 with their cascades. The training march, plain and `_field`: 1, 5 and 130 rays, max_steps 7 (dt_min > dt_max: the kernels
+without the median), 64 (steps of dt_min, at bound 2 and dt_gamma 0.013 also of t dt_gamma) and 1024 (all three regimes), dt_gamma 0, 1/128
+and 0.013, FOC_MARCH_SERIAL 0 and 1, counter base 0 and 37, a list that just fits and one too small for the last ray, the field form with
+pad_align 0 and 128 and with the box or the ranges given. The inference march (max_steps 64 and 1024): lists of 1, 70 and 300 entries with dead ones among them,
+foc_march_rays at n_step 1, 3, 8, 16 with the row form off and on, foc_march_rays_two_phase at n_step 1, 2, 4, 8, 16 in its four forms with
+flags 0, 1, 3 and (where the form writes sample-major arrays) 7. foc_composite_rays at n_step 1, 2, 3, 4, 8, 16, foc_composite_compact at 2, 4
+and 8 in both layouts with and without a deaths histogram, T_thresh 1e-4 and 0.5. foc_compact_alive at 1, 1023, 1025 and 2100 entries.
 
 Left out: the gradient of the background model's table (foc_background_backward: fp32 atomics, not bit-stable run to run in the default
 mode) and with it the whole background backward; the forward is covered. Every input is drawn on the host from a seeded generator.
@@ -46,14 +56,14 @@ def _option(name):
 
 
 ROOT = _option("--root") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-ALL_SECTIONS = ("per_sample", "ragged", "fixed", "combine", "node")
+ALL_SECTIONS = ("per_sample", "ragged", "fixed", "combine", "march", "node")
 SECTIONS = (_option("--sections") or ",".join(ALL_SECTIONS)).split(",")
 if set(SECTIONS) - set(ALL_SECTIONS):
     sys.exit(f"usage: output_digest.py [out.json] [--sections a,b] [--root DIR]: sections are {', '.join(ALL_SECTIONS)}, got {', '.join(SECTIONS)}")
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-from focnerf_amd._lib import lib, ptr, stream_of, check        # noqa: E402
+from focnerf_amd._lib import lib, ptr, stream_of, check, set_option, get_option       # noqa: E402
 import background_ref as br                                     # noqa: E402
 import ragged_ref as rr                                         # noqa: E402
 
@@ -262,6 +272,149 @@ def combine(T):
     put(f"combine[N={N},T={T}]", **res)
 
 
+# ---------------------------------------------------------------- marching, inference composite and compaction (raymarching.hip)
+MARCH_H = 32
+MARCH_FORMS = {"two": 0, "row": 1, "lane": 2, "staged": 3}
+
+
+def march_scene(bound, n_rays):
+    """A random occupancy bitfield (fill 0.5) and rays from around the box towards its middle, with their ranges."""
+    C = 1 + int(np.ceil(np.log2(bound)))
+    rng = np.random.default_rng(40 + int(bound))
+    bits = cuda(rng.integers(0, 256, C * MARCH_H ** 3 // 8).astype(np.uint8))
+    o = rng.normal(0, 1, (n_rays, 3)); o *= 1.6 * bound / np.linalg.norm(o, axis=1, keepdims=True)
+    d = rng.normal(0, 0.35 * bound, (n_rays, 3)) - o; d /= np.linalg.norm(d, axis=1, keepdims=True)
+    o, d = cuda(o.astype(np.float32)), cuda(d.astype(np.float32))
+    aabb = cuda(np.array([-bound] * 3 + [bound] * 3, np.float32))
+    nears, fars = full(n_rays), full(n_rays)
+    call(lib.foc_near_far_from_aabb, ptr(o), ptr(d), ptr(aabb), n_rays, 0.05, ptr(nears), ptr(fars))
+    return dict(C=C, bits=bits, o=o, d=d, aabb=aabb, nears=nears, fars=fars, noises=cuda(rng.random(n_rays).astype(np.float32)))
+
+
+def march_train(bound):
+    sc = march_scene(bound, 130)
+    C, H = sc["C"], MARCH_H
+    for N in (1, 5, 130):
+        for max_steps in (7, 64, 1024):
+            scratch = torch.zeros(int(lib.foc_march_rays_train_scratch_bytes(N, max_steps)), dtype=torch.uint8, device="cuda")
+            for dt_gamma in (0.0, 1 / 128, 0.013):
+                for serial in (0, 1):
+                    set_option("FOC_MARCH_SERIAL", serial)
+                    for base in (0, 37):
+                        # forms: plain; the field form with pad_align 0 / 128 and the box (ranges are outputs) or the ranges given
+                        forms = [("plain", 0, False)] + [(f"field,pad_align={pa},aabb={box}", pa, box) for pa in (0, 128) for box in (True, False)]
+                        for form, pad_align, box in forms:
+                            field = form != "plain"
+
+                            def run(M):
+                                counter = cuda(np.array([base, 0], np.int32))
+                                rays, deltas = full((N, 3), torch.int32), full((max(M, 1), 2))
+                                xyzs, dirs, sh = full((max(M, 1), 3)), full((max(M, 1), 3)), full((max(M, 1), 16), torch.float16)
+                                nears, fars = (full(N), full(N)) if box else (sc["nears"][:N].clone(), sc["fars"][:N].clone())
+                                if field:
+                                    call(lib.foc_march_rays_train_field, ptr(sc["o"]), ptr(sc["d"]), ptr(sc["bits"]), bound, dt_gamma, max_steps, N, C, H, M, ptr(nears),
+                                         ptr(fars), ptr(xyzs), ptr(sh), ptr(deltas), ptr(rays), ptr(counter), ptr(sc["noises"]), ptr(scratch), pad_align,
+                                         ptr(sc["aabb"]) if box else None, 0.05)
+                                    return counter, dict(enc_in=xyzs, sh=sh, deltas=deltas, rays=rays, counter=counter, nears=nears, fars=fars)
+                                call(lib.foc_march_rays_train, ptr(sc["o"]), ptr(sc["d"]), ptr(sc["bits"]), bound, dt_gamma, max_steps, N, C, H, M, ptr(nears), ptr(fars),
+                                     ptr(xyzs), ptr(dirs), ptr(deltas), ptr(rays), ptr(counter), ptr(sc["noises"]), ptr(scratch))
+                                return counter, dict(xyzs=xyzs, dirs=dirs, deltas=deltas, rays=rays, counter=counter)
+                            counter, _ = run(base + N * max_steps)
+                            end = int(counter[0])                                              # base + the samples marched
+                            tag = f"march_train[bound={bound},N={N},max_steps={max_steps},dt_gamma={dt_gamma:g},serial={serial},base={base},{form}]"
+                            put(tag + "[M=tight]", **run(end)[1])
+                            if end > base:
+                                put(tag + "[M=short]", **run(end - 1)[1])                      # the last ray with samples does not fit
+    set_option("FOC_MARCH_SERIAL", -1)
+
+
+def march_list(n_rays, length, seed):
+    """A list of `length` entries into n_rays rays, about a fifth of them dead (-1) where there is more than one."""
+    rng = np.random.default_rng(seed)
+    lst = rng.permutation(n_rays)[:length].astype(np.int32)
+    if length > 1:
+        lst[rng.random(length) < 0.2] = -1
+    return cuda(lst)
+
+
+def march_infer(bound):
+    sc = march_scene(bound, 300)
+    C, H = sc["C"], MARCH_H
+    rng = np.random.default_rng(60 + int(bound))
+    # some rays start at their near plane, the others a little way in
+    rays_t = torch.where(sc["nears"] < 1e30, sc["nears"] + cuda((rng.random(300) * (rng.random(300) < 0.5)).astype(np.float32)) * 0.5 * bound, sc["nears"])
+    for L in (1, 70, 300):
+        lst = march_list(300, L, L)
+        for dt_gamma, max_steps in ((0.0, 64), (1 / 128, 64), (1 / 128, 1024), (0.013, 64), (0.013, 1024)):
+            def run(fn, n_step, *tail):
+                x, dd, dl = full((L * n_step, 3)), full((L * n_step, 3)), full((L * n_step, 2))
+                call(fn, L, n_step, ptr(lst), ptr(rays_t), ptr(sc["o"]), ptr(sc["d"]), bound, dt_gamma, max_steps, C, H, ptr(sc["bits"]), ptr(sc["nears"]),
+                     ptr(sc["fars"]), ptr(x), ptr(dd), ptr(dl), ptr(sc["noises"]), *tail)
+                return dict(xyzs=x, dirs=dd, deltas=dl)
+            for row_max in (0, 1 << 30):
+                set_option("FOC_MARCH_RAYS_ROW_MAX", row_max)
+                for n_step in (1, 3, 8, 16):
+                    put(f"march_rays[bound={bound},L={L},dt_gamma={dt_gamma:g},max_steps={max_steps},n_step={n_step},row_max={row_max}]", **run(lib.foc_march_rays, n_step))
+                for n_step in (1, 2, 4, 8, 16):
+                    for form, code in MARCH_FORMS.items():
+                        if row_max and form != "two":                      # the walkers of the two phases alone read FOC_MARCH_RAYS_ROW_MAX
+                            continue
+                        set_option("FOC_OCC_MARCH_FORM", code)
+                        for flags in (0, 1, 3, 7):
+                            if flags & 4 and not lib.foc_march_rays_two_phase_sample_major(L, n_step, flags):
+                                continue
+                            scratch = torch.zeros(L + 4, dtype=torch.int32, device="cuda")
+                            put(f"march_rays_two_phase[bound={bound},L={L},dt_gamma={dt_gamma:g},max_steps={max_steps},n_step={n_step},row_max={row_max},form={form},flags={flags}]",
+                                **run(lib.foc_march_rays_two_phase, n_step, ptr(scratch), flags))
+    set_option("FOC_OCC_MARCH_FORM", -1)
+
+
+def march_composite():
+    n_rays = 1500
+    for L in (70, 1300):                                                   # (1300: two blocks of the compaction's count)
+        lst = march_list(n_rays, L, 7 + L)
+        for n_step in (1, 2, 3, 4, 8, 16):
+            rng = np.random.default_rng(100 * L + n_step)
+            sig = np.exp(rng.normal(0, 2, (L, n_step))).astype(np.float32)
+            rgb = rng.random((L, n_step, 3)).astype(np.float32)
+            dl = rng.uniform(0.01, 0.2, (L, n_step, 2)).astype(np.float32)
+            dl[np.arange(n_step)[None, :] >= rng.integers(0, n_step + 2, L)[:, None]] = 0.0      # a ray fills none, some or all of its slots
+            state = [rng.random(n_rays).astype(np.float32), (0.9 * rng.random(n_rays)).astype(np.float32), rng.random(n_rays).astype(np.float32),
+                     rng.random((n_rays, 3)).astype(np.float32)]
+            for T_thresh in (1e-4, 0.5):
+                tag = f"[L={L},n_step={n_step},T_thresh={T_thresh:g}]"
+                alive, (t, ws, dp, im) = lst.clone(), map(cuda, state)
+                call(lib.foc_composite_rays, L, n_step, T_thresh, ptr(alive), ptr(t), ptr(cuda(sig)), ptr(cuda(rgb)), ptr(cuda(dl)), ptr(ws), ptr(dp), ptr(im))
+                put("composite_rays" + tag, rays_alive=alive, rays_t=t, weights_sum=ws, depth=dp, image=im)
+                if n_step not in (2, 4, 8):                                # (2: the pointer-walking kernel with the compaction's count)
+                    continue
+                for sample_major in (0, 1):
+                    lay = (lambda a: np.ascontiguousarray(np.moveaxis(a, 0, 1))) if sample_major else (lambda a: a)
+                    for with_deaths in (False, True):
+                        alive, (t, ws, dp, im) = lst.clone(), map(cuda, state)
+                        out, n_out, blocks = full(L, torch.int32), full(1, torch.int32), torch.zeros(L // 1024 + 2, dtype=torch.int32, device="cuda")
+                        deaths = torch.zeros(n_step + 1, 64, dtype=torch.int32, device="cuda") if with_deaths else None
+                        call(lib.foc_composite_compact, L, n_step, T_thresh, ptr(alive), ptr(t), ptr(cuda(lay(sig))), ptr(cuda(lay(rgb))), ptr(cuda(lay(dl))), ptr(ws),
+                             ptr(dp), ptr(im), ptr(out), ptr(n_out), ptr(blocks), ptr(deaths), 1, n_step + 1, sample_major)
+                        put(f"composite_compact{tag}[sample_major={sample_major},deaths={with_deaths}]", rays_alive=alive, rays_t=t, weights_sum=ws, depth=dp, image=im,
+                            out=out, n_out=n_out, deaths=deaths)
+    for n in (1, 1023, 1025, 2100):
+        lst = march_list(3000, n, n)
+        out, n_out, scratch = full(n, torch.int32), full(1, torch.int32), torch.zeros(n // 1024 + 2, dtype=torch.int32, device="cuda")
+        call(lib.foc_compact_alive, ptr(lst), n, ptr(out), ptr(n_out), ptr(scratch))
+        put(f"compact_alive[n={n}]", out=out, n_out=n_out)
+
+
+def march():
+    saved = {name: get_option(name) for name in ("FOC_MARCH_SERIAL", "FOC_MARCH_RAYS_ROW_MAX", "FOC_OCC_MARCH_FORM")}
+    for bound in (1.0, 2.0):
+        march_train(bound)
+        march_infer(bound)
+    march_composite()
+    for name, value in saved.items():
+        set_option(name, value)
+
+
 # ---------------------------------------------------------------- the occupancy node and the native render loop, from Python
 NODE_KINDS = ("plain", "linear_bg", "tcnn_legacy", "foc", "tcnn")
 MARCHED = []         # samples marched by each training step of the node section (the summary says which remainders they leave)
@@ -363,6 +516,8 @@ def main():
                         fixed(N, T, noisy, per_ray_bg, ds)
     for T in (2, 65, 130) if "combine" in SECTIONS else ():
         combine(T)
+    if "march" in SECTIONS:
+        march()
     if "node" in SECTIONS:
         node()
     text = json.dumps(OUT, indent=0, sort_keys=True)
