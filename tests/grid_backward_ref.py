@@ -1,0 +1,853 @@
+"""Float64 reference of the hash-grid encoder's backward (csrc/gridencoder.hip k_grid_bwd and the binned family k_gbin_count_pt ->
+k_gbin_scans -> k_gbin_scatter_pms -> k_gbin_reduce -> k_gbin_det_finish; csrc/gridencoder_nd.hip for D = 4, 5), a bound per table element
+for every route a call can take, the cases, and a numpy fp32 / fp16 model of each route with deliberately wrong variants (MUTANTS).
+
+    grad_embeddings[row, c] = sum over the in-range points b, levels l and the 2^D corners k of the cell whose row is `row`:  w_k(b, l) * grad[l, b, c]
+    grad_inputs[b, d]       = sum_{l, c} grad[l, b, c] * dy_dx[b, l, d, c]
+
+Discrete decisions are the kernels': a point is in range when every coordinate is in [0, 1]; its cell at a level is floor of the FLOAT32
+position fmaf(x, scale, align_corners ? 0 : 0.5) with the level's float32 scale and resolution from oracle.grid_level_params (exp2 is not
+restated here: another last bit of the scale gives other cells); a corner's row is the reference's uint32 index walk / hash. Everything
+behind the cell is float64: position, in-cell fraction (position - cell), smoothstep, weights, products, sums. `reference()` also returns,
+per table element, the sum of the absolute values of the addends (`mag`), their number (`count`), and the number of (point, level) pairs
+that are out of range (`outside`).
+
+Condition on the inputs (`near_integer()`, asserted on the reference alone by test_grid_backward_ref.py): no in-range (point, level, axis)
+has its float64 position within 2^-18 of an integer unless the position is that integer exactly (x = 0 or 1 at a level whose
+scale + 0.5 is exact). The case builders redraw points that violate it.
+
+Bound per table element, by route
+---------------------------------
+Magnitudes follow fixed_tail_ref.py's rules: exact inputs carry 0; an fma with exact inputs carries |result| (one rounding); a sum or
+difference carries its operands' magnitudes plus |result|; a product a b carries mag(a)|b| + |a|mag(b) + |a b|. The position carries
+|pos|; the fraction pos - cell is exact in fp32 and keeps that magnitude (this is the term that matters at fine levels: an fp32 position
+near 2048 is 2^-13 away from the float64 one, and so are the weights); 1 - f, smoothstep and the D-fold product of the weights follow the
+rules; an addend a = w g carries m = mag(w)|g| + |a|. U = 2^-24 (fixed_tail_ref.U), C = 2, K = 16 (ragged_ref): an fp32 chain ending in a
+reduction over T terms is within C U (T + K) mag. h = 2^-11 is the unit roundoff of half, q = 2^-25 half the spacing of subnormal halves:
+rounding v to half costs at most h|v| + q.
+
+An EMITTED addend is what a route adds into a table element in one piece:
+  (a) fp32 chain. One corner's w g: f = C U K m. A merged run (binned routes, levels with resolution <= FOC_GB_MERGE_MAX_RES, default
+      GB_MERGE_MAX_RES 480: consecutive in-range lanes of an aligned 16-lane group in one cell, gb_run_flags) is summed on the lanes in up
+      to four scan steps and emitted once by its last lane: f = C U (r + K) (sum m + sum |a|), r the run's length.
+  (b) half tables round every emitted addend v once: h (|v| + f) + q. A FACTORED record (binned fp16, hashed levels above the merge
+      threshold with a power-of-two size of at least one segment, gb_fact_mask) carries p = w_y w_z g rounded to half and a 15-bit
+      fx = min(rint(f_x 2^15), 32767) / 2^15; the reduce forms a1 = fx p and a0 = p - a1 in fp32 (magnitudes by the rules) and `fixedf`
+      drops what lies below 2^-24 of each. Per addend: its share of p's half rounding ((fx or 1 - fx, + 2^-16) (h|p| + q)), |p| 2^-16 for
+      fx (2^-15 where the clamp at 32767 acts, f_x > 1 - 2^-15), and 2^-24 for the truncation. That truncation is toward -inf: a BIAS of
+      up to 2^-24 per addend, not a symmetric error; the bound carries it as a magnitude.
+  (c) the q of every half rounding above is the subnormal quantum; at gradient scale 2^-20 the bound is almost all q.
+  (d) the binned fp16 reduce adds the emitted halves as 2^24-scaled int64: exact, nothing.
+  (e) each chunk of a (level, segment) slot rounds its partial sum S_k through double -> float -> half: (U + h + U h)|S_k| + q. A slot with
+      one chunk, or FOC_DETERMINISTIC 1 / 2 (one conversion of the slot's exact total): |S| <= |reference| + (a) + (b). Default mode with k
+      chunks: sum |S_k| <= E, the sum of the |emitted addends| with their errors, and the k - 1 further packed half atomics round the
+      running sum: h E' + q each, E' = E (1 + U + h + U h) + k q. k = min(chunks of the slot, emitted addends of the element); the chunks
+      of a slot are ceil(records / CHUNK) with the records counted here (`slot_records()`): four per emitting point or run and level, one more
+      for a pair of corners along x whose rows lie in different segments of a dense level.
+  (f) scattered-atomic kernel. fp32 tables: the running sum over the element's n addends, C U (n + K) (sum m + sum |a|) + (n + K) 2^-126.
+      half tables: (a) + (b) per corner, and every one of the n packed half atomics rounds the running sum: n (h E + q).
+  (g) binned, fp32 tables: emitted addends stay fp32 ((a) only), the chunk sums them in double (n 2^-53 E), rounds to float once per chunk
+      (U |S_k|) and the chunks meet in float atomics (U E' each).
+grad_inputs: an fmaf chain over L C terms, C U (L C + K) sum |g dy| + (L C + K) 2^-126, + h |.| + q where the output is half.
+
+SEG_SHIFT, SEG and CHUNK below are csrc/gridencoder.hip's `#define GB_SEG_SHIFT`, `GB_SEG` and `GB_CHUNK`; MERGE_MAX_RES its
+`#define GB_MERGE_MAX_RES`.
+
+`model(case, route, mutant=None)` restates a route's arithmetic in numpy float32 / float16 (fp32 weights and products in the kernels' order,
+the four-step segmented scan over 16-lane groups, half rounding, the exact integer sum, the chunk rounding, sequential atomics in point
+order) so that the bound can be exercised without a GPU; a reference value is never computed with a mutant.
+"""
+import numpy as np
+
+import oracle
+from fixed_tail_ref import U
+from ragged_ref import C as CC, K as KK, TINY
+
+SEG_SHIFT = 13
+SEG = 1 << SEG_SHIFT
+CHUNK = 32768
+MERGE_MAX_RES = 480
+H16 = 2.0 ** -11
+Q16 = 2.0 ** -25
+HALF_MAX = 65504.0
+PRIMES = (1, 2654435761, 805459861, 3674653429, 2097192037, 1434869437, 2165219737)
+M32 = 0xFFFFFFFF
+
+MUTANTS = ("drop_run_tail", "run_ignores_group_edge", "zero_grad_tail_skips_run", "subnormal_flush", "neg_fract_carry", "fx_14_bits",
+           "pair_straddle_lost", "chunk_off_by_one", "odd_x_pair_twice", "round_per_addend", "oob_counts")
+
+FOC = (3, 2, 16, 16, 19, 2048, 0, False, 0)          # D, C, L, H, log2_hashmap_size, finest resolution, gridtype, align_corners, interpolation
+
+
+def route(kind="binned", half=True, factored=True, merge_max=MERGE_MAX_RES, det=0):
+    """kind 'binned' | 'atomic'; half: fp16 tables; factored / merge_max / det: FOC_GB_FACTORED, FOC_GB_MERGE_MAX_RES, FOC_DETERMINISTIC."""
+    return dict(kind=kind, half=bool(half), factored=bool(factored) and half and kind == "binned", merge_max=int(merge_max) if kind == "binned" else 0,
+                det=int(det) if half and kind == "binned" else 0)
+
+
+ROUTES = {
+    "binned16": route(), "binned32": route(half=False), "binned16_unfactored": route(factored=False), "binned16_unmerged": route(merge_max=0),
+    "binned16_12byte": route(factored=False, merge_max=0), "binned16_det1": route(det=1), "binned16_det2": route(det=2),
+    "atomic16": route("atomic"), "atomic32": route("atomic", half=False),
+    # no GPU route: every corner's addend on its own, summed exactly, rounded once (the oracle's arithmetic; any D)
+    "single16": dict(route(factored=False, merge_max=0), det=1), "single32": dict(route(half=False, merge_max=0), det=1),
+}
+
+
+# ---------------------------------------------------------------- grid
+def level_offsets(D, L, pls, H, log2_hash, align_corners):
+    """focnerf_amd.gridencoder.level_offsets (the GPU tests assert the two agree)."""
+    sizes = []
+    for l in range(L):
+        cells = int(np.ceil(H * pls ** l)) + (0 if align_corners else 1)
+        sizes.append(-(-min(2 ** log2_hash, cells ** D) // 8) * 8)
+    return np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+
+
+def make_case(name, spec, x, grad, **props):
+    D, C, L, H, lh, desired, gridtype, ac, interp = spec
+    pls = np.exp2(np.log2(desired / H) / (L - 1))
+    x = np.ascontiguousarray(x, np.float32)
+    grad = np.ascontiguousarray(grad, np.float16)
+    assert x.shape[1] == D and grad.shape == (L, x.shape[0], C)
+    return dict(name=name, spec=spec, D=D, C=C, L=L, H=H, gridtype=gridtype, ac=bool(ac), interp=interp, S=float(np.log2(pls)),
+                off=level_offsets(D, L, pls, H, lh, ac), x=x, grad=grad, B=x.shape[0], _lv={}, _ref=None, _bound={}, **props)
+
+
+def _fma32(x32, scale, add):
+    """fmaf(x, scale, add) for float32 x: the exact product in float64, the sum rounded to odd, then to float32 (no double rounding)."""
+    p = x32.astype(np.float64) * np.float64(scale)
+    s = p + add
+    bb = s - p
+    err = (p - (s - bb)) + (add - bb)
+    fix = (err != 0) & ((s.view(np.int64) & 1) == 0)
+    s = np.where(fix, np.nextafter(s, np.where(err > 0, np.inf, -np.inf)), s)
+    return s.astype(np.float32), err == 0
+
+
+def _rows(case, cell, size, res):
+    """Local rows [n, 2^D] of the corners (bit d of the corner index set = +1 along axis d): ge_index / grid_index in uint32 arithmetic."""
+    D = case["D"]
+    r1 = res if case["ac"] else res + 1
+    stride, strides = 1, []
+    for d in range(D):
+        if stride <= size:
+            strides.append(stride)
+            stride = (stride * r1) & M32
+        else:
+            strides.append(0)
+    hashed = case["gridtype"] == 0 and stride > size
+    k = np.arange(1 << D)
+    rows = np.zeros((cell.shape[0], 1 << D), np.uint64)
+    for d in range(D):
+        pg = (cell[:, d:d + 1].astype(np.uint64) + ((k >> d) & 1).astype(np.uint64)[None]) & M32
+        if hashed:
+            rows ^= (pg * np.uint64(PRIMES[d])) & np.uint64(M32)
+        else:
+            rows = (rows + pg * np.uint64(strides[d])) & np.uint64(M32)
+    return (rows % np.uint64(size)).astype(np.int64), hashed
+
+
+def level(case, l, oob_counts=False):
+    """Everything per level, cached: the in-range points, their cells, float64 / float32 fractions, rows."""
+    key = (l, oob_counts)
+    if key in case["_lv"]:
+        return case["_lv"][key]
+    scale, res = oracle.grid_level_params(l, case["S"], case["H"])
+    x = case["x"]
+    add = 0.0 if case["ac"] else 0.5
+    inside = np.all(x >= 0, axis=1) if oob_counts else np.all((x >= 0) & (x <= 1), axis=1)
+    idx = np.nonzero(inside)[0]
+    pos32, exact = _fma32(x[idx], scale, add)
+    pos64 = x[idx].astype(np.float64) * np.float64(scale) + add
+    cellf = np.floor(pos32)
+    cell = cellf.astype(np.int64)
+    size = int(case["off"][l + 1] - case["off"][l])
+    rows, hashed = _rows(case, cell, size, res)
+    dist = np.abs(pos64 - np.rint(pos64))
+    lv = dict(scale=scale, res=res, size=size, hashed=hashed, inside=inside, idx=idx, cell=cell, frac64=pos64 - cellf.astype(np.float64),
+              frac32=pos32 - cellf, mpos=np.abs(pos64), rows=rows, near=(dist < 2.0 ** -18) & ~((dist == 0) & exact),
+              pow2=size & (size - 1) == 0)
+    case["_lv"][key] = lv
+    return lv
+
+
+def near_integer(case):
+    """Number of in-range (point, level, axis) whose float64 position is within 2^-18 of an integer without being it exactly."""
+    return sum(int(level(case, l)["near"].sum()) for l in range(case["L"]))
+
+
+def near_points(case):
+    bad = np.zeros(case["B"], bool)
+    for l in range(case["L"]):
+        lv = level(case, l)
+        bad[lv["idx"][lv["near"].any(axis=1)]] = True
+    case["_lv"].clear()
+    return np.nonzero(bad)[0]
+
+
+# ---------------------------------------------------------------- float64 weights and their magnitudes
+def _mul(a, ma, b, mb):
+    return a * b, ma * np.abs(b) + np.abs(a) * mb + np.abs(a * b)
+
+
+def _axis_weights(case, lv):
+    """u[n, D, 2] = (1 - f, f) per axis after the interpolation, mu their magnitudes, du the derivative of f (for dy_dx)."""
+    f, mf = lv["frac64"], lv["mpos"]
+    du = np.ones_like(f)
+    if case["interp"] == 1:
+        v, mv = f, mf
+        t, mt = 3.0 - 2.0 * v, 2.0 * mv + np.abs(3.0 - 2.0 * v)
+        vv, mvv = _mul(v, mv, v, mv)
+        f, mf = _mul(vv, mvv, t, mt)
+        du = 6.0 * v * (1.0 - v)
+    u = np.stack([1.0 - f, f], axis=-1)
+    mu = np.stack([mf + np.abs(1.0 - f), mf], axis=-1)
+    return u, mu, du
+
+
+def _weights(case, lv, axes=None):
+    """w[n, 2^len(axes)] and magnitudes: the kernels' product order (w = 1; w *= u_d for d = 0 ..), first factor exact."""
+    u, mu, _ = _axis_weights(case, lv)
+    axes = list(range(case["D"])) if axes is None else axes
+    k = np.arange(1 << len(axes))
+    w = mw = None
+    for j, d in enumerate(axes):
+        bit = (k >> j) & 1
+        ud, mud = u[:, d, :][:, bit], mu[:, d, :][:, bit]
+        if w is None:
+            w, mw = ud, mud
+        else:
+            w, mw = _mul(w, mw, ud, mud)
+    return w, mw
+
+
+def _level_mode(case, lv, r):
+    if r["kind"] == "atomic":
+        return "corner"
+    if lv["res"] <= r["merge_max"]:
+        return "run"
+    if r["factored"] and case["gridtype"] == 0 and lv["hashed"] and lv["pow2"] and lv["size"] >= SEG:
+        return "fact"
+    return "corner"
+
+
+def _run_heads(case, lv, ignore_group_edge=False):
+    """head / tail flags of gb_run_flags for all B lanes (lanes behind B are out of range)."""
+    B = case["B"]
+    key = np.full(B, -1, np.int64)
+    key[lv["idx"]] = lv["cell"][:, 0] | (lv["cell"][:, 1] << 10) | (lv["cell"][:, 2] << 20)
+    inside = lv["inside"]
+    prev = np.concatenate([[-2], key[:-1]])
+    head = (key != prev) | ~inside
+    if not ignore_group_edge:
+        head |= (np.arange(B) & 15) == 0
+    nxt = np.concatenate([head[1:], [True]])
+    tail = inside & nxt
+    if not ignore_group_edge:
+        tail = inside & (nxt | ((np.arange(B) & 15) == 15))
+    return head, tail
+
+
+def _emit64(case, l, r):
+    """The emitted addends of one level on route r, float64: dict(row [n] local, v, f, hb [n, C]: value, fp32 bound, half / fx / truncation
+    bound; raw_row, a, m: every corner's row, addend and magnitude; for the binned routes rec_seg [m], the segment of every record)."""
+    lv = level(case, l)
+    C, D = case["C"], case["D"]
+    mode = _level_mode(case, lv, r)
+    g = case["grad"][l][lv["idx"]].astype(np.float64)                           # [n, C]
+    w, mw = _weights(case, lv)
+    a = w[:, :, None] * g[:, None, :]                                           # [n, K, C]
+    m = mw[:, :, None] * np.abs(g)[:, None, :] + np.abs(a)
+    n, K = w.shape
+    rows = lv["rows"]
+    out = {}
+    if mode == "run":
+        head, tail = _run_heads(case, lv)
+        rid = np.cumsum(head)[lv["idx"]] - 1                                      # run of every in-range point
+        first = np.nonzero(np.concatenate([[True], rid[1:] != rid[:-1]]))[0] if n else np.zeros(0, np.int64)     # rid ascends with the points
+        red = lambda t: np.add.reduceat(t, first, axis=0) if n else t
+        va, ab, mm = red(a), red(np.abs(a)), red(m)
+        length = np.diff(np.concatenate([first, [n]])).astype(np.float64)
+        last = np.concatenate([first[1:], [n]]).astype(np.int64) - 1              # the run's last point emits
+        e_rows, e_v = rows[last], va
+        e_f = CC * U * (length[:, None, None] + KK) * (mm + ab)
+    else:
+        e_rows, e_v, e_f = rows, a, CC * U * KK * m
+    if mode == "fact":
+        wyz, mwyz = _weights(case, lv, axes=[1, 2])                             # [n, 4]
+        p = wyz[:, :, None] * g[:, None, :]
+        mp = mwyz[:, :, None] * np.abs(g)[:, None, :] + np.abs(p)
+        fp = CC * U * KK * mp
+        u, mu, _ = _axis_weights(case, lv)
+        fx, mfx = u[:, 0, 1][:, None, None], mu[:, 0, 1][:, None, None]
+        qfx = np.where(fx > 1 - 2.0 ** -15, 2.0 ** -15, 2.0 ** -16)
+        a1, ma1 = _mul(fx, mfx, p, mp)
+        a0 = p - a1
+        ma0 = mp + ma1 + np.abs(a0)
+        ph = (np.abs(p) + fp) * (1 + H16) + Q16
+        rp = H16 * (np.abs(p) + fp) + Q16
+        hb1 = (np.abs(fx) + qfx) * rp + ph * qfx + 2.0 ** -24
+        hb0 = (np.abs(1 - fx) + qfx) * rp + ph * qfx + 2.0 ** -24
+        e_v = np.stack([a0, a1], axis=2).reshape(n, K, C)                       # corner 2 j + side
+        e_f = CC * U * KK * np.stack([ma0, ma1], axis=2).reshape(n, K, C)
+        e_hb = np.stack([hb0, hb1], axis=2).reshape(n, K, C)
+    elif r["half"]:
+        e_hb = H16 * (np.abs(e_v) + e_f) + Q16
+    else:
+        e_hb = np.zeros_like(e_v)
+    ne = e_rows.shape[0]
+    out.update(mode=mode, row=e_rows.reshape(-1), v=e_v.reshape(ne * K, C), f=e_f.reshape(ne * K, C), hb=e_hb.reshape(ne * K, C),
+               m=m.reshape(n * K, C), a=a.reshape(n * K, C), raw_row=rows.reshape(-1))
+    if r["kind"] == "binned":
+        s0, s1 = e_rows[:, 0::2] >> SEG_SHIFT, e_rows[:, 1::2] >> SEG_SHIFT                     # [ne, 4]
+        split = (s0 != s1) & (not lv["hashed"])
+        out["rec_seg"] = np.concatenate([s0.reshape(-1), s1[split]])
+        out["straddles"] = int(split.sum())
+    return out
+
+
+def _acc(target, o, size, rows, vals):
+    """target[o + rows] += vals, level-local rows (np.add.at is an order of magnitude slower)."""
+    vals = np.asarray(vals, np.float64)
+    if vals.ndim == 1:
+        vals = np.repeat(vals[:, None], target.shape[1], axis=1)
+    for c in range(target.shape[1]):
+        target[o:o + size, c] += np.bincount(rows, weights=vals[:, c], minlength=size)
+
+
+def slot_records(case, r):
+    """records[L, 64] of every (level, segment) slot on a binned route."""
+    rec = np.zeros((case["L"], 64), np.int64)
+    for l in range(case["L"]):
+        rec[l] = np.bincount(_emit64(case, l, r)["rec_seg"], minlength=64)
+    return rec
+
+
+def reference(case):
+    """dict(ge, mag, count [rows, C] float64; outside: number of out-of-range (point, level) pairs; touched [rows] bool)."""
+    if case["_ref"] is None:
+        n_rows, C = int(case["off"][-1]), case["C"]
+        ge, mag, cnt = np.zeros((n_rows, C)), np.zeros((n_rows, C)), np.zeros((n_rows, C))
+        touched = np.zeros(n_rows, bool)
+        outside = 0
+        for l in range(case["L"]):
+            e = _emit64(case, l, ROUTES["atomic32"])
+            o, size = int(case["off"][l]), level(case, l)["size"]
+            _acc(ge, o, size, e["raw_row"], e["a"]); _acc(mag, o, size, e["raw_row"], np.abs(e["a"])); _acc(cnt, o, size, e["raw_row"], np.ones(e["raw_row"].size))
+            touched[e["raw_row"] + o] = True
+            outside += case["B"] - level(case, l)["idx"].size
+        case["_ref"] = dict(ge=ge, mag=mag, count=cnt, outside=outside, touched=touched)
+    return case["_ref"]
+
+
+def bound(case, rname):
+    """[rows, C] float64: the docstring's bound of route ROUTES[rname] on |kernel - reference()['ge']|."""
+    if rname in case["_bound"]:
+        return case["_bound"][rname]
+    r = ROUTES[rname]
+    ref = reference(case)
+    n_rows, C = ref["ge"].shape
+    F, Hb, E, N, M, A = (np.zeros((n_rows, C)) for _ in range(6))
+    nck = np.ones(n_rows)
+    for l in range(case["L"]):
+        e = _emit64(case, l, r)
+        o = int(case["off"][l])
+        size = int(case["off"][l + 1]) - o
+        _acc(F, o, size, e["row"], e["f"]); _acc(Hb, o, size, e["row"], e["hb"]); _acc(N, o, size, e["row"], np.ones(e["row"].size))
+        _acc(E, o, size, e["row"], np.abs(e["v"]) + e["f"] + e["hb"])
+        _acc(M, o, size, e["raw_row"], e["m"]); _acc(A, o, size, e["raw_row"], np.abs(e["a"]))
+        if r["kind"] == "binned":
+            chunks = -(-np.bincount(e["rec_seg"], minlength=64) // CHUNK)
+            nck[o:o + size] = np.maximum(1, chunks[np.arange(size) >> SEG_SHIFT])
+    t = np.nonzero(ref["touched"])[0]                                             # the formulas on the touched rows only
+    full = np.zeros((n_rows, C))
+    F, Hb, E, N, M, A, cnt, nck, ge = F[t], Hb[t], E[t], N[t], M[t], A[t], ref["count"][t], nck[t], ref["ge"][t]
+    if r["kind"] == "atomic":
+        if r["half"]:
+            b = F + Hb + N * (H16 * E + Q16)
+        else:
+            b = CC * U * (cnt + KK) * (M + A) + (cnt + KK) * TINY
+    else:
+        k = np.minimum(nck[:, None], np.maximum(N, 1.0))
+        if r["det"]:
+            k = np.ones_like(k)
+        total = np.abs(ge) + F + Hb
+        if r["half"]:
+            rnd = U + H16 + U * H16
+            one = F + Hb + rnd * total + Q16
+            E2 = E * (1 + rnd) + k * Q16
+            many = F + Hb + rnd * E + k * Q16 + (k - 1) * (H16 * E2 + Q16)
+        else:
+            one = F + N * 2.0 ** -53 * E + U * total + (N + KK) * TINY
+            many = F + N * 2.0 ** -53 * E + U * E + (k - 1) * U * E * (1 + U) + (N + KK) * TINY
+        b = np.where(k <= 1, one, many)
+    full[t] = b
+    case["_bound"][rname] = full
+    return full
+
+
+def grad_inputs(case, dy_dx, half):
+    """dy_dx [B, L, D, C] (any float dtype; its values are the input) -> grad_inputs [B, D] float64 and its bound."""
+    g = np.transpose(case["grad"].astype(np.float64), (1, 0, 2))[:, :, None, :]          # [B, L, 1, C]
+    terms = g * dy_dx.astype(np.float64)
+    gi, mag = terms.sum(axis=(1, 3)), np.abs(terms).sum(axis=(1, 3))
+    T = case["L"] * case["C"]
+    b = CC * U * (T + KK) * mag + (T + KK) * TINY
+    if half:
+        b = b + H16 * (np.abs(gi) + b) + Q16
+    return gi, b
+
+
+def forward64(case, table):
+    """float64 forward out [L, B, C] and dy_dx [B, L, D, C] of `table` [rows, C] (out-of-range points: zeros)."""
+    D, C, L, B = case["D"], case["C"], case["L"], case["B"]
+    out, dy = np.zeros((L, B, C)), np.zeros((B, L, D, C))
+    t = table.astype(np.float64)
+    k = np.arange(1 << D)
+    for l in range(L):
+        lv = level(case, l)
+        u, _, du = _axis_weights(case, lv)
+        w, _ = _weights(case, lv)
+        vals = t[lv["rows"] + int(case["off"][l])]                                # [n, K, C]
+        out[l, lv["idx"]] = (w[:, :, None] * vals).sum(axis=1)
+        for d in range(D):
+            wd = np.ones_like(w)
+            for dd in range(D):
+                if dd != d:
+                    wd = wd * u[:, dd, :][:, (k >> dd) & 1]
+            sign = np.where((k >> d) & 1, 1.0, -1.0)[None]
+            dy[lv["idx"], l, d] = lv["scale"] * du[:, d:d + 1] * ((wd * sign)[:, :, None] * vals).sum(axis=1)
+    return out, dy
+
+
+# ---------------------------------------------------------------- numpy fp32 / fp16 model of the routes
+def _seq_add(elem, vals, dtype, n_elem):
+    """Sequential adds in `dtype` of vals (in array order) into their elements: what atomics in that order leave."""
+    out = np.zeros(n_elem, dtype)
+    if elem.size == 0:
+        return out
+    order = np.argsort(elem, kind="stable")
+    e, v = elem[order], vals[order].astype(dtype)
+    start = np.concatenate([[0], np.nonzero(np.diff(e))[0] + 1])
+    rank = np.arange(e.size) - np.repeat(start, np.diff(np.concatenate([start, [e.size]])))
+    with np.errstate(over="ignore", invalid="ignore"):
+        for k in range(int(rank.max()) + 1):
+            sel = rank == k
+            out[e[sel]] = (out[e[sel]] + v[sel]).astype(dtype)
+    return out
+
+
+def _shr(a, s):
+    out = np.zeros_like(a)
+    out[:, s:] = a[:, :-s]
+    return out
+
+
+def _model_level(case, l, r, mutant):
+    """Emitted addends of one level in the route's own arithmetic: elem [m] (local row * C + c), val [m] (float32, or half values as
+    float32), rec [m] record number in emission order, x_odd [m], and for factored levels ival [m] int64 (2^24-scaled) instead of val."""
+    lv = level(case, l, oob_counts=mutant == "oob_counts")
+    C, D, B = case["C"], case["D"], case["B"]
+    mode = _level_mode(case, lv, r)
+    n = lv["idx"].size
+    f = lv["frac32"].astype(np.float32)
+    if case["interp"] == 1:
+        f = (f * f) * (np.float32(3.0) - np.float32(2.0) * f)
+    one = np.float32(1.0)
+    k = np.arange(1 << D)
+    g = case["grad"][l][lv["idx"]].astype(np.float32)
+    rows = lv["rows"]
+    K = 1 << D
+
+    def h16(v):
+        with np.errstate(over="ignore"):
+            return v.astype(np.float16)
+
+    def flush(v16):
+        return np.where(np.abs(v16.astype(np.float32)) < 2.0 ** -14, np.float16(0), v16) if mutant == "subnormal_flush" else v16
+
+    if mode == "fact":
+        wyz = np.where((k[:4] & 1)[None] == 1, f[:, 1:2], one - f[:, 1:2]) * np.where((k[:4] >> 1)[None] == 1, f[:, 2:3], one - f[:, 2:3])
+        with np.errstate(over="ignore"):
+            p16 = flush(h16(wyz[:, :, None] * g[:, None, :]))                     # [n, 4, C]
+        p = p16.astype(np.float32)
+        if mutant == "fx_14_bits":
+            fx = np.minimum(np.rint(f[:, 0] * np.float32(16384.0)), 16383.0).astype(np.float32) / np.float32(16384.0)
+        else:
+            fx = np.minimum(np.rint(f[:, 0] * np.float32(32768.0)), 32767.0).astype(np.float32) / np.float32(32768.0)
+        with np.errstate(invalid="ignore"):
+            a1 = fx[:, None, None] * p
+            a0 = p - a1
+            av = np.stack([a0, a1], axis=2).reshape(n, K, C)                      # corner 2 j + side
+            iv = np.floor(av.astype(np.float64) * 2.0 ** 24)
+        if mutant == "neg_fract_carry":
+            iv = np.where((av < 0) & (av.astype(np.float64) * 16 > -2.0 ** -25), -2.0 ** 20, iv)
+        bad = ~np.isfinite(np.repeat(p, 2, axis=1).reshape(n, K, C))
+        iv = np.where(bad, 0, iv).astype(np.int64)
+        emit = np.arange(n)
+        val, ival = None, iv
+    else:
+        w = np.ones((n, K), np.float32)
+        for d in range(D):
+            w = w * np.where(((k >> d) & 1)[None] == 1, f[:, d:d + 1], one - f[:, d:d + 1])
+        with np.errstate(over="ignore"):
+            a = w[:, :, None] * g[:, None, :]                                     # [n, K, C] float32
+        emit = np.arange(n)
+        if mode == "run":
+            head, tail = _run_heads(case, lv, ignore_group_edge=mutant == "run_ignores_group_edge")
+            Bp = -(-B // 16) * 16
+            V = np.zeros((Bp, K * C), np.float32)
+            V[lv["idx"]] = a.reshape(n, K * C)
+            f0 = np.ones(Bp, bool)
+            f0[:B] = head
+            V, f0 = V.reshape(-1, 16, K * C), f0.reshape(-1, 16)
+            f1 = f0 | _shr(f0, 1); f2 = f1 | _shr(f1, 2); f3 = f2 | _shr(f2, 4)
+            with np.errstate(over="ignore", invalid="ignore"):
+                for s, fl in ((1, f0), (2, f1), (4, f2), (8, f3)):
+                    V = V + np.where(fl[:, :, None], np.float32(0), _shr(V, s))
+            V = V.reshape(Bp, K, C)
+            t = tail.copy()
+            if mutant == "drop_run_tail":
+                t &= ~((np.arange(B) & 15) == 15)
+            if mutant == "zero_grad_tail_skips_run":
+                t &= np.any(case["grad"][l] != 0, axis=1)
+            pos_of = np.full(B, -1, np.int64)
+            pos_of[lv["idx"]] = np.arange(n)
+            emit = pos_of[np.nonzero(t)[0]]
+            a = V[np.nonzero(t)[0]]
+        else:
+            a = a[emit]
+        val = flush(h16(a)).astype(np.float32) if r["half"] else a
+        ival = None
+    rows_e = rows[emit]
+    ne = emit.size
+    elem = (rows_e[:, :, None] * C + np.arange(C)[None, None]).reshape(-1)
+    x_odd = np.repeat((lv["cell"][emit, 0] & 1) == 1, K * C)
+    # records: (emitter, pair j) -> corners 2 j, 2 j + 1; a straddling pair of a dense level is two records
+    s0, s1 = rows_e[:, 0::2] >> SEG_SHIFT, rows_e[:, 1::2] >> SEG_SHIFT
+    split = (s0 != s1) & (not lv["hashed"])
+    seg_c = np.stack([s0, np.where(split, s1, s0)], axis=2).reshape(ne, K)        # segment whose record carries the corner
+    second = np.stack([np.zeros_like(split), split], axis=2).reshape(ne, K)
+    return dict(mode=mode, elem=elem, val=None if val is None else val.reshape(-1), ival=None if ival is None else ival.reshape(-1),
+                x_odd=x_odd, seg=np.repeat(seg_c.reshape(-1), C), second=np.repeat(second.reshape(-1), C),
+                pair=np.repeat((np.arange(ne)[:, None] * 4 + (np.arange(K) >> 1)[None]).reshape(-1), C), size=lv["size"])
+
+
+def model(case, rname, mutant=None):
+    """grad_embeddings [rows, C] as route ROUTES[rname] computes it (float32 for fp32 tables, float16 for half tables)."""
+    assert mutant is None or mutant in MUTANTS
+    r = ROUTES[rname]
+    C = case["C"]
+    n_rows = int(case["off"][-1])
+    dt = np.float16 if r["half"] else np.float32
+    out = np.zeros((n_rows, C), dt)
+    for l in range(case["L"]):
+        e = _model_level(case, l, r, mutant)
+        o, size = int(case["off"][l]), e["size"]
+        ne = size * C
+        if r["kind"] == "atomic":
+            res = _seq_add(e["elem"], e["val"], dt, ne)
+        else:
+            keep = np.ones(e["elem"].size, bool)
+            if mutant == "pair_straddle_lost":
+                keep &= ~e["second"]
+            # the rank of every record inside its slot, in emission order: record id = pair * 2 + second
+            recid = e["pair"] * 2 + e["second"]
+            first_of_rec = np.concatenate([[True], recid[1:] != recid[:-1]])
+            rec_no = np.cumsum(first_of_rec) - 1
+            seg_of_rec = e["seg"][first_of_rec]
+            rank = np.zeros(seg_of_rec.size, np.int64)
+            for s in np.unique(seg_of_rec):
+                sel = seg_of_rec == s
+                rank[sel] = np.arange(int(sel.sum()))
+            rk = rank[rec_no]
+            chunk = rk // CHUNK
+            if mutant == "chunk_off_by_one":
+                keep &= ~((rk % CHUNK == 0) & (rk > 0))
+            mult = np.where(e["x_odd"], 2, 1) if mutant == "odd_x_pair_twice" else np.ones(e["elem"].size, np.int64)
+            el, ch, mult = e["elem"][keep], chunk[keep], mult[keep]
+            nck = int(ch.max()) + 1 if ch.size else 1
+            if r["half"]:
+                if e["ival"] is not None:
+                    iv, bad = e["ival"][keep], np.zeros(el.size, bool)
+                    vals16 = None
+                else:
+                    v = e["val"][keep]
+                    bad = ~np.isfinite(v)
+                    iv = np.rint(np.where(bad, 0, v).astype(np.float64) * 2.0 ** 24).astype(np.int64)
+                if mutant == "round_per_addend":
+                    res = _seq_add(el, (iv * mult).astype(np.float64) * 2.0 ** -24, np.float16, ne)
+                else:
+                    acc = np.zeros((nck, ne), np.int64)
+                    np.add.at(acc, (ch, el), iv * mult)
+                    isbad = np.zeros((nck, ne), bool)
+                    isbad[ch[bad], el[bad]] = True
+                    with np.errstate(over="ignore"):
+                        if r["det"]:
+                            res = (acc.sum(axis=0).astype(np.float64) * 2.0 ** -24).astype(np.float32).astype(np.float16)
+                        else:
+                            part = (acc.astype(np.float64) * 2.0 ** -24).astype(np.float32).astype(np.float16)
+                            res = part[0]
+                            for c in range(1, nck):
+                                res = (res + part[c]).astype(np.float16)
+                    res = np.where(isbad.any(axis=0), np.float16(np.nan), res)
+            else:
+                acc = np.zeros((nck, ne), np.float64)
+                np.add.at(acc, (ch, el), e["val"][keep].astype(np.float64) * mult)
+                part = acc.astype(np.float32)
+                res = part[0]
+                for c in range(1, nck):
+                    res = (res + part[c]).astype(np.float32)
+        out[o:o + size] = res.reshape(size, C)
+    return out
+
+
+# ---------------------------------------------------------------- cases
+def _settle(spec, x, redraw, tries=40):
+    """Redraw (redraw(indices) -> new points) every point that violates the input condition; returns x."""
+    probe = make_case("probe", spec, x, np.zeros((spec[2], x.shape[0], spec[1]), np.float16))
+    for _ in range(tries):
+        bad = near_points(probe)
+        if bad.size == 0:
+            return probe["x"]
+        probe["x"][bad] = redraw(bad)
+    raise AssertionError("points stay within 2^-18 of a cell boundary")
+
+
+def _redraw_plain(rng, special, D):
+    """redraw() for _settle: fresh uniform points; a deliberate (special) point must not need one."""
+    def redraw(bad):
+        assert not special[bad].any(), "a deliberate point violates the input condition"
+        return rng.random((bad.size, D)).astype(np.float32)
+    return redraw
+
+
+def _grads(rng, L, B, C, scale):
+    g = (rng.standard_normal((L, B, C)) * 0.1 * scale).astype(np.float16)
+    g[:, ::7] = 0
+    g[:, 3::7, 0] = np.float16(-0.0)
+    return g
+
+
+def _fx_edge_points(spec):
+    """Points of the finest levels with x in cell 1 (|pos_x| < 2: the fp32 term of fx stays below 2^-18) and y, z anywhere, whose x
+    fraction is (k + 1/2) 2^-14 - 2^-20: a 15-bit fx holds it to 2^-20, a 14-bit one is 2^-15 off, and the fraction is small enough
+    for |p| 2^-16 to be most of the x + 1 corner's bound."""
+    D, C, L, H, lh, desired, *_ = spec
+    S = float(np.log2(np.exp2(np.log2(desired / H) / (L - 1))))
+    pts, rng = [], np.random.default_rng(99)
+    for l in range(L - 5, L):
+        scale, _ = oracle.grid_level_params(l, S, H)
+        for k in (1, 2, 3, 5):
+            fxv = (k + 0.5) * 2.0 ** -14 - 2.0 ** -20
+            pts.append([(0.5 + fxv) / scale, rng.random(), rng.random()])
+    return np.array(pts, np.float64)
+
+
+def _edges(scale_log2):
+    rng = np.random.default_rng(100)
+    B = 2000
+    x = rng.random((B, 3)).astype(np.float32)
+    fx = _fx_edge_points(FOC)
+    n_fx = fx.shape[0]
+    special = np.zeros(B, bool)
+    x[0], x[1], x[2] = 0.0, 1.0, np.float32(1.0) - np.float32(2.0 ** -24)
+    x[3, 0], x[4, 2], x[5, 1] = -0.01, 1.0001, 0.0
+    x[6] = (1.0, 0.0, 1.0)
+    x[40:40 + n_fx] = fx.astype(np.float32)
+    special[:7] = True
+    special[40:40 + n_fx] = True
+    x = _settle(FOC, x, _redraw_plain(rng, special, 3))
+    g = _grads(rng, 16, B, 2, 2.0 ** scale_log2)
+    g[:, 40:40 + n_fx] = (np.sign(g[:, 40:40 + n_fx].astype(np.float32) + 1e-30) * 0.75 * 2.0 ** scale_log2).astype(np.float16)
+    return make_case(f"edges_2^{scale_log2}", FOC, x, g, scale_log2=scale_log2, fx_points=np.arange(40, 40 + n_fx))
+
+
+def _cancel():
+    rng = np.random.default_rng(101)
+    n = 1000
+    p = rng.random((n, 3)).astype(np.float32)
+    p = _settle(FOC, p, lambda bad: rng.random((bad.size, 3)).astype(np.float32))
+    g = (rng.standard_normal((16, n, 2)) * 0.1).astype(np.float16)
+    return make_case("cancel", FOC, np.concatenate([p, p]), np.concatenate([g, -g], axis=1))
+
+
+def _overflow():
+    rng = np.random.default_rng(102)
+    p = _settle(FOC, rng.random((1, 3)).astype(np.float32), lambda bad: rng.random((bad.size, 3)).astype(np.float32))
+    x = np.repeat(p, 64, axis=0)
+    g = np.full((16, 64, 2), 60000.0, np.float16)
+    g[:, :, 1] = -g[:, :, 1]
+    g[8:, 1::2] = -g[8:, 1::2]                           # upper levels: alternating signs, totals cancel while sum |addend| overflows
+    return make_case("overflow", FOC, x, g)
+
+
+def _runs(B):
+    """Ray-coherent samples: nine rays (one axis-parallel, one of identical points with a constant gradient), run starts at every lane,
+    out-of-range and zero-gradient samples at the head, inside and at the tail of runs."""
+    rng = np.random.default_rng(200)
+    n_s = 128 if B > 300 else 17
+    n_rays = -(-B // n_s)
+    o = (rng.random((n_rays, 1, 3)) * 0.2).astype(np.float32)
+    d = rng.random((n_rays, 1, 3)).astype(np.float32)
+    if n_rays > 1:
+        d[1] = (1.0, 0.0, 0.0)
+    if n_rays > 2:
+        d[2] = 0.0
+    t = np.linspace(0.0, 0.85, n_s, dtype=np.float32)[None, :, None]
+    # a slow stretch at the start of every ray: steps of 1/600 give runs of every length up to the 16-lane cap at the coarse levels
+    t = np.where(np.arange(n_s)[None, :, None] < n_s // 2, t * np.float32(0.02), t)
+    x = (o + d * t).reshape(-1, 3)[:B].copy()
+    ident = np.zeros(B, bool)
+    ident[2 * n_s:3 * n_s] = True
+    if B > 40:
+        x[5::97] = -0.25
+        x[33:37, 1] = 1.5                                 # inside a run
+        x[48] = -1.0                                      # lane 0: the head of a group
+        x[63] = 2.0                                       # lane 15: the tail of a group
+    for _ in range(40):
+        c = make_case("probe", FOC, x, np.zeros((16, B, 2), np.float16))
+        bad = near_points(c)
+        if bad.size == 0:
+            break
+        if ident[bad].any():                              # the identical points move together
+            x[ident] = x[ident] + np.float32(2.0 ** -13)
+        nb = bad[~ident[bad]]
+        x[nb] = x[nb] + (rng.random((nb.size, 3)) * 2.0 ** -14).astype(np.float32)
+    else:
+        raise AssertionError("ray samples stay within 2^-18 of a cell boundary")
+    g = (rng.standard_normal((16, B, 2)) * 0.1).astype(np.float16)
+    g[:, ident[:B]] = np.array([0.1, -0.05], np.float16)
+    if B > 40:
+        g[:, 16:19] = 0                                   # head of a run
+        g[:, 24:26] = 0                                   # inside
+        g[:, 31] = 0                                      # tail at lane 15
+        g[:, 300:340] = 0
+        g[:, 143] = 0
+        tails = np.nonzero(_run_heads(c, level(c, 3))[1])[0]
+        g[:, tails[::5]] = 0                              # every fifth run of level 3 ends in a zero gradient
+    return make_case(f"runs_{B}", FOC, x, g)
+
+
+def _chunks(B):
+    """Random points of which no two neighbours share a level-0 cell (nothing merges there): 4 records per in-range point in that slot."""
+    rng = np.random.default_rng(300 + B)
+    x = rng.random((B, 3)).astype(np.float32)
+    scale, _ = oracle.grid_level_params(0, make_case("p", FOC, x[:1], np.zeros((16, 1, 2), np.float16))["S"], 16)
+    for _ in range(40):
+        cell = np.floor(_fma32(x, scale, 0.5)[0]).astype(np.int64)
+        same = np.nonzero(np.all(cell[1:] == cell[:-1], axis=1))[0] + 1
+        if same.size == 0:
+            x = _settle(FOC, x, lambda bad: rng.random((bad.size, 3)).astype(np.float32))
+            cell = np.floor(_fma32(x, scale, 0.5)[0]).astype(np.int64)
+            if not np.all(cell[1:] == cell[:-1], axis=1).any():
+                break
+            continue
+        x[same] = rng.random((same.size, 3)).astype(np.float32)
+    else:
+        raise AssertionError("neighbours keep sharing level-0 cells")
+    return make_case(f"chunks_{B}", FOC, x, _grads(rng, 16, B, 2, 1.0))
+
+
+def _straddle():
+    """130 points in cells of a dense level of more than one segment that have a pair of corners along x on both sides of a multiple of
+    8192 rows, each between random points (so that no run merges two of them)."""
+    rng = np.random.default_rng(400)
+    B = 1500
+    x = rng.random((B, 3)).astype(np.float32)
+    probe = make_case("p", FOC, x[:1], np.zeros((16, 1, 2), np.float16))
+    found = None
+    for l in range(16):
+        scale, res = oracle.grid_level_params(l, probe["S"], 16)
+        size = int(probe["off"][l + 1] - probe["off"][l])
+        if (res + 1) ** 3 > size or size <= SEG:
+            continue
+        cells = np.stack(np.meshgrid(*[np.arange(res)] * 3, indexing="ij"), axis=-1).reshape(-1, 3)
+        rows, hashed = _rows(probe, cells, size, res)
+        hit = cells[((rows[:, 0::2] >> SEG_SHIFT) != (rows[:, 1::2] >> SEG_SHIFT)).any(axis=1)]
+        if hit.size and not hashed:
+            found = (l, scale, hit)
+            break
+    assert found is not None
+    l, scale, hit = found
+    where = np.arange(10, 10 + 2 * 130, 2)
+    pick = hit[rng.integers(0, hit.shape[0], 130)]
+    x[where] = ((pick + 0.1 + 0.8 * rng.random((130, 3)) - 0.5) / scale).astype(np.float32)
+    special = np.zeros(B, bool)
+    special[where] = True
+
+    def redraw(bad):
+        new = rng.random((bad.size, 3)).astype(np.float32)
+        s = special[bad]
+        new[s] = ((hit[rng.integers(0, hit.shape[0], int(s.sum()))] + 0.1 + 0.8 * rng.random((int(s.sum()), 3)) - 0.5) / scale).astype(np.float32)
+        return new
+    x = _settle(FOC, x, redraw)
+    return make_case("straddle", FOC, x, _grads(rng, 16, B, 2, 1.0), straddle_level=l)
+
+
+SHAPES = {
+    "D2_C2": (2, 2, 8, 16, 15, 512, 0, False, 0),
+    "D3_C1": (3, 1, 8, 16, 15, 512, 0, False, 0),
+    "D3_C4": (3, 4, 6, 16, 14, 256, 0, False, 0),
+    "D3_C8": (3, 8, 4, 8, 14, 128, 0, False, 0),
+    "tiled": (3, 4, 8, 16, 15, 512, 1, False, 0),
+    "ac_smooth": (3, 2, 6, 8, 14, 128, 0, True, 1),
+    "D4": (4, 2, 8, 8, 14, 64, 0, False, 0),
+    "D5": (5, 2, 6, 4, 13, 24, 0, False, 0),
+}
+
+
+def _shape(name):
+    spec = SHAPES[name]
+    D, C, L = spec[:3]
+    rng = np.random.default_rng(500 + sum(map(ord, name)))
+    B = 1500
+    x = rng.random((B, D)).astype(np.float32)
+    x[0], x[1] = 0.0, 1.0
+    x[2, 0], x[3, D - 1] = -0.01, 1.0001
+    special = np.zeros(B, bool)
+    special[:4] = True
+    x = _settle(spec, x, _redraw_plain(rng, special, D))
+    table = rng.uniform(-1, 1, (int(level_offsets(D, L, np.exp2(np.log2(spec[5] / spec[3]) / (L - 1)), spec[3], spec[4], spec[7])[-1]), C))
+    return make_case(f"shape_{name}", spec, x, _grads(rng, L, B, C, 1.0), table=table.astype(np.float16))
+
+
+_CASES = None
+BUILDERS = {}
+for _s in (0, -14, -20, 10):
+    BUILDERS[f"edges_2^{_s}"] = (_edges, _s)
+BUILDERS["cancel"] = (_cancel,)
+BUILDERS["overflow"] = (_overflow,)
+for _b in (1, 15, 17, 1023, 1025, 3051):
+    BUILDERS[f"runs_{_b}"] = (_runs, _b)
+for _b in (8192, 8193, 20000):
+    BUILDERS[f"chunks_{_b}"] = (_chunks, _b)
+BUILDERS["straddle"] = (_straddle,)
+for _n in SHAPES:
+    BUILDERS[f"shape_{_n}"] = (_shape, _n)
+_BUILT = {}
+
+# which routes every case runs on (the GPU tests and the model's test walk the same plan)
+ALL8 = ("binned16", "binned32", "binned16_unfactored", "binned16_unmerged", "binned16_det1", "binned16_det2", "atomic16", "atomic32")
+PLAN = {n: ALL8 for n in BUILDERS if n.startswith("edges")}
+PLAN["cancel"] = ("binned16_12byte", "binned16", "binned32", "atomic16")
+PLAN["overflow"] = ("binned16", "binned16_12byte", "atomic16")
+PLAN.update({n: ("binned16", "binned32") for n in BUILDERS if n.startswith("runs")})
+PLAN["runs_3051"] = ("binned16", "binned32", "binned16_12byte", "binned16_det1", "atomic16")
+PLAN.update({n: ("binned16", "binned16_det1", "binned16_det2", "binned32") for n in BUILDERS if n.startswith("chunks")})
+PLAN["straddle"] = ("binned16", "binned32", "binned16_unfactored")
+PLAN.update({n: ("atomic16", "atomic32") for n in BUILDERS if n.startswith("shape")})
+
+
+def case(name):
+    """The case of that name, built once."""
+    if name not in _BUILT:
+        fn, *args = BUILDERS[name]
+        _BUILT[name] = fn(*args)
+        assert _BUILT[name]["name"] == name
+    return _BUILT[name]
+
+
+def names(prefix=""):
+    return [n for n in BUILDERS if n.startswith(prefix)]
