@@ -1,7 +1,9 @@
-// gridencoder.hip — multiresolution hash / tiled grid encoding for gfx950.
+// gridencoder.hip — multiresolution hash / tiled grid encoding for gfx950: the entry points, the D = 2 / 3 instances of the general
+// kernels, and the binned backward of the D = 3 / C = 2 tables.
 //
-// Semantics: gridencoder/src/gridencoder.cu of the reference (kernel_grid :87-245,
-// kernel_grid_backward :248-340, kernel_input_backward :343-369, kernel_grad_tv :506-610).
+// Semantics: gridencoder/src/gridencoder.cu of the reference. The arithmetic of a (point, level), the general kernels (forward with
+// dy_dx, atomic backward, grad_inputs, grad_tv) and their launches are written once in ge_common.h for every D; this file instantiates
+// them for GeDimCT<2> and GeDimCT<3> (ge_call), gridencoder_nd.hip for the runtime dimension (D = 4, 5).
 //
 // MI355X organisation:
 //  * Level placement is XCD-aware. Workgroups are dealt round-robin over the 8 XCDs
@@ -10,7 +12,9 @@
 //    is therefore decoded as  xcd = id % 8, level = xcd + 8 * (j / chunks), so a level's
 //    gathers all come from ONE XCD's L2 and stay resident there, instead of the reference's
 //    blockIdx.y = level (gridencoder.cu:103) which spreads every level over all eight L2s.
-//    This is a speed choice only: any placement gives the same result.
+//    This is a speed choice only: any placement gives the same result. The atomic backward and grad_tv decode their grid this way
+//    for every D; the forward walks level by level for D = 2 / 3 (k_grid_fwd_lbc) and keeps blockIdx.y = level for the runtime
+//    dimension (k_grid_fwd_pl, where the 1-D launches cost registers: ge_common.h).
 //  * Per-level scale / resolution are computed on the host (same libm expression as the
 //    oracle) and passed by value: no exp2f per thread, and the integer index math cannot
 //    drift with a device transcendental.
@@ -29,477 +33,10 @@
 
 #include "ge_common.h"
 
-// ---- index math (gridencoder.cu:50-84) -------------------------------------------------
-template <uint32_t D>
-__device__ __forceinline__ uint32_t ge_index(uint32_t gridtype, bool align_corners, uint32_t hashmap_size, uint32_t resolution,
-                                             const uint32_t (&pos_grid)[D]) {
-    constexpr uint32_t primes[7] = {1u, 2654435761u, 805459861u, 3674653429u, 2097192037u, 1434869437u, 2165219737u};
-    uint32_t stride = 1, index = 0;
-#pragma unroll
-    for (uint32_t d = 0; d < D; d++) {
-        if (stride <= hashmap_size) {
-            index += pos_grid[d] * stride;
-            stride *= align_corners ? resolution : (resolution + 1);
-        }
-    }
-    if (gridtype == 0 && stride > hashmap_size) {
-        uint32_t result = 0;
-#pragma unroll
-        for (uint32_t i = 0; i < D; i++) result ^= pos_grid[i] * primes[i];
-        index = result;
-    }
-    // `index % hashmap_size` (gridencoder.cu:83) without the integer division in the common cases: dense levels have
-    // index < size already, hashed levels have a power-of-two size (2^log2_hashmap_size); the generic path remains for
-    // tiled grids / odd sizes. A runtime u32 modulo is ~35 VALU instructions and this runs 8x per (point, level).
-    if (index >= hashmap_size) index = ((hashmap_size & (hashmap_size - 1u)) == 0u) ? (index & (hashmap_size - 1u)) : (index % hashmap_size);
-    return index;                  // row index; caller multiplies by C
-}
-
-// Decode a linear block id into (level, chunk) so that all blocks of a level share
-// blockIdx % 8, i.e. one XCD under the observed round-robin dispatch.
-__device__ __forceinline__ bool ge_decode_block(uint32_t id, uint32_t chunks, uint32_t L, uint32_t &level, uint32_t &chunk) {
-    const uint32_t xcd = id & 7u, j = id >> 3;
-    level = xcd + 8u * (j / chunks);
-    chunk = j % chunks;
-    return level < L;
-}
-
-template <uint32_t D>
-__device__ __forceinline__ bool ge_load_point(const float *__restrict__ inputs, uint32_t b, float (&x)[D]) {
-    bool oob = false;
-#pragma unroll
-    for (uint32_t d = 0; d < D; d++) { x[d] = inputs[(uint64_t)b * D + d]; oob |= (x[d] < 0 || x[d] > 1); }
-    return oob;
-}
-
-// The same 8 rows for D = 3 with the per-level decisions (which dimensions enter the dense index, dense or hashed, power-of-two
-// size) taken once on wave-uniform values and the per-axis terms shared between the corners: (p+1)*k = p*k + k in uint32, so every
-// row is two adds or two xors instead of ge_index's per-corner multiplies and branches. Bit-identical to ge_index per corner (corner idx: bit d set = +1 along axis d).
-__device__ __forceinline__ void ge_rows3(const uint32_t (&pos_grid)[3], uint32_t hashmap_size, uint32_t resolution, uint32_t gridtype,
-                                              bool align_corners, uint32_t (&rows)[8], bool *is_hashed = nullptr) {
-    const uint32_t r1 = align_corners ? resolution : resolution + 1u;
-    uint32_t stride = 1u, st[3];
-    bool part[3];
-#pragma unroll
-    for (int d = 0; d < 3; d++) { part[d] = stride <= hashmap_size; st[d] = part[d] ? stride : 0u; if (part[d]) stride *= r1; }
-    const bool hashed = gridtype == 0u && stride > hashmap_size;
-    if (is_hashed) *is_hashed = hashed;
-    uint32_t t[3][2];
-    if (hashed) {
-        constexpr uint32_t primes[3] = {1u, 2654435761u, 805459861u};
-#pragma unroll
-        for (int d = 0; d < 3; d++) { t[d][0] = pos_grid[d] * primes[d]; t[d][1] = t[d][0] + primes[d]; }
-    } else {
-#pragma unroll
-        for (int d = 0; d < 3; d++) { t[d][0] = pos_grid[d] * st[d]; t[d][1] = t[d][0] + st[d]; }
-    }
-    // `index % hashmap_size` (gridencoder.cu:83), decided once per level: a dense level that takes all three axes has index < size
-    // already; a power-of-two size (every hashed level: 2^log2_hashmap_size) is a mask; the division is left for tiled grids with odd sizes
-    const bool need_mod = hashed || stride > hashmap_size || !part[2];
-    const bool pow2 = (hashmap_size & (hashmap_size - 1u)) == 0u;
-    if (!need_mod) {
-#pragma unroll
-        for (uint32_t idx = 0; idx < 8; idx++) rows[idx] = t[0][idx & 1u] + t[1][(idx >> 1) & 1u] + t[2][(idx >> 2) & 1u];
-    } else if (pow2) {
-        const uint32_t mask = hashmap_size - 1u;
-        if (hashed) {
-#pragma unroll
-            for (uint32_t idx = 0; idx < 8; idx++) rows[idx] = (t[0][idx & 1u] ^ t[1][(idx >> 1) & 1u] ^ t[2][(idx >> 2) & 1u]) & mask;
-        } else {
-#pragma unroll
-            for (uint32_t idx = 0; idx < 8; idx++) rows[idx] = (t[0][idx & 1u] + t[1][(idx >> 1) & 1u] + t[2][(idx >> 2) & 1u]) & mask;
-        }
-    } else {
-#pragma unroll
-        for (uint32_t idx = 0; idx < 8; idx++) {
-            const uint32_t a = t[0][idx & 1u], b = t[1][(idx >> 1) & 1u], c = t[2][(idx >> 2) & 1u];
-            rows[idx] = (hashed ? (a ^ b ^ c) : (a + b + c)) % hashmap_size;
-        }
-    }
-}
-
-// ---- forward: one (point, level) ---------------------------------------------------------
-// out points at the C outputs of this (point, level); dy points at its [D,C] block or null.
-template <typename T, uint32_t D, uint32_t C, bool PAIRS = false>
-__device__ __forceinline__ void ge_forward_one(const float (&x)[D], bool oob, const T *__restrict__ table, uint32_t hashmap_size,
-                                               float scale, uint32_t resolution, T *__restrict__ out, T *__restrict__ dy,
-                                               uint32_t gridtype, bool align_corners, uint32_t interp) {
-    float results[C];
-#pragma unroll
-    for (uint32_t c = 0; c < C; c++) results[c] = 0.0f;
-    if (oob) {                                                   // gridencoder.cu:119-135
-        GeVec<T, C>::st(out, results);
-        if (dy) {
-#pragma unroll
-            for (uint32_t i = 0; i < D * C; i++) GeT<T>::st(dy + i, 0.0f);
-        }
-        return;
-    }
-    float pos[D], pos_deriv[D];
-    uint32_t pos_grid[D];
-#pragma unroll
-    for (uint32_t d = 0; d < D; d++) {                           // :147-159
-        pos[d] = fmaf(x[d], scale, align_corners ? 0.0f : 0.5f);
-        const float fl = floorf(pos[d]);
-        pos_grid[d] = (uint32_t)fl;
-        pos[d] -= (float)pos_grid[d];
-        if (interp == 1) {
-            const float v = pos[d];
-            pos_deriv[d] = 6 * v * (1.0f - v);
-            pos[d] = v * v * fmaf(-2.0f, v, 3.0f);
-        } else pos_deriv[d] = 1.0f;
-    }
-    // issue all 2^D gathers before consuming them (latency-bound: keep them in flight)
-    float vals[1u << D][C];
-    float ws[1u << D];
-    uint32_t rows3[8];
-    if constexpr (D == 3) ge_rows3(pos_grid, hashmap_size, resolution, gridtype, align_corners, rows3);
-    constexpr bool paired = PAIRS && D == 3 && C == 2 && sizeof(T) == 2;
-    if constexpr (paired) {
-        // The two corners along x of a (y, z) pair are ROW NEIGHBOURS whenever row(x+1) == row(x) ^ 1: always on a dense level with an
-        // even row, and on a hashed level for every even x (the hash xors x in with prime 1, so x -> x+1 flips bit 0 only). One
-        // 8-byte load of the aligned row pair then serves both corners — the gathers are bound by the number of distinct cache-line
-        // requests, not by bytes (tools/bench_gather.hip) — and only the other lanes issue the second, 4-byte load.
-        {
-            const uint32_t *tw = reinterpret_cast<const uint32_t *>(table);
-            uint2 wide[4];
-            uint32_t nar[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) wide[j] = *reinterpret_cast<const uint2 *>(tw + (rows3[2 * j] & ~1u));
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                nar[j] = 0u;
-                if (rows3[2 * j + 1] != (rows3[2 * j] ^ 1u)) nar[j] = tw[rows3[2 * j + 1]];
-            }
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const bool odd = (rows3[2 * j] & 1u) != 0u, pr = rows3[2 * j + 1] == (rows3[2 * j] ^ 1u);
-                const uint32_t v0 = odd ? wide[j].y : wide[j].x;
-                const uint32_t v1 = pr ? (odd ? wide[j].x : wide[j].y) : nar[j];
-                const __half2 h0 = *reinterpret_cast<const __half2 *>(&v0), h1 = *reinterpret_cast<const __half2 *>(&v1);
-                vals[2 * j][0] = __low2float(h0); vals[2 * j][1] = __high2float(h0);
-                vals[2 * j + 1][0] = __low2float(h1); vals[2 * j + 1][1] = __high2float(h1);
-            }
-        }
-    }
-#pragma unroll
-    for (uint32_t idx = 0; idx < (1u << D); idx++) {             // :167-191
-        float w = 1;
-        uint32_t pgl[D];
-#pragma unroll
-        for (uint32_t d = 0; d < D; d++) {
-            if ((idx & (1u << d)) == 0) { w *= 1 - pos[d]; pgl[d] = pos_grid[d]; }
-            else { w *= pos[d]; pgl[d] = pos_grid[d] + 1; }
-        }
-        ws[idx] = w;
-        if constexpr (!paired) {
-            uint32_t row;
-            if constexpr (D == 3) row = rows3[idx];
-            else row = ge_index<D>(gridtype, align_corners, hashmap_size, resolution, pgl);
-            GeVec<T, C>::ld(table + (uint64_t)row * C, vals[idx]);
-        }
-    }
-#pragma unroll
-    for (uint32_t idx = 0; idx < (1u << D); idx++) {
-#pragma unroll
-        for (uint32_t c = 0; c < C; c++) results[c] = fmaf(ws[idx], vals[idx][c], results[c]);
-    }
-    GeVec<T, C>::st(out, results);
-
-    if (dy) {                                                    // :201-244
-#pragma unroll
-        for (uint32_t gd = 0; gd < D; gd++) {
-            float rg[C];
-#pragma unroll
-            for (uint32_t c = 0; c < C; c++) rg[c] = 0.0f;
-#pragma unroll
-            for (uint32_t idx = 0; idx < (1u << (D - 1)); idx++) {
-                float w = scale;
-                uint32_t pgl[D];
-#pragma unroll
-                for (uint32_t nd = 0; nd < D - 1; nd++) {
-                    const uint32_t d = (nd >= gd) ? (nd + 1) : nd;
-                    if ((idx & (1u << nd)) == 0) { w *= 1 - pos[d]; pgl[d] = pos_grid[d]; }
-                    else { w *= pos[d]; pgl[d] = pos_grid[d] + 1; }
-                }
-                pgl[gd] = pos_grid[gd];
-                const uint32_t rl = ge_index<D>(gridtype, align_corners, hashmap_size, resolution, pgl);
-                pgl[gd] = pos_grid[gd] + 1;
-                const uint32_t rr = ge_index<D>(gridtype, align_corners, hashmap_size, resolution, pgl);
-                float vl[C], vr[C];
-                GeVec<T, C>::ld(table + (uint64_t)rl * C, vl);
-                GeVec<T, C>::ld(table + (uint64_t)rr * C, vr);
-#pragma unroll
-                for (uint32_t c = 0; c < C; c++) rg[c] = fmaf(w * (vr[c] - vl[c]), pos_deriv[gd], rg[c]);
-            }
-#pragma unroll
-            for (uint32_t c = 0; c < C; c++) GeT<T>::st(dy + gd * C + c, rg[c]);
-        }
-    }
-}
-
-// ---- forward, the shape FOC runs: hash gridtype, align_corners off, linear interpolation, fp16 tables with C = 2, D = 3, no dy_dx, row pairs
-// 8-byte aligned. ge_forward_one with every per-call decision already taken: what is left at run time is dense-or-hashed (wave-uniform,
-// decided by the caller with ge_level_hashed) and, on a hashed level, ONE lane-divergent branch (x odd: the four x+1 corners are no row
-// neighbours and take their own 4-byte loads) instead of four. Same arithmetic in the same order: bit-identical results.
-__host__ __device__ __forceinline__ bool ge_level_hashed(uint32_t hashmap_size, uint32_t resolution, uint32_t &st1, uint32_t &st2) {
-    const uint32_t r1 = resolution + 1u;                 // the reference's uint32 stride walk (gridencoder.cu:70-83), D = 3
-    uint32_t stride = 1u;
-    st1 = st2 = 0u;
-    if (stride <= hashmap_size) stride *= r1;
-    if (stride <= hashmap_size) { st1 = stride; stride *= r1; }
-    if (stride <= hashmap_size) { st2 = stride; stride *= r1; }
-    return stride > hashmap_size;
-}
-
-__device__ __forceinline__ void ge_forward_hash3(const float (&x)[3], bool oob, const uint32_t *__restrict__ tw, uint32_t hashmap_size, bool hashed,
-                                                 uint32_t st1, uint32_t st2, float scale, __half *__restrict__ out) {
-    if (oob) { *reinterpret_cast<uint32_t *>(out) = 0u; return; }
-    float pos[3];
-    uint32_t pg[3];
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-        const float p = fmaf(x[d], scale, 0.5f);         // >= 0.5 here (0 <= x <= 1): truncation is the floor, and p - floor(p) is exact —
-        pg[d] = (uint32_t)p;                             // v_fract_f32 returns that same value in one instruction
-        pos[d] = __builtin_amdgcn_fractf(p);
-    }
-    // rows as 32-bit BYTE offsets from the level's base: the loads take the base from scalar registers (global_load ... v_off, s[base])
-    // instead of a 64-bit address per lane and load (the launch wrapper admits this path for levels below 2^30 rows only)
-    const char *tb = reinterpret_cast<const char *>(tw);
-    // b0[j]: BYTE offset of the row of corner (x, y_j, z_j), j = y bit | z bit << 1; the row pair it belongs to starts at b0 & ~7.
-    uint32_t b0[4];
-    uint2 wide[4];
-    uint32_t nar[4] = {0u, 0u, 0u, 0u};
-    bool pr[4];
-    if (hashmap_size <= (1u << 22)) {
-        // Tables of at most 2^22 rows (every NeRF grid: log2_hashmap_size 19): the index arithmetic runs on byte offsets below 2^24 with
-        // FULL-RATE 24-bit multiplies. Only the low bits of the hash survive the `% hashmap_size` (a power of two here), and they depend on
-        // the low bits of the factors alone: (x ^ y P1 ^ z P2) & m, times 4, == ((x << 2) ^ y (4 (P1 & m)) ^ z (4 (P2 & m))) & (m << 2). The
-        // generic form below spends two quarter-rate 32-bit multiplies, a shift and a mask per corner; this one a shift for x, two
-        // v_mul_u32_u24 and one xor + and per corner (~20 of the ~100 VALU slots per point and level). A dense level likewise: strides
-        // below 2^22, rows below the table size.
-        const uint32_t x4 = pg[0] << 2;
-        uint32_t yz4[4];
-        if (hashed) {
-            const uint32_t m = hashmap_size - 1u, m4 = m << 2;
-            const uint32_t p1 = (2654435761u & m) << 2, p2 = (805459861u & m) << 2;
-            const uint32_t t1 = __umul24(pg[1], p1), t2 = __umul24(pg[2], p2);
-            yz4[0] = t1 ^ t2; yz4[1] = (t1 + p1) ^ t2; yz4[2] = t1 ^ (t2 + p2); yz4[3] = (t1 + p1) ^ (t2 + p2);
-#pragma unroll
-            for (int j = 0; j < 4; j++) b0[j] = (x4 ^ yz4[j]) & m4;
-#pragma unroll
-            for (int j = 0; j < 4; j++) wide[j] = *reinterpret_cast<const uint2 *>(tb + (b0[j] & ~7u));
-            const bool even = (x4 & 4u) == 0u;           // x even: x + 1 == x ^ 1, every (x, x+1) corner pair is an aligned row pair
-            if (!even) {
-#pragma unroll
-                for (int j = 0; j < 4; j++) nar[j] = *reinterpret_cast<const uint32_t *>(tb + (((x4 + 4u) ^ yz4[j]) & m4));
-            }
-#pragma unroll
-            for (int j = 0; j < 4; j++) pr[j] = even;
-        } else {
-            const uint32_t s1 = st1 << 2, s2 = st2 << 2;
-            const uint32_t t1 = __umul24(pg[1], s1), t2 = __umul24(pg[2], s2);
-            yz4[0] = t1 + t2; yz4[1] = (t1 + s1) + t2; yz4[2] = t1 + (t2 + s2); yz4[3] = (t1 + s1) + (t2 + s2);
-#pragma unroll
-            for (int j = 0; j < 4; j++) b0[j] = x4 + yz4[j];
-#pragma unroll
-            for (int j = 0; j < 4; j++) wide[j] = *reinterpret_cast<const uint2 *>(tb + (b0[j] & ~7u));
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                pr[j] = (b0[j] & 4u) == 0u;
-                if (!pr[j]) nar[j] = *reinterpret_cast<const uint32_t *>(tb + (b0[j] + 4u));
-            }
-        }
-    } else if (hashed) {
-        const uint32_t mask = hashmap_size - 1u;
-        const uint32_t t1 = pg[1] * 2654435761u, t2 = pg[2] * 805459861u;
-        const uint32_t yz[4] = {t1 ^ t2, (t1 + 2654435761u) ^ t2, t1 ^ (t2 + 805459861u), (t1 + 2654435761u) ^ (t2 + 805459861u)};
-#pragma unroll
-        for (int j = 0; j < 4; j++) b0[j] = ((pg[0] ^ yz[j]) & mask) << 2;
-#pragma unroll
-        for (int j = 0; j < 4; j++) wide[j] = *reinterpret_cast<const uint2 *>(tb + (b0[j] & ~7u));
-        const bool even = (pg[0] & 1u) == 0u;
-        if (!even) {
-#pragma unroll
-            for (int j = 0; j < 4; j++) nar[j] = *reinterpret_cast<const uint32_t *>(tb + ((((pg[0] + 1u) ^ yz[j]) & mask) << 2));
-        }
-#pragma unroll
-        for (int j = 0; j < 4; j++) pr[j] = even;
-    } else {
-        const uint32_t t1 = pg[1] * st1, t2 = pg[2] * st2;
-        const uint32_t yz[4] = {t1 + t2, (t1 + st1) + t2, t1 + (t2 + st2), (t1 + st1) + (t2 + st2)};
-#pragma unroll
-        for (int j = 0; j < 4; j++) b0[j] = (pg[0] + yz[j]) << 2;
-#pragma unroll
-        for (int j = 0; j < 4; j++) wide[j] = *reinterpret_cast<const uint2 *>(tb + (b0[j] & ~7u));
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            pr[j] = (b0[j] & 4u) == 0u;
-            if (!pr[j]) nar[j] = *reinterpret_cast<const uint32_t *>(tb + (b0[j] + 4u));
-        }
-    }
-    const float wx[2] = {1 - pos[0], pos[0]}, wy[2] = {1 - pos[1], pos[1]}, wz[2] = {1 - pos[2], pos[2]};
-    float res0 = 0.0f, res1 = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const bool odd = (b0[j] & 4u) != 0u;
-        const uint32_t v0 = odd ? wide[j].y : wide[j].x;
-        const uint32_t v1 = pr[j] ? (odd ? wide[j].x : wide[j].y) : nar[j];
-        const __half2 h0 = *reinterpret_cast<const __half2 *>(&v0), h1 = *reinterpret_cast<const __half2 *>(&v1);
-        const float w0 = (wx[0] * wy[j & 1]) * wz[j >> 1], w1 = (wx[1] * wy[j & 1]) * wz[j >> 1];
-        res0 = fmaf(w0, __low2float(h0), res0); res1 = fmaf(w0, __high2float(h0), res1);
-        res0 = fmaf(w1, __low2float(h1), res0); res1 = fmaf(w1, __high2float(h1), res1);
-    }
-    *reinterpret_cast<__half2 *>(out) = __halves2half2(__float2half_rn(ge_opaque(res0)), __float2half_rn(ge_opaque(res1)));
-}
-
-// One level of the fast shape or of the general one (`fast`: the launch-wide part of the decision, taken on the host).
-// ge_forward_hash3 addresses rows by 32-bit BYTE offsets inside the level: levels of up to 2^30 rows of 4 bytes; a hashed level must
-// have a power-of-two size (its `% hashmap_size` is a mask there). Within it, levels of at most 2^22 rows take the 24-bit multiplies.
-__host__ __device__ __forceinline__ bool ge_hash3_admits(uint32_t hashmap_size, bool hashed) {
-    return (!hashed || (hashmap_size & (hashmap_size - 1u)) == 0u) && hashmap_size <= (1u << 30);
-}
-
-template <typename T, uint32_t D, uint32_t C>
-__device__ __forceinline__ void ge_forward_level(const float (&x)[D], bool oob, const T *__restrict__ grid, uint32_t off0, uint32_t hashmap_size, float scale,
-                                                 uint32_t resolution, T *__restrict__ out, T *__restrict__ dy, uint32_t gridtype, bool align_corners,
-                                                 uint32_t interp, uint32_t pairs) {
-    const bool aligned = ((off0 | hashmap_size) & 1u) == 0u;                   // row pairs of this level are 8-byte aligned and inside it
-    if constexpr (sizeof(T) == 2 && D == 3 && C == 2) {
-        if (pairs == 2u && aligned) {
-            uint32_t st1, st2;
-            const bool hashed = ge_level_hashed(hashmap_size, resolution, st1, st2);
-            if (ge_hash3_admits(hashmap_size, hashed)) {
-                ge_forward_hash3(x, oob, reinterpret_cast<const uint32_t *>(grid) + off0, hashmap_size, hashed, st1, st2, scale,
-                                 reinterpret_cast<__half *>(out));
-                return;
-            }
-        }
-    }
-    if (pairs && aligned)
-        ge_forward_one<T, D, C, true>(x, oob, grid + (uint64_t)off0 * C, hashmap_size, scale, resolution, out, dy, gridtype, align_corners, interp);
-    else
-        ge_forward_one<T, D, C, false>(x, oob, grid + (uint64_t)off0 * C, hashmap_size, scale, resolution, out, dy, gridtype, align_corners, interp);
-}
-
-// Encoding workgroup f of a plain level walk -> chunk of 256 points and the range of levels it encodes: the `lc` leading levels (the
-// small dense tables, 1.4 MiB together for the default grid) are done by ONE workgroup per chunk, which loads its points once; the
-// levels from `lc` up follow one at a time. At those small levels a launch moves 12 bytes of position per 4 bytes of result: what
-// they cost is reading the positions (0.015 ms per level and 2 M points), not the gathers.
-__device__ __forceinline__ void ge_walk(uint32_t f, uint32_t chunks, uint32_t lc, uint32_t &chunk, uint32_t &l0, uint32_t &l1) {
-    const uint32_t grp = f / chunks;
-    chunk = f - grp * chunks;
-    if (lc < 2u) { l0 = grp; l1 = grp + 1u; }
-    else if (grp == 0u) { l0 = 0u; l1 = lc; }
-    else { l0 = lc + grp - 1u; l1 = l0 + 1u; }
-}
-
-// Level-major launch, outputs [L,B,C]: thread = point. `plain`: blocks are numbered level by level, so the whole chip walks ONE
-// level at a time and every XCD's 4 MiB L2 holds that level's table (<= 2 MiB at 2^19 x half2); otherwise a level is pinned to one
-// XCD (ge_decode_block), which balances badly because the cost of a level grows ~5x from level 0 to 15 (tools/time_levels.py).
-template <typename T, uint32_t D, uint32_t C>
-__global__ void __launch_bounds__(256) k_grid_fwd_lbc(const float *__restrict__ inputs, const T *__restrict__ grid,
-                                                      const int32_t *__restrict__ offsets, T *__restrict__ outputs,
-                                                      uint32_t B, uint32_t L, GeLevels lv, T *__restrict__ dy_dx,
-                                                      uint32_t gridtype, bool align_corners, uint32_t interp, uint32_t chunks, uint32_t plain,
-                                                      uint32_t pairs, uint32_t lc) {
-    uint32_t chunk, l0, l1;
-    if (plain) ge_walk(blockIdx.x, chunks, lc, chunk, l0, l1);
-    else { if (!ge_decode_block(blockIdx.x, chunks, L, l0, chunk)) return; l1 = l0 + 1u; }
-    const uint32_t b = chunk * 256 + threadIdx.x;
-    if (b >= B || l0 >= L) return;
-    float x[D];
-    const bool oob = ge_load_point<D>(inputs, b, x);
-    for (uint32_t level = l0; level < l1; level++) {
-        const uint32_t off0 = (uint32_t)offsets[level];
-        const uint32_t hashmap_size = (uint32_t)offsets[level + 1] - off0;
-        T *dy = dy_dx ? dy_dx + ((uint64_t)b * L + level) * D * C : nullptr;
-        ge_forward_level<T, D, C>(x, oob, grid, off0, hashmap_size, lv.scale[level], lv.resolution[level], outputs + ((uint64_t)level * B + b) * C, dy,
-                                  gridtype, align_corners, interp, pairs);
-    }
-}
-
-// Point-major launch, outputs [B, L*C]: consecutive lanes = consecutive levels of one point, so
-// the wave's store is contiguous. Thread id g -> b = g / L, level = g % L.
-template <typename T, uint32_t D, uint32_t C>
-__global__ void __launch_bounds__(256) k_grid_fwd_bl(const float *__restrict__ inputs, const T *__restrict__ grid,
-                                                     const int32_t *__restrict__ offsets, T *__restrict__ outputs,
-                                                     uint32_t B, uint32_t L, GeLevels lv, T *__restrict__ dy_dx,
-                                                     uint32_t gridtype, bool align_corners, uint32_t interp) {
-    const uint64_t total = (uint64_t)B * L;
-    for (uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x; g < total; g += (uint64_t)gridDim.x * 256) {
-        const uint32_t b = (uint32_t)(g / L), level = (uint32_t)(g - (uint64_t)b * L);
-        const uint32_t off0 = (uint32_t)offsets[level];
-        const uint32_t hashmap_size = (uint32_t)offsets[level + 1] - off0;
-        float x[D];
-        const bool oob = ge_load_point<D>(inputs, b, x);
-        T *dy = dy_dx ? dy_dx + ((uint64_t)b * L + level) * D * C : nullptr;
-        ge_forward_one<T, D, C>(x, oob, grid + (uint64_t)off0 * C, hashmap_size, lv.scale[level], lv.resolution[level],
-                                outputs + g * C, dy, gridtype, align_corners, interp);
-    }
-}
-
-// ---- backward ---------------------------------------------------------------------------
-template <typename T, uint32_t D, uint32_t C>
-__device__ __forceinline__ void ge_backward_one(const float (&x)[D], const float (&g)[C], T *__restrict__ grad_table,
-                                                uint32_t hashmap_size, float scale, uint32_t resolution,
-                                                uint32_t gridtype, bool align_corners, uint32_t interp) {
-    float pos[D];
-    uint32_t pos_grid[D];
-#pragma unroll
-    for (uint32_t d = 0; d < D; d++) {
-        pos[d] = fmaf(x[d], scale, align_corners ? 0.0f : 0.5f);
-        pos_grid[d] = (uint32_t)floorf(pos[d]);
-        pos[d] -= (float)pos_grid[d];
-        if (interp == 1) { const float v = pos[d]; pos[d] = v * v * fmaf(-2.0f, v, 3.0f); }
-    }
-#pragma unroll
-    for (uint32_t idx = 0; idx < (1u << D); idx++) {
-        float w = 1;
-        uint32_t pgl[D];
-#pragma unroll
-        for (uint32_t d = 0; d < D; d++) {
-            if ((idx & (1u << d)) == 0) { w *= 1 - pos[d]; pgl[d] = pos_grid[d]; }
-            else { w *= pos[d]; pgl[d] = pos_grid[d] + 1; }
-        }
-        const uint32_t row = ge_index<D>(gridtype, align_corners, hashmap_size, resolution, pgl);
-        float v[C];
-#pragma unroll
-        for (uint32_t c = 0; c < C; c++) v[c] = w * g[c];
-        GeAtomic<T>::template add<C>(grad_table + (uint64_t)row * C, v);
-    }
-}
-
-// grad layout: GRAD_BL ? [B, L*C] : [L, B, C].  Level-major XCD-aware launch, thread = point.
-template <typename T, uint32_t D, uint32_t C, bool GRAD_BL>
-__global__ void __launch_bounds__(256) k_grid_bwd(const T *__restrict__ grad, const float *__restrict__ inputs,
-                                                  const int32_t *__restrict__ offsets, T *__restrict__ grad_grid,
-                                                  uint32_t B, uint32_t L, GeLevels lv, uint32_t gridtype, bool align_corners,
-                                                  uint32_t interp, uint32_t chunks) {
-    uint32_t level, chunk;
-    if (!ge_decode_block(blockIdx.x, chunks, L, level, chunk)) return;
-    const uint32_t b = chunk * 256 + threadIdx.x;
-    if (b >= B) return;
-    float x[D];
-    if (ge_load_point<D>(inputs, b, x)) return;                   // :276-281
-    const uint32_t off0 = (uint32_t)offsets[level];
-    const uint32_t hashmap_size = (uint32_t)offsets[level + 1] - off0;
-    float g[C];
-    const T *gp = GRAD_BL ? grad + ((uint64_t)b * L + level) * C : grad + ((uint64_t)level * B + b) * C;
-    GeVec<T, C>::ld(gp, g);
-    bool any = false;
-#pragma unroll
-    for (uint32_t c = 0; c < C; c++) any |= (g[c] != 0.0f);
-    if (!any) return;
-    ge_backward_one<T, D, C>(x, g, grad_grid + (uint64_t)off0 * C, hashmap_size, lv.scale[level], lv.resolution[level],
-                             gridtype, align_corners, interp);
-}
-
-
 // ---------------------------------------------------------------------------------------------
 // Backward without scattered atomics: partition (bin) -> per-segment LDS accumulation.
 //
-// The atomic scatter above is bound by the chip's memory-side atomic unit: 64 lanes hitting 64
+// The atomic scatter (k_grid_bwd, ge_common.h) is bound by the chip's memory-side atomic unit: 64 lanes hitting 64
 // different 64-B lines run at ~20 G atomics/s whatever the schedule (MI355X_MICROARCH.md "Global
 // float atomics"; measured here: 2.1 M points x 128 atomics in 15.7 ms). This path turns the
 // scatter into streaming traffic:
@@ -533,57 +70,20 @@ template <typename T> struct GbRec;
 template <> struct GbRec<__half> { static constexpr uint32_t bytes = 8; };    // {u32 local row, half2}
 template <> struct GbRec<float> { static constexpr uint32_t bytes = 12; };    // u32 rows[] + float2 vals[]
 
-// cell and in-cell position of one (point, level): same arithmetic as ge_backward_one
-template <uint32_t D>
-__device__ __forceinline__ void gb_cell(const float (&x)[D], float scale, bool align_corners, uint32_t interp, uint32_t (&pos_grid)[D], float (&pos)[D]) {
-#pragma unroll
-    for (uint32_t d = 0; d < D; d++) {
-        pos[d] = fmaf(x[d], scale, align_corners ? 0.0f : 0.5f);
-        const float fl = floorf(pos[d]);
-        pos_grid[d] = (uint32_t)fl;
-        pos[d] -= fl;                               // == (float)pos_grid[d] for every in-range point (0 <= fl < 2^24): one conversion less per axis
-        if (interp == 1) { const float v = pos[d]; pos[d] = v * v * fmaf(-2.0f, v, 3.0f); }
-    }
-}
-template <uint32_t D>
-__device__ __forceinline__ void gb_cell_rows(const uint32_t (&pos_grid)[D], uint32_t hashmap_size, uint32_t resolution, uint32_t gridtype,
-                                             bool align_corners, uint32_t (&rows)[1u << D]) {
-#pragma unroll
-    for (uint32_t idx = 0; idx < (1u << D); idx++) {
-        uint32_t pgl[D];
-#pragma unroll
-        for (uint32_t d = 0; d < D; d++) pgl[d] = pos_grid[d] + ((idx >> d) & 1u);
-        rows[idx] = ge_index<D>(gridtype, align_corners, hashmap_size, resolution, pgl);
-    }
-}
-template <uint32_t D>
-__device__ __forceinline__ void gb_cell_weights(const float (&pos)[D], float (&ws)[1u << D]) {
-#pragma unroll
-    for (uint32_t idx = 0; idx < (1u << D); idx++) {
-        float w = 1;
-#pragma unroll
-        for (uint32_t d = 0; d < D; d++) w *= (idx & (1u << d)) ? pos[d] : 1 - pos[d];
-        ws[idx] = w;
-    }
-}
-// D = 3, two channels: the 8 trilinear weights and the 16 products pv[2 i + c] = ws[i] * g[c], corner i = bit d set -> +1 along axis d.
-__device__ __forceinline__ void gb_weighted_grads(const float (&pf)[3], float g0, float g1, float (&pv)[16]) {
+// D = 3, two channels: the 8 trilinear weights and the 16 products pv[2 i + c] = w_i * g[c], corner i = bit d set -> +1 along axis d
+// (ge_corner's weight; the rows of the corners come from ge_rows3, so its grid positions are not used).
+__device__ __forceinline__ void gb_weighted_grads(const uint32_t (&pg)[3], const float (&pf)[3], float g0, float g1, float (&pv)[16]) {
     // (packed fp32 multiplies, v_pk_mul_f32, were measured slower here: 14 packed + the moves that pair their operands vs 28 plain multiplies)
     float ws[8];
-    gb_cell_weights<3>(pf, ws);
+#pragma unroll
+    for (uint32_t i = 0; i < 8; i++) {
+        float w = 1;
+        uint32_t pgl[3];
+        ge_corner(GeDimCT<3>(), i, pf, pg, w, pgl);
+        ws[i] = w;
+    }
 #pragma unroll
     for (int i = 0; i < 8; i++) { pv[2 * i] = ws[i] * g0; pv[2 * i + 1] = ws[i] * g1; }
-}
-
-// corner rows + weights of one (point, level)
-template <uint32_t D>
-__device__ __forceinline__ void gb_corners(const float (&x)[D], uint32_t hashmap_size, float scale, uint32_t resolution, uint32_t gridtype,
-                                           bool align_corners, uint32_t interp, uint32_t (&rows)[1u << D], float (&ws)[1u << D]) {
-    float pos[D];
-    uint32_t pos_grid[D];
-    gb_cell<D>(x, scale, align_corners, interp, pos_grid, pos);
-    gb_cell_weights<D>(pos, ws);
-    gb_cell_rows<D>(pos_grid, hashmap_size, resolution, gridtype, align_corners, rows);
 }
 
 // ---- run merging (one-point-per-thread kernels) -------------------------------------------------
@@ -737,11 +237,11 @@ __device__ __forceinline__ void gb_count_tile(uint32_t *hist, uint32_t tile, uin
     for (uint32_t it = 0; it < GB_PM_TILE / THREADS; it++) {
         const uint32_t b = tile * GB_PM_TILE + it * THREADS + threadIdx.x;
         float x[3] = {0.f, 0.f, 0.f};
-        const bool inside = b < B && !ge_load_point<3>(inputs, b, x);
+        const bool inside = b < B && !ge_load_point(GeDimCT<3>(), inputs, b, x);
         for (uint32_t level = l_begin; level < l_end; level++) {
             const uint32_t resolution = lv.resolution[level];
             uint32_t pg[3]; float pf[3];
-            gb_cell<3>(x, lv.scale[level], align_corners, interp, pg, pf);
+            ge_cell(GeDimCT<3>(), x, lv.scale[level], align_corners, interp, pg, pf);
             bool emit = inside;
             if (resolution <= lv.merge_max_res) emit = gb_run_flags(inside, pg).tail;
             if (emit) {
@@ -812,11 +312,11 @@ __global__ void __launch_bounds__(256) k_grid_fwd_counted(const float *__restric
     const uint32_t b = chunk * 256 + threadIdx.x;
     if (l0 >= L || b >= B) return;
     float x[3];
-    const bool oob = ge_load_point<3>(inputs, b, x);
+    const bool oob = ge_load_point(GeDimCT<3>(), inputs, b, x);
     for (uint32_t level = l0; level < l1; level++) {
         const uint32_t off0 = (uint32_t)offsets[level];
         const uint32_t hashmap_size = (uint32_t)offsets[level + 1] - off0;
-        ge_forward_level<T, 3, 2>(x, oob, grid, off0, hashmap_size, lv.scale[level], lv.resolution[level], outputs + ((uint64_t)level * B + b) * 2,
+        ge_forward_level<T, GeDimCT<3>, 2>(GeDimCT<3>(), x, oob, grid, off0, hashmap_size, lv.scale[level], lv.resolution[level], outputs + ((uint64_t)level * B + b) * 2,
                                   (T *)nullptr, gridtype, align_corners, interp, pairs);
     }
 }
@@ -861,7 +361,7 @@ __global__ void __launch_bounds__(GB_PMS_WG, (sizeof(T) == 2 ? 8 : 4)) k_gbin_sc
     const uint32_t n_wg = n_tiles;
     const uint32_t b = tile * GB_PM_TILE + threadIdx.x;
     float x[3] = {0.f, 0.f, 0.f};
-    const bool inside = b < B && !ge_load_point<3>(inputs, b, x);
+    const bool inside = b < B && !ge_load_point(GeDimCT<3>(), inputs, b, x);
     // Gradient of the tile, one level at a time (fp16 -> one dword per point, fp32 -> two), through LDS: WAVE 0 requests the 1024 points'
     // values of level l + 1 with LDS-direct loads (global_load_lds_dword: no register destination; 16 x 64 lanes, coalesced on the
     // [L,B,C] planes of gridencoder.cu:283, one sector per lane on [B, L*C] rows) behind the first barrier of level l; everybody reads its
@@ -949,7 +449,7 @@ __global__ void __launch_bounds__(GB_PMS_WG, (sizeof(T) == 2 ? 8 : 4)) k_gbin_sc
             // 12 {row 0 | row 1, half2 v0, half2 v1}; the reduce rebuilds row 1 and both addends. One-third fewer record bytes written and
             // read back on the levels where nothing merges, four weights instead of eight, no run scan.
             uint32_t pg[3]; float pf[3];
-            gb_cell<3>(x, lv.scale[level], align_corners, interp, pg, pf);
+            ge_cell(GeDimCT<3>(), x, lv.scale[level], align_corners, interp, pg, pf);
             if (inside) {
                 const uint32_t mask = sz.size[level] - 1u;
                 const uint32_t ty0 = pg[1] * 2654435761u, ty1 = ty0 + 2654435761u, tz0 = pg[2] * 805459861u, tz1 = tz0 + 805459861u;
@@ -974,11 +474,11 @@ __global__ void __launch_bounds__(GB_PMS_WG, (sizeof(T) == 2 ? 8 : 4)) k_gbin_sc
         } else {
             const uint32_t resolution = lv.resolution[level];
             uint32_t pg[3]; float pf[3];
-            gb_cell<3>(x, lv.scale[level], align_corners, interp, pg, pf);
+            ge_cell(GeDimCT<3>(), x, lv.scale[level], align_corners, interp, pg, pf);
             uint32_t pv0[8], pv1[8];                       // record values: fp16 -> half2 bits in pv0; fp32 -> two floats
             bool emit = inside;
             float pv[16];
-            gb_weighted_grads(pf, g[0], g[1], pv);
+            gb_weighted_grads(pg, pf, g[0], g[1], pv);
             if (resolution <= lv.merge_max_res) {
                 const GbRun run = gb_run_flags(inside, pg);
                 emit = run.tail;
@@ -1366,78 +866,6 @@ __global__ void __launch_bounds__(GB_RTHREADS) k_gbin_det_finish(const GbHeader 
     (void)__builtin_amdgcn_global_atomic_fadd_v2f16((__attribute__((address_space(1))) v2h *)(dst + 2 * r), hv);
 }
 
-// gridencoder.cu:343-369: grad_inputs[b,d] = sum_{l,c} grad[l,b,c] * dy_dx[b,l,d,c]   (fp32 accumulate)
-template <typename T, uint32_t D, uint32_t C, bool GRAD_BL>
-__global__ void __launch_bounds__(256) k_grid_input_bwd(const T *__restrict__ grad, const T *__restrict__ dy_dx, T *__restrict__ grad_inputs,
-                                                        uint32_t B, uint32_t L) {
-    const uint64_t total = (uint64_t)B * D;
-    for (uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (uint64_t)gridDim.x * 256) {
-        const uint32_t b = (uint32_t)(t / D), d = (uint32_t)(t - (uint64_t)b * D);
-        float r = 0;
-        for (uint32_t l = 0; l < L; l++) {
-#pragma unroll
-            for (uint32_t c = 0; c < C; c++) {
-                const float gv = GeT<T>::ld(GRAD_BL ? grad + ((uint64_t)b * L + l) * C + c : grad + ((uint64_t)l * B + b) * C + c);
-                r = fmaf(gv, GeT<T>::ld(dy_dx + (((uint64_t)b * L + l) * D + d) * C + c), r);
-            }
-        }
-        GeT<T>::st(grad_inputs + t, r);
-    }
-}
-
-// gridencoder.cu:506-610 kernel_grad_tv
-template <typename T, uint32_t D, uint32_t C>
-__global__ void __launch_bounds__(256) k_grad_tv(const T *__restrict__ inputs, const T *__restrict__ grid, T *__restrict__ grad,
-                                                 const int32_t *__restrict__ offsets, float weight, uint32_t B, uint32_t L,
-                                                 GeLevels lv, uint32_t gridtype, bool align_corners, uint32_t chunks) {
-    uint32_t level, chunk;
-    if (!ge_decode_block(blockIdx.x, chunks, L, level, chunk)) return;
-    const uint32_t b = chunk * 256 + threadIdx.x;
-    if (b >= B) return;
-    float x[D];
-    bool oob = false;
-#pragma unroll
-    for (uint32_t d = 0; d < D; d++) { x[d] = GeT<T>::ld(inputs + (uint64_t)b * D + d); oob |= (x[d] < 0 || x[d] > 1); }
-    if (oob) return;
-    const uint32_t off0 = (uint32_t)offsets[level];
-    const uint32_t hashmap_size = (uint32_t)offsets[level + 1] - off0;
-    const float scale = lv.scale[level];
-    const uint32_t resolution = lv.resolution[level];
-    const T *tab = grid + (uint64_t)off0 * C;
-    uint32_t pos_grid[D];
-#pragma unroll
-    for (uint32_t d = 0; d < D; d++) pos_grid[d] = (uint32_t)floorf(fmaf(x[d], scale, align_corners ? 0.0f : 0.5f));
-    float results[C], idelta[C], center[C];
-#pragma unroll
-    for (uint32_t c = 0; c < C; c++) { results[c] = 0; idelta[c] = 0; }
-    const uint32_t row = ge_index<D>(gridtype, align_corners, hashmap_size, resolution, pos_grid);
-    GeVec<T, C>::ld(tab + (uint64_t)row * C, center);
-    const float w = weight / (float)(2 * D);
-#pragma unroll
-    for (uint32_t d = 0; d < D; d++) {
-        const uint32_t cur = pos_grid[d];
-        if (cur < resolution) {
-            pos_grid[d] = cur + 1;
-            float o[C];
-            GeVec<T, C>::ld(tab + (uint64_t)ge_index<D>(gridtype, align_corners, hashmap_size, resolution, pos_grid) * C, o);
-#pragma unroll
-            for (uint32_t c = 0; c < C; c++) { const float gv = center[c] - o[c]; results[c] += gv; idelta[c] = fmaf(gv, gv, idelta[c]); }
-        }
-        if (cur > 0) {
-            pos_grid[d] = cur - 1;
-            float o[C];
-            GeVec<T, C>::ld(tab + (uint64_t)ge_index<D>(gridtype, align_corners, hashmap_size, resolution, pos_grid) * C, o);
-#pragma unroll
-            for (uint32_t c = 0; c < C; c++) { const float gv = center[c] - o[c]; results[c] += gv; idelta[c] = fmaf(gv, gv, idelta[c]); }
-        }
-        pos_grid[d] = cur;
-    }
-    float v[C];
-#pragma unroll
-    for (uint32_t c = 0; c < C; c++) v[c] = w * results[c] * (1.0f / sqrtf(idelta[c] + 1e-9f));
-    GeAtomic<T>::template add<C>(grad + ((uint64_t)off0 + row) * C, v);
-}
-
 // ================================================================= host side
 // [L, B] units -> [B, L] units (a unit = the C features of one (point, level): 4 or 8 bytes). Thread = point: L coalesced plane reads,
 // one contiguous row store. Lets the public [B, L*C] op use the level-major forward kernel (0.39 vs 0.74 ms per 2 M random points).
@@ -1482,79 +910,14 @@ static int ge_make_levels(uint32_t L, float S, uint32_t H, GeLevels &lv) {
     return 0;
 }
 
-static inline uint32_t ge_xcd_grid(uint32_t chunks, uint32_t L) { return 8u * chunks * ((L + 7u) / 8u); }
-
-// Leading levels encoded by one workgroup per chunk (ge_walk): resolution <= 160 and at most L / 2 of them; fewer than two -> plain
-// walk. Measured on FOC's 16-level grid (forward + count, 2 M points): threshold 63 0.358 ms, 120 0.353, 160 0.350 (8 levels),
-// 250 without the L / 2 cap 0.353, 600 0.422, every level 0.640. FOC_GRID_FUSE_SMALL=0 switches it off.
-static uint32_t ge_small_levels(uint32_t L, const GeLevels &lv) {
-    const int on = foc_opt(FOC_OPT_GRID_FUSE_SMALL);
-    if (!on) return 0u;
-    const uint32_t finest = on > 1 ? (uint32_t)on : 160u;            // a value above 1 is taken as the resolution threshold (A/B runs)
-    const uint32_t most = L / 2;                                     // most levels in the shared group (10 / 12 / 14 / 16 of 16 measured: NOTEBOOK.md, rounds 1-4 section 9)
-    uint32_t lc = 0;
-    while (lc < most && lc < L && lv.resolution[lc] <= finest) lc++;
-    return lc >= 2u ? lc : 0u;
-}
-
-// FOC_GRID_PAIRS=0: one 4-byte load per corner (A/B runs). 16-byte groups of 4 rows (which would also cover x = 1 mod 4 on a hashed
-// level) were measured SLOWER: 0.064 vs 0.052 ms per 2 M random points and level — the 16-byte gather is not free like the 8-byte one.
-static bool ge_pairs_enabled() {
-    return foc_opt(FOC_OPT_GRID_PAIRS) != 0;
-}
-// The `pairs` argument of the level-major forward kernels: 0 = one load per corner, 1 = row pairs, 2 = row pairs and the call is of the
-// shape ge_forward_hash3 serves (the per-level part of that decision is taken in the kernel). FOC_GRID_FAST=0: never 2 (A/B runs).
-static uint32_t ge_pairs_mode(const void *emb, const void *dy_dx, size_t elem, uint32_t D, uint32_t C, uint32_t gridtype, bool ac, uint32_t interp) {
-    const int fast = foc_opt(FOC_OPT_GRID_FAST);
-    if (!ge_pairs_enabled() || ((uintptr_t)emb & 7u) != 0u || dy_dx) return 0u;
-    return (fast && elem == 2 && D == 3 && C == 2 && gridtype == 0u && !ac && interp == 0u) ? 2u : 1u;
-}
-
-template <typename T, uint32_t D, uint32_t C>
-static int ge_forward_launch(const float *inputs, const void *emb, const int32_t *offsets, void *outputs, uint32_t B, uint32_t L,
-                             const GeLevels &lv, void *dy_dx, uint32_t gridtype, bool ac, uint32_t interp, bool bl, hipStream_t st) {
-    const int lm_plain = 1;                      // blocks numbered level by level: the whole chip walks one level at a time (pinning a level to one XCD balanced badly)
-    if (bl) {
-        const uint64_t total = (uint64_t)B * L;
-        const uint32_t grid = (uint32_t)((total + 255) / 256 > 0x7FFFFFFFull ? 0x7FFFFFFFull : (total + 255) / 256);
-        hipLaunchKernelGGL((k_grid_fwd_bl<T, D, C>), dim3(grid), dim3(256), 0, st, inputs, (const T *)emb, offsets, (T *)outputs, B, L, lv,
-                           (T *)dy_dx, gridtype, ac, interp);
-    } else {
-        const uint32_t chunks = foc_div_up(B, 256);
-        const uint32_t lc = lm_plain ? ge_small_levels(L, lv) : 0u;
-        const uint32_t groups = lc >= 2u ? L - lc + 1u : L;
-        // FOC_GRID_FWD_LDS=<bytes>: unused dynamic LDS per workgroup — caps the resident workgroups per CU (occupancy experiments: what the
-        // forward's gathers cost with fewer waves in flight, NOTEBOOK.md, rounds 1-4 section 9)
-        const int pad_lds = 0;
-        hipLaunchKernelGGL((k_grid_fwd_lbc<T, D, C>), dim3(lm_plain ? chunks * groups : ge_xcd_grid(chunks, L)), dim3(256), (size_t)pad_lds, st, inputs, (const T *)emb, offsets,
-                           (T *)outputs, B, L, lv, (T *)dy_dx, gridtype, ac, interp, chunks, (uint32_t)lm_plain,
-                           ge_pairs_mode(emb, dy_dx, sizeof(T), D, C, gridtype, ac, interp), lc);
-    }
-    FOC_CHECK_LAUNCH("grid_encode_forward");
-    return FOC_OK;
-}
-
-template <typename T, uint32_t D>
-static int ge_forward_c(uint32_t C, const float *inputs, const void *emb, const int32_t *offsets, void *outputs, uint32_t B, uint32_t L,
-                        const GeLevels &lv, void *dy_dx, uint32_t gridtype, bool ac, uint32_t interp, bool bl, hipStream_t st) {
-    switch (C) {
-        case 1: return ge_forward_launch<T, D, 1>(inputs, emb, offsets, outputs, B, L, lv, dy_dx, gridtype, ac, interp, bl, st);
-        case 2: return ge_forward_launch<T, D, 2>(inputs, emb, offsets, outputs, B, L, lv, dy_dx, gridtype, ac, interp, bl, st);
-        case 4: return ge_forward_launch<T, D, 4>(inputs, emb, offsets, outputs, B, L, lv, dy_dx, gridtype, ac, interp, bl, st);
-        case 8: return ge_forward_launch<T, D, 8>(inputs, emb, offsets, outputs, B, L, lv, dy_dx, gridtype, ac, interp, bl, st);
-        default: foc_set_error("GridEncoding: C must be 1, 2, 4, or 8."); return FOC_E_INVALID;   // gridencoder.cu:381
-    }
-}
-
-template <typename T>
-static int ge_forward_d(uint32_t D, uint32_t C, const float *inputs, const void *emb, const int32_t *offsets, void *outputs, uint32_t B,
-                        uint32_t L, const GeLevels &lv, void *dy_dx, uint32_t gridtype, bool ac, uint32_t interp, bool bl, hipStream_t st) {
-    switch (D) {
-        case 2: return ge_forward_c<T, 2>(C, inputs, emb, offsets, outputs, B, L, lv, dy_dx, gridtype, ac, interp, bl, st);
-        case 3: return ge_forward_c<T, 3>(C, inputs, emb, offsets, outputs, B, L, lv, dy_dx, gridtype, ac, interp, bl, st);
-        case 4: case 5:                                    // gridencoder.cu:393-398: runtime-D kernels (gridencoder_nd.hip)
-            return ge_nd_forward(sizeof(T) == 2 ? FOC_F16 : FOC_F32, D, C, inputs, emb, offsets, outputs, B, L, lv, dy_dx, gridtype, ac, interp, bl, st);
-        default: foc_set_error("GridEncoding: D must be 2, 3, 4 or 5 (got %u)", D); return FOC_E_INVALID;
+// (dtype, D, C) of a call -> its launch (gridencoder.cu:393-398, 437-442, 633-638). D is refused first, then C (ge_dispatch), both
+// on the host before anything is launched.
+static int ge_call(GeOp op, const GeCall &a) {
+    switch (a.D) {
+        case 2: return ge_dispatch<GeDimCT<2>>(op, a);
+        case 3: return ge_dispatch<GeDimCT<3>>(op, a);
+        case 4: case 5: return ge_nd_dispatch(op, a);          // the runtime-D instances (gridencoder_nd.hip)
+        default: foc_set_error("GridEncoding: D must be 2, 3, 4 or 5 (got %u)", a.D); return FOC_E_INVALID;
     }
 }
 
@@ -1566,66 +929,11 @@ static int ge_forward(const float *inputs, const void *embeddings, const int32_t
     FOC_REQUIRE(dtype == FOC_F32 || dtype == FOC_F16, FOC_E_DTYPE, "grid_encode_forward: dtype must be FOC_F32 or FOC_F16");
     FOC_REQUIRE(L >= 1 && L <= GE_MAX_LEVELS, FOC_E_INVALID, "grid_encode_forward: L must be in [1,%d]", GE_MAX_LEVELS);
     FOC_REQUIRE(gridtype <= 1 && interp <= 1, FOC_E_INVALID, "grid_encode_forward: bad gridtype/interp");
-    if (B == 0) return FOC_OK;
-    GeLevels lv;
-    ge_make_levels(L, S, H, lv);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == FOC_F32) return ge_forward_d<float>(D, C, inputs, embeddings, offsets, outputs, B, L, lv, dy_dx, gridtype, align_corners != 0, interp, bl, st);
-    return ge_forward_d<__half>(D, C, inputs, embeddings, offsets, outputs, B, L, lv, dy_dx, gridtype, align_corners != 0, interp, bl, st);
-}
-
-template <typename T, uint32_t D, uint32_t C>
-static int ge_backward_launch(const void *grad, const float *inputs, const int32_t *offsets, void *grad_emb, uint32_t B, uint32_t L,
-                              const GeLevels &lv, const void *dy_dx, void *grad_inputs, uint32_t gridtype, bool ac, uint32_t interp,
-                              bool bl, hipStream_t st) {
-    const uint32_t chunks = foc_div_up(B, 256);
-    if (bl) hipLaunchKernelGGL((k_grid_bwd<T, D, C, true>), dim3(ge_xcd_grid(chunks, L)), dim3(256), 0, st, (const T *)grad, inputs, offsets,
-                               (T *)grad_emb, B, L, lv, gridtype, ac, interp, chunks);
-    else hipLaunchKernelGGL((k_grid_bwd<T, D, C, false>), dim3(ge_xcd_grid(chunks, L)), dim3(256), 0, st, (const T *)grad, inputs, offsets,
-                            (T *)grad_emb, B, L, lv, gridtype, ac, interp, chunks);
-    FOC_CHECK_LAUNCH("grid_encode_backward");
-    if (dy_dx && grad_inputs) {
-        const uint32_t g = foc_grid_1d((uint64_t)B * D, 256);
-        if (bl) hipLaunchKernelGGL((k_grid_input_bwd<T, D, C, true>), dim3(g), dim3(256), 0, st, (const T *)grad, (const T *)dy_dx, (T *)grad_inputs, B, L);
-        else hipLaunchKernelGGL((k_grid_input_bwd<T, D, C, false>), dim3(g), dim3(256), 0, st, (const T *)grad, (const T *)dy_dx, (T *)grad_inputs, B, L);
-        FOC_CHECK_LAUNCH("grid_encode_backward(inputs)");
-    }
-    return FOC_OK;
-}
-
-template <typename T, uint32_t D>
-static int ge_backward_c(uint32_t C, const void *grad, const float *inputs, const int32_t *offsets, void *grad_emb, uint32_t B, uint32_t L,
-                         const GeLevels &lv, const void *dy_dx, void *grad_inputs, uint32_t gridtype, bool ac, uint32_t interp, bool bl,
-                         hipStream_t st) {
-    switch (C) {
-        case 1: return ge_backward_launch<T, D, 1>(grad, inputs, offsets, grad_emb, B, L, lv, dy_dx, grad_inputs, gridtype, ac, interp, bl, st);
-        case 2: return ge_backward_launch<T, D, 2>(grad, inputs, offsets, grad_emb, B, L, lv, dy_dx, grad_inputs, gridtype, ac, interp, bl, st);
-        case 4: return ge_backward_launch<T, D, 4>(grad, inputs, offsets, grad_emb, B, L, lv, dy_dx, grad_inputs, gridtype, ac, interp, bl, st);
-        case 8: return ge_backward_launch<T, D, 8>(grad, inputs, offsets, grad_emb, B, L, lv, dy_dx, grad_inputs, gridtype, ac, interp, bl, st);
-        default: foc_set_error("GridEncoding: C must be 1, 2, 4, or 8."); return FOC_E_INVALID;
-    }
-}
-
-template <typename T, uint32_t D, uint32_t C>
-static int ge_tv_launch(const void *inputs, const void *emb, void *grad, const int32_t *offsets, float weight, uint32_t B, uint32_t L,
-                        const GeLevels &lv, uint32_t gridtype, bool ac, hipStream_t st) {
-    const uint32_t chunks = foc_div_up(B, 256);
-    hipLaunchKernelGGL((k_grad_tv<T, D, C>), dim3(ge_xcd_grid(chunks, L)), dim3(256), 0, st, (const T *)inputs, (const T *)emb, (T *)grad, offsets,
-                       weight, B, L, lv, gridtype, ac, chunks);
-    FOC_CHECK_LAUNCH("grad_total_variation");
-    return FOC_OK;
-}
-
-template <typename T, uint32_t D>
-static int ge_tv_c(uint32_t C, const void *inputs, const void *emb, void *grad, const int32_t *offsets, float weight, uint32_t B, uint32_t L,
-                   const GeLevels &lv, uint32_t gridtype, bool ac, hipStream_t st) {
-    switch (C) {
-        case 1: return ge_tv_launch<T, D, 1>(inputs, emb, grad, offsets, weight, B, L, lv, gridtype, ac, st);
-        case 2: return ge_tv_launch<T, D, 2>(inputs, emb, grad, offsets, weight, B, L, lv, gridtype, ac, st);
-        case 4: return ge_tv_launch<T, D, 4>(inputs, emb, grad, offsets, weight, B, L, lv, gridtype, ac, st);
-        case 8: return ge_tv_launch<T, D, 8>(inputs, emb, grad, offsets, weight, B, L, lv, gridtype, ac, st);
-        default: foc_set_error("GridEncoding: C must be 1, 2, 4, or 8."); return FOC_E_INVALID;
-    }
+    GeCall a = {};
+    a.dtype = dtype; a.D = D; a.C = C; a.B = B; a.L = L; a.gridtype = gridtype; a.interp = interp; a.ac = align_corners != 0; a.bl = bl;
+    a.inputs = inputs; a.emb = embeddings; a.offsets = offsets; a.out = outputs; a.dy_dx = dy_dx; a.st = (hipStream_t)stream;
+    ge_make_levels(L, S, H, a.lv);
+    return ge_call(GE_FORWARD, a);
 }
 
 
@@ -1845,26 +1153,12 @@ int foc_grid_encode_backward(const void *grad, const float *inputs, const void *
     FOC_REQUIRE(gridtype <= 1 && interp <= 1, FOC_E_INVALID, "grid_encode_backward: bad gridtype/interp");
     FOC_REQUIRE(!foc_opt(FOC_OPT_DETERMINISTIC), FOC_E_INVALID, "grid_encode_backward: FOC_DETERMINISTIC is set and this entry point scatters with float atomics "
                 "(arrival order); deterministic mode serves fp16 hash grids with D=3, C=2 through foc_grid_encode_backward_binned");
-    if (B == 0) return FOC_OK;
-    GeLevels lv;
-    ge_make_levels(L, S, H, lv);
-    hipStream_t st = (hipStream_t)stream;
-    const bool ac = align_corners != 0, bl = grad_is_bl != 0;
-    if (dtype == FOC_F32) {
-        switch (D) {
-            case 2: return ge_backward_c<float, 2>(C, grad, inputs, offsets, grad_embeddings, B, L, lv, dy_dx, grad_inputs, gridtype, ac, interp, bl, st);
-            case 3: return ge_backward_c<float, 3>(C, grad, inputs, offsets, grad_embeddings, B, L, lv, dy_dx, grad_inputs, gridtype, ac, interp, bl, st);
-        }
-    } else {
-        switch (D) {
-            case 2: return ge_backward_c<__half, 2>(C, grad, inputs, offsets, grad_embeddings, B, L, lv, dy_dx, grad_inputs, gridtype, ac, interp, bl, st);
-            case 3: return ge_backward_c<__half, 3>(C, grad, inputs, offsets, grad_embeddings, B, L, lv, dy_dx, grad_inputs, gridtype, ac, interp, bl, st);
-        }
-    }
-    if (D == 4 || D == 5)                                      // gridencoder.cu:437-442
-        return ge_nd_backward(dtype, D, C, grad, inputs, offsets, grad_embeddings, B, L, lv, dy_dx, grad_inputs, gridtype, ac, interp, bl, st);
-    foc_set_error("GridEncoding: D must be 2, 3, 4 or 5 (got %u)", D);
-    return FOC_E_INVALID;
+    GeCall a = {};
+    a.dtype = dtype; a.D = D; a.C = C; a.B = B; a.L = L; a.gridtype = gridtype; a.interp = interp; a.ac = align_corners != 0; a.bl = grad_is_bl != 0;
+    a.inputs = inputs; a.offsets = offsets; a.out = grad_embeddings; a.grad = grad; a.dy_dx = const_cast<void *>(dy_dx); a.grad_inputs = grad_inputs;
+    a.st = (hipStream_t)stream;
+    ge_make_levels(L, S, H, a.lv);
+    return ge_call(GE_BACKWARD, a);
 }
 
 uint64_t foc_grid_encode_backward_workspace_bytes(uint32_t B, uint32_t D, uint32_t C, uint32_t L, int dtype) {
@@ -1949,17 +1243,9 @@ static int gb_entry(const void *grad, const float *inputs, const int32_t *offset
     int rc = dtype == FOC_F32 ? gb_run<float>(grad, inputs, offsets, grad_embeddings, B, L, lv, gridtype, ac, interp, bl, workspace, counted, 0u, sz, 0, st)
                               : gb_run<__half>(grad, inputs, offsets, grad_embeddings, B, L, lv, gridtype, ac, interp, bl, workspace, counted, fact_mask, sz, det, st);
     if (rc) return rc;
-    if (dy_dx && grad_inputs) {
-        const uint32_t g = foc_grid_1d((uint64_t)B * 3, 256);
-        if (dtype == FOC_F32) {
-            if (bl) hipLaunchKernelGGL((k_grid_input_bwd<float, 3, 2, true>), dim3(g), dim3(256), 0, st, (const float *)grad, (const float *)dy_dx, (float *)grad_inputs, B, L);
-            else hipLaunchKernelGGL((k_grid_input_bwd<float, 3, 2, false>), dim3(g), dim3(256), 0, st, (const float *)grad, (const float *)dy_dx, (float *)grad_inputs, B, L);
-        } else {
-            if (bl) hipLaunchKernelGGL((k_grid_input_bwd<__half, 3, 2, true>), dim3(g), dim3(256), 0, st, (const __half *)grad, (const __half *)dy_dx, (__half *)grad_inputs, B, L);
-            else hipLaunchKernelGGL((k_grid_input_bwd<__half, 3, 2, false>), dim3(g), dim3(256), 0, st, (const __half *)grad, (const __half *)dy_dx, (__half *)grad_inputs, B, L);
-        }
-        FOC_CHECK_LAUNCH("grid_encode_backward(inputs)");
-    }
+    if (dy_dx && grad_inputs)
+        return dtype == FOC_F32 ? ge_input_backward_launch<float, GeDimCT<3>, 2>(grad, dy_dx, grad_inputs, B, 3u, L, bl, st)
+                                : ge_input_backward_launch<__half, GeDimCT<3>, 2>(grad, dy_dx, grad_inputs, B, 3u, L, bl, st);
     return FOC_OK;
 }
 
@@ -1992,25 +1278,11 @@ int foc_grad_total_variation(const void *inputs, const void *embeddings, void *g
     FOC_REQUIRE(dtype == FOC_F32 || dtype == FOC_F16, FOC_E_DTYPE, "grad_total_variation: dtype must be FOC_F32 or FOC_F16");
     FOC_REQUIRE(L >= 1 && L <= GE_MAX_LEVELS, FOC_E_INVALID, "grad_total_variation: L must be in [1,%d]", GE_MAX_LEVELS);
     FOC_REQUIRE(!foc_opt(FOC_OPT_DETERMINISTIC), FOC_E_INVALID, "grad_total_variation: FOC_DETERMINISTIC is set and this entry point scatters with float atomics (arrival order)");
-    if (B == 0) return FOC_OK;
-    GeLevels lv;
-    ge_make_levels(L, S, H, lv);
-    hipStream_t st = (hipStream_t)stream;
-    const bool ac = align_corners != 0;
-    if (dtype == FOC_F32) {
-        switch (D) {
-            case 2: return ge_tv_c<float, 2>(C, inputs, embeddings, grad, offsets, weight, B, L, lv, gridtype, ac, st);
-            case 3: return ge_tv_c<float, 3>(C, inputs, embeddings, grad, offsets, weight, B, L, lv, gridtype, ac, st);
-        }
-    } else {
-        switch (D) {
-            case 2: return ge_tv_c<__half, 2>(C, inputs, embeddings, grad, offsets, weight, B, L, lv, gridtype, ac, st);
-            case 3: return ge_tv_c<__half, 3>(C, inputs, embeddings, grad, offsets, weight, B, L, lv, gridtype, ac, st);
-        }
-    }
-    if (D == 4 || D == 5) return ge_nd_tv(dtype, D, C, inputs, embeddings, grad, offsets, weight, B, L, lv, gridtype, ac, st);      // gridencoder.cu:633-638
-    foc_set_error("GridEncoding: D must be 2, 3, 4 or 5 (got %u)", D);
-    return FOC_E_INVALID;
+    GeCall a = {};
+    a.dtype = dtype; a.D = D; a.C = C; a.B = B; a.L = L; a.gridtype = gridtype; a.ac = align_corners != 0;
+    a.inputs = inputs; a.emb = embeddings; a.offsets = offsets; a.out = grad; a.weight = weight; a.st = (hipStream_t)stream;
+    ge_make_levels(L, S, H, a.lv);
+    return ge_call(GE_TV, a);
 }
 
 } // extern "C"

@@ -1,5 +1,5 @@
-"""Float64 reference of the hash-grid encoder's backward (csrc/gridencoder.hip k_grid_bwd and the binned family k_gbin_count_pt ->
-k_gbin_scans -> k_gbin_scatter_pms -> k_gbin_reduce -> k_gbin_det_finish; csrc/gridencoder_nd.hip for D = 4, 5), a bound per table element
+"""Float64 reference of the hash-grid encoder's backward (csrc/ge_common.h k_grid_bwd, one kernel for D = 2..5, and the binned family of
+csrc/gridencoder.hip k_gbin_count_pt -> k_gbin_scans -> k_gbin_scatter_pms -> k_gbin_reduce -> k_gbin_det_finish), a bound per table element
 for every route a call can take, the cases, and a numpy fp32 / fp16 model of each route with deliberately wrong variants (MUTANTS).
 
     grad_embeddings[row, c] = sum over the in-range points b, levels l and the 2^D corners k of the cell whose row is `row`:  w_k(b, l) * grad[l, b, c]

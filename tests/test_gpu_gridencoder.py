@@ -46,11 +46,15 @@ CASES = [
     (3, 4, 8, 16, 15, 512, 1, False, 0),        # tiled
     (3, 8, 4, 8, 14, 128, 0, True, 1),          # align_corners + smoothstep
     (2, 2, 12, 16, 17, 2048, 0, False, 1),
-    # D = 4, 5 (gridencoder.cu:393-398: the reference dispatches D in {2,3,4,5}): runtime-D kernels, csrc/gridencoder_nd.hip
+    # D = 4, 5 (gridencoder.cu:393-398: the reference dispatches D in {2,3,4,5}): the general kernels of csrc/ge_common.h with D a runtime value (csrc/gridencoder_nd.hip)
     (4, 2, 8, 8, 14, 64, 0, False, 0),
     (4, 4, 5, 4, 12, 20, 1, True, 1),           # tiled, align_corners, smoothstep
     (5, 2, 6, 4, 13, 24, 0, False, 0),
     (5, 1, 4, 4, 12, 12, 0, False, 1),
+    # a tenth entry is B. L = 9: level 8 falls into the second group of eight block slots of the backward's and grad_tv's level decode and
+    # leaves seven slots idle; B = 257: a second chunk with one live thread
+    (4, 2, 9, 4, 12, 32, 0, False, 0, 257),
+    (5, 2, 9, 4, 12, 32, 0, False, 0, 257),
 ]
 CASES_BWD = CASES[:5] + CASES[6:]
 
@@ -58,9 +62,8 @@ CASES_BWD = CASES[:5] + CASES[6:]
 @pytest.mark.parametrize("case", CASES)
 @pytest.mark.parametrize("dtype", [np.float32, np.float16])
 def test_forward_bit_exact(case, dtype):
-    D, C, L, H, lh, desired, gridtype, ac, interp = case
+    D, C, L, H, lh, desired, gridtype, ac, interp, B = case if len(case) == 10 else case + (5000,)
     pls, S, off, table = _setup(D, C, L, H, lh, desired, 1, dtype, align_corners=ac)
-    B = 5000
     x = _points(B, D, 2)
     ref, ref_dy = oracle.grid_encode_forward(x, table, off, D, C, L, S, H, True, gridtype, ac, interp, acc_mode=1)
     tdt = torch.float32 if dtype == np.float32 else torch.float16
@@ -94,9 +97,8 @@ def test_forward_bit_exact(case, dtype):
 @pytest.mark.parametrize("atomic", ["0", "1"])      # 0: partition + LDS accumulation (D=3,C=2), 1: scattered-atomic kernel
 def test_backward(case, dtype, atomic, monkeypatch):
     monkeypatch.setenv("FOCNERF_GRID_ATOMIC", atomic)
-    D, C, L, H, lh, desired, gridtype, ac, interp = case
+    D, C, L, H, lh, desired, gridtype, ac, interp, B = case if len(case) == 10 else case + (4000,)
     pls, S, off, table = _setup(D, C, L, H, lh, desired, 3, dtype, align_corners=ac)
-    B = 4000
     x = _points(B, D, 4)
     rng = np.random.default_rng(9)
     grad = (rng.standard_normal((L, B, C)) * 0.1).astype(dtype)
@@ -285,6 +287,28 @@ def test_module_and_total_variation_in_four_and_five_dimensions(D):
     enc.grad_total_variation(weight=1e-2, inputs=x.detach(), bound=1)
     tv = oracle.grad_total_variation(xn, to_np(enc.embeddings), np.zeros_like(to_np(enc.embeddings)), to_np(enc.offsets), 1e-2, D, 2, 6, S, 4)
     np.testing.assert_allclose(to_np(enc.embeddings.grad), tv, atol=1e-6, rtol=1e-4)
+
+
+@pytest.mark.parametrize("case", CASES[-2:])
+@pytest.mark.parametrize("dtype", [np.float32, np.float16])
+def test_total_variation_on_the_ninth_level_and_in_a_chunk_of_one_point(case, dtype):
+    """grad_total_variation on the two L = 9, B = 257 cases of CASES (level 8 sits in the second group of eight block slots of the level
+    decode, point 256 is the one live thread of a second chunk), against the oracle: fp32 with the bound of the D = 4 / 5 test above,
+    fp16 (packed half atomics, order dependent) with the bound of test_backward's atomic kernel."""
+    D, C, L, H, lh, desired, gridtype, ac, interp, B = case
+    pls, S, off, table = _setup(D, C, L, H, lh, desired, 30 + D, dtype)
+    x = _points(B, D, 31 + D)
+    x[B - 1] = 0.37                                      # the one point of the second chunk, in range
+    xin = x.astype(dtype)                                # grad_total_variation takes the positions in the table dtype
+    tv_ref = oracle.grad_total_variation(xin, table, np.zeros_like(table), off, 1e-2, D, C, L, S, H).astype(np.float32)
+    tv = torch.zeros(int(off[-1]), C, dtype=torch.float32 if dtype == np.float32 else torch.float16, device="cuda")
+    _be().grad_total_variation(torch.from_numpy(xin).cuda(), torch.from_numpy(table).cuda(), tv, torch.from_numpy(off).cuda(), 1e-2, B, D, C, L, S, H, gridtype, ac)
+    got = to_np(tv).astype(np.float32)
+    if dtype == np.float32:
+        np.testing.assert_allclose(got, tv_ref, atol=1e-6, rtol=1e-4)
+    else:
+        assert np.abs(got - tv_ref).max() <= 2e-2 * np.abs(tv_ref).max() + 1e-3
+    assert np.abs(got[off[8]:off[9]]).sum() > 0          # level 8 received its gradient
 
 
 def test_full_batch_properties():

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """tools/output_digest.py [out.json] [--sections a,b] [--root DIR]: sha256 of every output of the per-sample, ragged-composite, fixed-step,
-combine and marching kernels on seeded inputs, and of the occupancy node driven from Python, as one JSON object {case: {output: digest}} — the bits
+combine, marching and grid-encoder kernels on seeded inputs, and of the occupancy node driven from Python, as one JSON object {case: {output: digest}} — the bits
 of one build — printed, or written to out.json with a one-line summary printed instead. Run it once per build on the same GPU
 (FOCNERF_LIB_PATH selects the library) and compare the two objects: equal = the same bits on every case.
---sections: of per_sample, ragged, fixed, combine, march, node (default: all). --root DIR: the checkout whose focnerf_amd package (and library)
+--sections: of per_sample, ragged, fixed, combine, march, grid, node (default: all). --root DIR: the checkout whose focnerf_amd package (and library)
 is imported instead of this one's — the `node` section runs the package's Python, so one copy of this tool serves both commits of a
 comparison.
 
@@ -28,6 +28,14 @@ pad_align 0 and 128 and with the box or the ranges given. The inference march (m
 foc_march_rays at n_step 1, 3, 8, 16 with the row form off and on, foc_march_rays_two_phase at n_step 1, 2, 4, 8, 16 in its four forms with
 flags 0, 1, 3 and (where the form writes sample-major arrays) 7. foc_composite_rays at n_step 1, 2, 3, 4, 8, 16, foc_composite_compact at 2, 4
 and 8 in both layouts with and without a deaths histogram, T_thresh 1e-4 and 0.5. foc_compact_alive at 1, 1023, 1025 and 2100 entries.
+
+`grid` (gridencoder.hip, gridencoder_nd.hip through the C ABI): forward [L,B,C] and [B, L*C], dy_dx and grad_inputs — the outputs no atomic
+touches — for D 2..5, C 1, 2, 4, 8 (fp16 tables: even C), both dtypes, hash and tiled grids, align_corners off and on, linear and
+smoothstep interpolation, L 1, 3, 9 and B 1, 257, 600, the points with exact 0 and 1 and a few outside [0, 1]. The atomically summed
+outputs only where arrival order cannot matter, which the tool asserts in float64 before it hashes: grad_embeddings of one level with
+H = 9 (scale 8), align_corners on, positions on multiples of 1/16 and small-integer gradients — every addend a multiple of 2^-5 and
+the sum of |addends| per table element below 2^6, so fp16 and fp32 adds are exact in any order; grad_total_variation on one tiled level
+with every point in a cell and a row of its own (one add onto zero per row).
 
 Left out: the gradient of the background model's table (foc_background_backward: fp32 atomics, not bit-stable run to run in the default
 mode) and with it the whole background backward; the forward is covered. Every input is drawn on the host from a seeded generator.
@@ -56,7 +64,7 @@ def _option(name):
 
 
 ROOT = _option("--root") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-ALL_SECTIONS = ("per_sample", "ragged", "fixed", "combine", "march", "node")
+ALL_SECTIONS = ("per_sample", "ragged", "fixed", "combine", "march", "grid", "node")
 SECTIONS = (_option("--sections") or ",".join(ALL_SECTIONS)).split(",")
 if set(SECTIONS) - set(ALL_SECTIONS):
     sys.exit(f"usage: output_digest.py [out.json] [--sections a,b] [--root DIR]: sections are {', '.join(ALL_SECTIONS)}, got {', '.join(SECTIONS)}")
@@ -415,6 +423,118 @@ def march():
         set_option(name, value)
 
 
+# ---------------------------------------------------------------- grid encoder (gridencoder.hip, gridencoder_nd.hip)
+GRID_PRIMES = np.array([1, 2654435761, 805459861, 3674653429, 2097192037], np.uint64)
+
+
+def grid_rows(cells, size, stride1, gridtype):
+    """Row of every cell tuple [N, D] on a level of `size` rows — gridencoder.cu:50-84 in uint32 arithmetic."""
+    m = np.uint64(0xFFFFFFFF)
+    cells = cells.astype(np.uint64)
+    index, stride = np.zeros(len(cells), np.uint64), 1
+    for d in range(cells.shape[1]):
+        if stride <= size:
+            index = (index + cells[:, d] * np.uint64(stride)) & m
+            stride = (stride * stride1) & 0xFFFFFFFF
+    if gridtype == 0 and stride > size:
+        index = np.zeros(len(cells), np.uint64)
+        for d in range(cells.shape[1]):
+            index ^= (cells[:, d] * GRID_PRIMES[d]) & m
+    return (index % np.uint64(size)).astype(np.int64)
+
+
+def grid_dtypes(C):
+    return [(torch.float32, 0)] + ([(torch.float16, 1)] if C % 2 == 0 else [])
+
+
+def grid_general():
+    from focnerf_amd.gridencoder import level_offsets
+    pls, H, log2_hash = 1.5, 4, 11
+    S = float(np.log2(pls))
+    for D in (2, 3, 4, 5):
+        for L in (1, 3, 9):
+            for ac in (False, True):
+                off = level_offsets(D, L, pls, H, log2_hash, ac)
+                d_off = cuda(off)
+                for B in (1, 257, 600):
+                    rng = np.random.default_rng(100 * D + 10 * L + B)
+                    x = rng.random((B, D)).astype(np.float32)
+                    if B > 8:
+                        x[0], x[1], x[4] = 0.0, 1.0, np.float32(1.0) - np.float32(1e-7)
+                        x[2, 0], x[3, D - 1], x[B - 2, 0] = -0.01, 1.0001, 2.5
+                    d_x = cuda(x)
+                    for C in (1, 2, 4, 8):
+                        table = rng.uniform(-1, 1, (int(off[-1]), C)).astype(np.float32)
+                        grad = (rng.standard_normal((L, B, C)) * 0.1).astype(np.float32)
+                        for tdt, code in grid_dtypes(C):
+                            d_t, d_g = cuda(table).to(tdt), cuda(grad).to(tdt)
+                            d_g_bl = d_g.permute(1, 0, 2).reshape(B, L * C).contiguous()
+                            for gridtype in (0, 1):
+                                for interp in (0, 1):
+                                    out, out_bl, dy = full((L, B, C), tdt), full((B, L * C), tdt), full((B, L * D * C), tdt)
+                                    call(lib.foc_grid_encode_forward, ptr(d_x), ptr(d_t), ptr(d_off), ptr(out), B, D, C, L, S, H, ptr(dy), gridtype, int(ac), interp, code, None)
+                                    call(lib.foc_grid_encode_forward_bl, ptr(d_x), ptr(d_t), ptr(d_off), ptr(out_bl), B, D, C, L, S, H, None, gridtype, int(ac), interp, code, None)
+                                    dy_bl = full((B, L * D * C), tdt)
+                                    call(lib.foc_grid_encode_forward_bl, ptr(d_x), ptr(d_t), ptr(d_off), ptr(out_bl), B, D, C, L, S, H, ptr(dy_bl), gridtype, int(ac), interp, code, None)
+                                    res = dict(out=out, out_bl=out_bl, dy_dx=dy, dy_dx_bl=dy_bl)
+                                    for bl, g in ((0, d_g), (1, d_g_bl)):
+                                        ge, gi = torch.zeros(int(off[-1]), C, dtype=tdt, device="cuda"), full((B, D), tdt)
+                                        call(lib.foc_grid_encode_backward, ptr(g), ptr(d_x), ptr(d_t), ptr(d_off), ptr(ge), B, D, C, L, S, H, ptr(dy), ptr(gi), gridtype, int(ac),
+                                             interp, code, bl, None)
+                                        res[f"grad_inputs[bl={bl}]"] = gi
+                                    put(f"grid[D={D},C={C},L={L},B={B},{'f16' if code else 'f32'},gridtype={gridtype},ac={ac},interp={interp}]", **res)
+
+
+def grid_exact_sums():
+    from focnerf_amd.gridencoder import level_offsets
+    H, B = 9, 257                                         # one level: scale = 2^0 * 9 - 1 = 8, resolution 9
+    for D in (2, 3, 4, 5):
+        rng = np.random.default_rng(500 + D)
+        # backward: align_corners on, positions on multiples of 1/16 -> in-cell fractions 0 or 0.5, weights multiples of 2^-D
+        off = level_offsets(D, 1, 1.0, H, 16, True)
+        size = int(off[1])
+        x = (rng.integers(0, 17, (B, D)) / 16.0).astype(np.float32)
+        pos = x.astype(np.float64) * 8.0
+        cell, frac = np.floor(pos), pos - np.floor(pos)
+        for C in (1, 2, 4, 8):
+            grad = rng.integers(-2, 3, (1, B, C)).astype(np.float32)
+            load = np.zeros((size, C))                    # sum of |addends| per table element, float64
+            for idx in range(1 << D):
+                up = (idx >> np.arange(D)) & 1
+                w = np.prod(np.where(up, frac, 1.0 - frac), axis=1)
+                assert np.all(w * 32 == np.round(w * 32))                          # every addend a multiple of 2^-5
+                np.add.at(load, grid_rows(cell + up, size, H, 0), np.abs(w[:, None] * grad[0]))
+            assert load.max() < 64.0, load.max()                                   # below 2^6: fp16 / fp32 adds are exact in any order
+            for tdt, code in grid_dtypes(C):
+                d_g = cuda(grad).to(tdt)
+                for bl, g in ((0, d_g), (1, d_g.permute(1, 0, 2).reshape(B, C).contiguous())):
+                    ge = torch.zeros(size, C, dtype=tdt, device="cuda")
+                    call(lib.foc_grid_encode_backward, ptr(g), ptr(cuda(x)), None, ptr(cuda(off)), ptr(ge), B, D, C, 1, 0.0, H, None, None, 0, 1, 0, code, bl, None)
+                    put(f"grid_backward_exact[D={D},C={C},{'f16' if code else 'f32'},bl={bl}]", grad_embeddings=ge)
+        # grad_total_variation: a tiled level, align_corners off, every point in a cell and a row of its own
+        off = level_offsets(D, 1, 1.0, H, 16, False)
+        size = int(off[1])
+        n = min(200, 8 ** D // 2)
+        flat = rng.permutation(8 ** D)[:n]
+        cell = 1 + np.stack([(flat // 8 ** d) % 8 for d in range(D)], axis=1)       # cells 1..8 per axis
+        xs = ((cell - 0.25) / 8.0).astype(np.float32)                               # floor(x * 8 + 0.5) = cell; exact in fp16
+        rows = grid_rows(cell, size, H + 1, 1)
+        assert len(np.unique(cell, axis=0)) == n and len(np.unique(rows)) == n
+        for C in (1, 2, 4, 8):
+            table = rng.uniform(-1, 1, (size, C)).astype(np.float32)
+            for tdt, code in grid_dtypes(C):
+                d_x = cuda(xs).to(tdt)
+                assert np.array_equal(np.floor(d_x.float().cpu().numpy().astype(np.float64) * 8.0 + 0.5), cell)
+                tv = torch.zeros(size, C, dtype=tdt, device="cuda")
+                call(lib.foc_grad_total_variation, ptr(d_x), ptr(cuda(table).to(tdt)), ptr(tv), ptr(cuda(off)), 0.01, n, D, C, 1, 0.0, H, 1, 0, code)
+                put(f"grid_tv_exact[D={D},C={C},{'f16' if code else 'f32'}]", grad=tv)
+
+
+def grid():
+    grid_general()
+    grid_exact_sums()
+
+
 # ---------------------------------------------------------------- the occupancy node and the native render loop, from Python
 NODE_KINDS = ("plain", "linear_bg", "tcnn_legacy", "foc", "tcnn")
 MARCHED = []         # samples marched by each training step of the node section (the summary says which remainders they leave)
@@ -518,6 +638,8 @@ def main():
         combine(T)
     if "march" in SECTIONS:
         march()
+    if "grid" in SECTIONS:
+        grid()
     if "node" in SECTIONS:
         node()
     text = json.dumps(OUT, indent=0, sort_keys=True)
