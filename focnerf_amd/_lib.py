@@ -80,6 +80,14 @@ class FocOccTrainTail(ctypes.Structure):
     ]
 
 
+class FocCulledField(ctypes.Structure):
+    """include/focnerf.h `FocCulledField`, field for field: one object's compact culled lists for foc_combine_select_composite_culled."""
+    _fields_ = [
+        ("mask", c_vp), ("offsets", c_vp), ("sigma_c", c_vp), ("rgb_c", c_vp),
+        ("m_occ", u32), ("density_scale", f32), ("thresh", f32), ("sigma_gain", f32),
+    ]
+
+
 # name -> (restype, [argtypes]) — one entry per declaration in include/focnerf.h
 SIGNATURES = {
     "foc_abi_version": (i32, []),
@@ -173,6 +181,8 @@ SIGNATURES = {
     "foc_combine_select_composite": (i32, [c_vp, u32, c_vp, c_vp, u32, u32, c_vp, u32, c_vp, c_vp, c_vp, c_vp]),
     "foc_combine_select4": (i32, [c_vp, c_vp, u64, c_vp]),
     "foc_combine_select_composite_attr": (i32, [c_vp, u32, c_vp, c_vp, u32, c_vp, c_vp, u32, u32, c_vp, u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "foc_combine_select_composite_culled": (i32, [ctypes.POINTER(FocCulledField), u32, u32, c_vp, u32, c_vp, c_vp, u32, u32, c_vp, u32, c_vp, c_vp, c_vp, c_vp,
+                                                  c_vp, c_vp, c_vp, c_vp]),
     "foc_combine_select4_ids": (i32, [c_vp, u32, c_vp, c_vp, u64, c_vp]),
     "foc_mo_select": (i32, [c_vp, c_vp, c_vp, c_vp, u64, u32, u32, c_vp]),
     "foc_fixed_field_pack": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, f32, u32, u32, f32, f32, c_vp, c_vp, c_vp, c_vp, u32, c_vp]),

@@ -145,6 +145,34 @@ class HipCombineOps:
         return image4, depth, att, merged, winner
 
     @staticmethod
+    def select_composite_culled(culled, nears, fars, bgs, n_obj=0, ids=None, want_merged=False, want_winner=False):
+        """`select_composite` / `select_composite_attr` from K objects' `fixedcull.CulledField` lists (one chunk of N rays x T steps, nears /
+        fars [N] fp32 contiguous). n_obj = 0: no attribution. -> (image4 [len(bgs),N,4], depth [N], Attribution or None, merged4 or None[,
+        winner [N,T] uint8 when want_winner])."""
+        import ctypes
+        from ._lib import lib, ptr, stream_of, check, require_cuda, FocCulledField
+        K, N, T, n_obj = len(culled), culled[0].N, culled[0].T, int(n_obj)
+        require_cuda(nears, fars, *[t for c in culled for t in (c.mask, c.offsets, c.sigma_c, c.rgb_c)])
+        dev = nears.device
+        objs = (FocCulledField * K)()
+        for o, c in zip(objs, culled):
+            o.mask, o.offsets, o.sigma_c, o.rgb_c = (None if t is None else t.data_ptr() for t in (c.mask, c.offsets, c.sigma_c, c.rgb_c))
+            o.m_occ, o.density_scale, o.thresh, o.sigma_gain = c.m_occ, c.density_scale, c.thresh, c.sigma_gain
+        image4 = torch.empty(len(bgs), N, 4, dtype=torch.float32, device=dev)
+        depth = torch.empty(N, dtype=torch.float32, device=dev)
+        merged = torch.empty(N, T, 4, dtype=torch.float32, device=dev) if want_merged else None
+        winner = torch.empty(N, T, dtype=torch.uint8, device=dev) if want_winner and n_obj else None
+        att = Attribution(torch.empty(N, n_obj, dtype=torch.float32, device=dev), torch.empty(N, n_obj, dtype=torch.float32, device=dev),
+                          torch.empty(N, dtype=torch.int32, device=dev)) if n_obj else None
+        cids = None if ids is None else (ctypes.c_uint32 * K)(*[int(i) for i in ids])
+        cbgs = (ctypes.c_float * len(bgs))(*[float(b) for b in bgs])
+        check(lib.foc_combine_select_composite_culled(objs, K, ctypes.sizeof(FocCulledField), cids, n_obj, ptr(nears), ptr(fars), N, T, cbgs, len(bgs),
+                                                      ptr(image4), ptr(depth), ptr(merged), ptr(att.weights if att else None),
+                                                      ptr(att.depth if att else None), ptr(att.instance if att else None), ptr(winner),
+                                                      stream_of(nears)), "combine_select_composite_culled")
+        return (image4, depth, att, merged, winner) if want_winner else (image4, depth, att, merged)
+
+    @staticmethod
     def select4_ids(field4, obj_id, acc4, acc_ids):
         """`select4` that keeps the identity: acc_ids (uint8, one per sample of acc4) takes `obj_id` where acc4 takes field4's rgb."""
         from ._lib import lib, ptr, stream_of, check, require_cuda
@@ -257,22 +285,18 @@ def combine_packed(fields4, nears, fars, bgs=(1.0, 0.0), want_merged=False, ops=
     return ops.select_composite(fields4, nears.contiguous().float(), fars.contiguous().float(), tuple(bgs), want_merged)
 
 
-def placed_field_fns(models, occupancies, placements, rays_o, rays_d, T, scene_aabb, yolo_details=None, weight_thresh=1e-10):
-    """Objects placed in one scene, ready for the combiner: -> (field_fns, nears, fars) for `ObjectCombiner.render_view(field_fns, N, nears,
-    fars, T, ...)` and `combine_packed`. Entry k is `models[k]` with its `occupancies[k]` (a `fixedcull.Occupancy`) under `placements[k]`
-    (a `Placement`; None = the identity) — the same model may appear more than once with different placements, and hiding an object
-    means leaving it out. rays_o / rays_d [N,3]: the view's rays; scene_aabb: float32 [6] tensor on their device. nears / fars [N] are
-    those of the view's rays against the scene's box (the first model's `min_near`, which all must share): every field is built along
-    them, and the composite must run along the same. yolo_details: None, or one entry per object."""
+def _placed_scene(who, models, occupancies, placements, rays_o, rays_d, T, scene_aabb, yolo_details):
+    """The arguments of `placed_field_fns` / `culled_field_fns`, checked: -> (per-object (model, plan, occupancy, placement, yolo) tuples,
+    rays_o, rays_d, T, box, nears, fars)."""
     from . import raymarching
     from .field import field_plan
-    from .fixedcull import _check_culled, _scene_box, culled_field4
+    from .fixedcull import _check_culled, _scene_box
     from .placement import Placement
     models, occupancies = list(models), list(occupancies)
     placements = [Placement() if p is None else p for p in placements]
     yolos = [None] * len(models) if yolo_details is None else list(yolo_details)
     if not (len(models) == len(occupancies) == len(placements) == len(yolos)) or not models:
-        raise ValueError(f"placed_field_fns: {len(models)} models, {len(occupancies)} occupancies, {len(placements)} placements, {len(yolos)} "
+        raise ValueError(f"{who}: {len(models)} models, {len(occupancies)} occupancies, {len(placements)} placements, {len(yolos)} "
                          "yolo_details: one of each per object, at least one object")
     rays_o = rays_o.contiguous().view(-1, 3).float()
     rays_d = rays_d.contiguous().view(-1, 3).float()
@@ -280,13 +304,26 @@ def placed_field_fns(models, occupancies, placements, rays_o, rays_d, T, scene_a
     plans = [field_plan(m) for m in models]
     for m, plan, occ, p in zip(models, plans, occupancies, placements):
         if not isinstance(p, Placement):
-            raise ValueError("placed_field_fns: placements must be focnerf_amd.Placement objects (or None for the identity)")
+            raise ValueError(f"{who}: placements must be focnerf_amd.Placement objects (or None for the identity)")
         _check_culled(m, plan, occ)
         if float(m.min_near) != float(models[0].min_near):
-            raise ValueError(f"placed_field_fns: the objects must share min_near (one near / far per ray): {float(m.min_near)} and "
+            raise ValueError(f"{who}: the objects must share min_near (one near / far per ray): {float(m.min_near)} and "
                              f"{float(models[0].min_near)}")
     box = _scene_box(scene_aabb, models[0], rays_o.device)
     nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, box, models[0].min_near)
+    return list(zip(models, plans, occupancies, placements, yolos)), rays_o, rays_d, T, box, nears, fars
+
+
+def placed_field_fns(models, occupancies, placements, rays_o, rays_d, T, scene_aabb, yolo_details=None, weight_thresh=1e-10):
+    """Objects placed in one scene, ready for the combiner: -> (field_fns, nears, fars) for `ObjectCombiner.render_view(field_fns, N, nears,
+    fars, T, ...)` and `combine_packed`. Entry k is `models[k]` with its `occupancies[k]` (a `fixedcull.Occupancy`) under `placements[k]`
+    (a `Placement`; None = the identity) — the same model may appear more than once with different placements, and hiding an object
+    means leaving it out. rays_o / rays_d [N,3]: the view's rays; scene_aabb: float32 [6] tensor on their device. nears / fars [N] are
+    those of the view's rays against the scene's box (the first model's `min_near`, which all must share): every field is built along
+    them, and the composite must run along the same. yolo_details: None, or one entry per object."""
+    from .fixedcull import culled_field4
+    objects, rays_o, rays_d, T, box, nears, fars = _placed_scene("placed_field_fns", models, occupancies, placements, rays_o, rays_d, T, scene_aabb,
+                                                                 yolo_details)
 
     def make(m, plan, occ, p, yolo):
         def fn(lo, hi, out=None):
@@ -294,7 +331,67 @@ def placed_field_fns(models, occupancies, placements, rays_o, rays_d, T, scene_a
                 out = torch.empty(hi - lo, T, 4, dtype=torch.float32, device=rays_o.device)
             return culled_field4(m, plan, rays_o[lo:hi], rays_d[lo:hi], nears[lo:hi], fars[lo:hi], box, T, weight_thresh, yolo, out, occ, p)
         return fn
-    return [make(*args) for args in zip(models, plans, occupancies, placements, yolos)], nears, fars
+    return [make(*args) for args in objects], nears, fars
+
+
+def culled_field_fns(models, occupancies, placements, rays_o, rays_d, T, scene_aabb, yolo_details=None, weight_thresh=1e-10):
+    """`placed_field_fns` for `combine_culled`: the same arguments and checks -> (fns, nears, fars), but `fns[k](lo, hi)` (hi > lo) stops in
+    front of the pack and returns the object's `fixedcull.CulledField` on rays lo:hi — no [hi-lo, T, 4] field is written."""
+    from .fixedcull import culled_lists
+    objects, rays_o, rays_d, T, box, nears, fars = _placed_scene("culled_field_fns", models, occupancies, placements, rays_o, rays_d, T, scene_aabb,
+                                                                 yolo_details)
+
+    def make(m, plan, occ, p, yolo):
+        def fn(lo, hi):
+            if not 0 <= lo < hi <= rays_o.shape[0]:
+                raise ValueError(f"culled_field_fns: rays {lo}:{hi} of {rays_o.shape[0]}: a non-empty range of the view's rays expected")
+            return culled_lists(m, plan, rays_o[lo:hi], rays_d[lo:hi], nears[lo:hi], fars[lo:hi], box, T, weight_thresh, yolo, occ, p)
+        return fn
+    return [make(*args) for args in objects], nears, fars
+
+
+def combine_culled(culled, nears, fars, bgs=(1.0, 0.0), want_merged=False, attribution=False, ops=HipCombineOps):
+    """`combine_packed` fed from the compact culled lists (include/focnerf.h foc_combine_select_composite_culled): culled = one
+    `fixedcull.CulledField` per object in checkpoint order, all on the same N rays and T steps as nears / fars [N]. Returns what
+    `combine_packed` returns for the objects' packed fields, bit for bit: (image4 [len(bgs),N,4], depth [N][, merged4 [N,T,4]][, Attribution]).
+    At most 16 objects: more need the dense pre-merge (`combine_packed`)."""
+    from .fixedcull import CulledField
+    culled = list(culled)
+    if not culled or len(culled) > 16:
+        raise ValueError(f"combine_culled: 1 to 16 objects per call, got {len(culled)} (more than 16: the dense path pre-merges, combine_packed)")
+    for c in culled:
+        if not isinstance(c, CulledField):
+            raise ValueError("combine_culled: the objects must be focnerf_amd.fixedcull.CulledField (what culled_field_fns' functions return)")
+        if (c.N, c.T) != (culled[0].N, culled[0].T):
+            raise ValueError(f"combine_culled: objects on {c.N} rays x {c.T} steps and on {culled[0].N} x {culled[0].T}: one chunk, one T expected")
+    if nears.numel() != culled[0].N or fars.numel() != culled[0].N:
+        raise ValueError(f"combine_culled: nears / fars of {nears.numel()} / {fars.numel()} rays, the objects' lists cover {culled[0].N}")
+    image4, depth, att, merged = ops.select_composite_culled(culled, nears.contiguous().float(), fars.contiguous().float(), tuple(bgs),
+                                                             len(culled) if attribution else 0, want_merged=want_merged)
+    out = (image4, depth, merged) if want_merged else (image4, depth)
+    return out + (att,) if attribution else out
+
+
+def render_scene_culled(models, occupancies, placements, rays_o, rays_d, T, scene_aabb, bgs=(1.0, 0.0), max_ray_batch=16384, attribution=False,
+                        yolo_details=None):
+    """One view of placed objects on ONE device through `culled_field_fns` + `combine_culled`, in chunks of `max_ray_batch` rays:
+    -> (image4 [len(bgs),N,4], depth [N][, Attribution]). The bits of `placed_field_fns` + `combine_packed` without the objects' dense
+    fields; every object still costs one host read of its occupied count per chunk."""
+    fns, nears, fars = culled_field_fns(models, occupancies, placements, rays_o, rays_d, T, scene_aabb, yolo_details)
+    N, dev, chunk, n_obj = nears.shape[0], nears.device, int(max_ray_batch), len(fns)
+    if chunk < 1:
+        raise ValueError(f"render_scene_culled: max_ray_batch must be >= 1, got {chunk}")
+    image4 = torch.empty(len(bgs), N, 4, dtype=torch.float32, device=dev)
+    depth = torch.empty(N, dtype=torch.float32, device=dev)
+    att = Attribution(torch.empty(N, n_obj, dtype=torch.float32, device=dev), torch.empty(N, n_obj, dtype=torch.float32, device=dev),
+                      torch.empty(N, dtype=torch.int32, device=dev)) if attribution else None
+    for lo in range(0, N, chunk):
+        hi = min(lo + chunk, N)
+        out = combine_culled([fn(lo, hi) for fn in fns], nears[lo:hi], fars[lo:hi], bgs, attribution=attribution)
+        image4[:, lo:hi], depth[lo:hi] = out[0], out[1]
+        if attribution:
+            att.weights[lo:hi], att.depth[lo:hi], att.instance[lo:hi] = out[2]
+    return (image4, depth, att) if attribution else (image4, depth)
 
 
 class ObjectCombiner:

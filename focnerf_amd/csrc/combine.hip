@@ -8,9 +8,12 @@
 // foc_composite_fixed_steps : the fixed-step alpha composite the reference writes with
 //   torch.cumprod (COMBINED.py:141-200 / nerf/renderer.py:169-221), one wave per ray with a
 //   wave product-scan over 64 samples at a time.
+// foc_combine_select_composite{,_attr} : select + composite (+ attribution) fused over K objects' dense packed fields;
+// foc_combine_select_composite_culled  : the same fed from the objects' compact culled lists (fixedcull.hip), no dense field.
 #include "common.h"
 #include "fs_common.h"        // fs_geom, fs_sample, fs_trans_scan: the fixed-step sample step of fixedstep.hip
 #include <string.h>
+#include <cmath>
 
 // ---------------------------------------------------------------- error plumbing
 static thread_local char g_err[512] = "";
@@ -111,69 +114,80 @@ struct CombineAttr {
     uint8_t *winner;                                   // [N,T] or nullptr
 };
 
-// The body of both kernels. NOBJ == 0: select + composite, nothing else (every attribution statement is compiled out and `at` is never
-// read). NOBJ = 4 / 8 / 16 >= n_obj: the winner id travels with the rgb through the select — replaced by the very comparison that replaces
-// the rgb — and each lane keeps NOBJ weight and NOBJ depth accumulators updated with compare-selects; the loops over objects are bounded by
-// the template argument, so the accumulators are registers (an array indexed by the winner itself would live in scratch memory). The
-// composite's own arithmetic is the same statements in the same order: image4 / depth / merged4 are bit for bit those of NOBJ == 0.
+// The statements of the fused select + composite, written once for the kernels that read dense packed fields (below) and the one that forms
+// its entries from the compact culled lists (k_combine_culled). NOBJ == 0: select + composite, nothing else (every attribution statement
+// is compiled out and `at` is never read). NOBJ = 4 / 8 / 16 >= n_obj: the winner id travels with the rgb through the select — replaced by
+// the very comparison that replaces the rgb — and each lane keeps NOBJ weight and NOBJ depth accumulators updated with compare-selects; the
+// loops over objects are bounded by the template argument, so the accumulators are registers (an array indexed by the winner itself would
+// live in scratch memory). The composite's own arithmetic is the same statements in the same order: image4 / depth / merged4 are bit for
+// bit those of NOBJ == 0.
 template <int NOBJ>
-__device__ __forceinline__ void combine_select_composite_body(const CombineFields &fields, const CombineAttr *at, uint32_t K,
-                                                              const float *__restrict__ nears, const float *__restrict__ fars, uint32_t N,
-                                                              uint32_t T, float bg0, float bg1, uint32_t n_bg, float *__restrict__ image4,
-                                                              float *__restrict__ depth, float4 *__restrict__ merged4) {
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t n = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (n >= N) return;
-    const FsGeom geo = fs_geom(nears, fars, n, T);
-    float Tc = 1.0f, r = 0, g = 0, b = 0, a = 0, d = 0, ws = 0;
+struct CombineAcc {
+    float Tc, r, g, b, a, d, ws;
     float aw[NOBJ > 0 ? NOBJ : 1], ad[NOBJ > 0 ? NOBJ : 1];
-    (void)aw; (void)ad;
+};
+template <int NOBJ>
+__device__ __forceinline__ void combine_acc_init(CombineAcc<NOBJ> &A) {
+    A.Tc = 1.0f; A.r = A.g = A.b = A.a = A.d = A.ws = 0.0f;
+#pragma unroll
+    for (int k = 0; k < (NOBJ > 0 ? NOBJ : 1); k++) A.aw[k] = A.ad[k] = 0.0f;
+}
+
+// the select: a later object's entry f (its id: idk) against the running best
+template <int NOBJ>
+__device__ __forceinline__ void combine_select_step(float4 &best, uint32_t &win, const float4 f, uint32_t idk) {
+    const float m = best.x;
+    if constexpr (NOBJ > 0) {
+        if (f.x > m) win = idk;
+    }
+    if (f.x > m) { best.y = f.y; best.z = f.z; best.w = f.w; }
+    best.x = (f.x != f.x || m != m) ? __builtin_nanf("") : (f.x > m ? f.x : m);      // torch.maximum propagates NaN
+}
+
+// what a lane's sample gives the composite; a lane past T holds no sample: all zero, no column
+struct CombineSample { float alpha, sigma, c0, c1, c2, oz; uint32_t win; };
+__device__ __forceinline__ CombineSample combine_no_sample() { return CombineSample{0, 0, 0, 0, 0, 0, 0xFFu}; }
+
+// the per-sample outputs of a lane that holds sample s
+template <int NOBJ>
+__device__ __forceinline__ void combine_store(const float4 best, uint32_t win, uint64_t s, float4 *__restrict__ merged4, const CombineAttr *at) {
+    if (merged4) merged4[s] = best;
+    if constexpr (NOBJ > 0) {
+        if (at->winner) at->winner[s] = (uint8_t)win;
+    }
+}
+// ... and its merged entry as the composite takes it (p: the sample's FsSample)
+__device__ __forceinline__ CombineSample combine_take(const float4 best, uint32_t win, const FsSample &p) {
+    CombineSample q;
+    q.sigma = best.x; q.c0 = best.y; q.c1 = best.z; q.c2 = best.w;
+    q.alpha = 1 - __expf(-p.delta * q.sigma);
+    q.oz = p.oz;
+    q.win = win;
+    return q;
+}
+
+// one 64-sample step of the composite on the merged samples
+template <int NOBJ>
+__device__ __forceinline__ void combine_accumulate(CombineAcc<NOBJ> &A, const CombineSample &q, bool valid, uint32_t lane) {
+    const float om = valid ? (1 - q.alpha + 1e-15f) : 1.0f;
+    const float w = q.alpha * fs_trans_scan(om, lane, A.Tc);
+    A.r = fmaf(w, q.c0, A.r); A.g = fmaf(w, q.c1, A.g); A.b = fmaf(w, q.c2, A.b);
+    A.a = fmaf(w, q.sigma, A.a); A.d = fmaf(w, q.oz, A.d); A.ws += w;
     if constexpr (NOBJ > 0) {
 #pragma unroll
-        for (int k = 0; k < NOBJ; k++) aw[k] = ad[k] = 0.0f;
-    }
-    for (uint32_t base = 0; base < T; base += 64) {
-        const uint32_t i = base + lane;
-        const bool valid = i < T;
-        float alpha = 0, sigma = 0, c0 = 0, c1 = 0, c2 = 0, oz = 0;
-        uint32_t win = 0xFFu;                                                    // lanes past T hold no sample: no column
-        if (valid) {
-            const uint64_t s = (uint64_t)n * T + i;
-            float4 best = fields.p[0][s];
-            if constexpr (NOBJ > 0) win = at->plane[0] ? (uint32_t)at->plane[0][s] : at->id[0];
-            for (uint32_t k = 1; k < K; k++) {
-                const float4 f = fields.p[k][s];
-                const float m = best.x;
-                if constexpr (NOBJ > 0) {
-                    const uint32_t idk = at->plane[k] ? (uint32_t)at->plane[k][s] : at->id[k];
-                    if (f.x > m) win = idk;
-                }
-                if (f.x > m) { best.y = f.y; best.z = f.z; best.w = f.w; }
-                best.x = (f.x != f.x || m != m) ? __builtin_nanf("") : (f.x > m ? f.x : m);      // torch.maximum propagates NaN
-            }
-            if (merged4) merged4[s] = best;
-            if constexpr (NOBJ > 0) {
-                if (at->winner) at->winner[s] = (uint8_t)win;
-            }
-            sigma = best.x; c0 = best.y; c1 = best.z; c2 = best.w;
-            const FsSample p = fs_sample(geo, i, i, T, false, 0.0f, 0.0f);
-            alpha = 1 - __expf(-p.delta * sigma);
-            oz = p.oz;
-        }
-        const float om = valid ? (1 - alpha + 1e-15f) : 1.0f;
-        const float w = alpha * fs_trans_scan(om, lane, Tc);
-        r = fmaf(w, c0, r); g = fmaf(w, c1, g); b = fmaf(w, c2, b);
-        a = fmaf(w, sigma, a); d = fmaf(w, oz, d); ws += w;
-        if constexpr (NOBJ > 0) {
-#pragma unroll
-            for (int k = 0; k < NOBJ; k++) {                                     // the statements of `ws` and `d`, kept by the winner's column only
-                const bool mine = win == (uint32_t)k;
-                aw[k] = mine ? aw[k] + w : aw[k];
-                ad[k] = mine ? fmaf(w, oz, ad[k]) : ad[k];
-            }
+        for (int k = 0; k < NOBJ; k++) {                                         // the statements of `ws` and `d`, kept by the winner's column only
+            const bool mine = q.win == (uint32_t)k;
+            A.aw[k] = mine ? A.aw[k] + w : A.aw[k];
+            A.ad[k] = mine ? fmaf(w, q.oz, A.ad[k]) : A.ad[k];
         }
     }
-    r = wave_sum(r); g = wave_sum(g); b = wave_sum(b); a = wave_sum(a); d = wave_sum(d); ws = wave_sum(ws);
+}
+
+// the ray's sums, backgrounds and clamp
+template <int NOBJ>
+__device__ __forceinline__ void combine_finish(CombineAcc<NOBJ> &A, const CombineAttr *at, uint32_t n, uint32_t N, uint32_t lane, float bg0, float bg1,
+                                               uint32_t n_bg, float *__restrict__ image4, float *__restrict__ depth) {
+    const float r = wave_sum(A.r), g = wave_sum(A.g), b = wave_sum(A.b), a = wave_sum(A.a), d = wave_sum(A.d), ws = wave_sum(A.ws);
     if constexpr (NOBJ > 0) {
         // one fixed tree per used column (no atomics: run-to-run bit-stable); every lane ends up with every sum, lane k stores column k
         const uint32_t n_obj = at->n_obj;
@@ -182,7 +196,7 @@ __device__ __forceinline__ void combine_select_composite_body(const CombineField
 #pragma unroll
         for (int k = 0; k < NOBJ; k++) {
             if ((uint32_t)k < n_obj) {                                           // wave-uniform
-                const float sw = wave_sum(aw[k]), sd = wave_sum(ad[k]);
+                const float sw = wave_sum(A.aw[k]), sd = wave_sum(A.ad[k]);
                 if (lane == (uint32_t)k) { my_w = sw; my_d = sd; }
                 if (sw > top) { top = sw; inst = k; }                            // strict: the first of equal columns; NaN and 0 never
             }
@@ -204,6 +218,41 @@ __device__ __forceinline__ void combine_select_composite_body(const CombineField
     }
 }
 
+// The body of both dense kernels: every lane reads its sample of each object's field4.
+template <int NOBJ>
+__device__ __forceinline__ void combine_select_composite_body(const CombineFields &fields, const CombineAttr *at, uint32_t K,
+                                                              const float *__restrict__ nears, const float *__restrict__ fars, uint32_t N,
+                                                              uint32_t T, float bg0, float bg1, uint32_t n_bg, float *__restrict__ image4,
+                                                              float *__restrict__ depth, float4 *__restrict__ merged4) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t n = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (n >= N) return;
+    const FsGeom geo = fs_geom(nears, fars, n, T);
+    CombineAcc<NOBJ> A;
+    combine_acc_init(A);
+    for (uint32_t base = 0; base < T; base += 64) {
+        const uint32_t i = base + lane;
+        const bool valid = i < T;
+        CombineSample q = combine_no_sample();
+        if (valid) {
+            const uint64_t s = (uint64_t)n * T + i;
+            float4 best = fields.p[0][s];
+            uint32_t win = 0xFFu;
+            if constexpr (NOBJ > 0) win = at->plane[0] ? (uint32_t)at->plane[0][s] : at->id[0];
+            for (uint32_t k = 1; k < K; k++) {
+                const float4 f = fields.p[k][s];
+                uint32_t idk = 0;
+                if constexpr (NOBJ > 0) idk = at->plane[k] ? (uint32_t)at->plane[k][s] : at->id[k];
+                combine_select_step<NOBJ>(best, win, f, idk);
+            }
+            combine_store<NOBJ>(best, win, s, merged4, at);
+            q = combine_take(best, win, fs_sample(geo, i, i, T, false, 0.0f, 0.0f));
+        }
+        combine_accumulate(A, q, valid, lane);
+    }
+    combine_finish(A, at, n, N, lane, bg0, bg1, n_bg, image4, depth);
+}
+
 __global__ void __launch_bounds__(256) k_combine_select_composite(CombineFields fields, uint32_t K, const float *__restrict__ nears,
                                                                   const float *__restrict__ fars, uint32_t N, uint32_t T, float bg0, float bg1,
                                                                   uint32_t n_bg, float *__restrict__ image4, float *__restrict__ depth,
@@ -217,6 +266,121 @@ __global__ void __launch_bounds__(256) k_combine_select_composite_attr(CombineFi
                                                                        uint32_t T, float bg0, float bg1, uint32_t n_bg, float *__restrict__ image4,
                                                                        float *__restrict__ depth, float4 *__restrict__ merged4) {
     combine_select_composite_body<NOBJ>(fields, &at, K, nears, fars, N, T, bg0, bg1, n_bg, image4, depth, merged4);
+}
+
+// ---------------------------------------------------------------- the same select + composite fed from K objects' compact culled lists
+// include/focnerf.h foc_combine_select_composite_culled. Object k arrives as foc_fixed_cull{,_placed} and the field kernels left it: the row
+// masks, their offsets and the compact sigma / rgb. One wave per ray, sample i on the lane, as k_fc_pack and the body above: the wave forms
+// object k's entry with the pack's statements (fs_common.h fs_infer_weight on the object's own transmittance carry Tk[k], the rgb masked
+// by w > thresh), feeds it to combine_select_step and composites: no field4 [N,T,4] exists. KMAX >= K bounds the loops over objects, so
+// the carries and the lanes' slots are registers. The objects travel by value in the kernel argument block (48 bytes each).
+struct CulledObj {
+    const uint64_t *mask; const uint32_t *offsets; const float *sigma_c, *rgb_c;
+    uint32_t m_occ; float density_scale, thresh, sigma_gain;
+};
+template <int KMAX> struct CulledObjs { CulledObj o[KMAX]; };
+
+#define CC_NO_BIT 0xFFFFFFFFu
+template <int KMAX, int NOBJ>
+__global__ void __launch_bounds__(256) k_combine_culled(CulledObjs<KMAX> objs, CombineAttr at, uint32_t K, const float *__restrict__ nears,
+                                                        const float *__restrict__ fars, uint32_t N, uint32_t T, float bg0, float bg1, uint32_t n_bg,
+                                                        float *__restrict__ image4, float *__restrict__ depth, float4 *__restrict__ merged4) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t n = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+    if (n >= N) return;
+    const FsGeom geo = fs_geom(nears, fars, n, T);
+    const uint32_t bit = n % FS_RAY_BLOCK;
+    const uint64_t below = (1ull << bit) - 1ull;
+    const uint64_t row0 = (uint64_t)(n / FS_RAY_BLOCK) * T;
+    CombineAcc<NOBJ> A;
+    combine_acc_init(A);
+    float Tk[KMAX];
+#pragma unroll
+    for (int k = 0; k < KMAX; k++) Tk[k] = 1.0f;
+    for (uint32_t base = 0; base < T; base += 64) {
+        const uint32_t i = base + lane;
+        const bool valid = i < T;
+        const uint32_t ic = valid ? i : T - 1;
+        const uint64_t row = row0 + ic, s = (uint64_t)n * T + ic;
+        const FsSample p = fs_sample(geo, i, ic, T, false, 0.0f, 0.0f);
+        // the lane's bit per object: its rank among the row's bits, or CC_NO_BIT. `plain`: an all-zero entry leaves every carry and every sum
+        // of this lane as it is — alpha = 1 - exp(-0) = 0, om = 1.0f, w = 0 — which needs finite exponents' factors and an oz that is not NaN
+        // (a ray that misses the box has oz = 0/0, and its depth is NaN by 0 * NaN in the dense composite too)
+        uint32_t pre[KMAX];
+        bool any = false, plain = fabsf(p.delta) < INFINITY && p.oz == p.oz;
+#pragma unroll
+        for (int k = 0; k < KMAX; k++) {
+            pre[k] = CC_NO_BIT;
+            if ((uint32_t)k < K) {                                               // wave-uniform
+                const uint64_t m = objs.o[k].mask[row];
+                if (valid && ((m >> bit) & 1ull)) { pre[k] = (uint32_t)__popcll(m & below); any = true; }
+                plain = plain && fabsf(p.delta * objs.o[k].density_scale) < INFINITY;
+            }
+        }
+        if (__ballot(any || !plain) == 0 && fabsf(A.Tc) < INFINITY) {            // no object has a bit for this ray in the tile: nothing changes
+            if (valid) {
+                uint32_t win = 0xFFu;
+                if constexpr (NOBJ > 0) win = at.id[0];
+                combine_store<NOBJ>(make_float4(0.0f, 0.0f, 0.0f, 0.0f), win, s, merged4, &at);
+            }
+            continue;
+        }
+        float4 best = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        uint32_t win = 0xFFu;
+#pragma unroll
+        for (int k = 0; k < KMAX; k++) {
+            if ((uint32_t)k < K) {
+                const CulledObj &o = objs.o[k];
+                float sigma = 0, c0 = 0, c1 = 0, c2 = 0;
+                if (pre[k] != CC_NO_BIT) {
+                    const uint32_t slot = o.offsets[row] + pre[k];
+                    if (slot < o.m_occ) {
+                        sigma = o.sigma_c[slot];
+                        if (o.sigma_gain != 1.0f) sigma *= o.sigma_gain;         // a placed object's density in world units, in front of the weights
+                        c0 = o.rgb_c[(uint64_t)slot * 3]; c1 = o.rgb_c[(uint64_t)slot * 3 + 1]; c2 = o.rgb_c[(uint64_t)slot * 3 + 2];
+                    }
+                }
+                const bool on = fs_infer_weight(Tk[k], p, valid, sigma, o.density_scale, lane) > o.thresh;
+                const float4 f = make_float4(sigma, on ? c0 : 0.0f, on ? c1 : 0.0f, on ? c2 : 0.0f);
+                if (k == 0) {
+                    best = f;
+                    if constexpr (NOBJ > 0) win = at.id[0];
+                } else {
+                    combine_select_step<NOBJ>(best, win, f, at.id[k]);
+                }
+            }
+        }
+        CombineSample q = combine_no_sample();
+        if (valid) {
+            combine_store<NOBJ>(best, win, s, merged4, &at);
+            q = combine_take(best, win, p);
+        }
+        combine_accumulate(A, q, valid, lane);
+    }
+    combine_finish(A, &at, n, N, lane, bg0, bg1, n_bg, image4, depth);
+}
+
+struct CulledLaunch {
+    const FocCulledField *objs; uint32_t K; CombineAttr at; const float *nears, *fars; uint32_t N, T; float bg0, bg1; uint32_t n_bg;
+    float *image4, *depth; float4 *merged4; hipStream_t stream;
+};
+template <int KMAX, int NOBJ>
+static void cc_launch(const CulledLaunch &L) {
+    CulledObjs<KMAX> o;
+    memset(&o, 0, sizeof(o));
+    for (uint32_t k = 0; k < L.K; k++) {
+        const FocCulledField &f = L.objs[k];
+        o.o[k] = CulledObj{f.mask, f.offsets, f.sigma_c, f.rgb_c, f.m_occ, f.density_scale, f.thresh, f.sigma_gain};
+    }
+    hipLaunchKernelGGL((k_combine_culled<KMAX, NOBJ>), dim3(foc_div_up(L.N, 4)), dim3(256), 0, L.stream, o, L.at, L.K, L.nears, L.fars, L.N, L.T, L.bg0,
+                       L.bg1, L.n_bg, L.image4, L.depth, L.merged4);
+}
+template <int KMAX>
+static void cc_launch_k(const CulledLaunch &L, uint32_t n_obj) {
+    if (n_obj == 0) cc_launch<KMAX, 0>(L);
+    else if (n_obj <= 4) cc_launch<KMAX, 4>(L);
+    else if (n_obj <= 8) cc_launch<KMAX, 8>(L);
+    else cc_launch<KMAX, 16>(L);
 }
 
 // Pre-merge of the objects that share a rank before the exchange (K objects on fewer GPUs): acc4 <- select(acc4, f4), same rule. The
@@ -403,6 +567,55 @@ int foc_combine_select_composite_attr(const float *const *fields4, uint32_t K, c
     else
         hipLaunchKernelGGL(k_combine_select_composite_attr<16>, grid, block, 0, (hipStream_t)stream, f, at, K, nears, fars, N, T, bgs[0], bg1, n_bg, image4, depth, m4);
     FOC_CHECK_LAUNCH("combine_select_composite_attr");
+    return FOC_OK;
+}
+
+int foc_combine_select_composite_culled(const FocCulledField *objs, uint32_t K, uint32_t struct_bytes, const uint32_t *ids, uint32_t n_obj,
+                                        const float *nears, const float *fars, uint32_t N, uint32_t T, const float *bgs, uint32_t n_bg, float *image4,
+                                        float *depth, float *merged4, float *obj_weights, float *obj_depth, int32_t *instance, uint8_t *winner,
+                                        void *stream) {
+    const char *who = "combine_select_composite_culled";
+    FocDeviceGuard foc_guard_(stream, nears);
+    FOC_REQUIRE(K >= 1 && K <= FOC_COMBINE_MAX_OBJECTS, FOC_E_INVALID, "%s: 1 <= K <= %d objects per call (got %u)", who, FOC_COMBINE_MAX_OBJECTS, K);
+    FOC_REQUIRE(struct_bytes == sizeof(FocCulledField), FOC_E_INVALID, "%s: FocCulledField of %u bytes, this library's has %u", who, struct_bytes,
+                (uint32_t)sizeof(FocCulledField));
+    FOC_REQUIRE(objs, FOC_E_INVALID, "%s: objs is null", who);
+    FOC_REQUIRE(n_obj <= FOC_COMBINE_MAX_OBJECTS, FOC_E_INVALID, "%s: n_obj <= %d objects (got %u)", who, FOC_COMBINE_MAX_OBJECTS, n_obj);
+    FOC_REQUIRE(n_bg >= 1 && n_bg <= 2 && bgs, FOC_E_INVALID, "%s: one or two backgrounds", who);
+    FOC_REQUIRE(T >= 2, FOC_E_INVALID, "%s: T must be >= 2", who);
+    FOC_REQUIRE((uint64_t)foc_div_up(N, FS_RAY_BLOCK) * FS_RAY_BLOCK * T < (1ull << 31), FOC_E_INVALID,
+                "%s: ceil(N/64)*64*T must stay below 2^31 (foc_fixed_cull's limit)", who);
+    CulledLaunch L;
+    memset(&L.at, 0, sizeof(L.at));
+    for (uint32_t k = 0; k < K; k++) {
+        const FocCulledField &f = objs[k];
+        FOC_REQUIRE(std::isfinite(f.sigma_gain) && f.sigma_gain > 0, FOC_E_INVALID, "%s: object %u: sigma_gain must be finite and > 0 (got %g)", who, k,
+                    (double)f.sigma_gain);
+        L.at.id[k] = ids ? ids[k] : k;
+        FOC_REQUIRE(n_obj == 0 || L.at.id[k] < n_obj, FOC_E_INVALID, "%s: ids[%u] = %u is not below n_obj = %u", who, k, L.at.id[k], n_obj);
+    }
+    if (N == 0) return FOC_OK;
+    FOC_REQUIRE(nears && fars && image4 && depth, FOC_E_INVALID, "%s: null pointer", who);
+    FOC_REQUIRE(n_obj == 0 || (obj_weights && obj_depth && instance), FOC_E_INVALID, "%s: obj_weights, obj_depth and instance must not be null when n_obj > 0", who);
+    for (uint32_t k = 0; k < K; k++) {
+        const FocCulledField &f = objs[k];
+        FOC_REQUIRE(f.mask && f.offsets, FOC_E_INVALID, "%s: object %u: null pointer (mask / offsets)", who, k);
+        FOC_REQUIRE(f.m_occ == 0 || (f.sigma_c && f.rgb_c), FOC_E_INVALID, "%s: object %u: null sigma / rgb with %u occupied samples", who, k, f.m_occ);
+        FOC_REQUIRE(((uintptr_t)f.mask & 7) == 0 && ((uintptr_t)f.offsets & 3) == 0 && ((uintptr_t)f.sigma_c & 3) == 0 && ((uintptr_t)f.rgb_c & 3) == 0,
+                    FOC_E_INVALID, "%s: object %u: mask must be 8-byte, offsets / sigma_c / rgb_c 4-byte aligned", who, k);
+    }
+    FOC_REQUIRE(((uintptr_t)merged4 & 15) == 0, FOC_E_INVALID, "%s: merged4 must be 16-byte aligned", who);
+    FOC_REQUIRE(((uintptr_t)obj_weights & 3) == 0 && ((uintptr_t)obj_depth & 3) == 0 && ((uintptr_t)instance & 3) == 0, FOC_E_INVALID,
+                "%s: obj_weights, obj_depth and instance must be 4-byte aligned", who);
+    L.objs = objs; L.K = K; L.nears = nears; L.fars = fars; L.N = N; L.T = T; L.bg0 = bgs[0]; L.bg1 = n_bg > 1 ? bgs[1] : 0.0f; L.n_bg = n_bg;
+    L.image4 = image4; L.depth = depth; L.merged4 = reinterpret_cast<float4 *>(merged4); L.stream = (hipStream_t)stream;
+    L.at.n_obj = n_obj;
+    L.at.obj_weights = obj_weights; L.at.obj_depth = obj_depth; L.at.instance = instance; L.at.winner = n_obj ? winner : nullptr;
+    if (K <= 2) cc_launch_k<2>(L, n_obj);
+    else if (K <= 4) cc_launch_k<4>(L, n_obj);
+    else if (K <= 8) cc_launch_k<8>(L, n_obj);
+    else cc_launch_k<16>(L, n_obj);
+    FOC_CHECK_LAUNCH(who);
     return FOC_OK;
 }
 

@@ -162,6 +162,14 @@ __device__ __forceinline__ float fs_norm(float x, float bound, float two_b) { re
 // ---------------------------------------------------------------- inference tail, one 64-sample tile of one ray
 struct FsRayAcc { float Tc, ws, dp, r, g, b; };
 
+// The inference path's own weight of the lane's sample, w = alpha * transmittance in front of it (the carry Tc moves behind the step):
+// what masks an object's rgb in fs_infer_tile and in the combine fed from culled lists (combine.hip k_combine_culled).
+__device__ __forceinline__ float fs_infer_weight(float &Tc, const FsSample &p, bool valid, float sigma, float density_scale, uint32_t lane) {
+    const float alpha = valid ? 1 - expf((-p.delta * density_scale) * sigma) : 0.0f;
+    const float om = valid ? (1 - alpha + 1e-15f) : 1.0f;
+    return alpha * fs_trans_scan(om, lane, Tc);
+}
+
 // 64 samples of ray n, sample i on the lane (sigma / c0..c2 are that sample's values; unread where i >= T): weights by wave scan, the
 // masked sums on the lane, the per-sample outputs written ray-major.
 template <bool PACK>
@@ -171,9 +179,7 @@ __device__ __forceinline__ void fs_infer_tile(FsRayAcc &a, const FsGeom &g, uint
     const bool valid = i < T;
     const uint64_t s = (uint64_t)n * T + (valid ? i : T - 1);
     const FsSample p = fs_sample_ld(g, i, valid ? i : T - 1, T, noise, s);
-    const float alpha = valid ? 1 - expf((-p.delta * density_scale) * sigma) : 0.0f;
-    const float om = valid ? (1 - alpha + 1e-15f) : 1.0f;
-    const float w = alpha * fs_trans_scan(om, lane, a.Tc);
+    const float w = fs_infer_weight(a.Tc, p, valid, sigma, density_scale, lane);
     if (valid) {
         a.ws += w; a.dp += w * p.oz;
         const bool on = w > thresh;

@@ -10,6 +10,9 @@ such samples is slightly higher, and a sample whose own weight stood at the 1e-1
     occ = Occupancy.estimate(model)      # any network with density(x): the full-grid passes of update_extra_state on own buffers
     render_field4(model, rays_o, rays_d, num_steps=T, out=buf, occupancy=occ)
     render_field4(model, rays_o, rays_d, num_steps=T, out=buf, occupancy=occ, placement=P, scene_aabb=box)     # placement.py
+
+`culled_lists` is the same sequence without its last step, the pack into a dense field4: it returns the compact lists as a `CulledField`,
+which `combine.combine_culled` selects and composites from directly.
 """
 import torch
 
@@ -135,14 +138,23 @@ def _check_culled(model, plan, occ):
         raise ValueError(f"render_field4: the occupancy grid covers bound {occ.bound}, the model bound {float(model.bound)}")
 
 
-def culled_field4(model, plan, rays_o, rays_d, nears, fars, aabb, T, weight_thresh, yolo_details, out, occ, placement=None):
-    """The culled field along GIVEN nears / fars [N] (of the rays against `aabb`): cull -> ONE host read of the count -> encoder +
-    whole-field kernel on the occupied samples -> culled pack. With a placement, `aabb` is the scene's box, the object's own box is
-    the model's, and the pack applies the placement's sigma gain."""
+class CulledField:
+    """One object on a ray chunk as the cull and the field kernels left it (include/focnerf.h `FocCulledField`): the row masks and offsets of
+    `fixed_cull`, the occupied samples' sigma_c [m_occ] / rgb_c [m_occ,3] (None when m_occ == 0) and the pack's arguments. What
+    `combine.combine_culled` reads in place of a dense field4; the object keeps its tensors alive."""
+    __slots__ = ("mask", "offsets", "m_occ", "sigma_c", "rgb_c", "density_scale", "thresh", "sigma_gain", "N", "T")
+
+    def __init__(self, mask, offsets, m_occ, sigma_c, rgb_c, density_scale, thresh, sigma_gain, N, T):
+        self.mask, self.offsets, self.m_occ, self.sigma_c, self.rgb_c = mask, offsets, int(m_occ), sigma_c, rgb_c
+        self.density_scale, self.thresh, self.sigma_gain = float(density_scale), float(thresh), float(sigma_gain)
+        self.N, self.T = int(N), int(T)
+
+
+def culled_lists(model, plan, rays_o, rays_d, nears, fars, aabb, T, weight_thresh, yolo_details, occ, placement=None):
+    """`culled_field4` in front of its pack, for N > 0 rays: cull -> ONE host read of the count -> emit -> encoder + whole-field kernel on
+    the occupied samples. -> a `CulledField` (sigma_gain 1 without a placement)."""
     from .field import field_infer
     N, dev = rays_o.shape[0], rays_o.device
-    if N == 0:
-        return out
     if occ.bitfield.device != dev:
         raise ValueError(f"render_field4: the occupancy bitfield is on {occ.bitfield.device}, the rays on {dev}")
     obj_aabb = None if placement is None else (model.aabb_train if model.training else model.aabb_infer)
@@ -153,13 +165,22 @@ def culled_field4(model, plan, rays_o, rays_d, nears, fars, aabb, T, weight_thre
         enc_in_c, dirs_c = fixed_cull_emit(rays_o, rays_d, nears, fars, aabb, T, model.bound, mask, offsets, m_occ, placement)
         obj_feat = model.encode_object_feature(yolo_details, dev) if plan.uses_object_feature else None
         sigma, rgb = field_infer(model, enc_in_c, dirs_c, dir_div=1, dir_block=0, obj_feat=obj_feat)
-    if placement is not None:
-        check(lib.foc_fixed_field_pack_culled_gain(ptr(sigma), ptr(rgb), ptr(mask), ptr(offsets), m_occ, ptr(nears), ptr(fars), N, T,
-                                                   float(model.density_scale), float(weight_thresh), float(placement.sigma_gain), ptr(out),
-                                                   stream_of(out)), "fixed_field_pack_culled_gain")
+    return CulledField(mask, offsets, m_occ, sigma, rgb, model.density_scale, weight_thresh, 1.0 if placement is None else placement.sigma_gain, N, T)
+
+
+def culled_field4(model, plan, rays_o, rays_d, nears, fars, aabb, T, weight_thresh, yolo_details, out, occ, placement=None):
+    """The culled field along GIVEN nears / fars [N] (of the rays against `aabb`): `culled_lists` -> culled pack. With a placement, `aabb`
+    is the scene's box, the object's own box is the model's, and the pack applies the placement's sigma gain."""
+    N = rays_o.shape[0]
+    if N == 0:
         return out
-    check(lib.foc_fixed_field_pack_culled(ptr(sigma), ptr(rgb), ptr(mask), ptr(offsets), m_occ, ptr(nears), ptr(fars), N, T, float(model.density_scale),
-                                          float(weight_thresh), ptr(out), stream_of(out)), "fixed_field_pack_culled")
+    c = culled_lists(model, plan, rays_o, rays_d, nears, fars, aabb, T, weight_thresh, yolo_details, occ, placement)
+    if placement is not None:
+        check(lib.foc_fixed_field_pack_culled_gain(ptr(c.sigma_c), ptr(c.rgb_c), ptr(c.mask), ptr(c.offsets), c.m_occ, ptr(nears), ptr(fars), N, T,
+                                                   c.density_scale, c.thresh, c.sigma_gain, ptr(out), stream_of(out)), "fixed_field_pack_culled_gain")
+        return out
+    check(lib.foc_fixed_field_pack_culled(ptr(c.sigma_c), ptr(c.rgb_c), ptr(c.mask), ptr(c.offsets), c.m_occ, ptr(nears), ptr(fars), N, T, c.density_scale,
+                                          c.thresh, ptr(out), stream_of(out)), "fixed_field_pack_culled")
     return out
 
 

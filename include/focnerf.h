@@ -632,6 +632,41 @@ int foc_combine_select_composite_attr(const float *const *fields4, uint32_t K, c
                                       float *merged4, float *obj_weights, float *obj_depth, int32_t *instance,
                                       uint8_t *winner, void *stream);
 
+/* The fused select + composite (+ attribution) fed directly from K objects' COMPACT culled lists: what foc_fixed_field_pack_culled{,_gain}
+ * per object followed by foc_combine_select_composite{,_attr} computes, bit for bit in every output, without any field4 [N,T,4] being
+ * written or read. One FocCulledField per object of the scene, as foc_fixed_cull{,_placed} and the field kernels left it; the array lives
+ * in host memory and travels by value in the kernel argument block. */
+typedef struct FocCulledField {
+    const uint64_t *mask;     /* [R], R = ceil(N/64) * T rows in foc_fixed_cull's layout; 8-byte aligned */
+    const uint32_t *offsets;  /* [R + 1] */
+    const float *sigma_c;     /* [m_occ]; may be NULL when m_occ == 0 */
+    const float *rgb_c;       /* [m_occ,3]; may be NULL when m_occ == 0 */
+    uint32_t m_occ;
+    float density_scale;      /* the pack's arguments */
+    float thresh;
+    float sigma_gain;         /* finite and > 0; 1: an unplaced object (foc_fixed_field_pack_culled's bits) */
+} FocCulledField;
+/* Entry of object k at sample (n, i), the pack's statements: row = (n/64) * T + i; occupied = bit n % 64 of mask[row] is set and
+ * slot = offsets[row] + popcount(mask[row] & ((1 << (n % 64)) - 1)) < m_occ. Occupied: sigma = sigma_c[slot], times sigma_gain when that is
+ * not 1, rgb = rgb_c[slot*3 ..]; otherwise all zero. Own weight w_k = alpha_k * prod_{j<i}(1 - alpha_j + 1e-15) with
+ * alpha_k = 1 - expf((-delta * density_scale_k) * sigma), along object k's OWN transmittance; entry = (sigma, w_k > thresh_k ? rgb : 0).
+ * Select, composite and attribution: foc_combine_select_composite_attr's, in its order — object 0 first, strict '>', NaN propagated;
+ * ids: host array of K object ids (NULL: object k is k), n_obj = 0: no attribution, then obj_weights / obj_depth / instance / winner are
+ * not written and may be NULL; n_obj > 0: as foc_combine_select_composite_attr (winner optional). merged4 [N,T,4] optional.
+ * A 64-sample tile of a ray in which no object has a bit is skipped by its wave when skipping changes no bit (finite sample spacing and
+ * normalised depth, a finite transmittance carry): every entry is zero there, alpha = 0 and 1 - 0 + 1e-15f == 1.0f, so carries and sums
+ * stay as they are; merged4 = (0,0,0,0) and winner = ids[0] are still written for it. A ray that misses the box (near = far = FLT_MAX)
+ * is never skipped: its depth is NaN (0 * NaN) as in the dense composite.
+ * Refused with FOC_E_INVALID before any launch: K == 0 or K > FOC_COMBINE_MAX_OBJECTS; struct_bytes != sizeof(FocCulledField); n_bg not 1
+ * or 2; T < 2; ceil(N/64) * 64 * T >= 2^31; a sigma_gain that is not finite and > 0; ids[k] >= n_obj; n_obj > FOC_COMBINE_MAX_OBJECTS;
+ * a null objs; and, for N > 0: null mask / offsets / nears / fars / image4 / depth, m_occ > 0 with a null sigma_c or rgb_c, a misaligned
+ * mask or merged4, n_obj > 0 with a null obj_weights / obj_depth / instance. N == 0 returns FOC_OK without a launch. No atomics, no shared
+ * memory, no synchronisation. */
+int foc_combine_select_composite_culled(const FocCulledField *objs, uint32_t K, uint32_t struct_bytes, const uint32_t *ids,
+                                        uint32_t n_obj, const float *nears, const float *fars, uint32_t N, uint32_t T,
+                                        const float *bgs, uint32_t n_bg, float *image4, float *depth, float *merged4,
+                                        float *obj_weights, float *obj_depth, int32_t *instance, uint8_t *winner, void *stream);
+
 /* foc_combine_select4 that keeps the identity: acc_ids [n] uint8 holds, per sample, the id of the object whose rgb acc4 holds
  * (the caller fills it with the first object's id). field4 is ONE object with the constant id `id` (< FOC_COMBINE_MAX_OBJECTS);
  * acc_ids[i] takes it exactly where acc4 takes field4's rgb. acc4 is updated as by foc_combine_select4, bit for bit. */
