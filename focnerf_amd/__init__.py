@@ -6,6 +6,9 @@ from . import _lib  # noqa: F401  (raises ImportError when libfocnerf_hip.so is 
 from .determinism import use_deterministic, is_deterministic, deterministic  # noqa: F401  (FOC_DETERMINISTIC: bit-reproducible training steps)
 from .combine import Attribution  # noqa: F401  (per-object mattes, depths and the instance map of a combined render)
 from .placement import Placement  # noqa: F401  (rotation, uniform scale and translation of an object in the combined render)
+from .mesh import (density_volume, scene_volume, marching_cubes, extract_geometry, extract_scene_geometry,  # noqa: F401  (triangle meshes
+                   write_ply, save_mesh)                                                                   # of objects and placed scenes)
 
 __all__ = ["raymarching", "gridencoder", "freqencoder", "ffmlp", "activation", "encoding", "shencoder",
-           "renderer", "network", "combine", "fixedcull", "use_deterministic", "is_deterministic", "deterministic", "Attribution", "placement", "Placement"]
+           "renderer", "network", "combine", "fixedcull", "use_deterministic", "is_deterministic", "deterministic", "Attribution", "placement", "Placement",
+           "mesh", "density_volume", "scene_volume", "marching_cubes", "extract_geometry", "extract_scene_geometry", "write_ply", "save_mesh"]

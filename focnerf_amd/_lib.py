@@ -232,6 +232,13 @@ SIGNATURES = {
     "foc_background_forward": (i32, [c_vp, c_vp, c_vp, f32, u32, c_vp, c_vp, f32, u32, c_vp, c_vp, c_vp]),
     "foc_background_backward_workspace_bytes": (u64, [u32]),
     "foc_background_backward": (i32, [c_vp, c_vp, c_vp, c_vp, f32, u32, c_vp, c_vp, f32, u32, c_vp, c_vp, c_vp, c_vp, u64, c_vp]),
+    "foc_mc_workspace_bytes": (u64, [u32, u32, u32]),
+    "foc_mc_count": (i32, [c_vp, u32, u32, u32, f32, c_vp, c_vp, c_vp]),
+    "foc_mc_emit": (i32, [c_vp, u32, u32, u32, f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "foc_lattice_cull_scratch_bytes": (u64, [u32]),
+    "foc_lattice_cull": (i32, [c_vp, c_vp, c_vp, u32, u32, u32, u32, u32, c_vp, c_vp, f32, c_vp, u32, u32, c_vp, c_vp, c_vp, c_vp, u64, c_vp]),
+    "foc_lattice_cull_emit": (i32, [c_vp, c_vp, c_vp, u32, u32, u32, u32, u32, c_vp, c_vp, c_vp, u32, c_vp, c_vp]),
+    "foc_volume_scatter_max": (i32, [c_vp, c_vp, c_vp, f32, c_vp, u32, c_vp]),
 }
 
 

@@ -1107,6 +1107,60 @@ int foc_background_backward(const void *grad_rgb, const float *rays_o, const flo
                             const void *weights, float *grad_embeddings, float *grad_weights, void *workspace, uint64_t workspace_bytes,
                             void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Triangle meshes (csrc/mesh.hip; no reference binding: nerf/utils.py:512-541 samples model.density on a lattice in 128^3 pieces
+ * through the host and calls PyMCubes). Orientation and ordering are DEFINED here; parity with PyMCubes is not pinned.
+ *
+ * Marching cubes. volume: fp32 u[nx, ny, nz], C-contiguous with z fastest; every dimension >= 2 and nx * ny * nz <= 2^29 (so that
+ * V <= 3 * 2^29 and F <= 5 * 2^29 fit uint32 and the indices int32), larger volumes are refused before any launch. thr finite.
+ *   A corner is inside iff u >= thr (a NaN is outside). Corner c of a cube sits at offset (c & 1, (c >> 1) & 1, (c >> 2) & 1) in
+ *   (x, y, z). The 12 edges are listed axis-major (x, y, z), within an axis by lower corner number. The 256 cases are those of
+ *   csrc/mc_table.h, generated by tools/make_mc_table.py (its docstring states the rule); triangles face the outside (lower values).
+ *   A vertex belongs to the lattice edge it lies on, owned by the edge's lower endpoint p: t = (thr - u[p]) / (u[p + e] - u[p]) in
+ *   fp32, position = index of p plus t along the axis, then origin + position * spacing per axis with one fmaf. It is computed once
+ *   per edge: the cubes around an edge share it. Vertices are numbered by (linear index of the owner, axis), triangles by (linear
+ *   index of the cube = of its corner 0, table order). Every slot comes from a prefix sum, never from an atomic: the same mesh on
+ *   every run and in both deterministic modes.
+ * foc_mc_count  fills workspace (foc_mc_workspace_bytes(nx, ny, nz) device bytes, 8-byte aligned, no initialisation needed; 0 is
+ *               returned for dimensions that are refused) and writes counts3 [3] uint32 on the device: V, F, and the number of 4096-point
+ *               groups that hold a non-finite value on a crossed edge (the caller refuses the volume when it is not 0).
+ * foc_mc_emit   after the caller read counts3 (its one synchronisation), with the SAME volume, dimensions, threshold and workspace:
+ *               vertices [V,3] fp32, triangles [F,3] int32, and with normals != NULL normals [V,3] fp32. Nothing is written past V / F
+ *               rows. origin3 / spacing3: 3 floats each IN HOST MEMORY (NULL: 0 / 1, the lattice-unit result); spacing non-zero.
+ *               Normals: the gradient of u by central differences (one-sided on the border) at the edge's two endpoints, mixed as
+ *               g0 + t (g1 - g0), divided per axis by the spacing, negated and normalised; a zero gradient gives (0, 0, 0).
+ * --------------------------------------------------------------------------- */
+uint64_t foc_mc_workspace_bytes(uint32_t nx, uint32_t ny, uint32_t nz);
+int foc_mc_count(const float *volume, uint32_t nx, uint32_t ny, uint32_t nz, float thr, void *workspace, uint32_t *counts3,
+                 void *stream);
+int foc_mc_emit(const float *volume, uint32_t nx, uint32_t ny, uint32_t nz, float thr, const void *workspace,
+                const float *origin3, const float *spacing3, float *vertices, float *normals, int32_t *triangles, void *stream);
+
+/* The density volume of an object, or of objects placed in a scene, on a lattice: which points need the network at all.
+ * Lattice point i (linear, z fastest, of rx * ry * rz <= 2^29 points) stands at (xs[ix], ys[iy], zs[iz]), per-axis fp32 coordinates on
+ * the device. A call treats the SLAB of `count` >= 1 points from `first`; bit i % 64 of mask[i / 64] (i counted from the slab's start)
+ * is point i's, R = ceil(count / 64) words.
+ *   world_to_object / obj_aabb (12 and 6 floats in host memory, both or neither): the point is mapped by foc_fixed_cull_placed's
+ *       q_k = ((A_k0 x + A_k1 y) + A_k2 z) + b_k — the same device function — and is empty outside obj_aabb_lo <= q <= obj_aabb_hi.
+ *   bitfield (may be NULL, then cascade / grid_size / bound are not read): the point's cell, foc_fixed_cull's, must be occupied.
+ * foc_lattice_cull       mask [R] uint64, offsets [R + 1] uint32 (exclusive prefix sum of the words' popcounts), count [1] uint32;
+ *                        scratch: foc_lattice_cull_scratch_bytes(count) device bytes. No synchronisation.
+ * foc_lattice_cull_emit  pos_c [m_occ,3] fp32: the set points' positions (q with a placement) in lattice order, as the network's
+ *                        density(x) takes them; nothing is written past m_occ rows.
+ * foc_volume_scatter_max volume[i] = max(volume[i], gain * sigma_c[slot(i)]) at the set bits of a slab of n points (`volume` points at
+ *                        the slab's first value); a NaN stays a NaN. Each point is touched once per call, calls run in stream order:
+ *                        no atomics. gain finite and > 0 (a placement's 1 / scale). */
+uint64_t foc_lattice_cull_scratch_bytes(uint32_t count);
+int foc_lattice_cull(const float *xs, const float *ys, const float *zs, uint32_t rx, uint32_t ry, uint32_t rz, uint32_t first,
+                     uint32_t count, const float *world_to_object, const float *obj_aabb, float bound, const uint8_t *bitfield,
+                     uint32_t cascade, uint32_t grid_size, uint64_t *mask, uint32_t *offsets, uint32_t *count_out, void *scratch,
+                     uint64_t scratch_bytes, void *stream);
+int foc_lattice_cull_emit(const float *xs, const float *ys, const float *zs, uint32_t rx, uint32_t ry, uint32_t rz, uint32_t first,
+                          uint32_t count, const float *world_to_object, const uint64_t *mask, const uint32_t *offsets,
+                          uint32_t m_occ, float *pos_c, void *stream);
+int foc_volume_scatter_max(const float *sigma_c, const uint64_t *mask, const uint32_t *offsets, float gain, float *volume,
+                           uint32_t n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
