@@ -8,7 +8,9 @@ from .combine import Attribution  # noqa: F401  (per-object mattes, depths and t
 from .placement import Placement  # noqa: F401  (rotation, uniform scale and translation of an object in the combined render)
 from .mesh import (density_volume, scene_volume, marching_cubes, extract_geometry, extract_scene_geometry,  # noqa: F401  (triangle meshes
                    write_ply, save_mesh)                                                                   # of objects and placed scenes)
+from .score import score_view, ViewScore  # noqa: F401  (PSNR and SSIM of a combined view for every background, on the device)
 
 __all__ = ["raymarching", "gridencoder", "freqencoder", "ffmlp", "activation", "encoding", "shencoder",
            "renderer", "network", "combine", "fixedcull", "use_deterministic", "is_deterministic", "deterministic", "Attribution", "placement", "Placement",
-           "mesh", "density_volume", "scene_volume", "marching_cubes", "extract_geometry", "extract_scene_geometry", "write_ply", "save_mesh"]
+           "mesh", "density_volume", "scene_volume", "marching_cubes", "extract_geometry", "extract_scene_geometry", "write_ply", "save_mesh",
+           "score", "score_view", "ViewScore"]

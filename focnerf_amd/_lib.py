@@ -19,6 +19,7 @@ c_vp = ctypes.c_void_p
 u32 = ctypes.c_uint32
 u64 = ctypes.c_uint64
 f32 = ctypes.c_float
+f64 = ctypes.c_double
 i32 = ctypes.c_int
 
 FOC_F32 = 0
@@ -239,6 +240,9 @@ SIGNATURES = {
     "foc_lattice_cull": (i32, [c_vp, c_vp, c_vp, u32, u32, u32, u32, u32, c_vp, c_vp, f32, c_vp, u32, u32, c_vp, c_vp, c_vp, c_vp, u64, c_vp]),
     "foc_lattice_cull_emit": (i32, [c_vp, c_vp, c_vp, u32, u32, u32, u32, u32, c_vp, c_vp, c_vp, u32, c_vp, c_vp]),
     "foc_volume_scatter_max": (i32, [c_vp, c_vp, c_vp, f32, c_vp, u32, c_vp]),
+    "foc_score_workspace_bytes": (u64, [u32, u32, u32]),
+    "foc_score_quantize": (i32, [c_vp, c_vp, c_vp, c_vp, u32, u32, u32, c_vp, c_vp, c_vp, c_vp]),
+    "foc_score_view": (i32, [c_vp, c_vp, u32, u32, u32, c_vp, u32, f64, f64, c_vp, c_vp, u64, c_vp]),
 }
 
 

@@ -1161,6 +1161,41 @@ int foc_lattice_cull_emit(const float *xs, const float *ys, const float *zs, uin
 int foc_volume_scatter_max(const float *sigma_c, const uint64_t *mask, const uint32_t *offsets, float gain, float *volume,
                            uint32_t n, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Scoring a combined view (csrc/score.hip; no reference binding: COMBINED.py:335-378 process_images_with_background copies the float
+ * image to the host and quantises it with numpy, :267-291 calculate_psnr, :295-332 ssim_rgba / ssim_channel run
+ * scipy.ndimage.gaussian_filter forty times per view in float64). H * W in 1 .. 2^30 pixels, B in 1 .. 8 backgrounds, N = H * W,
+ * images row-major; anything else is refused (FOC_E_INVALID) before any launch. No atomics anywhere: the same bits on every run, in
+ * both modes of FOC_DETERMINISTIC.
+ *
+ * foc_score_quantize  (:353-366) image4 [B,N,4] fp32, gt [N,4] fp32 (both 16-byte aligned), depth [N] fp32, bgs: B floats IN HOST
+ *     MEMORY -> pred_u8 [B,H,W,4], gt_u8 [B,H,W,4] (4-byte aligned), depth_u8 [H,W]; depth and depth_u8 may both be NULL.
+ *     A pixel whose own alpha is < 0.5 in fp32 (exactly 0.5 is kept) becomes (bg_b, bg_b, bg_b); alpha is then always 1; every channel
+ *     is uint8(trunc(fp32(x) * 255.0f)) — one fp32 multiply and truncation toward zero, numpy's (img * 255).astype(np.uint8), not
+ *     round-to-nearest. The ground truth is masked by ITS alpha, and every background starts from the original ground truth (the
+ *     reference edits a shared numpy view in place only when the image tensor already lives on the host; that is not reproduced).
+ *     Domain: finite inputs in [0, 1] (the composite's clamp, a loaded RGBA image); outside it numpy's cast is itself undefined and
+ *     nothing is promised.
+ * foc_score_view      pred_u8, gt_u8 as above; taps: the 2 * radius + 1 weights of the filter as float64 IN HOST MEMORY, symmetric,
+ *     radius <= 12; C1, C2 >= 0 -> out [B,4] float64 on the device: the sum over r, g, b, a of the squared byte differences (an
+ *     integer, exact below 2^53; it passes 2^32 at 800 x 800), then the mean over the pixels of the SSIM map of r, g and b.
+ *     The caller computes the taps as scipy does: radius = int(4.0 * sigma + 0.5), w_k = exp(-0.5 / sigma^2 * k^2) for
+ *     k = -radius .. radius, divided by their sum. The reference passes window_size = 11, which nothing there reads: sigma 1.5 means
+ *     13 taps. Borders are scipy's mode='reflect', the half-sample symmetric form d c b a | a b c d, for any H, W >= 1 (a dimension
+ *     smaller than the radius reflects repeatedly): with m = i mod 2n >= 0 the index is m if m < n, else 2n - 1 - m.
+ *     Per channel x = byte / 255.0 in float64; the five moments x, y, x^2, y^2, xy are filtered along the rows, then along the
+ *     columns, each as w_0 v_0 + sum_j w_j (v_+j + v_-j) with one fma per j; SSIM = (2 mu1 mu2 + C1)(2 s12 + C2) /
+ *     ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2)) with s = E[.] - mu mu, all in float64 (sigma^2 cancels against C2 = 9e-4).
+ *     workspace: foc_score_workspace_bytes(H, W, B) device bytes (0 for refused dimensions), 8-byte aligned, no initialisation;
+ *     `workspace_bytes` = its size, a smaller buffer is refused. One workgroup per (16 x 16 tile, background) writes its partial
+ *     sums there; a second kernel adds them in a fixed order. No synchronisation.
+ * --------------------------------------------------------------------------- */
+uint64_t foc_score_workspace_bytes(uint32_t H, uint32_t W, uint32_t B);
+int foc_score_quantize(const float *image4, const float *depth, const float *gt, const float *bgs, uint32_t H, uint32_t W, uint32_t B,
+                       uint8_t *pred_u8, uint8_t *gt_u8, uint8_t *depth_u8, void *stream);
+int foc_score_view(const uint8_t *pred_u8, const uint8_t *gt_u8, uint32_t H, uint32_t W, uint32_t B, const double *taps,
+                   uint32_t radius, double C1, double C2, double *out, void *workspace, uint64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
