@@ -9,8 +9,11 @@ from .placement import Placement  # noqa: F401  (rotation, uniform scale and tra
 from .mesh import (density_volume, scene_volume, marching_cubes, extract_geometry, extract_scene_geometry,  # noqa: F401  (triangle meshes
                    write_ply, save_mesh)                                                                   # of objects and placed scenes)
 from .score import score_view, ViewScore  # noqa: F401  (PSNR and SSIM of a combined view for every background, on the device)
+from . import optim  # noqa: F401
+from .optim import FusedAdam, LossScaler  # noqa: F401  (the trainer's optimizer step: overflow check, unscale and Adam in two launches)
 
 __all__ = ["raymarching", "gridencoder", "freqencoder", "ffmlp", "activation", "encoding", "shencoder",
            "renderer", "network", "combine", "fixedcull", "use_deterministic", "is_deterministic", "deterministic", "Attribution", "placement", "Placement",
            "mesh", "density_volume", "scene_volume", "marching_cubes", "extract_geometry", "extract_scene_geometry", "write_ply", "save_mesh",
-           "score", "score_view", "ViewScore"]
+           "score", "score_view", "ViewScore",
+           "optim", "FusedAdam", "LossScaler"]

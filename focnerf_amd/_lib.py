@@ -89,6 +89,34 @@ class FocCulledField(ctypes.Structure):
     ]
 
 
+class FocOptimTensor(ctypes.Structure):
+    """include/focnerf.h `FocOptimTensor`, field for field: one tensor of an optimizer step (tests/test_optim_host.py compares names, order, size)."""
+    _fields_ = [
+        ("param", c_vp), ("grad", c_vp), ("exp_avg", c_vp), ("exp_avg_sq", c_vp), ("step", c_vp),
+        ("lr_tensor", c_vp),
+        ("n", ctypes.c_int64),
+        ("lr", f64), ("beta1", f64), ("beta2", f64), ("eps", f64), ("weight_decay", f64),
+    ]
+
+
+class FocOptimStep(ctypes.Structure):
+    """include/focnerf.h `FocOptimStep`, field for field: one call of foc_optim_step."""
+    _fields_ = [
+        ("struct_bytes", u32),
+        ("tensor_bytes", u32),
+        ("n_tensors", ctypes.c_int32),
+        ("phase", u32), ("zero_grads", u32),
+        ("growth_interval", ctypes.c_int32),
+        ("growth_factor", f32), ("backoff_factor", f32),
+        ("tensors", ctypes.POINTER(FocOptimTensor)),
+        ("scale", c_vp),
+        ("growth_tracker", c_vp),
+        ("grad_scale", c_vp), ("found_inf", c_vp),
+        ("workspace", c_vp),
+        ("workspace_bytes", u64),
+    ]
+
+
 # name -> (restype, [argtypes]) — one entry per declaration in include/focnerf.h
 SIGNATURES = {
     "foc_abi_version": (i32, []),
@@ -243,6 +271,8 @@ SIGNATURES = {
     "foc_score_workspace_bytes": (u64, [u32, u32, u32]),
     "foc_score_quantize": (i32, [c_vp, c_vp, c_vp, c_vp, u32, u32, u32, c_vp, c_vp, c_vp, c_vp]),
     "foc_score_view": (i32, [c_vp, c_vp, u32, u32, u32, c_vp, u32, f64, f64, c_vp, c_vp, u64, c_vp]),
+    "foc_optim_workspace_bytes": (ctypes.c_size_t, [i32]),
+    "foc_optim_step": (i32, [ctypes.POINTER(FocOptimStep), c_vp]),
 }
 
 

@@ -21,6 +21,7 @@
 #ifndef FOCNERF_H
 #define FOCNERF_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -1195,6 +1196,70 @@ int foc_score_quantize(const float *image4, const float *depth, const float *gt,
                        uint8_t *pred_u8, uint8_t *gt_u8, uint8_t *depth_u8, void *stream);
 int foc_score_view(const uint8_t *pred_u8, const uint8_t *gt_u8, uint32_t H, uint32_t W, uint32_t B, const double *taps,
                    uint32_t radius, double C1, double C2, double *out, void *workspace, uint64_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * The optimizer step (csrc/optim.hip; no reference binding: the reference trainer runs torch.optim.Adam(betas=(0.9, 0.99), eps=1e-15)
+ * under torch's GradScaler, nerf/utils.py:1225-1235): the overflow check of the scaled grads, the decision to skip, the scale update,
+ * the unscale and Adam with L2 weight decay, for up to FOC_OPTIM_MAX_TENSORS fp32 tensors per call. Every tensor: param, grad, exp_avg,
+ * exp_avg_sq [n] fp32 contiguous (4-byte aligned; 16-byte accesses where all four are 16-byte aligned), step: its 0-dim fp32 counter
+ * on the device, lr_tensor: a 0-dim fp32 learning rate on the device or NULL (then `lr`). The descriptors are read on the host and
+ * travel in the kernel arguments: nothing of the struct has to outlive the call.
+ *
+ * Per element, in fp32, one rounding per operation: g = grad * inv_scale; if weight_decay != 0: g = fma(weight_decay, p, g);
+ * m = fma(g - m, 1 - beta1, m); v = fma(1 - beta2, g * g, beta2 * v); p = p - step_size * m / (sqrt(v) / bc2 + eps), with
+ * step_size = lr / (1 - beta1^t) and bc2 = sqrt(1 - beta2^t) computed in double from the tensor's own counter (t = step + 1) and
+ * rounded once, inv_scale = 1 / scale in fp32.
+ *
+ * Three forms, chosen by the pointers:
+ *   scale and growth_tracker (both device, fp32 and int32)     phase FOC_OPTIM_STEP: two launches. The check reads every grad; its last
+ *       workgroup decides: skip when any element is not finite; step counters advance unless skipped; scale and tracker follow
+ *       torch._amp_update_scale_ (overflow: scale *= backoff_factor, tracker = 0; else tracker += 1 and, when it reaches
+ *       growth_interval, scale *= growth_factor if that is finite, tracker = 0). The update then reads only the decision.
+ *       A step of MORE than 16 tensors: FOC_OPTIM_CHECK for every group (the check alone), FOC_OPTIM_DECIDE once (tensors are not
+ *       read), then for every group the external form below with found_inf = (float *)workspace + 5 and grad_scale =
+ *       (float *)workspace + 6, where the decision has left them — all with the same workspace, on one stream.
+ *   grad_scale and / or found_inf (device fp32, either may be NULL), scale NULL      somebody else (torch's GradScaler) has checked:
+ *       skipped when *found_inf != 0, inv_scale = 1 / *grad_scale (1 without it). Scale and tracker are not touched.
+ *   neither                                                    plain Adam.
+ * In the last two forms a one-workgroup launch writes the decision and the corrections and advances the counters, then the update runs
+ * as above. A skipped step leaves params, moments and counters bit-for-bit; zero_grads != 0 writes zeros to the grads in the same
+ * pass — also in a skipped step (the grads of a skipped step are of no use to anybody; torch would leave them).
+ * workspace: foc_optim_workspace_bytes(n_tensors) device bytes (0 for n_tensors outside 1 .. 16), 4-byte aligned, ZEROED ONCE by the
+ * caller; every call leaves its flag and ticket words at zero again, so steps and graph replays need no memset. One workspace serves
+ * one stream at a time.
+ * Refused with FOC_E_INVALID before any launch: a null struct; struct_bytes != sizeof(FocOptimStep) or tensor_bytes !=
+ * sizeof(FocOptimTensor); n_tensors outside 1 .. 16; a null pointer (tensors, workspace, a tensor's param / grad / exp_avg /
+ * exp_avg_sq / step; scale without growth_tracker or the reverse; CHECK or DECIDE without them); a negative size; a beta outside
+ * [0, 1); negative eps, lr or weight_decay; a workspace that is too small; a scaler together with external pointers. `stream` is a
+ * hipStream_t. No order-dependent sums: FOC_DETERMINISTIC changes nothing here and refuses nothing.
+ * --------------------------------------------------------------------------- */
+#define FOC_OPTIM_MAX_TENSORS 16
+#define FOC_OPTIM_CHUNK 4096 /* elements per chunk: one workgroup of the update */
+#define FOC_OPTIM_STEP 0
+#define FOC_OPTIM_CHECK 1
+#define FOC_OPTIM_DECIDE 2
+typedef struct FocOptimTensor {
+    float *param, *grad, *exp_avg, *exp_avg_sq, *step;
+    const float *lr_tensor;
+    int64_t n;
+    double lr, beta1, beta2, eps, weight_decay;
+} FocOptimTensor;
+typedef struct FocOptimStep {
+    uint32_t struct_bytes;
+    uint32_t tensor_bytes;
+    int32_t n_tensors;
+    uint32_t phase, zero_grads;
+    int32_t growth_interval;
+    float growth_factor, backoff_factor;
+    const FocOptimTensor *tensors;
+    float *scale;
+    int32_t *growth_tracker;
+    const float *grad_scale, *found_inf;
+    void *workspace;
+    uint64_t workspace_bytes;
+} FocOptimStep;
+size_t foc_optim_workspace_bytes(int n_tensors);
+int foc_optim_step(const FocOptimStep *step, void *stream);
 
 #ifdef __cplusplus
 }
