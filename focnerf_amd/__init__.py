@@ -11,9 +11,12 @@ from .mesh import (density_volume, scene_volume, marching_cubes, extract_geometr
 from .score import score_view, ViewScore  # noqa: F401  (PSNR and SSIM of a combined view for every background, on the device)
 from . import optim  # noqa: F401
 from .optim import FusedAdam, LossScaler  # noqa: F401  (the trainer's optimizer step: overflow check, unscale and Adam in two launches)
+from . import batch  # noqa: F401
+from .batch import DeviceDataset, RaySampler, photo_loss  # noqa: F401  (a training batch in one launch; loss, gradient and error map in one more)
 
 __all__ = ["raymarching", "gridencoder", "freqencoder", "ffmlp", "activation", "encoding", "shencoder",
            "renderer", "network", "combine", "fixedcull", "use_deterministic", "is_deterministic", "deterministic", "Attribution", "placement", "Placement",
            "mesh", "density_volume", "scene_volume", "marching_cubes", "extract_geometry", "extract_scene_geometry", "write_ply", "save_mesh",
            "score", "score_view", "ViewScore",
-           "optim", "FusedAdam", "LossScaler"]
+           "optim", "FusedAdam", "LossScaler",
+           "batch", "DeviceDataset", "RaySampler", "photo_loss"]

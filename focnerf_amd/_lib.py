@@ -24,7 +24,7 @@ i32 = ctypes.c_int
 
 FOC_F32 = 0
 FOC_F16 = 1
-
+FOC_U8 = 2      # images of foc_batch_sample only
 
 
 class FocOccTrainNode(ctypes.Structure):
@@ -273,6 +273,13 @@ SIGNATURES = {
     "foc_score_view": (i32, [c_vp, c_vp, u32, u32, u32, c_vp, u32, f64, f64, c_vp, c_vp, u64, c_vp]),
     "foc_optim_workspace_bytes": (ctypes.c_size_t, [i32]),
     "foc_optim_step": (i32, [ctypes.POINTER(FocOptimStep), c_vp]),
+    "foc_philox4x32_10": (i32, [ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32)]),
+    "foc_batch_workspace_bytes": (u64, []),
+    "foc_batch_sample": (i32, [c_vp, i32, u32, u32, u32, u32, c_vp, f32, f32, f32, f32, c_vp, c_vp, u64, u32, c_vp, i32, i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                               c_vp, u64, u32, c_vp]),
+    "foc_view_rays": (i32, [c_vp, f32, f32, f32, f32, u32, u32, c_vp, c_vp, c_vp]),
+    "foc_photo_loss_workspace_bytes": (u64, []),
+    "foc_photo_loss": (i32, [c_vp, i32, c_vp, u32, i32, f32, c_vp, u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, u64, c_vp]),
 }
 
 

@@ -294,7 +294,7 @@ def _background(bg_color, N, dev):
         return None, 1.0
     if torch.is_tensor(bg_color):
         if bg_color.numel() > 1:
-            return bg_color.to(dev, torch.float32).expand(N, 3).contiguous(), 0.0
+            return bg_color.to(dev, torch.float32).reshape(-1, 3).expand(N, 3).contiguous(), 0.0      # [3], [N,3] or the sampler's [1,N,3]
         return None, float(bg_color)
     return None, float(bg_color)
 

@@ -1261,6 +1261,66 @@ typedef struct FocOptimStep {
 size_t foc_optim_workspace_bytes(int n_tensors);
 int foc_optim_step(const FocOptimStep *step, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Training batches and the photometric loss (csrc/batch.hip; no reference binding: the reference builds a batch with torch ops in
+ * nerf/provider.py:398-447 NeRFDataset.collate and nerf/utils.py:57-157 get_rays, and its loss in nerf/utils.py:840-899
+ * Trainer.train_step). One launch each, no host synchronisation, no float atomics: the same bits on every run, FOC_DETERMINISTIC
+ * changes nothing and refuses nothing.
+ *
+ * Random numbers: Philox4x32-10, stateless (multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9, 0xBB67AE85). key = (seed low
+ * 32, seed high 32), counter = (ray index r, step low 32, step high 32, stream). Stream 0: word 0 the pixel, words 1 and 2 the two
+ * jitters of the error-map route; stream 1: words 0..2 the background colour. A uniform float is (w >> 8) * 2^-24, in [0, 1); a pixel is
+ * (uint64(w) * (H * W)) >> 32 (bias at most H * W / 2^32). Every value of a batch is a pure function of (seed, step, r); the number of
+ * workgroups does not change it. foc_philox4x32_10 is that function on the host (ctr: 4 words, key: 2 words -> out: 4 words).
+ *
+ * foc_batch_sample  images [V,H,W,C] (FOC_U8, FOC_F16 or FOC_F32; C = 3 or 4), poses [V,4,4] fp32, order [V] int32 (an epoch's
+ *     permutation), step: one int64, all on the device; view = order[step mod V] (an entry outside 0 .. V-1 is taken mod V). Outputs:
+ *     inds [N] int64, rays_o, rays_d, bg_color, gt_rgb [N,3] fp32, view [1] int32.
+ *     The pixel (nerf/utils.py:96): the draw above; with inds_coarse [N] int64 (:101-110, cells of the 128 x 128 error map; NULL
+ *     without), in fp32 with no contraction: row = min(int(float(c / 128) * sx + u1 * sx), H - 1) with sx = H / 128.f, the column
+ *     likewise from c % 128, sy = W / 128.f and u2. inds = row * W + col.
+ *     The ray (:131-139): x = ((col + 0.5f) - cx) / fx, y = ((row + 0.5f) - cy) / fy, n = sqrt((x x + y y) + 1), (x, y, 1) / n, then
+ *     rays_d[k] = (R[k][0] dx + R[k][1] dy) + R[k][2] dz with R the pose's 3 x 3; rays_o is the pose's translation, bit for bit.
+ *     The pixel's value: a uint8 is float(v) / 255.f, an fp16 is widened exactly. linear != 0 (:844-845, color_space 'linear') applies
+ *     srgb_to_linear (:52-53) to r, g, b in double, rounded once: x < 0.04045 ? x / 12.92 : pow((x + 0.055) / 1.055, 2.4).
+ *     Background and target (:847-858): with C = 4 and random_bg != 0, bg = the three stream-1 floats and gt = rgb * a + bg * (1 - a),
+ *     each product and sum its own fp32 operation; otherwise bg = 1 and gt = rgb (C = 3) or the same blend against 1 (C = 4).
+ *     The step counter advances inside the launch: every workgroup reads `step` first and takes a ticket when it is done, the last one
+ *     writes step + 1 and view and puts the ticket back to zero. A replayed graph draws batch t, t + 1, t + 2 with nothing from the host.
+ *     workspace: foc_batch_workspace_bytes() device bytes, 4-byte aligned, ZEROED ONCE by the caller; one workspace serves one stream
+ *     at a time. workgroups: 0 for the library's choice, or 1 .. 1024 (a test's way to show that the launch size changes nothing).
+ * foc_view_rays     the same ray arithmetic for all H * W pixels of one view, row-major (:127, the evaluation route): pose [4,4] on
+ *     the device -> rays_o, rays_d [H*W,3].
+ * foc_photo_loss    pred [N,3] (FOC_F32, or FOC_F16 widened exactly), gt [N,3] fp32; kind FOC_LOSS_MSE, or FOC_LOSS_HUBER with delta in
+ *     torch.nn.HuberLoss's definition (the reference's commented alternative, delta 0.1). Per component d = pred - gt;
+ *     MSE: l = d * d, g = 2 d; Huber: |d| <= delta: l = 0.5f * (d * d), g = d; else l = delta * (|d| - 0.5f * delta), g = +-delta.
+ *     ray_loss [N] = ((l0 + l1) + l2) / 3.f (:867); grad [N,3] = g / float(3 N), which is d(mean loss) / d(pred); loss [1] =
+ *     float(sum / N) with the sum in double: a fixed tree per workgroup, one slot per workgroup, the last workgroup (a ticket) adds
+ *     the slots in index order (:899). With error_map [V,16384] fp32 (NULL without), view [1] int32 and inds_coarse [N] int64:
+ *     error_map[view, c] = 0.1f * old + 0.9f * ray_loss (:893-894); the cells are distinct (a draw without replacement), so no
+ *     atomics; a view outside 0 .. V-1 updates nothing.
+ *     workspace: foc_photo_loss_workspace_bytes() device bytes, 8-byte aligned, ZEROED ONCE by the caller, one stream at a time.
+ * Refused before any launch: a null pointer; C not 3 or 4; an unknown dtype (FOC_E_DTYPE) or kind; N < 1; H * W outside 1 .. 2^30;
+ * V < 1; intrinsics that are not finite, fx or fy zero; a delta that is not finite and > 0; a workspace that is too small.
+ * The caller clamps N to H * W as the reference does (:73).
+ * --------------------------------------------------------------------------- */
+#define FOC_U8 2 /* image dtype of foc_batch_sample, beside FOC_F32 and FOC_F16 */
+#define FOC_LOSS_MSE 0
+#define FOC_LOSS_HUBER 1
+#define FOC_PHOTO_LOSS_MAX_WGS 256 /* slots of the loss's workspace */
+int foc_philox4x32_10(const uint32_t *ctr, const uint32_t *key, uint32_t *out);
+uint64_t foc_batch_workspace_bytes(void);
+int foc_batch_sample(const void *images, int image_dtype, uint32_t V, uint32_t H, uint32_t W, uint32_t C, const float *poses, float fx,
+                     float fy, float cx, float cy, const int32_t *order, int64_t *step, uint64_t seed, uint32_t N,
+                     const int64_t *inds_coarse, int random_bg, int linear, int64_t *inds, float *rays_o, float *rays_d, float *bg_color,
+                     float *gt_rgb, int32_t *view, void *workspace, uint64_t workspace_bytes, uint32_t workgroups, void *stream);
+int foc_view_rays(const float *pose, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W, float *rays_o, float *rays_d,
+                  void *stream);
+uint64_t foc_photo_loss_workspace_bytes(void);
+int foc_photo_loss(const void *pred, int pred_dtype, const float *gt, uint32_t N, int kind, float delta, float *error_map, uint32_t V,
+                   const int32_t *view, const int64_t *inds_coarse, float *ray_loss, float *grad, float *loss, void *workspace,
+                   uint64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
