@@ -2,8 +2,11 @@
 
 The reference imports `encoding.get_encoder('sphere_harmonics')` (nerf/network_ff.py:5,43) but
 ships neither encoding.py nor shencoder/ (SURVEY.md H2). This is the published degree-4 basis
-used by torch-ngp / instant-ngp, written with torch ops — PARITY UNPINNED (nothing in the
-reference tree to check it against; orthonormality is tested instead).
+used by torch-ngp / instant-ngp, written with torch ops. Nothing in the reference tree pins it,
+so the definition does: tests/pointwise_ref.py builds the basis from the associated-Legendre
+recurrence (Condon-Shortley phase) and the normalisation, tests/test_pointwise_ref.py holds this
+expression and every other copy in the tree to it (and the Gram matrix on the sphere to the
+identity), and tests/test_gpu_pointwise_reference.py holds the kernels to it.
 """
 import torch
 import torch.nn as nn

@@ -49,10 +49,13 @@ form's fb / bb.
 Routes: `ROUTES`, `kernels()` restates the selection of csrc/ffmlp.hip mlp_bwd_launch / mlp_bwd_fused_launch / mlp_bwd_entry. `PLAN`
 maps every case to the routes it runs on. Loop-edge batch sizes (`loop_case`) are computed from the number of compute units.
 
-Out of scope: hidden activations 1..5 (device expf / sinf / logf accuracy is a model of its own;
-test_gpu_ffmlp.py::test_other_hidden_activations_forward_and_backward stays), the colour-head and whole-field forms
-(foc_color_head_*, foc_field_forward_train*, foc_nerf_field_inference*: they emit no intermediates and existing tests pin them bit for
-bit, on integer data, to the plain MLP on the materialised input — which is what is measured here), and performance.
+Hidden activations 1..5 (exponential, sine, sigmoid, squareplus, softplus) are measured layer by layer in the same way by
+tests/pointwise_ref.py and tests/test_gpu_pointwise_reference.py, which build on this module's `product`, `delta`, `grad_inputs` and
+`grad_weights`: the float64 sum names the half (or halves) the activation saw, the activation has a bound of its own.
+
+Out of scope: the colour-head and whole-field forms (foc_color_head_*, foc_field_forward_train*, foc_nerf_field_inference*: they emit
+no intermediates and existing tests pin them bit for bit, on integer data, to the plain MLP on the materialised input — which is what
+is measured here; the SH half-row of the whole-field kernel is observed by test_gpu_pointwise_reference.py), and performance.
 """
 import math
 

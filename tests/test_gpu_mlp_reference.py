@@ -14,7 +14,8 @@ FOC_DETERMINISTIC=1, hidden 256 (also deterministic), wide input. Cases: twelve 
 row tiles; gradient scales 2^-16 .. 2^8; cancelling row pairs; totals beyond half; one inf in the gradient; and five loop-edge batches
 computed from the number of compute units at which the persistent kernels' workgroups meet rows a second time.
 
-Out of scope: hidden activations 1..5, the colour-head and whole-field forms, performance (mlp_ref's docstring says why).
+Hidden activations 1..5 have their own file, tests/test_gpu_pointwise_reference.py (same method, on this module's helpers).
+Out of scope: the colour-head and whole-field forms, performance (mlp_ref's docstring says why).
 
 Measured on MI355X (256 CUs), worst |kernel - float64| / bound, asserted <= 1, nothing excluded. The row-wise quantities have at most
 256 products per element, so nearly all of their bound is the half rounding of the result itself and a worst ratio just below 1 is what a
