@@ -9,6 +9,7 @@ from .placement import Placement  # noqa: F401  (rotation, uniform scale and tra
 from .mesh import (density_volume, scene_volume, marching_cubes, extract_geometry, extract_scene_geometry,  # noqa: F401  (triangle meshes
                    write_ply, save_mesh)                                                                   # of objects and placed scenes)
 from .score import score_view, ViewScore  # noqa: F401  (PSNR and SSIM of a combined view for every background, on the device)
+from .normals import density_gradient, field_normals, decode_normal_map, render_normals  # noqa: F401  (surface normals from the density field)
 from . import optim  # noqa: F401
 from .optim import FusedAdam, LossScaler  # noqa: F401  (the trainer's optimizer step: overflow check, unscale and Adam in two launches)
 from . import batch  # noqa: F401
@@ -18,5 +19,6 @@ __all__ = ["raymarching", "gridencoder", "freqencoder", "ffmlp", "activation", "
            "renderer", "network", "combine", "fixedcull", "use_deterministic", "is_deterministic", "deterministic", "Attribution", "placement", "Placement",
            "mesh", "density_volume", "scene_volume", "marching_cubes", "extract_geometry", "extract_scene_geometry", "write_ply", "save_mesh",
            "score", "score_view", "ViewScore",
+           "normals", "density_gradient", "field_normals", "decode_normal_map", "render_normals",
            "optim", "FusedAdam", "LossScaler",
            "batch", "DeviceDataset", "RaySampler", "photo_loss"]

@@ -252,6 +252,8 @@ SIGNATURES = {
     "foc_nerf_field_inference": (i32, [c_vp, i32, c_vp, u32, u32, u32, c_vp, u32, c_vp, u32, u32, u32, u32, c_vp, c_vp, c_vp, c_vp]),
     "foc_nerf_field_inference_pad": (i32, [c_vp, i32, c_vp, u32, u32, u32, c_vp, u32, c_vp, u32, u32, u32, u32, c_vp, c_vp, c_vp, f32, c_vp]),
     "foc_nerf_field_inference_pad31": (i32, [c_vp, i32, c_vp, u32, u32, u32, c_vp, u32, c_vp, u32, u32, u32, u32, c_vp, c_vp, c_vp, f32, c_vp]),
+    "foc_field_normals": (i32, [c_vp, u32, c_vp, c_vp, u32, u32, u32, f32, u32, u32, i32, u32, i32, c_vp, c_vp, u32, u32, u32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                c_vp]),
     "foc_mark_untrained_grid": (i32, [c_vp, u32, f32, f32, f32, f32, f32, u32, u32, c_vp, c_vp, c_vp]),
     "foc_grid_cells_xyz": (i32, [u32, u32, f32, c_vp, c_vp, c_vp]),
     "foc_grid_update_sample_workspace_bytes": (u64, [u32, u32]),

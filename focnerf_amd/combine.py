@@ -285,12 +285,13 @@ def combine_packed(fields4, nears, fars, bgs=(1.0, 0.0), want_merged=False, ops=
     return ops.select_composite(fields4, nears.contiguous().float(), fars.contiguous().float(), tuple(bgs), want_merged)
 
 
-def _placed_scene(who, models, occupancies, placements, rays_o, rays_d, T, scene_aabb, yolo_details):
+def _placed_scene(who, models, occupancies, placements, rays_o, rays_d, T, scene_aabb, yolo_details, channels="rgb"):
     """The arguments of `placed_field_fns` / `culled_field_fns`, checked: -> (per-object (model, plan, occupancy, placement, yolo) tuples,
     rays_o, rays_d, T, box, nears, fars)."""
     from . import raymarching
     from .field import field_plan
     from .fixedcull import _check_culled, _scene_box
+    from .normals import check_channels
     from .placement import Placement
     models, occupancies = list(models), list(occupancies)
     placements = [Placement() if p is None else p for p in placements]
@@ -306,6 +307,7 @@ def _placed_scene(who, models, occupancies, placements, rays_o, rays_d, T, scene
         if not isinstance(p, Placement):
             raise ValueError(f"{who}: placements must be focnerf_amd.Placement objects (or None for the identity)")
         _check_culled(m, plan, occ)
+        check_channels(who, channels, plan)
         if float(m.min_near) != float(models[0].min_near):
             raise ValueError(f"{who}: the objects must share min_near (one near / far per ray): {float(m.min_near)} and "
                              f"{float(models[0].min_near)}")
@@ -314,38 +316,40 @@ def _placed_scene(who, models, occupancies, placements, rays_o, rays_d, T, scene
     return list(zip(models, plans, occupancies, placements, yolos)), rays_o, rays_d, T, box, nears, fars
 
 
-def placed_field_fns(models, occupancies, placements, rays_o, rays_d, T, scene_aabb, yolo_details=None, weight_thresh=1e-10):
+def placed_field_fns(models, occupancies, placements, rays_o, rays_d, T, scene_aabb, yolo_details=None, weight_thresh=1e-10, channels="rgb"):
     """Objects placed in one scene, ready for the combiner: -> (field_fns, nears, fars) for `ObjectCombiner.render_view(field_fns, N, nears,
     fars, T, ...)` and `combine_packed`. Entry k is `models[k]` with its `occupancies[k]` (a `fixedcull.Occupancy`) under `placements[k]`
     (a `Placement`; None = the identity) — the same model may appear more than once with different placements, and hiding an object
     means leaving it out. rays_o / rays_d [N,3]: the view's rays; scene_aabb: float32 [6] tensor on their device. nears / fars [N] are
     those of the view's rays against the scene's box (the first model's `min_near`, which all must share): every field is built along
-    them, and the composite must run along the same. yolo_details: None, or one entry per object."""
+    them, and the composite must run along the same. yolo_details: None, or one entry per object. channels="normal": every field carries
+    its encoded surface normals (rotated into the scene) where the colour stands (`render_field4`); every network must be one the
+    normals kernel serves (ValueError otherwise)."""
     from .fixedcull import culled_field4
     objects, rays_o, rays_d, T, box, nears, fars = _placed_scene("placed_field_fns", models, occupancies, placements, rays_o, rays_d, T, scene_aabb,
-                                                                 yolo_details)
+                                                                 yolo_details, channels)
 
     def make(m, plan, occ, p, yolo):
         def fn(lo, hi, out=None):
             if out is None:
                 out = torch.empty(hi - lo, T, 4, dtype=torch.float32, device=rays_o.device)
-            return culled_field4(m, plan, rays_o[lo:hi], rays_d[lo:hi], nears[lo:hi], fars[lo:hi], box, T, weight_thresh, yolo, out, occ, p)
+            return culled_field4(m, plan, rays_o[lo:hi], rays_d[lo:hi], nears[lo:hi], fars[lo:hi], box, T, weight_thresh, yolo, out, occ, p, channels)
         return fn
     return [make(*args) for args in objects], nears, fars
 
 
-def culled_field_fns(models, occupancies, placements, rays_o, rays_d, T, scene_aabb, yolo_details=None, weight_thresh=1e-10):
+def culled_field_fns(models, occupancies, placements, rays_o, rays_d, T, scene_aabb, yolo_details=None, weight_thresh=1e-10, channels="rgb"):
     """`placed_field_fns` for `combine_culled`: the same arguments and checks -> (fns, nears, fars), but `fns[k](lo, hi)` (hi > lo) stops in
     front of the pack and returns the object's `fixedcull.CulledField` on rays lo:hi — no [hi-lo, T, 4] field is written."""
     from .fixedcull import culled_lists
     objects, rays_o, rays_d, T, box, nears, fars = _placed_scene("culled_field_fns", models, occupancies, placements, rays_o, rays_d, T, scene_aabb,
-                                                                 yolo_details)
+                                                                 yolo_details, channels)
 
     def make(m, plan, occ, p, yolo):
         def fn(lo, hi):
             if not 0 <= lo < hi <= rays_o.shape[0]:
                 raise ValueError(f"culled_field_fns: rays {lo}:{hi} of {rays_o.shape[0]}: a non-empty range of the view's rays expected")
-            return culled_lists(m, plan, rays_o[lo:hi], rays_d[lo:hi], nears[lo:hi], fars[lo:hi], box, T, weight_thresh, yolo, occ, p)
+            return culled_lists(m, plan, rays_o[lo:hi], rays_d[lo:hi], nears[lo:hi], fars[lo:hi], box, T, weight_thresh, yolo, occ, p, channels)
         return fn
     return [make(*args) for args in objects], nears, fars
 
@@ -373,11 +377,12 @@ def combine_culled(culled, nears, fars, bgs=(1.0, 0.0), want_merged=False, attri
 
 
 def render_scene_culled(models, occupancies, placements, rays_o, rays_d, T, scene_aabb, bgs=(1.0, 0.0), max_ray_batch=16384, attribution=False,
-                        yolo_details=None):
+                        yolo_details=None, channels="rgb"):
     """One view of placed objects on ONE device through `culled_field_fns` + `combine_culled`, in chunks of `max_ray_batch` rays:
     -> (image4 [len(bgs),N,4], depth [N][, Attribution]). The bits of `placed_field_fns` + `combine_packed` without the objects' dense
-    fields; every object still costs one host read of its occupied count per chunk."""
-    fns, nears, fars = culled_field_fns(models, occupancies, placements, rays_o, rays_d, T, scene_aabb, yolo_details)
+    fields; every object still costs one host read of its occupied count per chunk. channels="normal": a normal view of the scene
+    (`normals.decode_normal_map` of image4 for bgs (1, 0)); depth and attribution are those of the colour view."""
+    fns, nears, fars = culled_field_fns(models, occupancies, placements, rays_o, rays_d, T, scene_aabb, yolo_details, channels=channels)
     N, dev, chunk, n_obj = nears.shape[0], nears.device, int(max_ray_batch), len(fns)
     if chunk < 1:
         raise ValueError(f"render_scene_culled: max_ray_batch must be >= 1, got {chunk}")

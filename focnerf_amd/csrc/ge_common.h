@@ -17,6 +17,23 @@ struct GeLevels {
     uint32_t merge_max_res;                    // binned backward: levels up to this resolution merge runs of samples in one cell (count + scatter)
 };
 
+// Host: the per-level scale and resolution of a call (L <= GE_MAX_LEVELS, else 1), and the merge threshold of the binned backward
+static int ge_make_levels(uint32_t L, float S, uint32_t H, GeLevels &lv) {
+    if (L > GE_MAX_LEVELS) return 1;
+    for (uint32_t l = 0; l < L; l++) {
+        // gridencoder.cu:138-139, evaluated with the host libm (identical to oracle/oracle.c)
+        const float sc = exp2f((float)l * S) * (float)H - 1.0f;
+        lv.scale[l] = sc;
+        lv.resolution[l] = (uint32_t)ceil((double)sc) + 1;
+    }
+    for (uint32_t l = L; l < GE_MAX_LEVELS; l++) { lv.scale[l] = 0; lv.resolution[l] = 1; }
+    int merge_res = foc_opt(FOC_OPT_GB_MERGE_MAX_RES);                 // <= 1023: the run key packs 10 bits per axis
+    if (merge_res > 1023) merge_res = 1023;
+    if (merge_res < 0) merge_res = 0;
+    lv.merge_max_res = (uint32_t)merge_res;
+    return 0;
+}
+
 // ---- storage-type helpers -------------------------------------------------------------
 // Keeps an fp32 value materialised in a VGPR. Without it LLVM folds `(half)fma(a,b,c)` into
 // v_fma_mixlo_f16, which rounds the exact fma ONCE to fp16; the reference (and the oracle) round to

@@ -894,22 +894,6 @@ __global__ void __launch_bounds__(256) k_rows_to_planes(const U *__restrict__ ro
     }
 }
 
-static int ge_make_levels(uint32_t L, float S, uint32_t H, GeLevels &lv) {
-    if (L > GE_MAX_LEVELS) return 1;
-    for (uint32_t l = 0; l < L; l++) {
-        // gridencoder.cu:138-139, evaluated with the host libm (identical to oracle/oracle.c)
-        const float sc = exp2f((float)l * S) * (float)H - 1.0f;
-        lv.scale[l] = sc;
-        lv.resolution[l] = (uint32_t)ceil((double)sc) + 1;
-    }
-    for (uint32_t l = L; l < GE_MAX_LEVELS; l++) { lv.scale[l] = 0; lv.resolution[l] = 1; }
-    int merge_res = foc_opt(FOC_OPT_GB_MERGE_MAX_RES);                 // <= 1023: the run key packs 10 bits per axis
-    if (merge_res > 1023) merge_res = 1023;
-    if (merge_res < 0) merge_res = 0;
-    lv.merge_max_res = (uint32_t)merge_res;
-    return 0;
-}
-
 // (dtype, D, C) of a call -> its launch (gridencoder.cu:393-398, 437-442, 633-638). D is refused first, then C (ge_dispatch), both
 // on the host before anything is launched.
 static int ge_call(GeOp op, const GeCall &a) {

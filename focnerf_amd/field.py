@@ -75,6 +75,7 @@ class FieldPlan:
     background: bool = False            # the background model (encoder_bg -> bg_net) as one kernel each way (background.py, csrc/background.hip)
     occ_object: bool = False            # `occ` for an object-conditioned network: the node with the encoded object feature (occtrain._occ_train with the feature)
     native_loop_object: bool = False    # `native_loop` for an object-conditioned network: the step takes the feature (and the column-47 pad twin)
+    normals: bool = False               # sigma, the density logit's position gradient and the encoded normal in one kernel (normals.field_normals)
 
 
 def pad_twin(name, pad, obj):
@@ -144,6 +145,9 @@ def field_plan(model):
     bg_radius = getattr(model, "bg_radius", 0)
     occ_common = field and tail and same_activation and _on("FOC_FUSED_OCC")
     native_common = infer and getattr(model, "density_scale", 1) == 1 and plain_grid and _on("FOC_RENDER_NATIVE")
+    # csrc/normals.hip: the plain hash grid with 16 levels, the 32 -> 64 x (1..3) -> 16 ReLU sigma network whose column 0 is the density logit
+    normals = (hash_grid and plain_grid and enc.offsets.numel() == 17 and sigma_32_64 and sigma_16 and sigma.activation == 0
+               and 1 <= sigma.num_layers <= 3 and _on("FOC_FUSED_NORMALS"))
     return FieldPlan(
         grid=grid, levels=enc.offsets.numel() - 1 if grid is not None else 0, sigma=sigma, colour=colour, uses_object_feature=obj,
         field=field, tail=tail, infer=infer,
@@ -154,7 +158,8 @@ def field_plan(model):
         background=background,
         # an object-conditioned network: the object node sequences the whole-field kernels (their layer pairs), and no background model
         occ_object=occ_common and obj and whole_field and bg_radius <= 0,
-        native_loop_object=native_common and obj and bg_radius <= 0)
+        native_loop_object=native_common and obj and bg_radius <= 0,
+        normals=normals)
 
 
 def _raw_stream_of(device):

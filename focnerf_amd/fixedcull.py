@@ -150,10 +150,13 @@ class CulledField:
         self.N, self.T = int(N), int(T)
 
 
-def culled_lists(model, plan, rays_o, rays_d, nears, fars, aabb, T, weight_thresh, yolo_details, occ, placement=None):
+def culled_lists(model, plan, rays_o, rays_d, nears, fars, aabb, T, weight_thresh, yolo_details, occ, placement=None, channels="rgb"):
     """`culled_field4` in front of its pack, for N > 0 rays: cull -> ONE host read of the count -> emit -> encoder + whole-field kernel on
-    the occupied samples. -> a `CulledField` (sigma_gain 1 without a placement)."""
+    the occupied samples. -> a `CulledField` (sigma_gain 1 without a placement). channels="normal": rgb_c holds the encoded normals
+    0.5 + 0.5 n of `normals.field_normals`, rotated object -> scene by the placement's rotation."""
     from .field import field_infer
+    from .normals import check_channels, field_normals
+    want_normal = check_channels("render_field4", channels, plan)
     N, dev = rays_o.shape[0], rays_o.device
     if occ.bitfield.device != dev:
         raise ValueError(f"render_field4: the occupancy bitfield is on {occ.bitfield.device}, the rays on {dev}")
@@ -164,17 +167,20 @@ def culled_lists(model, plan, rays_o, rays_d, nears, fars, aabb, T, weight_thres
     if m_occ:
         enc_in_c, dirs_c = fixed_cull_emit(rays_o, rays_d, nears, fars, aabb, T, model.bound, mask, offsets, m_occ, placement)
         obj_feat = model.encode_object_feature(yolo_details, dev) if plan.uses_object_feature else None
-        sigma, rgb = field_infer(model, enc_in_c, dirs_c, dir_div=1, dir_block=0, obj_feat=obj_feat)
+        if want_normal:
+            sigma, rgb = field_normals(model, enc_in_c, None if placement is None else placement.rotation)
+        else:
+            sigma, rgb = field_infer(model, enc_in_c, dirs_c, dir_div=1, dir_block=0, obj_feat=obj_feat)
     return CulledField(mask, offsets, m_occ, sigma, rgb, model.density_scale, weight_thresh, 1.0 if placement is None else placement.sigma_gain, N, T)
 
 
-def culled_field4(model, plan, rays_o, rays_d, nears, fars, aabb, T, weight_thresh, yolo_details, out, occ, placement=None):
+def culled_field4(model, plan, rays_o, rays_d, nears, fars, aabb, T, weight_thresh, yolo_details, out, occ, placement=None, channels="rgb"):
     """The culled field along GIVEN nears / fars [N] (of the rays against `aabb`): `culled_lists` -> culled pack. With a placement, `aabb`
     is the scene's box, the object's own box is the model's, and the pack applies the placement's sigma gain."""
     N = rays_o.shape[0]
     if N == 0:
         return out
-    c = culled_lists(model, plan, rays_o, rays_d, nears, fars, aabb, T, weight_thresh, yolo_details, occ, placement)
+    c = culled_lists(model, plan, rays_o, rays_d, nears, fars, aabb, T, weight_thresh, yolo_details, occ, placement, channels)
     if placement is not None:
         check(lib.foc_fixed_field_pack_culled_gain(ptr(c.sigma_c), ptr(c.rgb_c), ptr(c.mask), ptr(c.offsets), c.m_occ, ptr(nears), ptr(fars), N, T,
                                                    c.density_scale, c.thresh, c.sigma_gain, ptr(out), stream_of(out)), "fixed_field_pack_culled_gain")
@@ -184,7 +190,7 @@ def culled_field4(model, plan, rays_o, rays_d, nears, fars, aabb, T, weight_thre
     return out
 
 
-def render_field4_culled(model, plan, rays_o, rays_d, T, weight_thresh, yolo_details, out, occ):
+def render_field4_culled(model, plan, rays_o, rays_d, T, weight_thresh, yolo_details, out, occ, channels="rgb"):
     """`render_field4` with an Occupancy (rays_o / rays_d [N,3] fp32 contiguous, out [N,T,4]): near_far -> cull -> ONE host read of the
     count -> encoder + whole-field kernel on the occupied samples -> culled pack."""
     from . import raymarching
@@ -193,7 +199,7 @@ def render_field4_culled(model, plan, rays_o, rays_d, T, weight_thresh, yolo_det
         return out
     aabb = model.aabb_train if model.training else model.aabb_infer
     nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, aabb, model.min_near)
-    return culled_field4(model, plan, rays_o, rays_d, nears, fars, aabb, T, weight_thresh, yolo_details, out, occ)
+    return culled_field4(model, plan, rays_o, rays_d, nears, fars, aabb, T, weight_thresh, yolo_details, out, occ, None, channels)
 
 
 def _scene_box(scene_aabb, model, dev):
@@ -206,7 +212,7 @@ def _scene_box(scene_aabb, model, dev):
     return scene_aabb.contiguous().view(-1)
 
 
-def render_field4_placed(model, plan, rays_o, rays_d, T, weight_thresh, yolo_details, out, occ, placement, scene_aabb=None):
+def render_field4_placed(model, plan, rays_o, rays_d, T, weight_thresh, yolo_details, out, occ, placement, scene_aabb=None, channels="rgb"):
     """`render_field4` with an Occupancy and a Placement: near / far of the view's rays against the SCENE's box (default: the model's),
     then the sequence of `render_field4_culled` through the placed entry points."""
     from . import raymarching
@@ -218,4 +224,4 @@ def render_field4_placed(model, plan, rays_o, rays_d, T, weight_thresh, yolo_det
         return out
     aabb = _scene_box(scene_aabb, model, rays_o.device)
     nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, aabb, model.min_near)
-    return culled_field4(model, plan, rays_o, rays_d, nears, fars, aabb, T, weight_thresh, yolo_details, out, occ, placement)
+    return culled_field4(model, plan, rays_o, rays_d, nears, fars, aabb, T, weight_thresh, yolo_details, out, occ, placement, channels)

@@ -442,7 +442,7 @@ def render_fixed_steps(model, rays_o, rays_d, yolo_details=None, num_steps=512, 
 
 @torch.no_grad()
 def render_field4(model, rays_o, rays_d, num_steps=512, weight_thresh=1e-10, yolo_details=None, out=None, occupancy=None, placement=None,
-                  scene_aabb=None):
+                  scene_aabb=None, channels="rgb"):
     """What the combiner needs from one object for a chunk of rays — COMBINED.py's `run` (:451-534 with upsample_steps=0, perturb off):
     `densities` [N,T] and `rgbs` [N,T,3] (zero where the object's own compositing weight is <= 1e-10) — PACKED as field4 [N,T,4] fp32
     (sigma, r, g, b), written into `out` when given. Fused path: sample -> encoder -> whole-field kernel -> weights + mask + pack
@@ -459,8 +459,13 @@ def render_field4(model, rays_o, rays_d, num_steps=512, weight_thresh=1e-10, yol
     placement (a `Placement`, default None = the paths above, unchanged; needs `occupancy`): the object stands rotated, scaled and moved
     in a scene. The T positions are those of the view's rays against `scene_aabb` (float32 [6] tensor, default the model's box); each is
     mapped into the object's frame, samples outside the object's own box are empty, and sigma is rescaled by 1 / scale
-    (include/focnerf.h foc_fixed_cull_placed)."""
+    (include/focnerf.h foc_fixed_cull_placed).
+
+    channels ("rgb", the default: everything above, unchanged; or "normal"): "normal" puts the encoded surface normal 0.5 + 0.5 n where the
+    colour stands (`normals.field_normals` in place of `field_infer`; with a placement the normal is rotated into the scene). Sigma, the
+    own-weight mask and the pack are the same. Needs `field_plan(model).normals` (ValueError otherwise, never a fallback)."""
     from .field import field_plan, field_infer
+    from .normals import check_channels, field_normals
     if placement is None and scene_aabb is not None:
         raise ValueError("render_field4: scene_aabb belongs to a placement; without one the object is rendered in its own box")
     if placement is not None and occupancy is None:
@@ -474,19 +479,26 @@ def render_field4(model, rays_o, rays_d, num_steps=512, weight_thresh=1e-10, yol
         out = torch.empty(N, T, 4, dtype=torch.float32, device=dev)
     assert out.shape == (N, T, 4) and out.dtype == torch.float32 and out.is_contiguous()
     plan = field_plan(model)
+    want_normal = check_channels("render_field4", channels, plan)
     if placement is not None:
         from .fixedcull import render_field4_placed
-        return render_field4_placed(model, plan, rays_o, rays_d, T, weight_thresh, yolo_details, out, occupancy, placement, scene_aabb)
+        return render_field4_placed(model, plan, rays_o, rays_d, T, weight_thresh, yolo_details, out, occupancy, placement, scene_aabb, channels)
     if occupancy is not None:
         from .fixedcull import render_field4_culled
-        return render_field4_culled(model, plan, rays_o, rays_d, T, weight_thresh, yolo_details, out, occupancy)
+        return render_field4_culled(model, plan, rays_o, rays_d, T, weight_thresh, yolo_details, out, occupancy, channels)
+    if want_normal and not (plan.infer and model.bg_radius <= 0):
+        raise ValueError("render_field4: channels='normal' needs a network the fused inference serves (field_plan(model).infer) without a "
+                         "background model")
     if plan.infer and model.bg_radius <= 0:
         aabb = model.aabb_train if model.training else model.aabb_infer
         nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, aabb, model.min_near)
         rb = ray_block_default()
         enc_in, _ = fixed_sample(rays_o, rays_d, nears, fars, aabb, None, T, model.bound, ray_block=rb)
         obj_feat = model.encode_object_feature(yolo_details, dev) if plan.uses_object_feature else None
-        sigma, rgb = field_infer(model, enc_in, rays_d, dir_div=T, dir_block=rb, obj_feat=obj_feat)
+        if want_normal:
+            sigma, rgb = field_normals(model, enc_in)
+        else:
+            sigma, rgb = field_infer(model, enc_in, rays_d, dir_div=T, dir_block=rb, obj_feat=obj_feat)
         check(lib.foc_fixed_field_pack(ptr(sigma), ptr(rgb), ptr(nears), ptr(fars), None, None, 1.0, N, T, float(model.density_scale),
                                        float(weight_thresh), None, None, None, ptr(out), rb, stream_of(sigma)), "fixed_field_pack")
         return out

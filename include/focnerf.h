@@ -489,6 +489,39 @@ int foc_nerf_field_inference_pad31(const void *enc, int enc_planar, const float 
                                    uint32_t color_layers, uint32_t hidden_dim, uint32_t activation, uint32_t B,
                                    float *sigma, float *rgb, const void *obj_feat, float input_pad, void *stream);
 
+/* Surface normals from the density field, one launch: sigma, the gradient of raw = h[0] with respect to the position, and the normal
+ * n = -grad / |grad| encoded as a colour, per sample (csrc/normals.hip). Extension: the reference has no such kernel; what it computes is
+ * torch.autograd.grad through its encoder (dy_dx) and its MLP.
+ *   xn [M,3] fp32, encoder coordinates in [0,1]; embeddings, offsets, D, C, L, S, H, gridtype, align_corners, interp, dtype, offsets_host as
+ *   foc_grid_encode_forward takes them (offsets_host is not read); sigma_weights: the sigma network's blob (foc_ffmlp_forward's layout,
+ *   input_dim 32, output_dim 16), fp16, 16-byte aligned.
+ *   rot9: NULL, or 9 fp32 in DEVICE memory: a row-major 3 x 3 rotation (object -> scene) applied to the normal.
+ *   Outputs, each may be NULL (all NULL or M = 0: nothing is launched): sigma [M] fp32; grad_raw [M,3] fp32 = d raw / d xn; normal_rgb [M,3]
+ *   fp32 = 0.5 + 0.5 (rot9) n; grad_enc [M,32] fp32 (16-byte aligned; NULL in production): d raw / d encoding, feature 2 l + c, exactly as
+ *   the contraction consumed it — it exists so that the stages can be checked one at a time, like forward_buffer / backward_buffer.
+ * Shape served — anything else is refused with FOC_E_INVALID (dtype: FOC_E_DTYPE) before any launch, the message names the argument:
+ *   D 3, C 2, L 16, dtype FOC_F16, gridtype 0 (hash), align_corners 0, interp 0 (linear); hidden_dim 64, activation 0 (ReLU), sigma_layers 1..3.
+ * Per sample:
+ *   encode     the 32 features with foc_grid_encode_forward's arithmetic and bits (fp32, each rounded to half once) and the 96 derivatives
+ *              dy_dx[l,d,c] = scale_l * sum over the 4 corner pairs along d of (w_a w_b) (v_right - v_left), from the same eight corner
+ *              rows; fp32, NOT rounded to half (foc_grid_encode_forward's dy_dx is stored in the table dtype).
+ *   forward    the sigma network as foc_nerf_field_inference runs it (fp32 MFMA sums, half once per layer, ReLU): sigma = exp(half(h[0]))
+ *              has the SAME BITS as that entry point's sigma on foc_grid_encode_forward's output for the same points.
+ *   backward   delta of the last hidden layer = [a > 0] W_out[0,:] (exact); per hidden matrix delta = [a > 0] half(W^T delta) (fp32 MFMA sum,
+ *              rounded to half once, gated by the forward's own post-ReLU half a); grad_enc = W0^T delta_0, the fp32 sum, not rounded.
+ *   contract   grad_raw[d] = sum_{l,c} grad_enc[l,c] dy_dx[l,d,c]: fp32 fmaf, two partial sums of 8 levels each ({0-3, 8-11} and {4-7, 12-15},
+ *              level then channel ascending), added once.
+ *   normalise  m = max_d |g_d|; m == 0 or a component not finite: n = 0; else u = g / m, n = -u / sqrt(u.u); n <- rot9 n; normal_rgb =
+ *              fma(0.5, n, 0.5). All fp32.
+ *   A point with a coordinate outside [0,1] has zero features and derivatives, as in the encoder: grad_enc = grad_raw = 0, n = 0,
+ *   normal_rgb = 0.5 exactly, sigma = exp(0).
+ * No atomics, no host synchronisation (capturable in a graph), nothing order-dependent: FOC_DETERMINISTIC changes nothing, and every subset
+ * of the outputs has the bits of the full call. */
+int foc_field_normals(const float *xn, uint32_t M, const void *embeddings, const uint32_t *offsets, uint32_t D, uint32_t C, uint32_t L,
+                      float S, uint32_t H, uint32_t gridtype, int align_corners, uint32_t interp, int dtype, const int32_t *offsets_host,
+                      const void *sigma_weights, uint32_t sigma_layers, uint32_t hidden_dim, uint32_t activation, const float *rot9,
+                      float *sigma, float *grad_raw, float *normal_rgb, void *grad_enc, void *stream);
+
 /* The colour network of a ray-ordered sample list without its materialised input (network_ff.py:104-108 builds
  * cin = [SH16(dir) | h[:,1:16] | 0] per sample, 64 B written and read twice): the kernels take the sigma network's output
  * rows h [B,16] fp16 and one SH row per ray, ray_sh [B / samples_per_ray, 16] fp16 (foc_fixed_sample), and place
