@@ -5,6 +5,9 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <map>
+#include <mutex>
+#include <tuple>
 #include "../../include/focnerf.h"
 
 #define FOC_WAVE 64
@@ -100,6 +103,53 @@ static inline uint32_t foc_grid_1d(uint64_t n, uint32_t block, uint32_t max_bloc
     if (g < 1) g = 1;
     if (g > max_blocks) g = max_blocks;
     return (uint32_t)g;
+}
+
+// ---- launch sizing of the persistent kernels (a grid capped at what the device holds at once, every workgroup resident from the start).
+// Both answers are for the CURRENT device (the entry points make the device of their call current, above) and are cached per device for the
+// life of the process, in every translation unit for the kernels it launches; the first question about a device or a kernel asks the runtime,
+// nothing allocates on the device or synchronises.
+static inline int foc_current_device() {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0) dev = 0;
+    return dev;
+}
+static inline uint32_t foc_num_cus(int dev = foc_current_device()) {
+    static std::mutex mu;
+    static std::map<int, uint32_t> cus;
+    std::lock_guard<std::mutex> lock(mu);
+    uint32_t &n = cus[dev];
+    if (!n) {
+        int v = 0;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
+        n = (uint32_t)v;
+    }
+    return n;
+}
+// Workgroups of `kern` that one CU holds at once at this block size and dynamic LDS (registers + LDS), in [1, 8]: a grid of CUs x 4 on a
+// kernel that fits 3 per CU runs a quarter of its workgroups in a second, three-quarters-empty round (measured: 2.025 -> 2.003 ms per
+// training step for the two forward kernels).
+static inline uint32_t foc_resident_blocks(const void *kern, uint32_t block, size_t lds, int dev = foc_current_device()) {
+    static std::mutex mu;
+    static std::map<std::tuple<int, const void *, uint32_t, size_t>, uint32_t> seen;
+    std::lock_guard<std::mutex> lock(mu);
+    uint32_t &n = seen[std::make_tuple(dev, kern, block, lds)];
+    if (!n) {
+        int v = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, kern, (int)block, lds) != hipSuccess || v < 1) v = 2;
+        n = (uint32_t)(v > 8 ? 8 : v);
+    }
+    return n;
+}
+// What every launcher of such a kernel does: opt in to more than 64 KiB of dynamic LDS, and cap the grid at CUs x per_cu workgroups —
+// per_cu = 0: as many as one CU holds (foc_resident_blocks), else the launcher's own fixed factor.
+template <typename K>
+static inline uint32_t foc_persistent_grid(K kern, uint32_t block, size_t lds, uint32_t grid, uint32_t per_cu = 0) {
+    const void *k = reinterpret_cast<const void *>(kern);
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const int dev = foc_current_device();                  // asked once per launch
+    const uint32_t cap = foc_num_cus(dev) * (per_cu ? per_cu : foc_resident_blocks(k, block, lds, dev));
+    return grid < cap ? grid : cap;
 }
 
 // fp32 -> fp16 of a value that was ROUNDED TO fp32 first, as a torch `.half()` of an fp32 tensor is. Without the barrier the

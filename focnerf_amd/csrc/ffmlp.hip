@@ -1250,44 +1250,11 @@ __global__ void __launch_bounds__(MLP_BLOCK, 2) k_nerf_infer(const _Float16 *__r
 }
 
 // ================================================================= host side
-// Per-device caches (the entry points make the stream's device current, common.h FocDeviceGuard): CU count and, per kernel, the number
-// of workgroups one CU holds.
-#define MLP_MAX_DEVICES 16
+// (the grid of every persistent kernel below: common.h foc_persistent_grid)
 // floats of the fp32 blob image at the head of the backward workspace (rounded up to 256 bytes: the slots behind it stay aligned)
 static inline uint64_t mlp_dw_blob_floats(uint32_t input_dim, uint32_t hidden_dim, uint32_t num_layers) {
     const uint64_t n = (uint64_t)hidden_dim * (input_dim + (uint64_t)hidden_dim * (num_layers - 1) + 16);
     return (n + 63) & ~(uint64_t)63;
-}
-static int mlp_device() {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MLP_MAX_DEVICES) dev = 0;
-    return dev;
-}
-static uint32_t mlp_num_cus() {
-    static uint32_t num_cus[MLP_MAX_DEVICES];
-    const int dev = mlp_device();
-    if (!num_cus[dev]) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        num_cus[dev] = (uint32_t)n;
-    }
-    return num_cus[dev];
-}
-
-// Workgroups of a persistent kernel that one CU holds at once (registers + LDS): the grid is capped at CUs x this, so that every
-// workgroup is resident from the start — a grid of CUs x 4 on a kernel that fits 3 per CU runs a quarter of its workgroups in a second,
-// three-quarters-empty round (measured: 2.025 -> 2.003 ms per training step for the two forward kernels).
-static uint32_t mlp_resident_blocks(const void *kern, size_t lds) {
-    static const void *seen[MLP_MAX_DEVICES][64];
-    static uint32_t blocks[MLP_MAX_DEVICES][64];
-    static int n_seen[MLP_MAX_DEVICES];
-    const int dev = mlp_device();
-    for (int i = 0; i < n_seen[dev]; i++) if (seen[dev][i] == kern) return blocks[dev][i];
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, MLP_BLOCK, lds) != hipSuccess || n < 1) n = 2;
-    if (n > 8) n = 8;
-    if (n_seen[dev] < 64) { seen[dev][n_seen[dev]] = kern; blocks[dev][n_seen[dev]] = (uint32_t)n; n_seen[dev]++; }
-    return (uint32_t)n;
 }
 
 // hidden_dim 256 (ffmlp_wide.hip): layer-by-layer kernels with one matrix resident in LDS
@@ -1338,11 +1305,7 @@ static int mlp_fwd_launch(const void *inputs, const void *weights, uint32_t B, u
     if (gen) kern = k_mlp_fwd<HIDDEN, NB, TRAIN, 0, true>;
     if constexpr (HIDDEN == 64 && !TRAIN) { if (head) kern = k_mlp_fwd<HIDDEN, NB, false, 2>; }
     else FOC_REQUIRE(!head, FOC_E_INVALID, "color_head_forward: hidden_dim must be 64");
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    const uint32_t n_tiles = foc_div_up(B, 32 * NB);
-    uint32_t grid = foc_div_up(n_tiles, MLP_WAVES);
-    const uint32_t cap = mlp_num_cus() * mlp_resident_blocks(reinterpret_cast<const void *>(kern), lds);
-    if (grid > cap) grid = cap;
+    const uint32_t grid = foc_persistent_grid(kern, MLP_BLOCK, lds, foc_div_up(foc_div_up(B, 32 * NB), MLP_WAVES));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(MLP_BLOCK), lds, st, (const _Float16 *)inputs, (const _Float16 *)weights, (_Float16 *)fwd_buf,
                        (_Float16 *)outputs, B, in_dim, num_layers, act, head ? *head : MlpHead{nullptr, nullptr, 1u, 16u, nullptr, 0.0f});
     FOC_CHECK_LAUNCH(TRAIN ? "ffmlp_forward" : "ffmlp_inference");
@@ -1409,11 +1372,8 @@ static int mlp_bwd_fused_launch(const void *grad, const void *inputs, const void
                                                        : k_mlp_bwd_fused<HIDDEN, NL, NB, true, 2, false>);
     }
     else FOC_REQUIRE(!head, FOC_E_INVALID, "color_head_backward: hidden_dim must be 64 and num_layers 2 or 3");
-    if (lds_launch > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_launch);
     const uint32_t n_w = HIDDEN * ((has_obj ? HEAD_OBJ_LD : in_dim) + HIDDEN * (NL - 1) + 16);
-    uint32_t grid = foc_div_up(B, 4 * RW);
-    const uint32_t cap = min(mlp_num_cus() * 2, MLP_DW_MAX_SLOTS);
-    if (grid > cap) grid = cap;
+    const uint32_t grid = min(foc_persistent_grid(kern, MLP_BLOCK, lds_launch, foc_div_up(B, 4 * RW), 2u), MLP_DW_MAX_SLOTS);
     // workspace: [fp32 blob image (object-conditioned head only)] [one slot of (NL + 1) x 4096 floats per workgroup] — no zero fill, no atomics
     float *slots = ws + mlp_dw_blob_floats(has_obj ? HEAD_OBJ_LD : in_dim, HIDDEN, NL);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(MLP_BLOCK), lds_launch, st, (const _Float16 *)grad, (const _Float16 *)inputs, (const _Float16 *)weights,
@@ -1443,7 +1403,7 @@ static int mlp_dw_launch(const void *grad, const void *inputs, const void *fwd_b
     const int wgs_per_cu = 8;                    // split-K workgroups per CU over all layers
     // 16 output tiles per workgroup: hidden x hidden, or hidden x in_dim for an input layer wider than the hidden layers
     const uint32_t tiles = ((HIDDEN + 31) / 32) * ((max((uint32_t)HIDDEN, in_dim) + 31) / 32), GZ = (tiles + 15) / 16;
-    const uint32_t capx = foc_div_up(mlp_num_cus() * (uint32_t)wgs_per_cu, (num_layers + 1) * GZ);
+    const uint32_t capx = foc_div_up(foc_num_cus() * (uint32_t)wgs_per_cu, (num_layers + 1) * GZ);
     if (gx > capx) gx = capx;
     if (gx < 1) gx = 1;
     auto kern = k_mlp_dw<HIDDEN>;
@@ -1482,11 +1442,7 @@ static int mlp_bwd_launch(const void *grad, const void *inputs, const void *weig
     const size_t lds = mlp_bwd_lds<HIDDEN>(in_dim, num_layers, dx);
     FOC_REQUIRE(lds <= 160 * 1024, FOC_E_INVALID, "ffmlp_backward: weights (%zu B) do not fit the 160 KiB LDS", lds);
     auto kern = gen ? k_mlp_bwd<HIDDEN, NB, true> : k_mlp_bwd<HIDDEN, NB, false>;
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    const uint32_t n_tiles = foc_div_up(B, 32 * NB);
-    uint32_t grid = foc_div_up(n_tiles, MLP_WAVES);
-    const uint32_t cap = mlp_num_cus() * 4;
-    if (grid > cap) grid = cap;
+    const uint32_t grid = foc_persistent_grid(kern, MLP_BLOCK, lds, foc_div_up(foc_div_up(B, 32 * NB), MLP_WAVES), 4u);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(MLP_BLOCK), lds, st, (const _Float16 *)grad, (const _Float16 *)weights, (const _Float16 *)fwd_buf,
                        (_Float16 *)bwd_buf, (_Float16 *)grad_inputs, B, in_dim, num_layers, act);
     FOC_CHECK_LAUNCH("ffmlp_backward(activations)");
@@ -1510,10 +1466,7 @@ static int nerf_infer_launch(const void *enc, const float *dirs, uint32_t dir_di
         FOC_REQUIRE(planar && relu, FOC_E_INVALID, "nerf_field_inference_pad31: a pad needs planar encodings and ReLU networks");
         kern = blk ? k_nerf_infer<NLS, NLC, true, true, true, false, true> : k_nerf_infer<NLS, NLC, true, true, false, false, true>;
     }
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    uint32_t grid = foc_div_up(foc_div_up(B, 64), MLP_WAVES);
-    const uint32_t cap = mlp_num_cus() * mlp_resident_blocks(reinterpret_cast<const void *>(kern), lds);
-    if (grid > cap) grid = cap;
+    const uint32_t grid = foc_persistent_grid(kern, MLP_BLOCK, lds, foc_div_up(foc_div_up(B, 64), MLP_WAVES));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(MLP_BLOCK), lds, st, (const _Float16 *)enc, dirs, dir_div, dir_block, n_dirs, (const _Float16 *)w_sigma,
                        (const _Float16 *)w_color, B, relu, sigma, rgb, (const _Float16 *)obj, pad);
     FOC_CHECK_LAUNCH("nerf_field_inference");

@@ -116,18 +116,6 @@ __global__ void __launch_bounds__(WIDE_BLOCK, 1) k_wide_layer(const _Float16 *__
     }
 }
 
-static uint32_t wide_num_cus() {
-    static uint32_t n_cus[16];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-    if (!n_cus[dev]) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        n_cus[dev] = (uint32_t)n;
-    }
-    return n_cus[dev];
-}
-
 template <bool TRANS, int EPI>
 static int wide_launch(const char *what, const void *X, uint32_t ldx, const void *W, uint32_t n_w, uint32_t k_w, void *Y, uint32_t ldy, const void *mask, uint32_t ldm,
                        uint32_t B, hipStream_t st, int act = FOC_ACT_NONE) {
@@ -136,10 +124,7 @@ static int wide_launch(const char *what, const void *X, uint32_t ldx, const void
     FOC_REQUIRE(ldx % 8 == 0 && ldx >= ((K + 15) / 16) * 16, FOC_E_INVALID, "%s: activation rows must hold whole 16-wide k-chunks (ld %u, K %u)", what, ldx, K);
     const size_t lds = (size_t)((N + 31) / 32) * ((K + 15) / 16) * 1024;
     auto kern = k_wide_layer<TRANS, EPI>;
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    uint32_t grid = foc_div_up(foc_div_up(B, 32), 4);
-    const uint32_t cap = wide_num_cus() * (lds > 80 * 1024 ? 1u : 2u);
-    if (grid > cap) grid = cap;
+    const uint32_t grid = foc_persistent_grid(kern, WIDE_BLOCK, lds, foc_div_up(foc_div_up(B, 32), 4), lds > 80 * 1024 ? 1u : 2u);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(WIDE_BLOCK), lds, st, (const _Float16 *)X, ldx, (const _Float16 *)W, n_w, k_w, (_Float16 *)Y, ldy, (const _Float16 *)mask, ldm, B, act);
     FOC_CHECK_LAUNCH(what);
     return FOC_OK;

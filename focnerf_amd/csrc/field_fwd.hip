@@ -163,26 +163,11 @@ __global__ void __launch_bounds__(MLP_BLOCK, FF_MIN_WAVES) k_field_fwd_train(con
     }
 }
 
-static uint32_t ff_num_cus() {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    return (uint32_t)n;
-}
-
 template <int NLS, int NLC, bool RELU>
 static int ff_launch(const void *planes, const void *w_sigma, const void *w_color, void *h, void *c, uint32_t B, const MlpHead &hd, hipStream_t st) {
     auto kern = k_field_fwd_train<NLS, NLC, RELU>;
     const size_t lds = (size_t)((4 + (NLS - 1) * 8 + 4) + (4 + (NLC - 1) * 8 + 4)) * 1024 + 256;
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    static int resident = 0;                                 // workgroups of this kernel one CU holds (registers + LDS): the grid is capped at CUs x that
-    if (!resident) {
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, MLP_BLOCK, lds) != hipSuccess || n < 1) n = 2;
-        resident = n > 8 ? 8 : n;
-    }
-    uint32_t grid = foc_div_up(foc_div_up(B, 32), MLP_WAVES);
-    const uint32_t cap = ff_num_cus() * (uint32_t)resident;
-    if (grid > cap) grid = cap;
+    const uint32_t grid = foc_persistent_grid(kern, MLP_BLOCK, lds, foc_div_up(foc_div_up(B, 32), MLP_WAVES));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(MLP_BLOCK), lds, st, (const _Float16 *)planes, (const _Float16 *)w_sigma, (const _Float16 *)w_color,
                        (_Float16 *)h, (_Float16 *)c, B, hd);
     FOC_CHECK_LAUNCH("field_forward_train");

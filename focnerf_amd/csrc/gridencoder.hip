@@ -1011,17 +1011,7 @@ static uint32_t gb_fact_mask(uint32_t L, const GeLevels &lv, const int32_t *offs
 }
 
 // workgroups of k_gbin_scatter_pms one CU holds (fp16 tables: two 1024-thread workgroups, fp32 tables: one)
-static uint32_t gb_scatter_resident(size_t elem) {
-    static uint32_t cus[16];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-    if (!cus[dev]) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        cus[dev] = (uint32_t)n;
-    }
-    return cus[dev] * (elem == 2 ? 2u : 1u);
-}
+static uint32_t gb_scatter_resident(size_t elem) { return foc_num_cus() * (elem == 2 ? 2u : 1u); }
 
 template <typename T>
 static int gb_run(const void *grad, const float *inputs, const int32_t *offsets, void *grad_emb, uint32_t B, uint32_t L, const GeLevels &lv,

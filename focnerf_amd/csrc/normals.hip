@@ -253,26 +253,12 @@ __global__ void __launch_bounds__(MLP_BLOCK, 2) k_field_normals(const float *__r
     }
 }
 
-static uint32_t fn_num_cus() {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    return (uint32_t)n;
-}
-
 template <int NLS>
 static int fn_launch(const float *xn, uint32_t M, const void *emb, const uint32_t *offsets, const GeLevels &lv, const void *w, const float *rot9, float *sigma,
                      float *grad_raw, float *normal_rgb, float *grad_enc, hipStream_t st) {
     auto kern = k_field_normals<NLS>;
     const size_t lds = (size_t)((4 + (NLS - 1) * 8 + 4) + (2 + (NLS - 1) * 8) + 4) * 1024 + sizeof(FnLevelsLds);
-    static int resident = 0;                                 // workgroups of this kernel one CU holds: the grid is capped at CUs x that
-    if (!resident) {
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, MLP_BLOCK, lds) != hipSuccess || n < 1) n = 2;
-        resident = n > 8 ? 8 : n;
-    }
-    uint32_t grid = foc_div_up(foc_div_up(M, 32), MLP_WAVES);
-    const uint32_t cap = fn_num_cus() * (uint32_t)resident;
-    if (grid > cap) grid = cap;
+    const uint32_t grid = foc_persistent_grid(kern, MLP_BLOCK, lds, foc_div_up(foc_div_up(M, 32), MLP_WAVES));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(MLP_BLOCK), lds, st, xn, M, (const __half *)emb, offsets, lv, (const _Float16 *)w, rot9, sigma, grad_raw, normal_rgb,
                        grad_enc);
     FOC_CHECK_LAUNCH("foc_field_normals");

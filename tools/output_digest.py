@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""tools/output_digest.py [out.json] [--sections a,b] [--root DIR]: sha256 of every output of the per-sample, ragged-composite, fixed-step,
+"""tools/output_digest.py [out.json] [--sections a,b] [--root DIR]: sha256 of every output of the fused-MLP, per-sample, ragged-composite, fixed-step,
 combine, marching and grid-encoder kernels on seeded inputs, and of the occupancy node driven from Python, as one JSON object {case: {output: digest}} — the bits
 of one build — printed, or written to out.json with a one-line summary printed instead. Run it once per build on the same GPU
 (FOCNERF_LIB_PATH selects the library) and compare the two objects: equal = the same bits on every case.
---sections: of per_sample, ragged, fixed, combine, march, grid, node (default: all). --root DIR: the checkout whose focnerf_amd package (and library)
+--sections: of mlp, per_sample, ragged, fixed, combine, march, grid, node (default: all). --root DIR: the checkout whose focnerf_amd package (and library)
 is imported instead of this one's — the `node` section runs the package's Python, so one copy of this tool serves both commits of a
 comparison.
 
@@ -28,6 +28,16 @@ pad_align 0 and 128 and with the box or the ranges given. The inference march (m
 foc_march_rays at n_step 1, 3, 8, 16 with the row form off and on, foc_march_rays_two_phase at n_step 1, 2, 4, 8, 16 in its four forms with
 flags 0, 1, 3 and (where the form writes sample-major arrays) 7. foc_composite_rays at n_step 1, 2, 3, 4, 8, 16, foc_composite_compact at 2, 4
 and 8 in both layouts with and without a deaths histogram, T_thresh 1e-4 and 0.5. foc_compact_alive at 1, 1023, 1025 and 2100 entries.
+
+`mlp` (ffmlp.hip, field_fwd.hip, normals.hip through the C ABI; FOC_DETERMINISTIC on, so that the weight gradients of the two-kernel backward are
+sums in a fixed order): at 1, 31, 33, 65, 129 and 257 rows — a ragged 32-row tile and the next one, past k_nerf_infer's 64-row tile, past
+k_mlp_bwd_fused's 128-row group, past one workgroup of 64-row tiles. foc_ffmlp_forward (outputs, forward buffer), _inference and _forward_planar at
+hidden 16, 32, 64, 128, 1 to 3 layers, input 16, 32, 64, relu, none and sigmoid (row-major only); foc_ffmlp_backward on the same shapes with
+FOC_MLP_BWD_FUSED 1 and 0, from the stored activations and (single-pass kernel) re-evaluating them, with and without a backward buffer, and
+foc_ffmlp_backward_planar: grad_inputs, grad_weights, the backward buffer. The colour head, the training forward of both networks and the field
+inference each with their _pad / _pad31 twins, with and without an object feature: foc_color_head_forward / _backward at 2 and 3 layers, c_width 4
+and 16 (outputs, grad_h, grad_w, grad_obj); foc_field_forward_train on the five layer pairs, relu and none; foc_nerf_field_inference planar and
+row-major, dir_block 0 and 64, dir_div 1 and 4. foc_field_normals at 1, 2, 3 sigma layers with every optional output, with and without a rotation.
 
 `grid` (gridencoder.hip, gridencoder_nd.hip through the C ABI): forward [L,B,C] and [B, L*C], dy_dx and grad_inputs — the outputs no atomic
 touches — for D 2..5, C 1, 2, 4, 8 (fp16 tables: even C), both dtypes, hash and tiled grids, align_corners off and on, linear and
@@ -64,7 +74,7 @@ def _option(name):
 
 
 ROOT = _option("--root") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-ALL_SECTIONS = ("per_sample", "ragged", "fixed", "combine", "march", "grid", "node")
+ALL_SECTIONS = ("mlp", "per_sample", "ragged", "fixed", "combine", "march", "grid", "node")
 SECTIONS = (_option("--sections") or ",".join(ALL_SECTIONS)).split(",")
 if set(SECTIONS) - set(ALL_SECTIONS):
     sys.exit(f"usage: output_digest.py [out.json] [--sections a,b] [--root DIR]: sections are {', '.join(ALL_SECTIONS)}, got {', '.join(SECTIONS)}")
@@ -623,7 +633,151 @@ def node():
             del m
 
 
+# ---------------------------------------------------------------- fused MLP family (ffmlp.hip, field_fwd.hip, normals.hip) through the C ABI
+MLP_ROWS = (1, 31, 33, 65, 129, 257)
+MLP_PAIRS = ((1, 2), (1, 3), (2, 2), (2, 3), (3, 3))     # (sigma_layers, color_layers) the kernels of both networks are built for
+ACT_RELU, ACT_SIGMOID, ACT_NONE = 0, 3, 6
+
+
+def mlp_half(rng, shape, scale):
+    return cuda((rng.standard_normal(shape) * scale).astype(np.float16))
+
+
+def mlp_blob(rng, in_dim, hidden, layers):
+    return mlp_half(rng, hidden * (in_dim + hidden * (layers - 1) + 16), 0.25)
+
+
+def mlp_planes(x):
+    """[B, in_dim] rows as the encoder's [in_dim / 2, B, 2] planes."""
+    B, in_dim = x.shape
+    return x.view(B, in_dim // 2, 2).permute(1, 0, 2).contiguous()
+
+
+def mlp_plain():
+    ws = torch.empty(max(int(lib.foc_ffmlp_backward_workspace_bytes(64, h, 3)) for h in (16, 32, 64, 128)), dtype=torch.uint8, device="cuda")
+    for hidden in (16, 32, 64, 128):
+        for layers in (1, 2, 3):
+            for in_dim in (16, 32, 64):
+                for act in (ACT_RELU, ACT_NONE, ACT_SIGMOID):
+                    for B in MLP_ROWS:
+                        rng = np.random.default_rng(((hidden * 10 + layers) * 100 + in_dim) * 1000 + 10 * B + act)
+                        x, W, grad = mlp_half(rng, (B, in_dim), 1.0), mlp_blob(rng, in_dim, hidden, layers), mlp_half(rng, (B, 16), 0.1)
+                        xp = mlp_planes(x)
+                        tag = f"[hidden={hidden},layers={layers},in={in_dim},act={act},B={B}]"
+                        f16 = lambda *shape: full(shape, torch.float16)
+                        fb, out, out_inf, ib = f16(layers, B, hidden), f16(B, 16), f16(B, 16), f16(B, hidden)
+                        call(lib.foc_ffmlp_forward, ptr(x), ptr(W), B, in_dim, 16, hidden, layers, act, ACT_NONE, ptr(fb), ptr(out))
+                        call(lib.foc_ffmlp_inference, ptr(x), ptr(W), B, in_dim, 16, hidden, layers, act, ACT_NONE, ptr(ib), ptr(out_inf))
+                        res = dict(outputs=out, forward_buffer=fb, inference=out_inf)
+                        if act != ACT_SIGMOID:                               # the general activations are served on row-major inputs only
+                            res["planar"] = f16(B, 16)
+                            call(lib.foc_ffmlp_forward_planar, ptr(xp), ptr(W), B, in_dim, 16, hidden, layers, act, ACT_NONE, ptr(res["planar"]))
+                        put("ffmlp_forward" + tag, **res)
+                        for fused in (1, 0):
+                            set_option("FOC_MLP_BWD_FUSED", fused)
+                            one_pass = fused and hidden <= 64 and act != ACT_SIGMOID        # the shapes k_mlp_bwd_fused serves (in_dim <= 64, layers <= 4 here)
+                            res = {}
+                            # stored activations with the backward buffer; then (single-pass kernel only) re-evaluated ones, with and without it; then planar
+                            forms = [("stored", fb, True, False)] + ([("recomp", None, False, False), ("recomp+bb", None, True, False), ("planar", None, False, True)] if one_pass else [])
+                            for name, fwd, with_bb, planar in forms:
+                                bb, gi, gw = f16(layers, B, hidden) if with_bb else None, f16(*((in_dim // 2, B, 2) if planar else (B, in_dim))), f16(W.numel())
+                                if planar:
+                                    call(lib.foc_ffmlp_backward_planar, ptr(grad), ptr(xp), ptr(W), B, in_dim, 16, hidden, layers, act, ACT_NONE, 1, ptr(gi), ptr(gw), ptr(ws), ws.numel())
+                                else:
+                                    call(lib.foc_ffmlp_backward, ptr(grad), ptr(x), ptr(W), ptr(fwd), B, in_dim, 16, hidden, layers, act, ACT_NONE, 1, ptr(bb), ptr(gi), ptr(gw),
+                                         ptr(ws), ws.numel())
+                                res.update({f"grad_inputs[{name}]": gi, f"grad_weights[{name}]": gw, f"backward_buffer[{name}]": bb})
+                            put(f"ffmlp_backward{tag}[fused={fused}]", **res)
+    set_option("FOC_MLP_BWD_FUSED", 1)
+
+
+def mlp_head_forms(rng):
+    """(suffix, object feature, input_pad) of an entry point and its _pad / _pad31 twins; input_pad None: the entry point takes none."""
+    obj = mlp_half(rng, 16, 0.8)
+    return (("", None, None), ("", obj, None), ("_pad", obj, 1.0), ("_pad31", None, 1.0))
+
+
+def mlp_fields():
+    T = 4                                                                   # samples per ray
+    ws = torch.empty(int(lib.foc_ffmlp_backward_workspace_bytes(48, 64, 3)), dtype=torch.uint8, device="cuda")
+    for B in MLP_ROWS:
+        rng = np.random.default_rng(7000 + B)
+        n_rays = (B + T - 1) // T
+        x, hrows, ray_sh = mlp_half(rng, (B, 32), 1.0), mlp_half(rng, (B, 16), 0.7), mlp_half(rng, (n_rays, 16), 0.5)
+        xp, g_h0 = mlp_planes(x), mlp_half(rng, B, 0.05)
+        for suffix, obj, pad in mlp_head_forms(rng):
+            pad_args = () if pad is None else (pad,)
+            form = f"{suffix or 'plain'},obj={obj is not None}"
+            ld0 = 48 if obj is not None else 32
+            for layers in (2, 3):
+                W = mlp_blob(rng, ld0, 64, layers)
+                for cw in (4, 16):
+                    grad = mlp_half(rng, (B, cw), 0.05)
+                    for act in (ACT_RELU, ACT_NONE):
+                        out, g_h, g_w = full((B, cw), torch.float16), full((B, 16), torch.float16), full(W.numel(), torch.float16)
+                        g_obj = full(16) if obj is not None else None
+                        call(getattr(lib, "foc_color_head_forward" + suffix), ptr(hrows), ptr(ray_sh), T, ptr(W), B, 64, layers, act, ptr(out), cw, ptr(obj), *pad_args)
+                        call(getattr(lib, "foc_color_head_backward" + suffix), ptr(grad), ptr(hrows), ptr(ray_sh), T, ptr(g_h0), ptr(W), B, 64, layers, act, ptr(g_h), ptr(g_w),
+                             ptr(ws), ws.numel(), cw, ptr(obj), ptr(g_obj), *pad_args)
+                        put(f"color_head[{form},layers={layers},c_width={cw},act={act},B={B}]", outputs=out, grad_h=g_h, grad_w=g_w, grad_obj=g_obj)
+            for nls, nlc in MLP_PAIRS:
+                Ws, Wc = mlp_blob(rng, 32, 64, nls), mlp_blob(rng, ld0, 64, nlc)
+                for act in (ACT_RELU, ACT_NONE):
+                    for cw in (4, 16):
+                        h, c = full((B, 16), torch.float16), full((B, cw), torch.float16)
+                        call(getattr(lib, "foc_field_forward_train" + suffix), ptr(xp), ptr(Ws), nls, ptr(ray_sh), T, ptr(Wc), nlc, 64, act, B, ptr(h), ptr(c), cw, ptr(obj), *pad_args)
+                        put(f"field_forward_train[{form},layers={nls}/{nlc},act={act},c_width={cw},B={B}]", h=h, c=c)
+                # the inference of both networks: an object feature or a pad goes with the planes and ReLU
+                for planar, dir_block in ((1, 0), (1, 64), (0, 0), (0, 64)):
+                    if not planar and (obj is not None or pad is not None):
+                        continue
+                    for dir_div in (1, 4):
+                        n_dirs = (B + dir_div - 1) // dir_div
+                        dirs = rng.standard_normal((n_dirs, 3)); dirs /= np.linalg.norm(dirs, axis=1, keepdims=True)
+                        d_dirs = cuda(dirs.astype(np.float32))
+                        for act in (ACT_RELU,) if (obj is not None or pad is not None) else (ACT_RELU, ACT_NONE):
+                            sigma, rgb = full(B), full((B, 3))
+                            call(getattr(lib, "foc_nerf_field_inference" + suffix), ptr(xp if planar else x), planar, ptr(d_dirs), dir_div, dir_block, n_dirs, ptr(Ws), nls, ptr(Wc), nlc,
+                                 64, act, B, ptr(sigma), ptr(rgb), ptr(obj), *pad_args)
+                            put(f"nerf_field_inference[{form},layers={nls}/{nlc},planar={planar},dir_block={dir_block},dir_div={dir_div},act={act},B={B}]", sigma=sigma, rgb=rgb)
+
+
+def mlp_normals():
+    from focnerf_amd.gridencoder import level_offsets
+    pls, H, L = 1.5, 4, 16
+    off = level_offsets(3, L, pls, H, 11)
+    rng = np.random.default_rng(9000)
+    table, d_off = cuda(rng.uniform(-0.5, 0.5, (int(off[-1]), 2)).astype(np.float16)), cuda(off)
+    rot = np.linalg.qr(rng.standard_normal((3, 3)))[0].astype(np.float32)
+    for M in MLP_ROWS:
+        x = rng.random((M, 3)).astype(np.float32)
+        if M > 8:
+            x[0], x[1], x[2, 0] = 0.0, 1.0, -0.01                           # the box's corners and a point outside it
+        d_x = cuda(x)
+        for nls in (1, 2, 3):
+            W = mlp_blob(rng, 32, 64, nls)
+            for rot9 in (None, cuda(rot)):
+                sigma, g_raw, n_rgb, g_enc = full(M), full((M, 3)), full((M, 3)), full((M, 32))
+                call(lib.foc_field_normals, ptr(d_x), M, ptr(table), ptr(d_off), 3, 2, L, float(np.log2(pls)), H, 0, 0, 0, 1, None, ptr(W), nls, 64, ACT_RELU, ptr(rot9), ptr(sigma),
+                     ptr(g_raw), ptr(n_rgb), ptr(g_enc))
+                put(f"field_normals[layers={nls},rot={rot9 is not None},M={M}]", sigma=sigma, grad_raw=g_raw, normal_rgb=n_rgb, grad_enc=g_enc)
+
+
+def mlp():
+    saved = {name: get_option(name) for name in ("FOC_DETERMINISTIC", "FOC_MLP_BWD_FUSED")}
+    try:
+        set_option("FOC_DETERMINISTIC", 1)                                  # the weight gradients of the two-kernel backward: sums in a fixed order
+        mlp_plain()
+        mlp_fields()
+        mlp_normals()
+    finally:
+        for name, value in saved.items():
+            set_option(name, value)
+
+
 def main():
+    if "mlp" in SECTIONS:
+        mlp()
     if "per_sample" in SECTIONS:
         per_sample()
     if "ragged" in SECTIONS:
