@@ -53,6 +53,9 @@ grad_inputs: an fmaf chain over L C terms, C U (L C + K) sum |g dy| + (L C + K) 
 SEG_SHIFT, SEG and CHUNK below are csrc/gridencoder.hip's `#define GB_SEG_SHIFT`, `GB_SEG` and `GB_CHUNK`; MERGE_MAX_RES its
 `#define GB_MERGE_MAX_RES`.
 
+The forward itself (out, dy_dx) and grad_tv have their own reference, with the fp32 fraction as an exact operand instead of |pos|:
+tests/grid_forward_ref.py, which imports the building blocks below (_fma32, level, _rows, _axis_weights, _weights) and holds `forward64`.
+
 `model(case, route, mutant=None)` restates a route's arithmetic in numpy float32 / float16 (fp32 weights and products in the kernels' order,
 the four-step segmented scan over 16-lane groups, half rounding, the exact integer sum, the chunk rounding, sequential atomics in point
 order) so that the bound can be exercised without a GPU; a reference value is never computed with a mutant.
@@ -400,25 +403,10 @@ def grad_inputs(case, dy_dx, half):
 
 
 def forward64(case, table):
-    """float64 forward out [L, B, C] and dy_dx [B, L, D, C] of `table` [rows, C] (out-of-range points: zeros)."""
-    D, C, L, B = case["D"], case["C"], case["L"], case["B"]
-    out, dy = np.zeros((L, B, C)), np.zeros((B, L, D, C))
-    t = table.astype(np.float64)
-    k = np.arange(1 << D)
-    for l in range(L):
-        lv = level(case, l)
-        u, _, du = _axis_weights(case, lv)
-        w, _ = _weights(case, lv)
-        vals = t[lv["rows"] + int(case["off"][l])]                                # [n, K, C]
-        out[l, lv["idx"]] = (w[:, :, None] * vals).sum(axis=1)
-        for d in range(D):
-            wd = np.ones_like(w)
-            for dd in range(D):
-                if dd != d:
-                    wd = wd * u[:, dd, :][:, (k >> dd) & 1]
-            sign = np.where((k >> d) & 1, 1.0, -1.0)[None]
-            dy[lv["idx"], l, d] = lv["scale"] * du[:, d:d + 1] * ((wd * sign)[:, :, None] * vals).sum(axis=1)
-    return out, dy
+    """float64 forward out [L, B, C] and dy_dx [B, L, D, C] of `table` at the float64 position: grid_forward_ref.forward64, where the forward's
+    reference lives (imported on the call: that module imports this one)."""
+    import grid_forward_ref
+    return grid_forward_ref.forward64(case, table)
 
 
 # ---------------------------------------------------------------- numpy fp32 / fp16 model of the routes

@@ -62,6 +62,9 @@ CASES_BWD = CASES[:5] + CASES[6:]
 @pytest.mark.parametrize("case", CASES)
 @pytest.mark.parametrize("dtype", [np.float32, np.float16])
 def test_forward_bit_exact(case, dtype):
+    # oracle.c is a port of the same source as the kernels, with the same fmaf sequence: a misreading the two share passes here. The check
+    # against the DEFINITION (float64, a bound per element, every launch form) is tests/test_gpu_grid_forward_reference.py, and
+    # tests/test_grid_forward_ref.py holds oracle.c itself to that reference.
     D, C, L, H, lh, desired, gridtype, ac, interp, B = case if len(case) == 10 else case + (5000,)
     pls, S, off, table = _setup(D, C, L, H, lh, desired, 1, dtype, align_corners=ac)
     x = _points(B, D, 2)

@@ -101,8 +101,11 @@ def test_grad_inputs_and_small_dimensions_against_autograd(name):
     _, gi_o = _oracle_backward(case, np.float16, dy=dy_o)
     gi_ref, gi_b = G.grad_inputs(case, dy_o, half=True)
     assert np.all(np.abs(gi_o.astype(np.float64) - gi_ref) <= gi_b)
-    # the oracle's forward agrees with forward64 to half precision of the table values
-    assert np.abs(out_o.astype(np.float64) - out64).max() <= 2.0 ** -10 * 1.01
+    # the oracle's forward lies inside the forward reference's per-element bound (grid_forward_ref: the float64 forward at the fp32 fraction)
+    import grid_forward_ref as F
+    fref = F.reference(case, case["table"])
+    assert np.all(np.abs(out_o.astype(np.float64) - fref["out"]) <= fref["out_b"]) and np.all(np.abs(dy_o.astype(np.float64) - fref["dy"]) <= fref["dy_b"])
+    assert (fref["out_b"] > 0).mean() > 0.9
 
 
 def test_case_properties():
