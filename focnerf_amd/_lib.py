@@ -10,279 +10,29 @@ import os
 
 import torch  # noqa: F401  (must be imported first: the library then binds to torch's HIP runtime)
 
+from . import _header
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # FOCNERF_LIB_PATH: another build of the same library (A/B timing of kernel variants on one box, tools/ab_libs.sh)
 LIB_PATH = os.environ.get("FOCNERF_LIB_PATH") or os.path.join(_HERE, "libfocnerf_hip.so")
 
-c_u8p = ctypes.c_void_p
 c_vp = ctypes.c_void_p
-u32 = ctypes.c_uint32
-u64 = ctypes.c_uint64
-f32 = ctypes.c_float
-f64 = ctypes.c_double
-i32 = ctypes.c_int
-
-FOC_F32 = 0
-FOC_F16 = 1
-FOC_U8 = 2      # images of foc_batch_sample only
 
 
-class FocOccTrainNode(ctypes.Structure):
-    """include/focnerf.h `FocOccTrainNode`, field for field (tests/test_abi.py parses the header and compares names, order and size)."""
-    _fields_ = [
-        ("struct_bytes", u32),
-        ("n_rays", u32), ("max_steps", u32), ("cascade", u32), ("grid_size", u32), ("cap", u32), ("pad_align", u32),
-        ("bound", f32), ("dt_gamma", f32), ("min_near", f32),
-        ("rays_o", c_vp), ("rays_d", c_vp), ("aabb", c_vp), ("jitter", c_vp),
-        ("bitfield", c_vp),
-        ("nears", c_vp), ("fars", c_vp), ("enc_in", c_vp), ("deltas", c_vp),
-        ("sh_rows", c_vp),
-        ("rays", c_vp), ("counter", c_vp), ("march_scratch", c_vp),
-        ("levels", u32), ("base_resolution", u32), ("gridtype", u32), ("interp", u32),
-        ("align_corners", ctypes.c_int32), ("table_dtype", ctypes.c_int32),
-        ("per_level_scale_log2", f32),
-        ("embeddings", c_vp),
-        ("offsets", c_vp), ("offsets_host", c_vp),
-        ("planes", c_vp), ("grid_workspace", c_vp),
-        ("grid_workspace_bytes", u64),
-        ("sigma_input_dim", u32), ("sigma_hidden", u32), ("sigma_layers", u32), ("sigma_activation", u32), ("sigma_output_activation", u32),
-        ("color_hidden", u32), ("color_layers", u32), ("color_activation", u32), ("c_width", u32),
-        ("w_sigma", c_vp), ("w_color", c_vp),
-        ("h", c_vp), ("c", c_vp),
-        ("T_thresh", f32), ("density_scale", f32), ("bg_scalar", f32),
-        ("bg_ray", c_vp),
-        ("weights_sum", c_vp), ("image_raw", c_vp), ("image", c_vp), ("depth", c_vp),
-        ("precounted", ctypes.c_int32),
-        ("grad_image", c_vp), ("grad_ws", c_vp),
-        ("grad_c", c_vp), ("grad_h0", c_vp), ("grad_h", c_vp), ("grad_planes", c_vp), ("grad_w_color", c_vp), ("grad_w_sigma", c_vp),
-        ("grad_embeddings", c_vp), ("mlp_workspace", c_vp),
-        ("mlp_workspace_bytes", u64),
-    ]
+def _find_header():
+    """include/focnerf.h of the source tree, or the copy setup.py puts beside this file in an installed package."""
+    paths = [os.path.join(os.path.dirname(_HERE), "include", "focnerf.h"), os.path.join(_HERE, "focnerf.h")]
+    for p in paths:
+        if os.path.exists(p):
+            return p
+    raise ImportError(f"focnerf_amd: focnerf.h, which the binding is read from, is at neither {paths[0]} nor {paths[1]}")
 
 
-class FocOccTrainObject(ctypes.Structure):
-    """include/focnerf.h `FocOccTrainObject`, field for field: what an object-conditioned network adds to the node, beside it."""
-    _fields_ = [
-        ("struct_bytes", u32),
-        ("input_pad", f32),
-        ("obj_feat", c_vp),
-        ("ray_sumsq", c_vp),
-        ("grad_sumsq", c_vp),
-        ("grad_obj", c_vp),
-    ]
-
-
-class FocOccTrainTail(ctypes.Structure):
-    """include/focnerf.h `FocOccTrainTail`, field for field: the tail's optional per-ray buffers (distortion, depth_raw), beside the node."""
-    _fields_ = [
-        ("struct_bytes", u32),
-        ("ray_dist", c_vp), ("ray_wm", c_vp), ("depth_raw", c_vp),
-        ("grad_dist", c_vp), ("grad_depth", c_vp),
-    ]
-
-
-class FocCulledField(ctypes.Structure):
-    """include/focnerf.h `FocCulledField`, field for field: one object's compact culled lists for foc_combine_select_composite_culled."""
-    _fields_ = [
-        ("mask", c_vp), ("offsets", c_vp), ("sigma_c", c_vp), ("rgb_c", c_vp),
-        ("m_occ", u32), ("density_scale", f32), ("thresh", f32), ("sigma_gain", f32),
-    ]
-
-
-class FocOptimTensor(ctypes.Structure):
-    """include/focnerf.h `FocOptimTensor`, field for field: one tensor of an optimizer step (tests/test_optim_host.py compares names, order, size)."""
-    _fields_ = [
-        ("param", c_vp), ("grad", c_vp), ("exp_avg", c_vp), ("exp_avg_sq", c_vp), ("step", c_vp),
-        ("lr_tensor", c_vp),
-        ("n", ctypes.c_int64),
-        ("lr", f64), ("beta1", f64), ("beta2", f64), ("eps", f64), ("weight_decay", f64),
-    ]
-
-
-class FocOptimStep(ctypes.Structure):
-    """include/focnerf.h `FocOptimStep`, field for field: one call of foc_optim_step."""
-    _fields_ = [
-        ("struct_bytes", u32),
-        ("tensor_bytes", u32),
-        ("n_tensors", ctypes.c_int32),
-        ("phase", u32), ("zero_grads", u32),
-        ("growth_interval", ctypes.c_int32),
-        ("growth_factor", f32), ("backoff_factor", f32),
-        ("tensors", ctypes.POINTER(FocOptimTensor)),
-        ("scale", c_vp),
-        ("growth_tracker", c_vp),
-        ("grad_scale", c_vp), ("found_inf", c_vp),
-        ("workspace", c_vp),
-        ("workspace_bytes", u64),
-    ]
-
-
-# name -> (restype, [argtypes]) — one entry per declaration in include/focnerf.h
-SIGNATURES = {
-    "foc_abi_version": (i32, []),
-    "foc_last_error": (ctypes.c_char_p, []),
-    "foc_arch": (ctypes.c_char_p, []),
-    "foc_near_far_from_aabb": (i32, [c_vp, c_vp, c_vp, u32, f32, c_vp, c_vp, c_vp]),
-    "foc_sph_from_ray": (i32, [c_vp, c_vp, f32, u32, c_vp, c_vp]),
-    "foc_morton3D": (i32, [c_vp, u32, c_vp, c_vp]),
-    "foc_morton3D_invert": (i32, [c_vp, u32, c_vp, c_vp]),
-    "foc_packbits": (i32, [c_vp, u32, f32, c_vp, c_vp]),
-    "foc_march_rays_train": (i32, [c_vp, c_vp, c_vp, f32, f32, u32, u32, u32, u32, u32, c_vp, c_vp,
-                                   c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "foc_march_rays_train_field": (i32, [c_vp, c_vp, c_vp, f32, f32, u32, u32, u32, u32, u32, c_vp, c_vp,
-                                         c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, u32, c_vp, f32, c_vp]),
-    "foc_set_option": (i32, [ctypes.c_char_p, i32]),
-    "foc_get_option": (i32, [ctypes.c_char_p, c_vp]),
-    "foc_guard_pick_device": (i32, [i32, i32, i32, i32]),
-    "foc_grid_forward_index_path": (i32, [u32, u32, u32]),
-    "foc_view_tile_order": (i32, [c_vp, u32, u32, u32, c_vp, c_vp, c_vp]),
-    "foc_occ_train_forward": (i32, [ctypes.POINTER(FocOccTrainNode), c_vp]),
-    "foc_occ_train_backward": (i32, [ctypes.POINTER(FocOccTrainNode), c_vp]),
-    "foc_occ_train_forward_pad31": (i32, [ctypes.POINTER(FocOccTrainNode), f32, c_vp]),
-    "foc_occ_train_backward_pad31": (i32, [ctypes.POINTER(FocOccTrainNode), f32, c_vp]),
-    "foc_occ_train_forward_obj": (i32, [ctypes.POINTER(FocOccTrainNode), ctypes.POINTER(FocOccTrainObject), c_vp]),
-    "foc_occ_train_backward_obj": (i32, [ctypes.POINTER(FocOccTrainNode), ctypes.POINTER(FocOccTrainObject), c_vp]),
-    "foc_occ_tail_forward_sumsq": (i32, [c_vp, c_vp, u32, c_vp, c_vp, u32, u32, f32, f32, c_vp, f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "foc_occ_tail_backward_sumsq": (i32, [c_vp, c_vp, c_vp, c_vp, u32, c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, f32, f32, c_vp, f32, c_vp, c_vp, c_vp, c_vp]),
-    "foc_occ_tail_forward": (i32, [c_vp, c_vp, u32, c_vp, c_vp, u32, u32, f32, f32, c_vp, f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "foc_occ_tail_backward": (i32, [c_vp, c_vp, c_vp, c_vp, u32, c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, f32, f32, c_vp, f32, c_vp, c_vp, c_vp]),
-    "foc_occ_tail_forward_dist": (i32, [c_vp, c_vp, u32, c_vp, c_vp, u32, u32, f32, f32, c_vp, f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                        c_vp]),
-    "foc_occ_tail_backward_dist": (i32, [c_vp, c_vp, c_vp, c_vp, u32, c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, f32, f32, c_vp, f32, c_vp, c_vp, c_vp, c_vp,
-                                         c_vp, c_vp, c_vp]),
-    "foc_occ_tail_forward_depth": (i32, [c_vp, c_vp, u32, c_vp, c_vp, u32, u32, f32, f32, c_vp, f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                         c_vp, c_vp]),
-    "foc_occ_tail_backward_depth": (i32, [c_vp, c_vp, c_vp, c_vp, u32, c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, f32, f32, c_vp, f32, c_vp, c_vp, c_vp, c_vp,
-                                          c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "foc_occ_train_forward_tail": (i32, [ctypes.POINTER(FocOccTrainNode), ctypes.POINTER(FocOccTrainObject), f32, ctypes.POINTER(FocOccTrainTail), c_vp]),
-    "foc_occ_train_backward_tail": (i32, [ctypes.POINTER(FocOccTrainNode), ctypes.POINTER(FocOccTrainObject), f32, ctypes.POINTER(FocOccTrainTail), c_vp]),
-    "foc_march_rays_train_scratch_bytes": (u64, [u32, u32]),
-    "foc_composite_rays_train_forward": (i32, [c_vp, c_vp, c_vp, c_vp, u32, u32, f32, c_vp, c_vp, c_vp, c_vp]),
-    "foc_composite_rays_train_backward": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, f32,
-                                                c_vp, c_vp, c_vp]),
-    "foc_march_rays": (i32, [u32, u32, c_vp, c_vp, c_vp, c_vp, f32, f32, u32, u32, u32, c_vp, c_vp, c_vp,
-                             c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "foc_composite_rays": (i32, [u32, u32, f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "foc_compact_alive": (i32, [c_vp, u32, c_vp, c_vp, c_vp, c_vp]),
-    "foc_march_rays_two_phase": (i32, [u32, u32, c_vp, c_vp, c_vp, c_vp, f32, f32, u32, u32, u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, i32, c_vp]),
-    "foc_composite_compact": (i32, [u32, u32, f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, i32, c_vp]),
-    "foc_march_rays_two_phase_fills": (i32, [u32, i32]),
-    "foc_march_rays_two_phase_sample_major": (i32, [u32, u32, i32]),
-    "foc_occ_render_step_scratch_bytes": (u64, [u32]),
-    "foc_occ_render_step": (i32, [u32, u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, f32, f32, u32, u32, u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                  c_vp, c_vp, c_vp, u32, f32, u32, c_vp, u32, c_vp, u32, u32, c_vp, f32, c_vp, c_vp, c_vp, c_vp, u32, c_vp, u32, u32, c_vp]),
-    "foc_occ_render_step_pad31": (i32, [u32, u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, f32, f32, u32, u32, u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                        c_vp, c_vp, c_vp, u32, f32, u32, c_vp, u32, c_vp, u32, u32, c_vp, f32, c_vp, c_vp, c_vp, c_vp, u32, c_vp, u32, u32, f32,
-                                        c_vp]),
-    "foc_occ_render_step_pad": (i32, [u32, u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, f32, f32, u32, u32, u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                      c_vp, c_vp, c_vp, u32, f32, u32, c_vp, u32, c_vp, u32, u32, c_vp, f32, c_vp, c_vp, c_vp, c_vp, u32, c_vp, u32, u32, f32,
-                                      c_vp]),
-    "foc_grid_encode_forward": (i32, [c_vp, c_vp, c_vp, c_vp, u32, u32, u32, u32, f32, u32, c_vp, u32, i32, u32,
-                                      i32, c_vp, c_vp]),
-    "foc_grid_encode_forward_bl": (i32, [c_vp, c_vp, c_vp, c_vp, u32, u32, u32, u32, f32, u32, c_vp, u32, i32, u32,
-                                         i32, c_vp, c_vp]),
-    "foc_grid_encode_backward": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, u32, u32, f32, u32, c_vp, c_vp,
-                                       u32, i32, u32, i32, i32, c_vp, c_vp]),
-    "foc_grid_encode_backward_workspace_bytes": (u64, [u32, u32, u32, u32, i32]),
-    "foc_grid_planes_to_rows": (i32, [c_vp, c_vp, u32, u32, u32, c_vp]),
-    "foc_grid_rows_to_planes": (i32, [c_vp, c_vp, u32, u32, u32, c_vp]),
-    "foc_grid_encode_backward_binned": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, u32, u32, f32, u32, c_vp, c_vp,
-                                              u32, i32, u32, i32, i32, c_vp, c_vp, u64, c_vp]),
-    "foc_grid_encode_forward_counted": (i32, [c_vp, c_vp, c_vp, c_vp, u32, u32, u32, u32, f32, u32, u32, i32, u32, i32, c_vp, c_vp, u64, c_vp]),
-    "foc_grid_encode_backward_count": (i32, [c_vp, c_vp, u32, u32, u32, u32, f32, u32, u32, i32, u32, i32, c_vp, c_vp, u64, c_vp]),
-    "foc_grid_encode_backward_binned_counted": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, u32, u32, f32, u32, c_vp, c_vp,
-                                                      u32, i32, u32, i32, i32, c_vp, c_vp, u64, c_vp]),
-    "foc_grad_total_variation": (i32, [c_vp, c_vp, c_vp, c_vp, f32, u32, u32, u32, u32, f32, u32, u32, i32, i32, c_vp]),
-    "foc_freq_encode_forward": (i32, [c_vp, u32, u32, u32, u32, c_vp, c_vp]),
-    "foc_freq_encode_backward": (i32, [c_vp, c_vp, u32, u32, u32, u32, c_vp, c_vp]),
-    "foc_ffmlp_forward": (i32, [c_vp, c_vp, u32, u32, u32, u32, u32, u32, u32, c_vp, c_vp, c_vp]),
-    "foc_ffmlp_inference": (i32, [c_vp, c_vp, u32, u32, u32, u32, u32, u32, u32, c_vp, c_vp, c_vp]),
-    "foc_ffmlp_backward": (i32, [c_vp, c_vp, c_vp, c_vp, u32, u32, u32, u32, u32, u32, u32, i32,
-                                 c_vp, c_vp, c_vp, c_vp, u64, c_vp]),
-    "foc_ffmlp_backward_workspace_bytes": (u64, [u32, u32, u32]),
-    "foc_ffmlp_forward_planar": (i32, [c_vp, c_vp, u32, u32, u32, u32, u32, u32, u32, c_vp, c_vp]),
-    "foc_ffmlp_backward_planar": (i32, [c_vp, c_vp, c_vp, u32, u32, u32, u32, u32, u32, u32, i32, c_vp, c_vp, c_vp, u64, c_vp]),
-    "foc_allocate_splitk": (i32, [u64]),
-    "foc_free_splitk": (i32, []),
-    "foc_combine_select": (i32, [c_vp, c_vp, c_vp, c_vp, u64, c_vp]),
-    "foc_combine_pack_keys": (i32, [c_vp, u32, c_vp, u64, c_vp]),
-    "foc_combine_unpack": (i32, [c_vp, u32, c_vp, c_vp, c_vp, u64, c_vp]),
-    "foc_combine_select_composite": (i32, [c_vp, u32, c_vp, c_vp, u32, u32, c_vp, u32, c_vp, c_vp, c_vp, c_vp]),
-    "foc_combine_select4": (i32, [c_vp, c_vp, u64, c_vp]),
-    "foc_combine_select_composite_attr": (i32, [c_vp, u32, c_vp, c_vp, u32, c_vp, c_vp, u32, u32, c_vp, u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "foc_combine_select_composite_culled": (i32, [ctypes.POINTER(FocCulledField), u32, u32, c_vp, u32, c_vp, c_vp, u32, u32, c_vp, u32, c_vp, c_vp, c_vp, c_vp,
-                                                  c_vp, c_vp, c_vp, c_vp]),
-    "foc_combine_select4_ids": (i32, [c_vp, u32, c_vp, c_vp, u64, c_vp]),
-    "foc_mo_select": (i32, [c_vp, c_vp, c_vp, c_vp, u64, u32, u32, c_vp]),
-    "foc_fixed_field_pack": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, f32, u32, u32, f32, f32, c_vp, c_vp, c_vp, c_vp, u32, c_vp]),
-    "foc_fixed_cull_scratch_bytes": (u64, [u32, u32]),
-    "foc_fixed_cull": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, f32, c_vp, u32, u32, c_vp, c_vp, c_vp, c_vp, u64, c_vp]),
-    "foc_fixed_cull_emit": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, f32, c_vp, c_vp, u32, c_vp, c_vp, c_vp]),
-    "foc_fixed_field_pack_culled": (i32, [c_vp, c_vp, c_vp, c_vp, u32, c_vp, c_vp, u32, u32, f32, f32, c_vp, c_vp]),
-    "foc_fixed_cull_placed": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, c_vp, c_vp, f32, c_vp, u32, u32, c_vp, c_vp, c_vp, c_vp, u64, c_vp]),
-    "foc_fixed_cull_emit_placed": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, c_vp, f32, f32, c_vp, c_vp, u32, c_vp, c_vp, c_vp]),
-    "foc_fixed_field_pack_culled_gain": (i32, [c_vp, c_vp, c_vp, c_vp, u32, c_vp, c_vp, u32, u32, f32, f32, f32, c_vp, c_vp]),
-    "foc_composite_fixed_steps":(i32, [c_vp, c_vp, c_vp, c_vp, u32, u32, f32, c_vp, c_vp, c_vp]),
-    "foc_fixed_sample": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, f32, c_vp, c_vp, c_vp, u32, c_vp]),
-    "foc_fixed_tail_forward": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, f32, u32, u32, f32, f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, u32, c_vp, c_vp]),
-    "foc_fixed_tail_backward": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, f32, u32, u32, f32, f32, c_vp, c_vp, u32, c_vp, c_vp]),
-    "foc_fixed_tail_forward_dist": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, f32, u32, u32, f32, f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, u32, c_vp, c_vp,
-                                          c_vp, c_vp]),
-    "foc_fixed_tail_backward_dist": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, f32, u32, u32, f32, f32, c_vp, c_vp, u32,
-                                           c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "foc_fixed_head_forward": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, u32, c_vp]),
-    "foc_fixed_head_backward": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, u32, u32, f32, c_vp, u32, c_vp]),
-    "foc_color_head_forward": (i32, [c_vp, c_vp, u32, c_vp, u32, u32, u32, u32, c_vp, u32, c_vp, c_vp]),
-    "foc_field_forward_train": (i32, [c_vp, c_vp, u32, c_vp, u32, c_vp, u32, u32, u32, u32, c_vp, c_vp, u32, c_vp, c_vp]),
-    "foc_color_head_backward": (i32, [c_vp, c_vp, c_vp, u32, c_vp, c_vp, u32, u32, u32, u32, c_vp, c_vp, c_vp, u64, u32, c_vp, c_vp, c_vp]),
-    "foc_color_head_forward_pad": (i32, [c_vp, c_vp, u32, c_vp, u32, u32, u32, u32, c_vp, u32, c_vp, f32, c_vp]),
-    "foc_color_head_backward_pad": (i32, [c_vp, c_vp, c_vp, u32, c_vp, c_vp, u32, u32, u32, u32, c_vp, c_vp, c_vp, u64, u32, c_vp, c_vp, f32, c_vp]),
-    "foc_field_forward_train_pad": (i32, [c_vp, c_vp, u32, c_vp, u32, c_vp, u32, u32, u32, u32, c_vp, c_vp, u32, c_vp, f32, c_vp]),
-    "foc_color_head_forward_pad31": (i32, [c_vp, c_vp, u32, c_vp, u32, u32, u32, u32, c_vp, u32, c_vp, f32, c_vp]),
-    "foc_color_head_backward_pad31": (i32, [c_vp, c_vp, c_vp, u32, c_vp, c_vp, u32, u32, u32, u32, c_vp, c_vp, c_vp, u64, u32, c_vp, c_vp, f32, c_vp]),
-    "foc_field_forward_train_pad31": (i32, [c_vp, c_vp, u32, c_vp, u32, c_vp, u32, u32, u32, u32, c_vp, c_vp, u32, c_vp, f32, c_vp]),
-    "foc_fixed_composite_forward": (i32, [c_vp, c_vp, c_vp, f32, u32, u32, f32, c_vp, c_vp]),
-    "foc_fixed_composite_backward": (i32, [c_vp, c_vp, c_vp, c_vp, f32, u32, u32, f32, c_vp, c_vp, c_vp]),
-    "foc_sample_head_forward": (i32, [c_vp, c_vp, u64, c_vp, c_vp, c_vp, u32, c_vp]),
-    "foc_sample_head_backward": (i32, [c_vp, c_vp, c_vp, u64, c_vp, u32, c_vp]),
-    "foc_sh_encode": (i32, [c_vp, u64, c_vp, c_vp]),
-    "foc_rgb_head_forward": (i32, [c_vp, u64, c_vp, c_vp]),
-    "foc_rgb_head_backward": (i32, [c_vp, c_vp, u64, c_vp, c_vp]),
-    "foc_fixed_render_inference": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, f32, u32, u32, f32, f32, c_vp, c_vp, c_vp, c_vp, u32, c_vp, c_vp]),
-    "foc_nerf_field_inference": (i32, [c_vp, i32, c_vp, u32, u32, u32, c_vp, u32, c_vp, u32, u32, u32, u32, c_vp, c_vp, c_vp, c_vp]),
-    "foc_nerf_field_inference_pad": (i32, [c_vp, i32, c_vp, u32, u32, u32, c_vp, u32, c_vp, u32, u32, u32, u32, c_vp, c_vp, c_vp, f32, c_vp]),
-    "foc_nerf_field_inference_pad31": (i32, [c_vp, i32, c_vp, u32, u32, u32, c_vp, u32, c_vp, u32, u32, u32, u32, c_vp, c_vp, c_vp, f32, c_vp]),
-    "foc_field_normals": (i32, [c_vp, u32, c_vp, c_vp, u32, u32, u32, f32, u32, u32, i32, u32, i32, c_vp, c_vp, u32, u32, u32, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                c_vp]),
-    "foc_mark_untrained_grid": (i32, [c_vp, u32, f32, f32, f32, f32, f32, u32, u32, c_vp, c_vp, c_vp]),
-    "foc_grid_cells_xyz": (i32, [u32, u32, f32, c_vp, c_vp, c_vp]),
-    "foc_grid_update_sample_workspace_bytes": (u64, [u32, u32]),
-    "foc_grid_update_sample": (i32, [c_vp, u32, u32, f32, u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, u64, c_vp]),
-    "foc_grid_update_apply_workspace_bytes": (u64, [u32, u32]),
-    "foc_grid_update_apply": (i32, [c_vp, u32, u32, c_vp, c_vp, u32, f32, f32, f32, c_vp, c_vp, c_vp, u64, c_vp]),
-    "foc_background_forward": (i32, [c_vp, c_vp, c_vp, f32, u32, c_vp, c_vp, f32, u32, c_vp, c_vp, c_vp]),
-    "foc_background_backward_workspace_bytes": (u64, [u32]),
-    "foc_background_backward": (i32, [c_vp, c_vp, c_vp, c_vp, f32, u32, c_vp, c_vp, f32, u32, c_vp, c_vp, c_vp, c_vp, u64, c_vp]),
-    "foc_mc_workspace_bytes": (u64, [u32, u32, u32]),
-    "foc_mc_count": (i32, [c_vp, u32, u32, u32, f32, c_vp, c_vp, c_vp]),
-    "foc_mc_emit": (i32, [c_vp, u32, u32, u32, f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "foc_lattice_cull_scratch_bytes": (u64, [u32]),
-    "foc_lattice_cull": (i32, [c_vp, c_vp, c_vp, u32, u32, u32, u32, u32, c_vp, c_vp, f32, c_vp, u32, u32, c_vp, c_vp, c_vp, c_vp, u64, c_vp]),
-    "foc_lattice_cull_emit": (i32, [c_vp, c_vp, c_vp, u32, u32, u32, u32, u32, c_vp, c_vp, c_vp, u32, c_vp, c_vp]),
-    "foc_volume_scatter_max": (i32, [c_vp, c_vp, c_vp, f32, c_vp, u32, c_vp]),
-    "foc_score_workspace_bytes": (u64, [u32, u32, u32]),
-    "foc_score_quantize": (i32, [c_vp, c_vp, c_vp, c_vp, u32, u32, u32, c_vp, c_vp, c_vp, c_vp]),
-    "foc_score_view": (i32, [c_vp, c_vp, u32, u32, u32, c_vp, u32, f64, f64, c_vp, c_vp, u64, c_vp]),
-    "foc_optim_workspace_bytes": (ctypes.c_size_t, [i32]),
-    "foc_optim_step": (i32, [ctypes.POINTER(FocOptimStep), c_vp]),
-    "foc_philox4x32_10": (i32, [ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32)]),
-    "foc_batch_workspace_bytes": (u64, []),
-    "foc_batch_sample": (i32, [c_vp, i32, u32, u32, u32, u32, c_vp, f32, f32, f32, f32, c_vp, c_vp, u64, u32, c_vp, i32, i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
-                               c_vp, u64, u32, c_vp]),
-    "foc_view_rays": (i32, [c_vp, f32, f32, f32, f32, u32, u32, c_vp, c_vp, c_vp]),
-    "foc_photo_loss_workspace_bytes": (u64, []),
-    "foc_photo_loss": (i32, [c_vp, i32, c_vp, u32, i32, f32, c_vp, u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, u64, c_vp]),
-}
+# The binding is the header: DEFINES name -> int for every `#define FOC_*`, STRUCTS name -> ctypes.Structure for every `typedef struct`,
+# SIGNATURES name -> (restype, [argtypes]) for every `foc_*` declaration; a pointer argument is `c_vp` unless it points to one of the structs.
+DEFINES, STRUCTS, SIGNATURES = _header.read(_find_header())
+globals().update(STRUCTS)       # FocOccTrainNode, FocOccTrainObject, FocOccTrainTail, FocCulledField, FocOptimTensor, FocOptimStep
+FOC_F32, FOC_F16, FOC_U8 = DEFINES["FOC_F32"], DEFINES["FOC_F16"], DEFINES["FOC_U8"]      # FOC_U8: images of foc_batch_sample only
 
 
 def _load():

@@ -21,10 +21,10 @@ import ctypes
 
 import torch
 
-from ._lib import FocOptimStep, FocOptimTensor, check, lib, stream_of
+from ._lib import DEFINES, FocOptimStep, FocOptimTensor, check, lib, stream_of
 
-CHUNK = 4096                    # elements per workgroup of the kernels (include/focnerf.h FOC_OPTIM_CHUNK)
-MAX_TENSORS = 16                # tensors per call (FOC_OPTIM_MAX_TENSORS)
+CHUNK = DEFINES["FOC_OPTIM_CHUNK"]                    # elements per workgroup of the kernels (include/focnerf.h)
+MAX_TENSORS = DEFINES["FOC_OPTIM_MAX_TENSORS"]        # tensors per call
 _PHASE_STEP, _PHASE_CHECK, _PHASE_DECIDE = 0, 1, 2
 _WS_FOUND, _WS_SCALE_USED = 5, 6    # words of the workspace where the decide phase leaves found_inf and the scale of this step's grads
 

@@ -16,6 +16,7 @@ import subprocess
 
 from setuptools import Extension, find_packages, setup
 from setuptools.command.build_ext import build_ext
+from setuptools.command.build_py import build_py
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROCM = os.environ.get("ROCM_HOME", "/opt/rocm")
@@ -27,6 +28,12 @@ class BuildHip(build_ext):
         super().run()
         if self.inplace:                      # the in-tree layout the tests and INTEGRATION.md use: focnerf_amd/ext on PYTHONPATH
             subprocess.check_call(["make", "-C", os.path.join(HERE, "focnerf_amd", "csrc", "ext"), "-j4"])
+
+
+class BuildPy(build_py):
+    def run(self):                            # the binding is read from the header (focnerf_amd/_lib.py): an installed package carries its copy
+        super().run()
+        self.copy_file(os.path.join(HERE, "include", "focnerf.h"), os.path.join(self.build_lib, "focnerf_amd", "focnerf.h"))
 
 
 def shim(name):
@@ -52,8 +59,8 @@ if __name__ == "__main__":
         version="0.2.0",
         description="FOCNeRF volume-rendering hot path on MI355X (gfx950): hand-written HIP kernels behind the reference's extension API",
         packages=find_packages(include=["focnerf_amd", "focnerf_amd.*"]),
-        package_data={"focnerf_amd": ["libfocnerf_hip.so"]},
+        package_data={"focnerf_amd": ["libfocnerf_hip.so", "focnerf.h"]},
         ext_modules=[shim(n) for n in ("raymarching", "gridencoder", "freqencoder", "ffmlp")],
-        cmdclass={"build_ext": BuildHip},
+        cmdclass={"build_ext": BuildHip, "build_py": BuildPy},
         zip_safe=False,
     )

@@ -3,8 +3,11 @@ import ctypes
 import os
 import re
 
+import pytest
+
+from util import HEADER, build_c_abi_consumer, c_struct_layouts
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(REPO, "include", "focnerf.h")
 
 
 def _declared():
@@ -64,30 +67,40 @@ def test_argument_validation_needs_no_gpu():
     assert rc == 1 and b"workspace of" in lib.foc_last_error()
 
 
-def test_occ_train_node_struct_matches_the_header_and_is_validated_on_the_host():
-    """include/focnerf.h `FocOccTrainNode` against its ctypes mirror (focnerf_amd/_lib.py): same field names in the same order, and the size
-    a C compiler gives the header's struct; a null node, a node of another size and an empty node are refused before any launch."""
-    import re
-    import subprocess
-    import tempfile
+STRUCTS = ["FocCulledField", "FocOccTrainNode", "FocOccTrainObject", "FocOccTrainTail", "FocOptimTensor", "FocOptimStep"]
+
+
+@pytest.fixture(scope="module")
+def c_layouts(tmp_path_factory):
+    return c_struct_layouts(tmp_path_factory.mktemp("layout"), STRUCTS)
+
+
+def test_the_binding_has_exactly_the_headers_structs():
     from focnerf_amd import _lib
-    text = open(HEADER).read()
-    body = re.search(r"typedef struct FocOccTrainNode \{(.*?)\} FocOccTrainNode;", text, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        first, *rest = decl.split(",")
-        names.append(re.findall(r"[A-Za-z_0-9]+$", first.strip())[0])
-        names += [r.strip().lstrip("*").strip() for r in rest]
-    assert names == [f[0] for f in _lib.FocOccTrainNode._fields_]
-    with tempfile.TemporaryDirectory() as tmp:
-        src = os.path.join(tmp, "sz.c")
-        open(src, "w").write('#include <stdio.h>\n#include "%s"\nint main(void) { printf("%%zu", sizeof(FocOccTrainNode)); return 0; }\n' % HEADER)
-        subprocess.run(["gcc", "-o", os.path.join(tmp, "sz"), src], check=True)
-        assert int(subprocess.run([os.path.join(tmp, "sz")], capture_output=True, text=True, check=True).stdout) == ctypes.sizeof(_lib.FocOccTrainNode)
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    assert re.findall(r"typedef\s+struct\s+(\w+)", text) == STRUCTS == list(_lib.STRUCTS)
+    assert all(getattr(_lib, n) is _lib.STRUCTS[n] and issubclass(_lib.STRUCTS[n], ctypes.Structure) for n in STRUCTS)
+    assert ctypes.sizeof(_lib.FocCulledField) == 48
+
+
+@pytest.mark.parametrize("name", STRUCTS)
+def test_struct_layout_matches_the_header(name, c_layouts):
+    """Every struct that travels by pointer, as gcc lays out include/focnerf.h against its ctypes class (focnerf_amd/_lib.py, read from the
+    same header by focnerf_amd/_header.py): the field names in order — found here by tests/util.py's own regex —, sizeof, and the offset
+    of every field."""
+    from focnerf_amd import _lib
+    S = getattr(_lib, name)
+    size, offsets = c_layouts[name]
+    assert list(offsets) == [f[0] for f in S._fields_]
+    assert size == ctypes.sizeof(S)
+    assert offsets == {n: getattr(S, n).offset for n in offsets}
+
+
+def test_occ_train_node_struct_matches_the_header_and_is_validated_on_the_host():
+    """include/focnerf.h `FocOccTrainNode` (its layout: test_struct_layout_matches_the_header above): a null node, a node of another size and
+    an empty node are refused before any launch."""
+    from focnerf_amd import _lib
+    assert len(_lib.FocOccTrainNode._fields_) == 69 and _lib.FocOccTrainNode._fields_[0][0] == "struct_bytes"
     lib = _lib.lib
     for fn in (lib.foc_occ_train_forward, lib.foc_occ_train_backward):
         assert fn(None, None) == 1 and b"null node" in lib.foc_last_error()
@@ -100,13 +113,116 @@ def test_occ_train_node_struct_matches_the_header_and_is_validated_on_the_host()
         assert fn(ctypes.byref(node), None) == 1 and b"workspace" in lib.foc_last_error()
 
 
+# ---------------------------------------------------------------- the header reader (focnerf_amd/_header.py)
+def _same(got, want):
+    return got[0] is want[0] and len(got[1]) == len(want[1]) and all(g is w for g, w in zip(got[1], want[1]))
+
+
+def test_reader_gives_these_signatures_literally():
+    """One entry point per row of the reader's type map, written out by hand and compared by identity: the ctypes functions get exactly
+    these objects, and `c_vp` is what bench.py and the stream-wrapping of `_lib._Lib` test a last argument against."""
+    from ctypes import POINTER, c_char_p, c_double as f64, c_float as f32, c_int, c_size_t, c_uint32 as u32, c_uint64 as u64
+    from focnerf_amd import _lib
+    vp, S = _lib.c_vp, _lib.SIGNATURES
+    assert vp is ctypes.c_void_p and isinstance(S, dict) and all(isinstance(a, list) for _, a in S.values())
+    want = {
+        "foc_last_error": (c_char_p, []),                                                       # `const char *` returned, `(void)`
+        "foc_abi_version": (c_int, []),
+        "foc_set_option": (c_int, [c_char_p, c_int]),                                           # `const char *` taken
+        "foc_march_rays_train_scratch_bytes": (u64, [u32, u32]),                                # a uint64_t return
+        "foc_optim_workspace_bytes": (c_size_t, [c_int]),                                       # size_t
+        "foc_score_view": (c_int, [vp, vp, u32, u32, u32, vp, u32, f64, f64, vp, vp, u64, vp]),   # double, uint64_t
+        "foc_combine_select_composite": (c_int, [vp, u32, vp, vp, u32, u32, vp, u32, vp, vp, vp, vp]),      # `const float *const *`
+        "foc_occ_train_forward_tail": (c_int, [POINTER(_lib.FocOccTrainNode), POINTER(_lib.FocOccTrainObject), f32, POINTER(_lib.FocOccTrainTail), vp]),
+        "foc_combine_select_composite_culled": (c_int, [POINTER(_lib.FocCulledField), u32, u32, vp, u32, vp, vp, u32, u32, vp, u32, vp, vp, vp, vp,
+                                                        vp, vp, vp, vp]),
+        "foc_philox4x32_10": (c_int, [vp, vp, vp]),                                             # `uint32_t *`: a pointer like every other
+        "foc_packbits": (c_int, [vp, u32, f32, vp, vp]),                                        # `uint8_t *`
+    }
+    for name, sig in want.items():
+        assert _same(S[name], sig), (name, S[name])
+    assert _lib.FocOptimTensor._fields_[5:8] == [("lr_tensor", vp), ("n", ctypes.c_int64), ("lr", f64)]                      # int64_t
+    assert _lib.FocOptimStep._fields_[2:4] == [("n_tensors", ctypes.c_int32), ("phase", u32)]                                # int32_t
+    assert dict(_lib.FocOptimStep._fields_)["tensors"] is POINTER(_lib.FocOptimTensor)
+    assert _lib.FocOccTrainNode._fields_[10:15] == [(n, vp) for n in ("rays_o", "rays_d", "aabb", "jitter", "bitfield")]    # `a, *b` lists
+    assert (_lib.FOC_F32, _lib.FOC_F16, _lib.FOC_U8) == (0, 1, 2) and _lib.DEFINES["FOC_OPTIM_CHUNK"] == 4096
+    assert all(n.startswith("FOC_") and type(v) is int for n, v in _lib.DEFINES.items()) and len(_lib.DEFINES) == 17
+
+
+def test_header_is_looked_for_in_the_tree_then_beside_the_package(tmp_path, monkeypatch):
+    from focnerf_amd import _lib
+    assert os.path.samefile(_lib._find_header(), HEADER)
+    monkeypatch.setattr(_lib, "_HERE", str(tmp_path / "site" / "focnerf_amd"))
+    with pytest.raises(ImportError) as e:
+        _lib._find_header()
+    assert str(tmp_path / "site" / "include" / "focnerf.h") in str(e.value) and str(tmp_path / "site" / "focnerf_amd" / "focnerf.h") in str(e.value)
+    os.makedirs(tmp_path / "site" / "focnerf_amd")
+    (tmp_path / "site" / "focnerf_amd" / "focnerf.h").write_text("")
+    assert _lib._find_header() == str(tmp_path / "site" / "focnerf_amd" / "focnerf.h")       # an installed package: setup.py's copy
+
+
+def test_reader_reads_a_small_header():
+    from focnerf_amd import _header
+    defines, structs, sigs = _header.parse("""
+        /* a comment with int foc_not_this(void); inside */
+        #ifndef H
+        #define H
+        #include <stdint.h>
+        #ifdef __cplusplus
+        extern "C" {
+        #endif
+        #define FOC_N 0x10   /* sixteen */
+        typedef struct FocA { uint32_t n, m; const float *p, *q; double d; } FocA;   // trailing
+        typedef struct FocB { const FocA *a; FocA **list; int64_t k; } FocB;
+        uint64_t foc_f(const FocB *b, const FocA *const *as, const char *name,
+                       int32_t i, void *stream);
+        const char *foc_g(void);
+        #ifdef __cplusplus
+        }
+        #endif
+        #endif
+    """)
+    A, B, vp = structs["FocA"], structs["FocB"], ctypes.c_void_p
+    assert defines == {"FOC_N": 16} and list(structs) == ["FocA", "FocB"] and list(sigs) == ["foc_f", "foc_g"]
+    assert A._fields_ == [("n", ctypes.c_uint32), ("m", ctypes.c_uint32), ("p", vp), ("q", vp), ("d", ctypes.c_double)]
+    assert B._fields_ == [("a", ctypes.POINTER(A)), ("list", vp), ("k", ctypes.c_int64)]
+    assert _same(sigs["foc_f"], (ctypes.c_uint64, [ctypes.POINTER(B), vp, ctypes.c_char_p, ctypes.c_int32, vp]))
+    assert _same(sigs["foc_g"], (ctypes.c_char_p, []))
+
+
+@pytest.mark.parametrize("text, names", [
+    ("int foc_f(uint16_t n);", "uint16_t"),                                  # an unknown scalar: never taken for a pointer or an int
+    ("int foc_f(uint8_t n);", "uint8_t"),                                    # known behind a pointer only
+    ("int foc_f(unsigned int n);", "unsigned int n"),
+    ("int foc_f(hipStream_t *s);", "hipStream_t"),
+    ("long foc_f(void);", "long"),
+    ("int foc_f(uint32_t);", "uint32_t"),                                    # an argument without a name
+    ("int foc_f();", "foc_f"),
+    ("int foc_f(const FocLater *p);\ntypedef struct FocLater { int a; } FocLater;", "FocLater"),     # a struct not declared yet
+    ("typedef struct FocA { const FocNone *p; } FocA;", "FocNone"),
+    ("typedef struct FocA { float v[3]; } FocA;", "v[3]"),
+    ("typedef struct FocA { uint32_t a : 3; } FocA;", "a : 3"),
+    ("int foc_f(void);\nint other(void);", "other"),                         # stray text: a declaration that is not foc_*
+    ("static int foc_f(void);", "static"),
+    ("int foc_f(void (*cb)(int));", "cb"),
+    ("int foc_f(void)\nint foc_g(void);", "foc_f"),                          # a lost semicolon
+    ("int foc_f(void);\n}", "}"),
+    ('extern "C" {\nint foc_f(void);', "never closed"),
+    ("#if FOC_X\nint foc_f(void);\n#endif", "#if FOC_X"),                    # a declaration behind a condition it cannot evaluate
+    ("#define FOC_X 1.5f", "1.5f"),
+    ("#define FOC_X (1 << \\\n 4)", "FOC_X"),
+])
+def test_reader_refuses_what_it_does_not_know(text, names):
+    from focnerf_amd import _header
+    with pytest.raises(ImportError) as e:
+        _header.parse(text)
+    assert names in str(e.value), str(e.value)
+
+
 def test_a_c_caller_links_the_library_and_gets_host_side_refusals(tmp_path):
     """tests/c_abi_consumer.cpp, mode "cpu": a program that is not Python includes include/focnerf.h, links libfocnerf_hip.so and gets the ABI
     version, refusals with messages, the option table — without a device (the device half runs in tests/test_gpu_edge_cases.py)."""
     import subprocess
-    import sys
-    sys.path.insert(0, os.path.join(REPO, "tests"))
-    from util import build_c_abi_consumer
     import oracle                                                    # noqa: F401 — builds oracle/_build/liboracle.so if it is missing
     exe = build_c_abi_consumer(tmp_path)
     r = subprocess.run([exe, "cpu"], capture_output=True, text=True, timeout=120)
@@ -144,7 +260,6 @@ def test_forward_index_path_admission_needs_no_gpu():
 
 
 def test_ops_refuse_cpu_tensors():
-    import pytest
     import torch
     from focnerf_amd import raymarching
     if torch.cuda.is_available():

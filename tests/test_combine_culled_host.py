@@ -1,31 +1,8 @@
 """CPU: the host side of the combine fed from culled lists (include/focnerf.h FocCulledField / foc_combine_select_composite_culled,
-combine.combine_culled / culled_field_fns): the struct as C and as ctypes see it, the refusals that need no device, the argument checks."""
+combine.combine_culled / culled_field_fns): the refusals that need no device, the argument checks."""
 import ctypes
-import os
-import re
-import subprocess
 
 import pytest
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(REPO, "include", "focnerf.h")
-
-
-def test_culled_field_struct_matches_the_header(tmp_path):
-    from focnerf_amd import _lib
-    text = open(HEADER).read()
-    body = re.search(r"typedef struct FocCulledField \{(.*?)\} FocCulledField;", text, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = [re.findall(r"[A-Za-z_0-9]+$", decl.strip())[0] for decl in body.split(";") if decl.strip()]
-    assert names == [f[0] for f in _lib.FocCulledField._fields_]
-    src = tmp_path / "sz.c"
-    prints = "".join(' printf("%%zu ", offsetof(FocCulledField, %s));' % n for n in names)
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(void) { printf("%%zu ", sizeof(FocCulledField));%s return 0; }\n'
-                   % (HEADER, prints))
-    subprocess.run(["gcc", "-o", str(tmp_path / "sz"), str(src)], check=True)
-    got = [int(v) for v in subprocess.run([str(tmp_path / "sz")], capture_output=True, text=True, check=True).stdout.split()]
-    assert got == [ctypes.sizeof(_lib.FocCulledField)] + [getattr(_lib.FocCulledField, n).offset for n in names]
-    assert got[0] == 48
 
 
 def test_refusals_need_no_gpu():

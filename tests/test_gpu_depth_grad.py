@@ -13,7 +13,7 @@ cannot exclude. Every pre-existing output of the _depth forward is bit for bit t
 with grad_depth NULL or 0 is the plain backward's bits, a ray that is clamped or whose own grad_depth is 0 has the plain rows, rows behind a
 stop carry no depth gradient, guard elements around depth_raw keep their sentinel.
 
-The struct's header text against its ctypes mirror and the host-side refusals need no GPU: tests/test_depth_ref.py.
+The struct's layout against gcc's (tests/test_abi.py) and the host-side refusals (tests/test_depth_ref.py) need no GPU.
 
 Through the network the depth does not depend on the colour network (t, near and far carry no gradient, the weights are the density's): a
 depth-only loss gives a non-zero gradient on the embeddings and the density blob and an exactly zero one on the colour blob and the object

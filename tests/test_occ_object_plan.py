@@ -2,22 +2,18 @@
 
   * `field.field_plan`'s two verdicts for it (`occ_object`, `native_loop_object`) across networks, switches, layer pairs and a background
     radius, with `occ` / `native_loop` as they were;
-  * include/focnerf.h `FocOccTrainObject` against its ctypes mirror;
   * every refusal of foc_occ_train_forward_obj / _backward_obj, foc_occ_render_step_pad and the *_sumsq tails: non-zero, a message that
     names the entry point, nothing enqueued (there is no device to enqueue on);
   * a mask that is not per ray raises before anything is launched.
 """
 import ctypes
 import os
-import re
-import subprocess
 
 import pytest
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
-HEADER = os.path.join(REPO, "include", "focnerf.h")
 
 pytestmark = pytest.mark.skipif(not os.path.exists(os.path.join(REPO, "focnerf_amd", "libfocnerf_hip.so")), reason="libfocnerf_hip.so not built")
 
@@ -79,32 +75,6 @@ def test_layer_pairs_of_the_object_node(monkeypatch):
         assert bool(p.occ_object) is want and bool(p.native_loop_object) is want, (sigma_layers, colour_layers)
     p = _plan(_net("tcnn", num_layers=2, num_layers_color=3))                       # tinycudann counts hidden layers: (1, 2)
     assert (p.sigma.num_layers, p.colour.num_layers) == (1, 2) and p.occ_object and p.native_loop_object
-
-
-# ---------------------------------------------------------------- the struct
-def _struct_fields(name):
-    text = open(HEADER).read()
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), text, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        first, *rest = decl.split(",")
-        names.append(re.findall(r"[A-Za-z_0-9]+$", first.strip())[0])
-        names += [r.strip().lstrip("*").strip() for r in rest]
-    return names
-
-
-def test_object_struct_matches_the_header(tmp_path):
-    from focnerf_amd import _lib
-    assert _struct_fields("FocOccTrainObject") == [f[0] for f in _lib.FocOccTrainObject._fields_]
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include "%s"\nint main(void) { printf("%%zu %%zu", sizeof(FocOccTrainObject), sizeof(FocOccTrainNode)); return 0; }\n' % HEADER)
-    subprocess.run(["gcc", "-o", str(tmp_path / "sz"), str(src)], check=True)
-    sizes = subprocess.run([str(tmp_path / "sz")], capture_output=True, text=True, check=True).stdout.split()
-    assert [int(v) for v in sizes] == [ctypes.sizeof(_lib.FocOccTrainObject), ctypes.sizeof(_lib.FocOccTrainNode)]
 
 
 # ---------------------------------------------------------------- refusals

@@ -2,18 +2,12 @@
 refusals), and what focnerf_amd.optim promises without a device: state dicts that go both ways with torch's Adam and GradScaler, the
 constructor's refusals, the exports."""
 import ctypes
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import adam_ref
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(REPO, "include", "focnerf.h")
 
 
 # ---------------------------------------------------------------- the reference itself
@@ -76,32 +70,15 @@ def test_scale_rule_is_torchs_amp_update_scale_rule():
 
 
 # ---------------------------------------------------------------- C ABI
-def _struct_fields(name):
-    text = open(HEADER).read()
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), text, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        first, *rest = decl.split(",")
-        names.append(re.findall(r"[A-Za-z_0-9]+$", first.strip())[0])
-        names += [r.strip().lstrip("*").strip() for r in rest]
-    return names
-
-
 def test_optim_structs_match_the_header(tmp_path):
+    """The layouts of FocOptimStep / FocOptimTensor against gcc's: tests/test_abi.py test_struct_layout_matches_the_header. Here: the sizes
+    the call states about itself and the two limits, as gcc prints them from include/focnerf.h."""
     from focnerf_amd import _lib, optim
-    assert _struct_fields("FocOptimStep") == [f[0] for f in _lib.FocOptimStep._fields_]
-    assert _struct_fields("FocOptimTensor") == [f[0] for f in _lib.FocOptimTensor._fields_]
+    from util import c_header_values
     assert _lib.FocOptimStep._fields_[0][0] == "struct_bytes"
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include "%s"\nint main(void) { printf("%%zu %%zu %%d %%d", sizeof(FocOptimStep), sizeof(FocOptimTensor), '
-                   'FOC_OPTIM_CHUNK, FOC_OPTIM_MAX_TENSORS); return 0; }\n' % HEADER)
-    subprocess.run(["gcc", "-o", str(tmp_path / "sz"), str(src)], check=True)
-    out = subprocess.run([str(tmp_path / "sz")], capture_output=True, text=True, check=True).stdout.split()
-    assert [int(x) for x in out] == [ctypes.sizeof(_lib.FocOptimStep), ctypes.sizeof(_lib.FocOptimTensor), optim.CHUNK, optim.MAX_TENSORS]
+    out = c_header_values(tmp_path, ["sizeof(FocOptimStep)", "sizeof(FocOptimTensor)", "FOC_OPTIM_CHUNK", "FOC_OPTIM_MAX_TENSORS"])
+    assert out == [ctypes.sizeof(_lib.FocOptimStep), ctypes.sizeof(_lib.FocOptimTensor), optim.CHUNK, optim.MAX_TENSORS]
+    assert out[2:] == [4096, 16]
     assert _lib.lib.foc_abi_version() == 2
 
 

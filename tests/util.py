@@ -1,5 +1,8 @@
 """Shared helpers for the GPU parity tests."""
 import math
+import os
+import re
+import subprocess
 
 import numpy as np
 import torch
@@ -61,12 +64,40 @@ def assert_bits_equal(got, ref, what=""):
     raise AssertionError("\n".join(lines))
 
 
+HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "focnerf.h")
+
+
+def c_header_values(tmp_path, exprs):
+    """What gcc makes of C expressions of integer value over include/focnerf.h (`sizeof(FocOptimStep)`, `FOC_OPTIM_CHUNK`, ...): one
+    program, compiled and run once; the ints in the order asked."""
+    src = os.path.join(str(tmp_path), "values.c")
+    with open(src, "w") as f:
+        f.write('#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(void) {\n%s    return 0;\n}\n'
+                % (HEADER, "".join('    printf("%%lld\\n", (long long)(%s));\n' % e for e in exprs)))
+    subprocess.run(["gcc", "-o", src[:-2], src], check=True)
+    return [int(v) for v in subprocess.run([src[:-2]], capture_output=True, text=True, check=True).stdout.split()]
+
+
+def c_struct_fields(name):
+    """The field names of `typedef struct name { ... } name;` in include/focnerf.h, in order — found without the package's header reader,
+    so that a field it dropped shows."""
+    with open(HEADER) as f:
+        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), f.read(), re.S).group(1)
+    decls = re.sub(r"/\*.*?\*/", "", body, flags=re.S).split(";")
+    return [re.findall(r"\w+$", d.strip())[0] for decl in decls if decl.strip() for d in decl.split(",")]
+
+
+def c_struct_layouts(tmp_path, names):
+    """name -> (sizeof, {field: offsetof}) as gcc lays out the header's structs: one C program for all of them."""
+    fields = {n: c_struct_fields(n) for n in names}
+    got = iter(c_header_values(tmp_path, [e for n in names for e in ["sizeof(%s)" % n] + ["offsetof(%s, %s)" % (n, f) for f in fields[n]]]))
+    return {n: (next(got), {f: next(got) for f in fields[n]}) for n in names}
+
+
 def build_c_abi_consumer(tmp_path):
     """tests/c_abi_consumer.cpp -> an executable under tmp_path: a caller of include/focnerf.h written against the HIP runtime API only (plain g++,
     no torch, no Python), linked with the library and with the C oracle it checks the results against. Returns the executable's path."""
-    import os
-    import subprocess
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    repo =os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
     exe = os.path.join(str(tmp_path), "c_abi_consumer")
     libs = [os.path.join(repo, "focnerf_amd"), os.path.join(repo, "oracle", "_build"), os.path.join(rocm, "lib")]
