@@ -8,6 +8,11 @@
 //   foc_lattice_cull / _emit  which points of a lattice slab lie in an object's box and in an occupied cell (fc_place.h: the placement and the
 //                           cell test of the fixed-step cull), and their compact position list in lattice order
 //   foc_volume_scatter_max  volume = max(volume, gain * sigma) at those points
+//   foc_points_cull / _emit the same cull for a LIST of points (the mask and emit kernels are templates over where a point comes from), emitting
+//                           the object-frame position and / or the encoder's coordinates: the front of the scene point query (query.py)
+//   foc_surface_frame       per compacted point the unit normal of the density gradient (unit_normal.h, shared with normals.hip), rotated
+//                           into the world, and the direction the colour network is asked about (against the normal, or from an eye point)
+//   foc_scene_select        the scatter with a payload: the object with the strictly largest gained sigma keeps index, colour and normal
 //
 // Slots come from prefix sums, never from atomics: the same mesh on every run, in both deterministic modes. Shape, as fixedcull.hip: a
 // CHUNK is 64 consecutive points (one ballot word), one wave owns a GROUP of up to 64 consecutive chunks; lane j keeps what chunk j
@@ -17,6 +22,8 @@
 #include "common.h"
 #include "occ_cell.h"
 #include "fc_place.h"
+#include "fs_common.h"
+#include "unit_normal.h"
 #define MC_TABLE_ATTR __device__
 #include "mc_table.h"
 
@@ -225,20 +232,30 @@ __global__ void __launch_bounds__(256) k_mc_emit(const float *__restrict__ vol, 
     }
 }
 
-// ---------------------------------------------------------------- lattice cull
-struct LcDim { uint32_t ry, rz, first, count; };
+// ---------------------------------------------------------------- lattice cull, point cull
+// Where a point comes from: the slab of a separable lattice (per-axis coordinates) or a list [count,3]. A source is wave-uniform and passed
+// by value; `at` clamps past the end (the caller masks such a lane out).
+struct LcLattice {
+    const float *xs, *ys, *zs;
+    uint32_t ry, rz, first, count;
+    __device__ __forceinline__ void at(uint32_t local, float &x, float &y, float &z) const {
+        const uint32_t i = first + min(local, count - 1u);
+        const uint32_t s = ry * rz, ix = i / s, r = i - ix * s, iy = r / rz;
+        x = xs[ix]; y = ys[iy]; z = zs[r - iy * rz];
+    }
+};
+struct LcList {
+    const float *points;
+    uint32_t count;
+    __device__ __forceinline__ void at(uint32_t local, float &x, float &y, float &z) const {
+        const float *p = points + (uint64_t)min(local, count - 1u) * 3;
+        x = p[0]; y = p[1]; z = p[2];
+    }
+};
 
-__device__ __forceinline__ void lc_point(const float *__restrict__ xs, const float *__restrict__ ys, const float *__restrict__ zs, const LcDim &L, uint32_t local,
-                                         float &x, float &y, float &z) {
-    const uint32_t i = L.first + min(local, L.count - 1u);
-    const uint32_t s = L.ry * L.rz, ix = i / s, r = i - ix * s, iy = r / L.rz;
-    x = xs[ix]; y = ys[iy]; z = zs[r - iy * L.rz];
-}
-
-template <bool PLACED, bool GRID>
-__global__ void __launch_bounds__(256) k_lc_mask(const float *__restrict__ xs, const float *__restrict__ ys, const float *__restrict__ zs, LcDim L, FcGrid G,
-                                                 FcPlace P, uint32_t W, uint32_t n_groups, uint64_t *__restrict__ mask, uint32_t *__restrict__ offsets,
-                                                 uint32_t *__restrict__ group_total) {
+template <bool PLACED, bool GRID, class SRC>
+__global__ void __launch_bounds__(256) k_lc_mask(SRC S, FcGrid G, FcPlace P, uint32_t W, uint32_t n_groups, uint64_t *__restrict__ mask,
+                                                 uint32_t *__restrict__ offsets, uint32_t *__restrict__ group_total) {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t g = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
     if (g >= n_groups) return;
@@ -247,8 +264,8 @@ __global__ void __launch_bounds__(256) k_lc_mask(const float *__restrict__ xs, c
     for (uint32_t j = 0; j < chunks; j++) {
         const uint32_t local = (c0 + j) * 64u + lane;
         float x, y, z;
-        lc_point(xs, ys, zs, L, local, x, y, z);
-        bool occ = local < L.count;
+        S.at(local, x, y, z);
+        bool occ = local < S.count;
         if (PLACED) {
             float qx, qy, qz;
             fc_to_object(P, x, y, z, qx, qy, qz);
@@ -265,25 +282,32 @@ __global__ void __launch_bounds__(256) k_lc_mask(const float *__restrict__ xs, c
     if (lane == 63) group_total[g] = (uint32_t)incl;
 }
 
-template <bool PLACED>
-__global__ void __launch_bounds__(256) k_lc_emit(const float *__restrict__ xs, const float *__restrict__ ys, const float *__restrict__ zs, LcDim L, FcPlace P,
-                                                 const uint64_t *__restrict__ mask, const uint32_t *__restrict__ offsets, uint32_t m_occ,
-                                                 float *__restrict__ pos_c) {
-    for (uint32_t local = blockIdx.x * 256 + threadIdx.x; local < L.count; local += gridDim.x * 256) {
+// pos_c = the point in the object's frame, xn_c = (pos + bound) / (2 bound) (fs_norm: the emit of the fixed-step cull); either may be null
+template <bool PLACED, class SRC>
+__global__ void __launch_bounds__(256) k_lc_emit(SRC S, FcPlace P, const uint64_t *__restrict__ mask, const uint32_t *__restrict__ offsets, uint32_t m_occ,
+                                                 float bound, float *__restrict__ pos_c, float *__restrict__ xn_c) {
+    const float two_b = 2 * bound;
+    for (uint32_t local = blockIdx.x * 256 + threadIdx.x; local < S.count; local += gridDim.x * 256) {
         const uint32_t c = local >> 6, l = local & 63;
         const uint64_t m = mask[c];
         if (!((m >> l) & 1ull)) continue;
         const uint32_t slot = offsets[c] + (uint32_t)__popcll(m & ((1ull << l) - 1ull));
         if (slot >= m_occ) continue;
         float x, y, z;
-        lc_point(xs, ys, zs, L, local, x, y, z);
+        S.at(local, x, y, z);
         if (PLACED) {
             float qx, qy, qz;
             fc_to_object(P, x, y, z, qx, qy, qz);
             x = qx; y = qy; z = qz;
         }
-        float *p = pos_c + (uint64_t)slot * 3;
-        p[0] = x; p[1] = y; p[2] = z;
+        if (pos_c) {
+            float *p = pos_c + (uint64_t)slot * 3;
+            p[0] = x; p[1] = y; p[2] = z;
+        }
+        if (xn_c) {
+            float *e = xn_c + (uint64_t)slot * 3;
+            e[0] = fs_norm(x, bound, two_b); e[1] = fs_norm(y, bound, two_b); e[2] = fs_norm(z, bound, two_b);
+        }
     }
 }
 
@@ -297,6 +321,65 @@ __global__ void __launch_bounds__(256) k_volume_scatter_max(const float *__restr
         const float v = gain * sigma_c[offsets[c] + (uint32_t)__popcll(m & ((1ull << l) - 1ull))];
         const float cur = volume[i];
         volume[i] = (v > cur || v != v) ? v : cur;
+    }
+}
+
+// the scatter with a payload: at the set bits v = gain * sigma_c[slot]; v > best_sigma[i] (strict: a tie keeps what is there, a NaN v never
+// wins) takes the point for `id` with its colour and normal. One thread per point, each point touched once: no atomics.
+__global__ void __launch_bounds__(256) k_scene_select(const float *__restrict__ sigma_c, const float *__restrict__ rgb_c, const float *__restrict__ normal_c,
+                                                      const uint64_t *__restrict__ mask, const uint32_t *__restrict__ offsets, float gain, int32_t id,
+                                                      float *__restrict__ best_sigma, int32_t *__restrict__ best_id, float *__restrict__ best_rgb,
+                                                      float *__restrict__ best_normal, uint32_t n) {
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        const uint32_t c = i >> 6, l = i & 63;
+        const uint64_t m = mask[c];
+        if (!((m >> l) & 1ull)) continue;
+        const uint32_t slot = offsets[c] + (uint32_t)__popcll(m & ((1ull << l) - 1ull));
+        const float v = gain * sigma_c[slot];
+        if (!(v > best_sigma[i])) continue;
+        best_sigma[i] = v;
+        best_id[i] = id;
+        if (best_rgb) {
+            const float *s = rgb_c + (uint64_t)slot * 3;
+            float *d = best_rgb + (uint64_t)i * 3;
+            d[0] = s[0]; d[1] = s[1]; d[2] = s[2];
+        }
+        if (best_normal) {
+            const float *s = normal_c + (uint64_t)slot * 3;
+            float *d = best_normal + (uint64_t)i * 3;
+            d[0] = s[0]; d[1] = s[1]; d[2] = s[2];
+        }
+    }
+}
+
+// per compacted point: the object-frame normal of grad_raw_c (unit_normal.h), its rotation into the world, and the direction the colour
+// network is asked about: against the normal, or from the eye to the point; (0, 0, -1) where that direction does not exist
+struct SfFrame { float R[9], eye[3]; };
+template <bool EYE, bool ROT>
+__global__ void __launch_bounds__(256) k_surface_frame(const float *__restrict__ grad_raw_c, const float *__restrict__ pos_c, uint32_t m, SfFrame F,
+                                                       float *__restrict__ dirs_c, float *__restrict__ normal_c) {
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < m; i += gridDim.x * 256) {
+        float n[3] = {0.0f, 0.0f, 0.0f}, v[3];
+        if (grad_raw_c) {
+            const float g[3] = {grad_raw_c[(uint64_t)i * 3], grad_raw_c[(uint64_t)i * 3 + 1], grad_raw_c[(uint64_t)i * 3 + 2]};
+            un_unit_normal(g, n);
+        }
+        if (dirs_c) {
+            if (EYE) {
+                const float d[3] = {pos_c[(uint64_t)i * 3] - F.eye[0], pos_c[(uint64_t)i * 3 + 1] - F.eye[1], pos_c[(uint64_t)i * 3 + 2] - F.eye[2]};
+                un_unit_normal(d, v);            // -(d / |d|): negated below
+            } else {
+                v[0] = n[0]; v[1] = n[1]; v[2] = n[2];
+            }
+            const bool none = v[0] == 0.0f && v[1] == 0.0f && v[2] == 0.0f;
+            float *o = dirs_c + (uint64_t)i * 3;
+            o[0] = none ? 0.0f : -v[0]; o[1] = none ? 0.0f : -v[1]; o[2] = none ? -1.0f : -v[2];
+        }
+        if (normal_c) {
+            if (ROT) un_rotate(F.R, n);
+            float *o = normal_c + (uint64_t)i * 3;
+            o[0] = n[0]; o[1] = n[1]; o[2] = n[2];
+        }
     }
 }
 
@@ -340,6 +423,57 @@ static bool lc_slab_ok(const char *who, uint32_t rx, uint32_t ry, uint32_t rz, u
         return false;
     }
     return true;
+}
+
+// foc_lattice_cull / foc_points_cull behind the refusals that concern where the points come from: the placement, the grid, the scratch, then
+// the mask, scan and finish launches
+template <class SRC>
+static int lc_cull(const char *who, const SRC &S, const float *world_to_object, const float *obj_aabb, float bound, const uint8_t *bitfield, uint32_t cascade,
+                   uint32_t grid_size, uint64_t *mask, uint32_t *offsets, uint32_t *count_out, void *scratch, uint64_t scratch_bytes, void *stream) {
+    FOC_REQUIRE((world_to_object == nullptr) == (obj_aabb == nullptr), FOC_E_INVALID, "%s: world_to_object and obj_aabb (host arrays of 12 and 6 floats) come together", who);
+    FOC_REQUIRE(!world_to_object || (fc_all_finite(world_to_object, 12) && fc_all_finite(obj_aabb, 6)), FOC_E_INVALID, "%s: non-finite world_to_object / obj_aabb", who);
+    FcGrid G{};
+    if (bitfield) {
+        FOC_REQUIRE(cascade >= 1 && cascade <= 16, FOC_E_INVALID, "%s: cascade must be 1..16 (got %u)", who, cascade);
+        FOC_REQUIRE(grid_size >= 2 && grid_size <= 1024 && (grid_size & (grid_size - 1)) == 0, FOC_E_INVALID,
+                    "%s: grid_size must be a power of two in 2..1024 (got %u)", who, grid_size);
+        const uint64_t cells = (uint64_t)cascade * grid_size * grid_size * grid_size;
+        FOC_REQUIRE(cells < (1ull << 32), FOC_E_INVALID, "%s: cascade * grid_size^3 must fit 32 bits", who);
+        FOC_REQUIRE(std::isfinite(bound) && bound > 0, FOC_E_INVALID, "%s: bound must be finite and > 0", who);
+        G.bits = bitfield; G.bound = bound; G.Cf = (float)cascade; G.Hm1 = (float)(grid_size - 1);
+        G.H3 = (float)((uint64_t)grid_size * grid_size * grid_size); G.H = grid_size; G.n_cells = (uint32_t)cells;
+    }
+    const uint32_t count = S.count;
+    FOC_REQUIRE(scratch_bytes >= foc_lattice_cull_scratch_bytes(count), FOC_E_INVALID, "%s: scratch of %llu bytes, foc_lattice_cull_scratch_bytes(%u) asks for %llu", who,
+                (unsigned long long)scratch_bytes, count, (unsigned long long)foc_lattice_cull_scratch_bytes(count));
+    FOC_REQUIRE((((uintptr_t)mask) & 7) == 0, FOC_E_INVALID, "%s: mask must be 8-byte aligned", who);
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t W = ms_chunks(count), NG = ms_groups(W);
+    const FcPlace P = world_to_object ? fc_place(world_to_object, obj_aabb, 1.0f) : FcPlace{};
+    uint32_t *group_total = reinterpret_cast<uint32_t *>(scratch);
+    const dim3 grid(foc_div_up(NG, 4)), block(256);
+    if (world_to_object && bitfield) hipLaunchKernelGGL((k_lc_mask<true, true, SRC>), grid, block, 0, st, S, G, P, W, NG, mask, offsets, group_total);
+    else if (world_to_object) hipLaunchKernelGGL((k_lc_mask<true, false, SRC>), grid, block, 0, st, S, G, P, W, NG, mask, offsets, group_total);
+    else if (bitfield) hipLaunchKernelGGL((k_lc_mask<false, true, SRC>), grid, block, 0, st, S, G, P, W, NG, mask, offsets, group_total);
+    else hipLaunchKernelGGL((k_lc_mask<false, false, SRC>), grid, block, 0, st, S, G, P, W, NG, mask, offsets, group_total);
+    FOC_CHECK_LAUNCH(who);
+    hipLaunchKernelGGL(k_ms_scan, dim3(1), dim3(1024), 0, st, group_total, (uint32_t *)nullptr, (const uint32_t *)nullptr, NG, offsets + W, count_out, 1u);
+    FOC_CHECK_LAUNCH(who);
+    hipLaunchKernelGGL(k_ms_finish, dim3(foc_grid_1d(W, 256)), dim3(256), 0, st, group_total, offsets, (const uint32_t *)nullptr, (uint32_t *)nullptr, W);
+    FOC_CHECK_LAUNCH(who);
+    return FOC_OK;
+}
+
+template <class SRC>
+static int lc_emit(const char *who, const SRC &S, const float *world_to_object, float bound, const uint64_t *mask, const uint32_t *offsets, uint32_t m_occ,
+                   float *pos_c, float *xn_c, void *stream) {
+    FOC_REQUIRE(!world_to_object || fc_all_finite(world_to_object, 12), FOC_E_INVALID, "%s: non-finite world_to_object", who);
+    const float no_box[6] = {0, 0, 0, 0, 0, 0};                // the emit pass reads the mask: the box is not consulted again
+    const dim3 grid(foc_grid_1d(S.count, 256)), block(256);
+    if (world_to_object) hipLaunchKernelGGL((k_lc_emit<true, SRC>), grid, block, 0, (hipStream_t)stream, S, fc_place(world_to_object, no_box, 1.0f), mask, offsets, m_occ, bound, pos_c, xn_c);
+    else hipLaunchKernelGGL((k_lc_emit<false, SRC>), grid, block, 0, (hipStream_t)stream, S, FcPlace{}, mask, offsets, m_occ, bound, pos_c, xn_c);
+    FOC_CHECK_LAUNCH(who);
+    return FOC_OK;
 }
 
 extern "C" {
@@ -402,38 +536,8 @@ int foc_lattice_cull(const float *xs, const float *ys, const float *zs, uint32_t
     FOC_REQUIRE(xs && ys && zs && mask && offsets && count_out && scratch, FOC_E_INVALID, "lattice_cull: null pointer");
     if (!lc_slab_ok("lattice_cull", rx, ry, rz, first, count)) return FOC_E_INVALID;
     FOC_REQUIRE(count >= 1, FOC_E_INVALID, "lattice_cull: an empty slab");
-    FOC_REQUIRE((world_to_object == nullptr) == (obj_aabb == nullptr), FOC_E_INVALID, "lattice_cull: world_to_object and obj_aabb (host arrays of 12 and 6 floats) come together");
-    FOC_REQUIRE(!world_to_object || (fc_all_finite(world_to_object, 12) && fc_all_finite(obj_aabb, 6)), FOC_E_INVALID, "lattice_cull: non-finite world_to_object / obj_aabb");
-    FcGrid G{};
-    if (bitfield) {
-        FOC_REQUIRE(cascade >= 1 && cascade <= 16, FOC_E_INVALID, "lattice_cull: cascade must be 1..16 (got %u)", cascade);
-        FOC_REQUIRE(grid_size >= 2 && grid_size <= 1024 && (grid_size & (grid_size - 1)) == 0, FOC_E_INVALID,
-                    "lattice_cull: grid_size must be a power of two in 2..1024 (got %u)", grid_size);
-        const uint64_t cells = (uint64_t)cascade * grid_size * grid_size * grid_size;
-        FOC_REQUIRE(cells < (1ull << 32), FOC_E_INVALID, "lattice_cull: cascade * grid_size^3 must fit 32 bits");
-        FOC_REQUIRE(std::isfinite(bound) && bound > 0, FOC_E_INVALID, "lattice_cull: bound must be finite and > 0");
-        G.bits = bitfield; G.bound = bound; G.Cf = (float)cascade; G.Hm1 = (float)(grid_size - 1);
-        G.H3 = (float)((uint64_t)grid_size * grid_size * grid_size); G.H = grid_size; G.n_cells = (uint32_t)cells;
-    }
-    FOC_REQUIRE(scratch_bytes >= foc_lattice_cull_scratch_bytes(count), FOC_E_INVALID, "lattice_cull: scratch of %llu bytes, foc_lattice_cull_scratch_bytes(%u) asks for %llu",
-                (unsigned long long)scratch_bytes, count, (unsigned long long)foc_lattice_cull_scratch_bytes(count));
-    FOC_REQUIRE((((uintptr_t)mask) & 7) == 0, FOC_E_INVALID, "lattice_cull: mask must be 8-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const uint32_t W = ms_chunks(count), NG = ms_groups(W);
-    const LcDim L{ry, rz, first, count};
-    const FcPlace P = world_to_object ? fc_place(world_to_object, obj_aabb, 1.0f) : FcPlace{};
-    uint32_t *group_total = reinterpret_cast<uint32_t *>(scratch);
-    const dim3 grid(foc_div_up(NG, 4)), block(256);
-    if (world_to_object && bitfield) hipLaunchKernelGGL((k_lc_mask<true, true>), grid, block, 0, st, xs, ys, zs, L, G, P, W, NG, mask, offsets, group_total);
-    else if (world_to_object) hipLaunchKernelGGL((k_lc_mask<true, false>), grid, block, 0, st, xs, ys, zs, L, G, P, W, NG, mask, offsets, group_total);
-    else if (bitfield) hipLaunchKernelGGL((k_lc_mask<false, true>), grid, block, 0, st, xs, ys, zs, L, G, P, W, NG, mask, offsets, group_total);
-    else hipLaunchKernelGGL((k_lc_mask<false, false>), grid, block, 0, st, xs, ys, zs, L, G, P, W, NG, mask, offsets, group_total);
-    FOC_CHECK_LAUNCH("lattice_cull");
-    hipLaunchKernelGGL(k_ms_scan, dim3(1), dim3(1024), 0, st, group_total, (uint32_t *)nullptr, (const uint32_t *)nullptr, NG, offsets + W, count_out, 1u);
-    FOC_CHECK_LAUNCH("lattice_cull");
-    hipLaunchKernelGGL(k_ms_finish, dim3(foc_grid_1d(W, 256)), dim3(256), 0, st, group_total, offsets, (const uint32_t *)nullptr, (uint32_t *)nullptr, W);
-    FOC_CHECK_LAUNCH("lattice_cull");
-    return FOC_OK;
+    return lc_cull("lattice_cull", LcLattice{xs, ys, zs, ry, rz, first, count}, world_to_object, obj_aabb, bound, bitfield, cascade, grid_size, mask, offsets,
+                   count_out, scratch, scratch_bytes, stream);
 }
 
 int foc_lattice_cull_emit(const float *xs, const float *ys, const float *zs, uint32_t rx, uint32_t ry, uint32_t rz, uint32_t first, uint32_t count,
@@ -443,13 +547,66 @@ int foc_lattice_cull_emit(const float *xs, const float *ys, const float *zs, uin
     FOC_REQUIRE(xs && ys && zs && mask && offsets && pos_c, FOC_E_INVALID, "lattice_cull_emit: null pointer");
     if (!lc_slab_ok("lattice_cull_emit", rx, ry, rz, first, count)) return FOC_E_INVALID;
     FOC_REQUIRE(count >= 1, FOC_E_INVALID, "lattice_cull_emit: an empty slab");
-    FOC_REQUIRE(!world_to_object || fc_all_finite(world_to_object, 12), FOC_E_INVALID, "lattice_cull_emit: non-finite world_to_object");
-    const LcDim L{ry, rz, first, count};
-    const float no_box[6] = {0, 0, 0, 0, 0, 0};                // the emit pass reads the mask: the box is not consulted again
-    const dim3 grid(foc_grid_1d(count, 256)), block(256);
-    if (world_to_object) hipLaunchKernelGGL(k_lc_emit<true>, grid, block, 0, (hipStream_t)stream, xs, ys, zs, L, fc_place(world_to_object, no_box, 1.0f), mask, offsets, m_occ, pos_c);
-    else hipLaunchKernelGGL(k_lc_emit<false>, grid, block, 0, (hipStream_t)stream, xs, ys, zs, L, FcPlace{}, mask, offsets, m_occ, pos_c);
-    FOC_CHECK_LAUNCH("lattice_cull_emit");
+    return lc_emit("lattice_cull_emit", LcLattice{xs, ys, zs, ry, rz, first, count}, world_to_object, 1.0f, mask, offsets, m_occ, pos_c, nullptr, stream);
+}
+
+int foc_points_cull(const float *points, uint32_t M, const float *world_to_object, const float *obj_aabb, float bound, const uint8_t *bitfield, uint32_t cascade,
+                    uint32_t grid_size, uint64_t *mask, uint32_t *offsets, uint32_t *count_out, void *scratch, uint64_t scratch_bytes, void *stream) {
+    FocDeviceGuard foc_guard_(stream, points);
+    if (M == 0) return FOC_OK;
+    FOC_REQUIRE(points && mask && offsets && count_out && scratch, FOC_E_INVALID, "points_cull: null pointer");
+    FOC_REQUIRE(M <= MC_MAX_POINTS, FOC_E_INVALID, "points_cull: M must not exceed 2^29 points (got %u)", M);
+    return lc_cull("points_cull", LcList{points, M}, world_to_object, obj_aabb, bound, bitfield, cascade, grid_size, mask, offsets, count_out, scratch,
+                   scratch_bytes, stream);
+}
+
+int foc_points_cull_emit(const float *points, uint32_t M, const float *world_to_object, float bound, const uint64_t *mask, const uint32_t *offsets,
+                         uint32_t m_occ, float *pos_c, float *xn_c, void *stream) {
+    FocDeviceGuard foc_guard_(stream, points);
+    if (M == 0 || m_occ == 0 || !(pos_c || xn_c)) return FOC_OK;
+    FOC_REQUIRE(points && mask && offsets, FOC_E_INVALID, "points_cull_emit: null pointer");
+    FOC_REQUIRE(M <= MC_MAX_POINTS && m_occ <= M, FOC_E_INVALID, "points_cull_emit: M must not exceed 2^29 points and m_occ not M (got %u, %u)", M, m_occ);
+    FOC_REQUIRE(!xn_c || (std::isfinite(bound) && bound > 0), FOC_E_INVALID, "points_cull_emit: bound must be finite and > 0 for xn_c");
+    return lc_emit("points_cull_emit", LcList{points, M}, world_to_object, xn_c ? bound : 1.0f, mask, offsets, m_occ, pos_c, xn_c, stream);
+}
+
+int foc_surface_frame(const float *grad_raw_c, const float *pos_c, uint32_t m, const float *rot9, int mode, const float *eye_obj, float *dirs_c,
+                      float *normal_c, void *stream) {
+    FocDeviceGuard foc_guard_(stream, grad_raw_c ? grad_raw_c : pos_c);
+    FOC_REQUIRE(mode == 0 || mode == 1, FOC_E_INVALID, "surface_frame: mode must be 0 (normal) or 1 (eye), got %d", mode);
+    if (m == 0 || !(dirs_c || normal_c)) return FOC_OK;
+    FOC_REQUIRE(m <= MC_MAX_POINTS, FOC_E_INVALID, "surface_frame: m must not exceed 2^29 points (got %u)", m);
+    const bool eye = mode == 1 && dirs_c;
+    FOC_REQUIRE(grad_raw_c || !(normal_c || (dirs_c && !eye)), FOC_E_INVALID, "surface_frame: null pointer (grad_raw_c: the normal and the mode-0 direction come from it)");
+    FOC_REQUIRE(!eye || (pos_c && eye_obj), FOC_E_INVALID, "surface_frame: null pointer (mode 1 takes pos_c and eye_obj, 3 floats in host memory)");
+    FOC_REQUIRE(!eye || fc_all_finite(eye_obj, 3), FOC_E_INVALID, "surface_frame: non-finite eye_obj");
+    FOC_REQUIRE(!rot9 || fc_all_finite(rot9, 9), FOC_E_INVALID, "surface_frame: non-finite rot9");
+    SfFrame F{};
+    if (rot9) for (int k = 0; k < 9; k++) F.R[k] = rot9[k];
+    if (eye) for (int k = 0; k < 3; k++) F.eye[k] = eye_obj[k];
+    const dim3 grid(foc_grid_1d(m, 256)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    const bool rot = rot9 && normal_c;
+    if (eye && rot) hipLaunchKernelGGL((k_surface_frame<true, true>), grid, block, 0, st, grad_raw_c, pos_c, m, F, dirs_c, normal_c);
+    else if (eye) hipLaunchKernelGGL((k_surface_frame<true, false>), grid, block, 0, st, grad_raw_c, pos_c, m, F, dirs_c, normal_c);
+    else if (rot) hipLaunchKernelGGL((k_surface_frame<false, true>), grid, block, 0, st, grad_raw_c, pos_c, m, F, dirs_c, normal_c);
+    else hipLaunchKernelGGL((k_surface_frame<false, false>), grid, block, 0, st, grad_raw_c, pos_c, m, F, dirs_c, normal_c);
+    FOC_CHECK_LAUNCH("surface_frame");
+    return FOC_OK;
+}
+
+int foc_scene_select(const float *sigma_c, const float *rgb_c, const float *normal_c, const uint64_t *mask, const uint32_t *offsets, float gain,
+                     int32_t object_index, float *best_sigma, int32_t *best_id, float *best_rgb, float *best_normal, uint32_t n, void *stream) {
+    FocDeviceGuard foc_guard_(stream, best_sigma);
+    if (n == 0) return FOC_OK;
+    FOC_REQUIRE(sigma_c && mask && offsets && best_sigma && best_id, FOC_E_INVALID, "scene_select: null pointer");
+    FOC_REQUIRE((rgb_c == nullptr) == (best_rgb == nullptr) && (normal_c == nullptr) == (best_normal == nullptr), FOC_E_INVALID,
+                "scene_select: rgb_c / best_rgb and normal_c / best_normal come in pairs");
+    FOC_REQUIRE(n <= MC_MAX_POINTS, FOC_E_INVALID, "scene_select: n must not exceed 2^29 points (got %u)", n);
+    FOC_REQUIRE(std::isfinite(gain) && gain > 0, FOC_E_INVALID, "scene_select: gain must be finite and > 0 (got %g)", (double)gain);
+    hipLaunchKernelGGL(k_scene_select, dim3(foc_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, sigma_c, rgb_c, normal_c, mask, offsets, gain, object_index,
+                       best_sigma, best_id, best_rgb, best_normal, n);
+    FOC_CHECK_LAUNCH("scene_select");
     return FOC_OK;
 }
 

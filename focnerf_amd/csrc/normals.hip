@@ -34,6 +34,7 @@
 // No atomics, no host synchronisation, nothing order-dependent: the same bits on every run, whichever outputs are asked for.
 #include "mlp_common.h"
 #include "ge_common.h"
+#include "unit_normal.h"
 
 #define FN_LEVELS 16
 
@@ -235,18 +236,9 @@ __global__ void __launch_bounds__(MLP_BLOCK, 2) k_field_normals(const float *__r
             for (int d = 0; d < 3; d++) grad_raw[row_raw * 3 + d] = gr[d];
         }
         if (normal_rgb) {
-            const float m = fmaxf(fmaxf(fabsf(gr[0]), fabsf(gr[1])), fabsf(gr[2]));
-            float n[3] = {0.0f, 0.0f, 0.0f};
-            if (m > 0.0f && isfinite(gr[0]) && isfinite(gr[1]) && isfinite(gr[2])) {
-                const float u0 = gr[0] / m, u1 = gr[1] / m, u2 = gr[2] / m;
-                const float len = sqrtf(fmaf(u2, u2, fmaf(u1, u1, u0 * u0)));
-                n[0] = -u0 / len; n[1] = -u1 / len; n[2] = -u2 / len;
-            }
-            if (rot9) {
-                const float r0 = fmaf(R[2], n[2], fmaf(R[1], n[1], R[0] * n[0])), r1 = fmaf(R[5], n[2], fmaf(R[4], n[1], R[3] * n[0])),
-                            r2 = fmaf(R[8], n[2], fmaf(R[7], n[1], R[6] * n[0]));
-                n[0] = r0; n[1] = r1; n[2] = r2;
-            }
+            float n[3];
+            un_unit_normal(gr, n);               // unit_normal.h: the rule the point pipeline's frame kernel shares
+            if (rot9) un_rotate(R, n);
 #pragma unroll
             for (int d = 0; d < 3; d++) normal_rgb[row_raw * 3 + d] = fmaf(0.5f, n[d], 0.5f);
         }

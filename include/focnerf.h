@@ -1195,6 +1195,54 @@ int foc_lattice_cull_emit(const float *xs, const float *ys, const float *zs, uin
 int foc_volume_scatter_max(const float *sigma_c, const uint64_t *mask, const uint32_t *offsets, float gain, float *volume,
                            uint32_t n, void *stream);
 
+/* A placed scene at ARBITRARY points (csrc/mesh.hip; focnerf_amd/query.py sequences the calls): the lattice cull for a list, the frame
+ * of a surface point, and the select that keeps the winning object's density, index, colour and normal per point.
+ *
+ * foc_points_cull / foc_points_cull_emit: foc_lattice_cull / foc_lattice_cull_emit for points [M,3] fp32 on the device, in world units,
+ *   point i in place of lattice point i. The SAME kernels (templates over where a point comes from), hence the same arithmetic in the same
+ *   order: q by foc_fixed_cull_placed's device function, the box test, then the cell test, the bitfield read only for points still in
+ *   question; a point with a NaN coordinate is never inside a box (every comparison fails). mask [R] uint64, offsets [R + 1] uint32,
+ *   count_out [1] uint32 with R = ceil(M / 64); scratch: foc_lattice_cull_scratch_bytes(M) device bytes. M <= 2^29. world_to_object /
+ *   obj_aabb: 12 and 6 floats in host memory, both or neither. Refused (FOC_E_INVALID) before anything is enqueued: a null pointer, M > 2^29,
+ *   non-finite host arrays, a bad cascade / grid_size / bound with a bitfield, a scratch smaller than asked for. M = 0 returns FOC_OK and
+ *   enqueues nothing (no output is written). No host synchronisation.
+ *   The emit writes either or both of (a NULL one is skipped; both NULL or m_occ = 0: nothing is enqueued), m_occ rows each and nothing
+ *   past them:
+ *     pos_c [m_occ,3] fp32  the point in the object's frame: q with world_to_object, the point itself without
+ *     xn_c  [m_occ,3] fp32  (pos + bound) / (2 bound): the encoder's coordinates, with the arithmetic (one addition, one division by the
+ *                           fp32 product 2 bound) of foc_fixed_cull_emit_placed's enc_in_c. bound finite and > 0 (not read without xn_c).
+ *
+ * foc_surface_frame: one thread per compacted point, m <= 2^29 of them. grad_raw_c [m,3] fp32 is foc_field_normals' grad_raw of the points
+ *   (object frame), pos_c [m,3] their object-frame positions.
+ *     n_obj     foc_field_normals' normalise rule — the same device function (csrc/unit_normal.h): m = max|g_d|; zero or a component not
+ *               finite: n = 0; else u = g / m, n = -u / sqrt(u.u).
+ *     normal_c  [m,3] = rot9 n_obj with that kernel's rotate order (per row fmaf from the product of column 0); n_obj when rot9 is NULL.
+ *               rot9: 9 finite floats IN HOST MEMORY, row-major (object -> world).
+ *     dirs_c    [m,3], the view direction the colour network is asked about. mode 0 (NORMAL): -n_obj, or (0, 0, -1) where n_obj = 0.
+ *               mode 1 (EYE): pos_c - eye_obj at unit length by the same scale-by-max rule in fp32, or (0, 0, -1) where that difference is
+ *               zero or not finite; eye_obj: 3 finite floats in host memory, the eye in the OBJECT's frame (mapped in float64 by the
+ *               caller and rounded once).
+ *   dirs_c or normal_c may be NULL (both: nothing is enqueued). grad_raw_c may be NULL when neither normal_c nor a mode-0 dirs_c is asked
+ *   for; pos_c and eye_obj are read in mode 1 with dirs_c only. Refused: another mode, a null pointer that is needed, non-finite host arrays.
+ *
+ * foc_scene_select: foc_volume_scatter_max's twin with a payload, for a run of n <= 2^29 points (the best_* pointers stand at the run's
+ *   first point, mask / offsets are the run's). At every set bit i: v = gain * sigma_c[slot(i)], one fp32 multiply; if v > best_sigma[i]:
+ *   best_sigma[i] = v, best_id[i] = object_index, best_rgb[i] = rgb_c[slot], best_normal[i] = normal_c[slot]. rgb_c / best_rgb and
+ *   normal_c / best_normal may be NULL in pairs. The comparison is strict: on a tie the earlier call's object stays (the tie rule of
+ *   foc_combine_select). A NaN v never wins — this DIFFERS from foc_volume_scatter_max, which propagates a NaN into the volume. Points
+ *   whose bit is clear are not touched. Each point is touched once per call and calls run in stream order: no atomics, nothing depends on
+ *   the order of arrival, the same bits on every run. gain finite and > 0. n = 0 returns FOC_OK. */
+int foc_points_cull(const float *points, uint32_t M, const float *world_to_object, const float *obj_aabb, float bound,
+                    const uint8_t *bitfield, uint32_t cascade, uint32_t grid_size, uint64_t *mask, uint32_t *offsets,
+                    uint32_t *count_out, void *scratch, uint64_t scratch_bytes, void *stream);
+int foc_points_cull_emit(const float *points, uint32_t M, const float *world_to_object, float bound, const uint64_t *mask,
+                         const uint32_t *offsets, uint32_t m_occ, float *pos_c, float *xn_c, void *stream);
+int foc_surface_frame(const float *grad_raw_c, const float *pos_c, uint32_t m, const float *rot9, int mode, const float *eye_obj,
+                      float *dirs_c, float *normal_c, void *stream);
+int foc_scene_select(const float *sigma_c, const float *rgb_c, const float *normal_c, const uint64_t *mask, const uint32_t *offsets,
+                     float gain, int32_t object_index, float *best_sigma, int32_t *best_id, float *best_rgb, float *best_normal,
+                     uint32_t n, void *stream);
+
 /* ---------------------------------------------------------------------------
  * Scoring a combined view (csrc/score.hip; no reference binding: COMBINED.py:335-378 process_images_with_background copies the float
  * image to the host and quantises it with numpy, :267-291 calculate_psnr, :295-332 ssim_rgba / ssim_channel run
