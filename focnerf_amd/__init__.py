@@ -10,7 +10,7 @@ from .mesh import (density_volume, scene_volume, marching_cubes, extract_geometr
                    write_ply, save_mesh, Mesh, extract_mesh, extract_scene_mesh, read_ply_attributes)      # of objects and placed scenes)
 from .query import query_scene, SceneSample  # noqa: F401  (a placed scene at arbitrary points: density, winning object, colour, normal)
 from .score import score_view, ViewScore  # noqa: F401  (PSNR and SSIM of a combined view for every background, on the device)
-from .normals import density_gradient, field_normals, decode_normal_map, render_normals  # noqa: F401  (surface normals from the density field)
+from .normals import density_gradient, field_normals, decode_normal_map, render_normals, normal_map_finish  # noqa: F401  (surface normals from the density field)
 from . import optim  # noqa: F401
 from .optim import FusedAdam, LossScaler  # noqa: F401  (the trainer's optimizer step: overflow check, unscale and Adam in two launches)
 from . import batch  # noqa: F401
@@ -21,6 +21,6 @@ __all__ = ["raymarching", "gridencoder", "freqencoder", "ffmlp", "activation", "
            "mesh", "density_volume", "scene_volume", "marching_cubes", "extract_geometry", "extract_scene_geometry", "write_ply", "save_mesh",
            "Mesh", "extract_mesh", "extract_scene_mesh", "read_ply_attributes", "query", "query_scene", "SceneSample",
            "score", "score_view", "ViewScore",
-           "normals", "density_gradient", "field_normals", "decode_normal_map", "render_normals",
+           "normals", "density_gradient", "field_normals", "decode_normal_map", "render_normals", "normal_map_finish",
            "optim", "FusedAdam", "LossScaler",
            "batch", "DeviceDataset", "RaySampler", "photo_loss"]

@@ -96,6 +96,20 @@ struct FocDeviceGuard {
 
 static inline uint32_t foc_div_up(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
 
+// `mode` of foc_occ_render_step_normals (include/focnerf.h states the two values)
+#define FOC_OCC_NORMALS_ONLY 1u
+#define FOC_OCC_NORMALS_AUX 2u
+
+// Host functions one translation unit offers the others, not exported from the library.
+#define FOC_INTERNAL __attribute__((visibility("hidden")))
+extern "C" {
+// raymarching.hip: foc_composite_compact carrying a second payload (occrender.hip, the render step's normals beside its colours)
+FOC_INTERNAL int composite_compact_aux(uint32_t n_alive, uint32_t n_step, float T_thresh, int32_t *rays_alive, float *rays_t, const float *sigmas,
+                                       const float *rgbs, const float *aux, const float *deltas, float *weights_sum, float *depth, float *image,
+                                       float *aux_image, int32_t *out, int32_t *n_out, int32_t *block_counts, int32_t *deaths, uint32_t deaths_base,
+                                       uint32_t deaths_len, int sample_major, void *stream);
+}
+
 // Grid for a grid-stride elementwise kernel: enough workgroups to fill 256 CUs x 8,
 // capped so tiny problems do not launch empty blocks.
 static inline uint32_t foc_grid_1d(uint64_t n, uint32_t block, uint32_t max_blocks = 256 * 8) {

@@ -141,7 +141,6 @@ static inline bool head_layer_pair(uint32_t sigma_layers, uint32_t color_layers)
 // Host: the bodies behind the exported foc_<name>, foc_<name>_pad (pad31 false) and foc_<name>_pad31 (pad31 true) entry points, for the
 // sequences inside the library (occtrain.hip, occrender.hip) that serve every layout of the colour input. field_fwd.hip, ffmlp.hip.
 extern "C" {
-#define FOC_INTERNAL __attribute__((visibility("hidden")))
 FOC_INTERNAL int field_forward_train(const void *planes, const void *sigma_weights, uint32_t sigma_layers, const void *ray_sh, uint32_t samples_per_ray,
                                      const void *color_weights, uint32_t color_layers, uint32_t hidden_dim, uint32_t activation, uint32_t B, void *h, void *c,
                                      uint32_t out_width, const void *obj_feat, float input_pad, bool pad31, void *stream);

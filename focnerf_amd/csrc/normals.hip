@@ -257,7 +257,35 @@ static int fn_launch(const float *xn, uint32_t M, const void *emb, const uint32_
     return FOC_OK;
 }
 
+// A composited normal map out of its accumulators (foc_normal_map_finish): acc = sum_k w_k (0.5 + 0.5 n_k), W = sum_k w_k, so that
+// s = 2 acc - W = sum_k w_k n_k (2 acc exact, one rounding); normal = s / |s| by un_unit_normal's rule on -s (a negation is exact); the encoded
+// map on a white background is acc + (1 - W), as the renderer finishes a colour image. One pixel per lane, nothing shared.
+__global__ void __launch_bounds__(256) k_normal_map_finish(const float *__restrict__ acc, const float *__restrict__ weights_sum, uint32_t N, float *__restrict__ normal,
+                                                           float *__restrict__ normal_rgb) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= N) return;
+    const float W = weights_sum[i], rest = 1.0f - W;
+    float g[3], n[3];
+#pragma unroll
+    for (int d = 0; d < 3; d++) g[d] = -(2.0f * acc[(uint64_t)i * 3 + d] - W);
+    un_unit_normal(g, n);
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+        normal[(uint64_t)i * 3 + d] = n[d];
+        normal_rgb[(uint64_t)i * 3 + d] = acc[(uint64_t)i * 3 + d] + rest;
+    }
+}
+
 extern "C" {
+
+int foc_normal_map_finish(const float *normal_acc, const float *weights_sum, uint32_t N, float *normal, float *normal_rgb, void *stream) {
+    FocDeviceGuard foc_guard_(stream, normal_acc);
+    if (N == 0) return FOC_OK;
+    FOC_REQUIRE(normal_acc && weights_sum && normal && normal_rgb, FOC_E_INVALID, "foc_normal_map_finish: null pointer (normal_acc, weights_sum, normal, normal_rgb)");
+    hipLaunchKernelGGL(k_normal_map_finish, dim3(foc_div_up(N, 256)), dim3(256), 0, (hipStream_t)stream, normal_acc, weights_sum, N, normal, normal_rgb);
+    FOC_CHECK_LAUNCH("foc_normal_map_finish");
+    return FOC_OK;
+}
 
 int foc_field_normals(const float *xn, uint32_t M, const void *embeddings, const uint32_t *offsets, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
                       uint32_t gridtype, int align_corners, uint32_t interp, int dtype, const int32_t *offsets_host, const void *sigma_weights,

@@ -937,16 +937,31 @@ __device__ __forceinline__ void rm_record_deaths(const RmDeaths &dh, bool died, 
 
 // ---------------------------------------------------------------- R10 (raymarching.cu:818-905)
 // What a ray accumulates over the calls of a view, and the three pieces both composite kernels are made of.
-struct RmAcc { float t, weight_sum, d, r, g, b; };
-__device__ __forceinline__ RmAcc rm_acc_load(int index, const float *__restrict__ rays_t, const float *__restrict__ weights_sum, const float *__restrict__ depth,
-                                             const float *__restrict__ image) {
-    return RmAcc{rays_t[index], weights_sum[index], depth[index], image[index * 3], image[index * 3 + 1], image[index * 3 + 2]};
+// AUX (compile time): a SECOND payload of three floats per sample rides along — the encoded normal next to the colour in the native render step
+// (foc_occ_render_step_normals, mode AUX) — accumulated with the first payload's weights into a second [N,3] image. One set of weights, one
+// stop test, one deaths histogram; AUX = false is the code it was before the flag existed (same members, same kernel arguments).
+template <bool AUX> struct RmAcc { float t, weight_sum, d, r, g, b; };
+template <> struct RmAcc<true> { float t, weight_sum, d, r, g, b, x, y, z; };
+// what the second payload adds to a kernel's arguments: its samples (laid out as rgbs) and its accumulator (laid out as image)
+template <bool AUX> struct RmSide : RmDeaths {};
+template <> struct RmSide<true> : RmDeaths { const float *aux; float *aux_image; };
+template <bool AUX>
+__device__ __forceinline__ RmAcc<AUX> rm_acc_load(int index, const float *__restrict__ rays_t, const float *__restrict__ weights_sum, const float *__restrict__ depth,
+                                                  const float *__restrict__ image, const RmSide<AUX> &side) {
+    if constexpr (AUX)
+        return RmAcc<true>{rays_t[index], weights_sum[index], depth[index], image[index * 3], image[index * 3 + 1], image[index * 3 + 2],
+                           side.aux_image[index * 3], side.aux_image[index * 3 + 1], side.aux_image[index * 3 + 2]};
+    else
+        return RmAcc<false>{rays_t[index], weights_sum[index], depth[index], image[index * 3], image[index * 3 + 1], image[index * 3 + 2]};
 }
 // one sample (:862-896) -> the ray ends here: the slot holds no sample (dt0 == 0), or the transmittance before it was below T_thresh.
 // Not free: k_composite_rays compiles to 153 / 218 instructions (COUNT off / on) through this function and rm_composite_finish, to 140 / 203 with
 // both spelled out in it (scalar control flow; registers, occupancy and the burst-1 view's time are unchanged): NOTEBOOK "One definition of the
 // occupancy march". Compare the counts again when changing either function.
-__device__ __forceinline__ bool rm_composite_sample(RmAcc &a, float sigma, float dt0, float dt1, float c0, float c1, float c2, float T_thresh) {
+// (p0, p1, p2: the sample's second payload, read with AUX only)
+template <bool AUX>
+__device__ __forceinline__ bool rm_composite_sample(RmAcc<AUX> &a, float sigma, float dt0, float dt1, float c0, float c1, float c2, float p0, float p1, float p2,
+                                                    float T_thresh) {
     if (dt0 == 0) return true;
     const float alpha = 1.0f - __expf(-sigma * dt0);
     const float T = 1 - a.weight_sum;
@@ -955,20 +970,22 @@ __device__ __forceinline__ bool rm_composite_sample(RmAcc &a, float sigma, float
     a.t += dt1;
     a.d = fmaf(weight, a.t, a.d);
     a.r = fmaf(weight, c0, a.r); a.g = fmaf(weight, c1, a.g); a.b = fmaf(weight, c2, a.b);
+    if constexpr (AUX) { a.x = fmaf(weight, p0, a.x); a.y = fmaf(weight, p1, a.y); a.z = fmaf(weight, p2, a.z); }
     return T < T_thresh;
 }
 // List entry n after its burst: ended at slot `ended_at` (marked dead) or still going (its t is kept for the next call); the accumulators go back.
 // Every lane of the wave comes here — `index` < 0: beyond the list or already marked dead (stays dead, nothing to accumulate).
 // COUNT: the wave also adds its number of surviving entries to block_counts[n / 1024] (zeroed by the caller) — the first pass of the ordered
 // compaction that follows in the native render step (k_compact_count otherwise) — and records where its rays died.
-template <bool COUNT>
-__device__ __forceinline__ void rm_composite_finish(uint32_t n, int index, const RmAcc &a, bool ended, uint32_t ended_at, uint32_t n_step,
+template <bool COUNT, bool AUX>
+__device__ __forceinline__ void rm_composite_finish(uint32_t n, int index, const RmAcc<AUX> &a, bool ended, uint32_t ended_at, uint32_t n_step,
                                                     int32_t *__restrict__ rays_alive, float *__restrict__ rays_t, float *__restrict__ weights_sum,
-                                                    float *__restrict__ depth, float *__restrict__ image, int32_t *__restrict__ block_counts, const RmDeaths &dh) {
+                                                    float *__restrict__ depth, float *__restrict__ image, int32_t *__restrict__ block_counts, const RmSide<AUX> &dh) {
     if (index >= 0) {
         if (ended) rays_alive[n] = -1; else rays_t[index] = a.t;
         weights_sum[index] = a.weight_sum; depth[index] = a.d;
         image[index * 3] = a.r; image[index * 3 + 1] = a.g; image[index * 3 + 2] = a.b;
+        if constexpr (AUX) { dh.aux_image[index * 3] = a.x; dh.aux_image[index * 3 + 1] = a.y; dh.aux_image[index * 3 + 2] = a.z; }
     }
     if (COUNT) {
         const uint64_t alive = __ballot(index >= 0 && !ended);
@@ -977,24 +994,32 @@ __device__ __forceinline__ void rm_composite_finish(uint32_t n, int index, const
     }
 }
 
-template <bool COUNT>
+template <bool COUNT, bool AUX = false>
 __global__ void __launch_bounds__(64) k_composite_rays(uint32_t n_alive, uint32_t n_step, float T_thresh,
                                  int32_t *__restrict__ rays_alive, float *__restrict__ rays_t,
                                  const float *__restrict__ sigmas, const float *__restrict__ rgbs, const float *__restrict__ deltas,
                                  float *__restrict__ weights_sum, float *__restrict__ depth, float *__restrict__ image, int32_t *__restrict__ block_counts,
-                                 RmDeaths dh) {
+                                 RmSide<AUX> dh) {
     const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
     const int index = n < n_alive ? rays_alive[n] : -1;
-    RmAcc a = {};
+    RmAcc<AUX> a = {};
     uint32_t step = 0;
     if (index >= 0) {
         // ray-major [n_alive][n_step] (the reference's layout) or sample-major [n_step][n_alive] (dh.sample_major: the native render step)
         const uint64_t first = dh.sample_major ? (uint64_t)n : (uint64_t)n * n_step, hop = dh.sample_major ? (uint64_t)n_alive : 1ull;
         const float *s = sigmas + first, *c = rgbs + first * 3, *dl = deltas + first * 2;
-        a = rm_acc_load(index, rays_t, weights_sum, depth, image);
+        a = rm_acc_load(index, rays_t, weights_sum, depth, image, dh);
+        if constexpr (AUX) {
+            const float *p = dh.aux + first * 3;
+            while (step < n_step) {
+                if (rm_composite_sample(a, s[0], dl[0], dl[1], c[0], c[1], c[2], p[0], p[1], p[2], T_thresh)) break;
+                s += hop; c += 3 * hop; p += 3 * hop; dl += 2 * hop; step++;
+            }
+        } else {
         while (step < n_step) {
-            if (rm_composite_sample(a, s[0], dl[0], dl[1], c[0], c[1], c[2], T_thresh)) break;
+            if (rm_composite_sample(a, s[0], dl[0], dl[1], c[0], c[1], c[2], 0.0f, 0.0f, 0.0f, T_thresh)) break;
             s += hop; c += 3 * hop; dl += 2 * hop; step++;
+        }
         }
     }
     rm_composite_finish<COUNT>(n, index, a, step < n_step, step, n_step, rays_alive, rays_t, weights_sum, depth, image, block_counts, dh);
@@ -1004,25 +1029,29 @@ __global__ void __launch_bounds__(64) k_composite_rays(uint32_t n_alive, uint32_
 // 16-byte loads (NS, 3 NS and 2 NS consecutive floats: whole cache lines per lane, every load in flight at once) and then runs the serial
 // accumulation on registers — with the pointer-chasing loop above a burst of 8 is 8 dependent rounds of 4-byte loads at a 32-byte lane stride
 // (86 us per 5.1 M samples, 1.4 TB/s). Same operations in the same order: same bits.
-template <int NS, bool COUNT>
+// AUX: 3 NS more floats per lane, loaded the same way and kept in registers like the rest, not staged in LDS: the compiler gives the counting
+// kernels 64 / 112 / 254 VGPRs at NS 4 / 8 / 16 (72 / 176 at 8 / 16 without the payload), no spills, 8 / 4 / 2 waves per SIMD — every load of a
+// lane is in flight before its first use, which is what the kernel lives on, not on waves to switch between.
+template <int NS, bool COUNT, bool AUX = false>
 __global__ void __launch_bounds__(64) k_composite_rays_pre(uint32_t n_alive, float T_thresh, int32_t *__restrict__ rays_alive, float *__restrict__ rays_t,
                                      const float *__restrict__ sigmas, const float *__restrict__ rgbs, const float *__restrict__ deltas,
                                      float *__restrict__ weights_sum, float *__restrict__ depth, float *__restrict__ image, int32_t *__restrict__ block_counts,
-                                     RmDeaths dh) {
+                                     RmSide<AUX> dh) {
     static_assert(NS % 4 == 0, "whole float4 loads");
     const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
     const int index = n < n_alive ? rays_alive[n] : -1;
-    RmAcc a = {};
+    RmAcc<AUX> a = {};
     bool ended = false;
     uint32_t ended_at = 0;
     if (index >= 0) {
-        float sg[NS], cl[3 * NS], dl[2 * NS];
+        float sg[NS], cl[3 * NS], dl[2 * NS], px[AUX ? 3 * NS : 1];
         if (dh.sample_major) {             // [NS][n_alive]: consecutive lanes read consecutive rays of one slot
 #pragma unroll
             for (int i = 0; i < NS; i++) {
                 const uint64_t m = (uint64_t)i * n_alive + n;
                 sg[i] = sigmas[m];
                 cl[3 * i] = rgbs[m * 3]; cl[3 * i + 1] = rgbs[m * 3 + 1]; cl[3 * i + 2] = rgbs[m * 3 + 2];
+                if constexpr (AUX) { px[3 * i] = dh.aux[m * 3]; px[3 * i + 1] = dh.aux[m * 3 + 1]; px[3 * i + 2] = dh.aux[m * 3 + 2]; }
                 const float2 v = *reinterpret_cast<const float2 *>(deltas + m * 2);
                 dl[2 * i] = v.x; dl[2 * i + 1] = v.y;
             }
@@ -1036,33 +1065,44 @@ __global__ void __launch_bounds__(64) k_composite_rays_pre(uint32_t n_alive, flo
         for (int i = 0; i < 3 * NS / 4; i++) { const float4 v = pc[i]; cl[4 * i] = v.x; cl[4 * i + 1] = v.y; cl[4 * i + 2] = v.z; cl[4 * i + 3] = v.w; }
 #pragma unroll
         for (int i = 0; i < 2 * NS / 4; i++) { const float4 v = pd[i]; dl[4 * i] = v.x; dl[4 * i + 1] = v.y; dl[4 * i + 2] = v.z; dl[4 * i + 3] = v.w; }
+        if constexpr (AUX) {
+            const float4 *pp = reinterpret_cast<const float4 *>(dh.aux + (uint64_t)n * NS * 3);
+#pragma unroll
+            for (int i = 0; i < 3 * NS / 4; i++) { const float4 v = pp[i]; px[4 * i] = v.x; px[4 * i + 1] = v.y; px[4 * i + 2] = v.z; px[4 * i + 3] = v.w; }
         }
-        a = rm_acc_load(index, rays_t, weights_sum, depth, image);
+        }
+        a = rm_acc_load(index, rays_t, weights_sum, depth, image, dh);
 #pragma unroll
         for (int step = 0; step < NS; step++) {
             if (!ended) {
                 ended_at = (uint32_t)step;
-                ended = rm_composite_sample(a, sg[step], dl[2 * step], dl[2 * step + 1], cl[3 * step], cl[3 * step + 1], cl[3 * step + 2], T_thresh);
+                if constexpr (AUX)
+                    ended = rm_composite_sample(a, sg[step], dl[2 * step], dl[2 * step + 1], cl[3 * step], cl[3 * step + 1], cl[3 * step + 2], px[3 * step],
+                                                px[3 * step + 1], px[3 * step + 2], T_thresh);
+                else
+                ended = rm_composite_sample(a, sg[step], dl[2 * step], dl[2 * step + 1], cl[3 * step], cl[3 * step + 1], cl[3 * step + 2], 0.0f, 0.0f, 0.0f, T_thresh);
             }
         }
     }
     rm_composite_finish<COUNT>(n, index, a, ended, ended_at, (uint32_t)NS, rays_alive, rays_t, weights_sum, depth, image, block_counts, dh);
 }
 
-template <bool COUNT>
+template <bool COUNT, bool AUX = false>
 static void rm_launch_composite(uint32_t n_alive, uint32_t n_step, float T_thresh, int32_t *rays_alive, float *rays_t, const float *sigmas, const float *rgbs,
                                 const float *deltas, float *weights_sum, float *depth, float *image, int32_t *block_counts, hipStream_t st,
-                                RmDeaths dh = RmDeaths{nullptr, 0u, 1u, 0}) {
-    const bool aligned = ((reinterpret_cast<uintptr_t>(sigmas) | reinterpret_cast<uintptr_t>(rgbs) | reinterpret_cast<uintptr_t>(deltas)) & 15u) == 0;
+                                RmSide<AUX> dh = RmSide<AUX>{RmDeaths{nullptr, 0u, 1u, 0}}) {
+    uintptr_t addresses = reinterpret_cast<uintptr_t>(sigmas) | reinterpret_cast<uintptr_t>(rgbs) | reinterpret_cast<uintptr_t>(deltas);
+    if constexpr (AUX) addresses |= reinterpret_cast<uintptr_t>(dh.aux);
+    const bool aligned = (addresses & 15u) == 0;
     // (`burst`: the run-time n_step argument of the general kernel; the others have it in their name)
     const auto launch = [&](auto kernel, auto... burst) {
         hipLaunchKernelGGL(kernel, dim3(foc_div_up(n_alive, 64)), dim3(64), 0, st, n_alive, burst..., T_thresh, rays_alive, rays_t, sigmas, rgbs, deltas, weights_sum, depth,
                            image, block_counts, dh);
     };
-    if (aligned && n_step == 4u) launch(k_composite_rays_pre<4, COUNT>);
-    else if (aligned && n_step == 8u) launch(k_composite_rays_pre<8, COUNT>);
-    else if (aligned && n_step == 16u) launch(k_composite_rays_pre<16, COUNT>);
-    else launch(k_composite_rays<COUNT>, n_step);
+    if (aligned && n_step == 4u) launch(k_composite_rays_pre<4, COUNT, AUX>);
+    else if (aligned && n_step == 8u) launch(k_composite_rays_pre<8, COUNT, AUX>);
+    else if (aligned && n_step == 16u) launch(k_composite_rays_pre<16, COUNT, AUX>);
+    else launch(k_composite_rays<COUNT, AUX>, n_step);
 }
 
 // ---------------------------------------------------------------- ordered compaction of rays_alive >= 0
@@ -1097,6 +1137,22 @@ __global__ void __launch_bounds__(1024) k_compact_scatter(const int32_t *__restr
 }
 
 // ================================================================= host entry points
+/* foc_composite_rays + the ordered compaction of the survivors into `out` (count in n_out), the compaction's counting pass done by the
+ * composite kernel itself: block_counts = int32[n_alive / 1024 + 2], ZEROED by the caller on this stream. (csrc/occrender.hip) */
+template <bool AUX>
+static int rm_composite_compact(uint32_t n_alive, uint32_t n_step, float T_thresh, int32_t *rays_alive, float *rays_t, const float *sigmas, const float *rgbs,
+                                const float *deltas, float *weights_sum, float *depth, float *image, int32_t *out, int32_t *n_out, int32_t *block_counts,
+                                const RmSide<AUX> &side, hipStream_t st) {
+    rm_launch_composite<true, AUX>(n_alive, n_step, T_thresh, rays_alive, rays_t, sigmas, rgbs, deltas, weights_sum, depth, image, block_counts, st, side);
+    FOC_CHECK_LAUNCH("composite_compact(composite)");
+    const uint32_t nb = foc_div_up(n_alive, 1024);
+    hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, st, block_counts, nb, n_out);
+    FOC_CHECK_LAUNCH("composite_compact(scan)");
+    hipLaunchKernelGGL(k_compact_scatter, dim3(nb), dim3(1024), 0, st, rays_alive, n_alive, block_counts, out);
+    FOC_CHECK_LAUNCH("composite_compact(scatter)");
+    return FOC_OK;
+}
+
 extern "C" {
 
 int foc_near_far_from_aabb(const float *rays_o, const float *rays_d, const float *aabb, uint32_t N, float min_near,
@@ -1381,8 +1437,6 @@ int foc_composite_rays(uint32_t n_alive, uint32_t n_step, float T_thresh, int32_
     return FOC_OK;
 }
 
-/* foc_composite_rays + the ordered compaction of the survivors into `out` (count in n_out), the compaction's counting pass done by the
- * composite kernel itself: block_counts = int32[n_alive / 1024 + 2], ZEROED by the caller on this stream. (csrc/occrender.hip) */
 int foc_composite_compact(uint32_t n_alive, uint32_t n_step, float T_thresh, int32_t *rays_alive, float *rays_t,
                           const float *sigmas, const float *rgbs, const float *deltas, float *weights_sum, float *depth,
                           float *image, int32_t *out, int32_t *n_out, int32_t *block_counts, int32_t *deaths, uint32_t deaths_base, uint32_t deaths_len,
@@ -1391,16 +1445,8 @@ int foc_composite_compact(uint32_t n_alive, uint32_t n_step, float T_thresh, int
     FOC_REQUIRE(n_alive > 0 && rays_alive && rays_t && sigmas && rgbs && deltas && weights_sum && depth && image && out && n_out && block_counts, FOC_E_INVALID,
                 "composite_compact: null pointer");
     FOC_REQUIRE(!deaths || deaths_len >= 1, FOC_E_INVALID, "composite_compact: empty death histogram");
-    hipStream_t st = (hipStream_t)stream;
-    rm_launch_composite<true>(n_alive, n_step, T_thresh, rays_alive, rays_t, sigmas, rgbs, deltas, weights_sum, depth, image, block_counts, st,
-                              RmDeaths{deaths, deaths_base, deaths ? deaths_len : 1u, sample_major ? 1 : 0});
-    FOC_CHECK_LAUNCH("composite_compact(composite)");
-    const uint32_t nb = foc_div_up(n_alive, 1024);
-    hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, st, block_counts, nb, n_out);
-    FOC_CHECK_LAUNCH("composite_compact(scan)");
-    hipLaunchKernelGGL(k_compact_scatter, dim3(nb), dim3(1024), 0, st, rays_alive, n_alive, block_counts, out);
-    FOC_CHECK_LAUNCH("composite_compact(scatter)");
-    return FOC_OK;
+    return rm_composite_compact(n_alive, n_step, T_thresh, rays_alive, rays_t, sigmas, rgbs, deltas, weights_sum, depth, image, out, n_out, block_counts,
+                                RmSide<false>{RmDeaths{deaths, deaths_base, deaths ? deaths_len : 1u, sample_major ? 1 : 0}}, (hipStream_t)stream);
 }
 
 int foc_compact_alive(const int32_t *rays_alive, uint32_t n_alive, int32_t *out, int32_t *n_out, int32_t *scratch, void *stream) {
@@ -1420,3 +1466,16 @@ int foc_compact_alive(const int32_t *rays_alive, uint32_t n_alive, int32_t *out,
 }
 
 } // extern "C"
+
+// foc_composite_compact with a second payload (common.h): aux [n_alive * n_step, 3] laid out as rgbs, accumulated into aux_image [N,3] with the
+// weights of the first. Everything else — what is written, which rays are marked, counted and recorded in `deaths` — is foc_composite_compact's.
+int composite_compact_aux(uint32_t n_alive, uint32_t n_step, float T_thresh, int32_t *rays_alive, float *rays_t, const float *sigmas, const float *rgbs,
+                          const float *aux, const float *deltas, float *weights_sum, float *depth, float *image, float *aux_image, int32_t *out, int32_t *n_out,
+                          int32_t *block_counts, int32_t *deaths, uint32_t deaths_base, uint32_t deaths_len, int sample_major, void *stream) {
+    FocDeviceGuard foc_guard_(stream, rays_alive);
+    FOC_REQUIRE(n_alive > 0 && rays_alive && rays_t && sigmas && rgbs && aux && deltas && weights_sum && depth && image && aux_image && out && n_out && block_counts,
+                FOC_E_INVALID, "composite_compact_aux: null pointer");
+    FOC_REQUIRE(!deaths || deaths_len >= 1, FOC_E_INVALID, "composite_compact_aux: empty death histogram");
+    return rm_composite_compact(n_alive, n_step, T_thresh, rays_alive, rays_t, sigmas, rgbs, deltas, weights_sum, depth, image, out, n_out, block_counts,
+                                RmSide<true>{RmDeaths{deaths, deaths_base, deaths ? deaths_len : 1u, sample_major ? 1 : 0}, aux, aux_image}, (hipStream_t)stream);
+}

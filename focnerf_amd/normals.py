@@ -3,7 +3,8 @@ sigma, the position gradient of the density logit and the encoded normal per sam
 
     sigma, grad = density_gradient(model, x)                 # world units; fused where field_plan(model).normals, else through autograd
     sigma, normal_rgb = field_normals(model, xn, rotation)   # the drop-in counterpart of field.field_infer: "rgb" = 0.5 + 0.5 n
-    normal, opacity, encoded = render_normals(model, rays_o, rays_d)
+    normal, opacity, encoded = render_normals(model, rays_o, rays_d)                       # 512 fixed steps per ray
+    normal, opacity, encoded = render_normals(model, rays_o, rays_d, path="occupancy")     # the occupancy march's own samples
 
 A normal encoded as 0.5 + 0.5 n is an ordinary colour to everything behind the field: `render_field4(..., channels="normal")`,
 `fixedcull.culled_lists`, `combine.placed_field_fns`, `culled_field_fns` and `render_scene_culled` take `channels="normal"` and the packs,
@@ -134,10 +135,38 @@ def decode_normal_map(image4_pair):
     return normal.float(), opacity.float()
 
 
+def normal_map_finish(normal_acc, weights_sum):
+    """The composite's accumulators of an encoded-normal payload -> (normal [N,3], unit or 0; normal_rgb [N,3], the encoded map on a white
+    background): `foc_normal_map_finish`, one launch. normal_acc [N,3] = sum_k w_k (0.5 + 0.5 n_k), weights_sum [N], fp32 on the GPU."""
+    acc, ws = normal_acc.contiguous().view(-1, 3), weights_sum.contiguous().view(-1)
+    if acc.dtype != torch.float32 or ws.dtype != torch.float32 or not acc.is_cuda or acc.shape[0] != ws.shape[0]:
+        raise ValueError(f"normal_map_finish: fp32 GPU tensors [N,3] and [N] expected, got {tuple(normal_acc.shape)} {normal_acc.dtype} and "
+                         f"{tuple(weights_sum.shape)} {weights_sum.dtype} on {normal_acc.device}")
+    normal, encoded = torch.empty_like(acc), torch.empty_like(acc)
+    check(lib.foc_normal_map_finish(ptr(acc), ptr(ws), acc.shape[0], ptr(normal), ptr(encoded), stream_of(acc)), "normal_map_finish")
+    return normal, encoded
+
+
 @torch.no_grad()
-def render_normals(model, rays_o, rays_d, num_steps=512, occupancy=None, placement=None, scene_aabb=None):
+def render_normals(model, rays_o, rays_d, num_steps=512, occupancy=None, placement=None, scene_aabb=None, path="fixed"):
     """A normal map of one object: `render_field4(channels="normal")`, the fixed-step composite against the backgrounds (1, 0) and
-    `decode_normal_map`. -> normal [N,3] (unit or 0), opacity [N], encoded [N,3] (the 0.5 + 0.5 n image on the white background)."""
+    `decode_normal_map`. -> normal [N,3] (unit or 0), opacity [N], encoded [N,3] (the 0.5 + 0.5 n image on the white background).
+    path="occupancy": the same triple from the occupancy march instead (`model.run_cuda(normals="only")` with dt_gamma 0, max_steps 1024,
+    T_thresh 1e-4; under autocast, as a colour view is rendered): the samples a colour view of the object takes, not num_steps per ray.
+    One object in its own frame: `occupancy=` / `placement=` raise with it (placed scenes stay on the fixed-step combiner)."""
+    if path not in ("fixed", "occupancy"):
+        raise ValueError(f"render_normals: path must be 'fixed' or 'occupancy', got {path!r}")
+    if path == "occupancy":
+        if occupancy is not None or placement is not None:
+            raise ValueError("render_normals: path='occupancy' renders one object in its own frame through its own occupancy grid; "
+                             "occupancy= / placement= belong to path='fixed'")
+        if not getattr(model, "cuda_ray", False):
+            raise ValueError("render_normals: path='occupancy' needs a model built with cuda_ray=True (an occupancy grid to march)")
+        rays_o = rays_o.contiguous().view(-1, 3).float()
+        rays_d = rays_d.contiguous().view(-1, 3).float()
+        with torch.autocast("cuda", dtype=torch.float16):
+            out = model.run_cuda(rays_o, rays_d, dt_gamma=0, max_steps=1024, T_thresh=1e-4, normals="only")
+        return out["normal"], out["weights_sum"], out["normal_rgb"]
     from . import raymarching
     from .combine import combine_packed
     from .fixedstep import render_field4

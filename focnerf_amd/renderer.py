@@ -231,7 +231,7 @@ class NeRFRenderer(nn.Module):
         return sigmas if self.density_scale == 1 else self.density_scale * sigmas      # x * 1 == x: no launch for the default scale
 
     def run_cuda(self, rays_o, rays_d, dt_gamma=0, bg_color=None, perturb=False, force_all_rays=False, max_steps=1024, T_thresh=1e-4,
-                 device_compaction=None, yolo_details=None, distortion=False, depth_grad=False, **kwargs):
+                 device_compaction=None, yolo_details=None, distortion=False, depth_grad=False, normals=False, **kwargs):
         """Samples only where the occupancy bitfield is set (legacy/nerf/renderer.py:256-376). Training: one marching pass, one
         evaluation of the field, one compositing node. Inference: rays advance a few samples at a time and leave the list once they are
         opaque or out of the box.
@@ -243,12 +243,21 @@ class NeRFRenderer(nn.Module):
         per-sample weights and raises ValueError.
         depth_grad=True (fused training node only) makes 'depth' differentiable (want_depth_grad: the tail's backward takes its gradient, as
         the fixed-step tail's does); the default keeps the reference's semantics, whose composite ignores grad_depth: 'depth' then carries
-        no gradient. Every other route raises ValueError."""
+        no gradient. Every other route raises ValueError.
+        normals (inference, the native loop only) renders the surface normals of the density field from the march's own samples
+        (csrc/occrender.hip, foc_occ_render_step_normals): "only" -> 'normal' [...,3] (unit, or 0 where nothing was hit or the sum vanishes),
+        'normal_rgb' [...,3] (the 0.5 + 0.5 n map on a white background), 'depth', 'weights_sum', and no 'image' — no encoder planes, no colour
+        network; True -> the colour result plus 'weights_sum', 'normal' and 'normal_rgb', colour and normal composited from the same samples
+        with the same weights. 'depth' and 'weights_sum' have the bits of normals=False, True's 'image' too, and True's normals "only"'s. A
+        background model (bg_radius > 0) contributes colour only. Never a silent fallback: ValueError where the native loop or the normals
+        kernel does not serve the call (training mode, gradients on, autocast off, device_compaction=False, field_plan: normals, native_loop)."""
         o, d, lead = _flat_rays(rays_o, rays_d)
         n, dev = o.shape[0], o.device
         out = {}
         from .field import field_plan
         plan = field_plan(self)
+        if normals is not False:
+            self._check_occ_normals(normals, plan, o, device_compaction, yolo_details is not None and plan.uses_object_feature)
         obj16 = outside = None
         if yolo_details is not None and plan.uses_object_feature:
             out['criterion_outside_mask'] = None
@@ -289,7 +298,7 @@ class NeRFRenderer(nn.Module):
             raise ValueError("run_cuda: depth_grad=True needs the fused occupancy training node, whose tail alone takes the depth's gradient: a CUDA "
                              "device, model.train(), gradients and autocast enabled, a network that node serves, and FOC_FUSED_OCC unset or 1")
         near, far = raymarching.near_far_from_aabb(o, d, self._aabb(), self.min_near)
-        background = self._background_colour(o, d, bg_color)
+        background = self._background_colour(o, d, bg_color) if normals != "only" else None
         if self.training:
             slot = self.step_counter[self.local_step % 16]
             slot.zero_()
@@ -311,7 +320,18 @@ class NeRFRenderer(nn.Module):
             # bit for bit: tests/test_gpu_network.py), else the reference's loop as it is; True = the native loop, else the Python loop with the
             # list compacted on the device and its length read late; False = the reference's loop (boolean mask, a host round trip per iteration)
             # the native loop serves the networks of the whole-field kernel on the GPU, under autocast (fp16 table and weights): plan.native_loop
-            if ((device_compaction is None or device_compaction) and o.is_cuda and torch.is_autocast_enabled() and not torch.is_grad_enabled()
+            if normals is not False:                                  # (_check_occ_normals: the native loop serves this call)
+                normal_acc = torch.zeros(n, 3, dtype=torch.float32, device=dev)
+                self._native_inference_loop(plan, o, d, near, far, alive, t_now, opacity, depth, image, perturb, dt_gamma, max_steps, T_thresh, obj16,
+                                            normal_acc=normal_acc, normals_only=normals == "only")
+                from .normals import normal_map_finish
+                normal, encoded = normal_map_finish(normal_acc, opacity)
+                out['weights_sum'], out['normal'], out['normal_rgb'] = opacity, normal.view(*lead, 3), encoded.view(*lead, 3)
+                if normals == "only":
+                    out['depth'] = (torch.clamp(depth - near, min=0) / (far - near)).view(*lead)      # _finish's depth
+                    return out
+                marched = max_steps
+            elif ((device_compaction is None or device_compaction) and o.is_cuda and torch.is_autocast_enabled() and not torch.is_grad_enabled()
                     and (plan.native_loop if obj16 is None else plan.native_loop_object)):
                 self._native_inference_loop(plan, o, d, near, far, alive, t_now, opacity, depth, image, perturb, dt_gamma, max_steps, T_thresh, obj16)
                 marched = max_steps                                   # the Python loop below has nothing left to do
@@ -363,15 +383,40 @@ class NeRFRenderer(nn.Module):
         out['image'], out['depth'] = self._finish(image, depth, opacity, near, far, background, lead)
         return out
 
+    def _check_occ_normals(self, normals, plan, o, device_compaction, with_object):
+        """run_cuda(normals=...) is served by the native inference loop and the fused normals kernel, or refused: each condition by name."""
+        who = f"run_cuda(normals={normals!r})"
+        if normals is not True and normals != "only":
+            raise ValueError(f"{who}: normals must be False, True or 'only'")
+        if self.training:
+            raise ValueError(f"{who}: the model is in training mode; normals are rendered by the inference loop (model.eval())")
+        if torch.is_grad_enabled():
+            raise ValueError(f"{who}: gradients are enabled; the native inference loop runs under torch.no_grad()")
+        if not torch.is_autocast_enabled():
+            raise ValueError(f"{who}: autocast is off; the native inference loop runs under torch.autocast('cuda') (fp16 table and weights)")
+        if device_compaction is not None and not device_compaction:
+            raise ValueError(f"{who}: device_compaction=False asks for the reference's Python loop, which renders no normals")
+        if not plan.normals:
+            raise ValueError(f"{who}: field_plan(model).normals is false: the fused normals kernel does not serve this network (hash grid with 16 "
+                             "levels of 2 features, linear, align_corners off; sigma network 32 -> 64 x 1..3 -> 16 with ReLU; FOC_FUSED_NORMALS not 0)")
+        if not (plan.native_loop_object if with_object else plan.native_loop):
+            raise ValueError(f"{who}: field_plan(model).{'native_loop_object' if with_object else 'native_loop'} is false: the native inference loop "
+                             "does not serve this network (the whole-field inference kernel, density_scale 1, a plain hash grid; FOC_RENDER_NATIVE not 0)")
+        if not o.is_cuda:
+            raise ValueError(f"{who}: the rays are not on a GPU; the native inference loop is HIP kernels")
+
     # ------------------------------------------------------------------ the inference loop, one native call per iteration
-    def _native_inference_loop(self, plan, o, d, near, far, alive, t_now, opacity, depth, image, perturb, dt_gamma, max_steps, T_thresh, obj16=None):
+    def _native_inference_loop(self, plan, o, d, near, far, alive, t_now, opacity, depth, image, perturb, dt_gamma, max_steps, T_thresh, obj16=None,
+                               normal_acc=None, normals_only=False):
         """The loop of legacy/nerf/renderer.py:323-372 with every iteration ONE call into the library (csrc/occrender.hip: march, encode,
         whole-field kernel, composite, compaction) on buffers allocated once per view; bursts of FOC_RENDER_BURST samples per ray, the live
         count read `FOC_RENDER_COUNT_LAG` iterations late, the reference's stopping point reproduced. Same samples, same per-ray
         accumulation order: the same image and depth bit for bit on every configuration the tests run (jittered first samples with the
         same noise included), with one caveat spelled out at the burst rule below — a re-derivation of t that can differ by an ulp where a
         single advance more than doubles t while fewer than half of the rays are alive.
-        obj16: the encoded object feature of an object-conditioned network (plan.native_loop_object), handed to every step."""
+        obj16: the encoded object feature of an object-conditioned network (plan.native_loop_object), handed to every step.
+        normal_acc [n,3] (zeros): every step is foc_occ_render_step_normals and accumulates the samples' encoded normals there — next to the
+        colour, or with normals_only in its place (`image` is then not touched, no planes and no colours are allocated)."""
         from ._lib import lib, ptr, stream_of, check
         from .field import _half_of, half_cache_scope, pad_twin, fused_mlp, object_feature_half
         n, dev = o.shape[0], o.device
@@ -395,8 +440,9 @@ class NeRFRenderer(nn.Module):
         from ._lib import get_option
         piece = min(cap, max(1024, get_option("FOC_OCC_FIELD_PIECE")))
         samples = torch.empty(cap * 8, dtype=torch.float32, device=dev)
-        planes = torch.empty(L * piece * 2, dtype=torch.float16, device=dev)
-        sigma, rgb = torch.empty(cap, dtype=torch.float32, device=dev), torch.empty(cap * 3, dtype=torch.float32, device=dev)
+        planes = torch.empty(L * piece * 2, dtype=torch.float16, device=dev) if not normals_only else None
+        sigma, rgb = torch.empty(cap, dtype=torch.float32, device=dev), torch.empty(cap * 3, dtype=torch.float32, device=dev) if not normals_only else None
+        normal_rgb = torch.empty(cap * 3, dtype=torch.float32, device=dev) if normal_acc is not None else None
         lists = [alive, torch.empty_like(alive)]
         count = torch.empty(1, dtype=torch.int32, device=dev)
         scratch = torch.empty(lib.foc_occ_render_step_scratch_bytes(n), dtype=torch.uint8, device=dev)
@@ -413,6 +459,11 @@ class NeRFRenderer(nn.Module):
         # a constant last column of the colour input (network_tcnn_legacy.py: column 31 = 1.0; network_tcnn.py: column 47 = 1.0): the step's
         # twin, the pad before the stream
         render_step, pad_args = pad_twin("foc_occ_render_step", plan.colour_input_pad, plan.uses_object_feature)
+        if normal_acc is not None:                              # one entry point for every colour input: the pad and its column, then the normals
+            pad = float(plan.colour_input_pad)
+            render_step = lib.foc_occ_render_step_normals
+            mode = 1 if normals_only else 2                     # FOC_OCC_NORMALS_ONLY / FOC_OCC_NORMALS_AUX (include/focnerf.h)
+            pad_args = (pad, 0 if pad == 0 else (47 if plan.uses_object_feature else 31), mode, ptr(normal_rgb), ptr(normal_acc))
         obj_h = object_feature_half(obj16, "native inference loop")
         with half_cache_scope():
             emb, ws, wc = _half_of(enc.embeddings), _half_of(sn.weights), _half_of(cn.weights)
@@ -427,9 +478,9 @@ class NeRFRenderer(nn.Module):
                 check(render_step(live, burst, ptr(src), ptr(dst), ptr(count), ptr(t_now), ptr(o), ptr(d), float(self.bound), float(dt_gamma),
                                               int(max_steps), self.cascade, self.grid_size, ptr(self.density_bitfield), ptr(near), ptr(far),
                                               ptr(jitter if marched == 0 else still), ptr(samples), ptr(planes), ptr(sigma), ptr(rgb), ptr(emb),
-                                              ptr(enc.offsets), None, L, plan.grid.log2_scale, plan.grid.base_resolution, ptr(ws), plan.sigma.num_layers, ptr(wc),
+                                              ptr(enc.offsets), None, L, plan.grid.log2_scale, plan.grid.base_resolution, ptr(ws), plan.sigma.num_layers, ptr(None if normals_only else wc),
                                               plan.colour.num_layers, plan.sigma.activation,
-                                              ptr(obj_h), float(T_thresh), ptr(opacity), ptr(depth), ptr(image), ptr(scratch), flags, ptr(deaths), marched, n_deaths,
+                                              ptr(obj_h), float(T_thresh), ptr(opacity), ptr(depth), ptr(None if normals_only else image), ptr(scratch), flags, ptr(deaths), marched, n_deaths,
                                               *pad_args, st), "occ_render_step")
                 state["it"], state["marched"] = it + 1, marched + burst
 

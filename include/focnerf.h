@@ -269,6 +269,37 @@ int foc_occ_render_step_pad(uint32_t n_alive, uint32_t n_step, const int32_t *ra
                             const void *sigma_weights, uint32_t sigma_layers, const void *color_weights, uint32_t color_layers, uint32_t activation,
                             const void *obj_feat, float T_thresh, float *weights_sum, float *depth, float *image, void *scratch, uint32_t flags,
                             int32_t *deaths, uint32_t deaths_base, uint32_t deaths_len, float input_pad, void *stream);
+/* foc_occ_render_step with the surface normal of every sample as a payload of the composite: prepare, march and compaction are that step's,
+ * foc_field_normals runs on the march's normalised positions, piece by piece (FOC_OCC_FIELD_PIECE), with rot9 NULL and no grad_raw / grad_enc.
+ * Arguments as foc_occ_render_step, then:
+ *   input_pad, pad_column  the colour input's constant last column, and which one: 0 (none; input_pad must be 0: foc_occ_render_step), 31
+ *                          (foc_occ_render_step_pad31) or 47 (foc_occ_render_step_pad)
+ *   mode                   1 = FOC_OCC_NORMALS_ONLY, 2 = FOC_OCC_NORMALS_AUX (the names the sources and this text use for the two values; the
+ *                          header defines no macro for them)
+ *   normal_rgb             fp32 [n_alive * n_step, 3] scratch: the encoded normal 0.5 + 0.5 n of every sample slot, laid out as rgb
+ *   normal_acc             fp32 [N, 3], zeroed by the caller before a view's first call: sum_k w_k (0.5 + 0.5 n_k), accumulated as image is
+ *                          (foc_normal_map_finish turns it into a normal map)
+ * FOC_OCC_NORMALS_ONLY: march -> foc_field_normals (sigma and normal_rgb) -> foc_composite_compact with rgbs = normal_rgb, image = normal_acc.
+ *   No encoder planes, no colour network: planes, rgb, image, color_weights and obj_feat may be NULL and are not touched. weights_sum, depth,
+ *   rays_t, the output list, count and deaths are BIT-IDENTICAL to foc_occ_render_step's on the same arguments (foc_field_normals' sigma has
+ *   the bits of foc_nerf_field_inference's), and normal_acc to what that step's image would be with normal_rgb for its colours.
+ * FOC_OCC_NORMALS_AUX: the colour step as it is (encode, field with the given pad) plus foc_field_normals for normal_rgb alone on the same
+ *   pieces, then ONE composite that accumulates both payloads with one set of weights, one stop at T_thresh and one deaths histogram.
+ *   weights_sum, depth, image, rays_t, list, count and deaths are bit-identical to the colour step's, normal_acc to FOC_OCC_NORMALS_ONLY's.
+ * Refused with FOC_E_INVALID before anything is enqueued, the message names the argument: mode not one of the two; pad_column not 0, 31 or 47;
+ *   pad_column 0 with input_pad != 0, 31 with obj_feat, 47 without it; a non-zero pad with (sigma_layers, color_layers) outside (1,2), (1,3),
+ *   (2,2), (2,3), (3,3); NULL normal_rgb / normal_acc; with n_alive > 0 a NULL pointer the mode needs (AUX: every one of the colour step's),
+ *   and whatever foc_field_normals refuses (L != 16, sigma_layers outside 1..3, activation not ReLU, a misaligned sigma_weights: the level
+ *   width 2, the hash gridtype, linear interpolation and hidden 64 are this step's own). */
+int foc_occ_render_step_normals(uint32_t n_alive, uint32_t n_step, const int32_t *rays_alive, int32_t *rays_alive_out, int32_t *count,
+                                float *rays_t, const float *rays_o, const float *rays_d, float bound, float dt_gamma, uint32_t max_steps,
+                                uint32_t C, uint32_t H, const uint8_t *grid, const float *nears, const float *fars, const float *noises,
+                                float *samples, void *planes, float *sigma, float *rgb,
+                                const void *embeddings, const int32_t *offsets, const int32_t *offsets_host, uint32_t L, float S, uint32_t base_res,
+                                const void *sigma_weights, uint32_t sigma_layers, const void *color_weights, uint32_t color_layers, uint32_t activation,
+                                const void *obj_feat, float T_thresh, float *weights_sum, float *depth, float *image, void *scratch, uint32_t flags,
+                                int32_t *deaths, uint32_t deaths_base, uint32_t deaths_len, float input_pad, uint32_t pad_column, uint32_t mode,
+                                float *normal_rgb, float *normal_acc, void *stream);
 
 int foc_compact_alive(const int32_t *rays_alive, uint32_t n_alive, int32_t *out, int32_t *n_out,
                       int32_t *scratch, void *stream);
@@ -521,6 +552,12 @@ int foc_field_normals(const float *xn, uint32_t M, const void *embeddings, const
                       float S, uint32_t H, uint32_t gridtype, int align_corners, uint32_t interp, int dtype, const int32_t *offsets_host,
                       const void *sigma_weights, uint32_t sigma_layers, uint32_t hidden_dim, uint32_t activation, const float *rot9,
                       float *sigma, float *grad_raw, float *normal_rgb, void *grad_enc, void *stream);
+/* A composited normal map out of its accumulators, one launch over N pixels: normal_acc [N,3] = sum_k w_k (0.5 + 0.5 n_k) (the image a
+ * composite makes of foc_field_normals' normal_rgb: foc_occ_render_step_normals) and weights_sum [N] = W. Per pixel, all fp32:
+ *   s = 2 acc - W per component (= sum_k w_k n_k; 2 acc is exact, one rounding); m = max_d |s_d|; m == 0 or a component not finite: normal = 0;
+ *   else u = s / m, normal = u / sqrt(u.u) (foc_field_normals' rule); normal_rgb = acc + (1 - W): the encoded map on a white background.
+ * normal [N,3], normal_rgb [N,3]; neither may alias an input. No atomics, nothing order-dependent: FOC_DETERMINISTIC changes nothing. */
+int foc_normal_map_finish(const float *normal_acc, const float *weights_sum, uint32_t N, float *normal, float *normal_rgb, void *stream);
 
 /* The colour network of a ray-ordered sample list without its materialised input (network_ff.py:104-108 builds
  * cin = [SH16(dir) | h[:,1:16] | 0] per sample, 64 B written and read twice): the kernels take the sigma network's output
