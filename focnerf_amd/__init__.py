@@ -13,6 +13,8 @@ from .score import score_view, ViewScore  # noqa: F401  (PSNR and SSIM of a comb
 from .normals import density_gradient, field_normals, decode_normal_map, render_normals, normal_map_finish  # noqa: F401  (surface normals from the density field)
 from . import optim  # noqa: F401
 from .optim import FusedAdam, LossScaler  # noqa: F401  (the trainer's optimizer step: overflow check, unscale and Adam in two launches)
+from . import ema  # noqa: F401
+from .ema import ParameterEMA  # noqa: F401  (torch_ema's ExponentialMovingAverage; its update rides in FusedAdam's update launch)
 from . import batch  # noqa: F401
 from .batch import DeviceDataset, RaySampler, photo_loss  # noqa: F401  (a training batch in one launch; loss, gradient and error map in one more)
 
@@ -22,5 +24,5 @@ __all__ = ["raymarching", "gridencoder", "freqencoder", "ffmlp", "activation", "
            "Mesh", "extract_mesh", "extract_scene_mesh", "read_ply_attributes", "query", "query_scene", "SceneSample",
            "score", "score_view", "ViewScore",
            "normals", "density_gradient", "field_normals", "decode_normal_map", "render_normals", "normal_map_finish",
-           "optim", "FusedAdam", "LossScaler",
+           "optim", "FusedAdam", "LossScaler", "ema", "ParameterEMA",
            "batch", "DeviceDataset", "RaySampler", "photo_loss"]

@@ -16,7 +16,8 @@ new batch each time by itself:
 Random numbers are Philox4x32-10 with counter (ray, step, stream) and key seed (include/focnerf.h): a batch is a pure function of
 (seed, step), whatever the launch size. Torch's random stream is NOT reproduced: a seeded run here draws other pixels than a seeded
 reference run. Out of scope: patch_size > 1 (it exists for the LPIPS term), batches of more than one view (the
-reference's loader always has batch_size=1), the 64 x 64 YOLO ray mask (passed through `yolo_details` as today) and the parameter EMA.
+reference's loader always has batch_size=1) and the 64 x 64 YOLO ray mask (passed through `yolo_details` as today). The parameter EMA
+is not a batch matter: focnerf_amd/ema.py `ParameterEMA` takes it inside `FusedAdam.step(ema=...)`.
 There is no fallback: without the library the import fails.
 """
 from typing import NamedTuple, Optional, Union

@@ -177,7 +177,7 @@ class half_cache_scope:
     ONLY cache: outside it every forward converts again, as the reference does on every call (grid.py:41-44; ffmlp.py:23) — validity
     cannot be inferred from the parameter itself, because writes through `.data` (torch_ema's copy_to / restore around every
     evaluation, nerf/utils.py:1164-1174; `reset_parameters`) leave its version counter untouched. Re-entrant; the outermost exit drops
-    the copies."""
+    the copies, and so does `drop_half_cache()` (ParameterEMA.copy_to / restore call it) while the scope stays open."""
 
     def __enter__(self):
         global _half_scope
@@ -190,6 +190,13 @@ class half_cache_scope:
         global _half_scope
         _half_scope = self._outer
         return False
+
+
+def drop_half_cache():
+    """Forget what an open `half_cache_scope` holds: somebody has written the parameters in place (ParameterEMA.copy_to / restore), which
+    neither their identity nor their version counter shows. The scope stays open and fills again. No scope open: nothing to do."""
+    if _half_scope is not None:
+        _half_scope.clear()
 
 
 def _half_of(param):

@@ -13,6 +13,9 @@ GradScaler (main_nerf.py:211,472, nerf/utils.py:1225-1235): about twenty small l
     scaler.scale(loss).backward()                  # a second one, nothing else; no host synchronisation, so it captures in a graph
     opt.step(scaler=scaler, zero_grads=True)       # (there is no scaler.update(): the step has done it)
 
+    ema = ParameterEMA(model.parameters(), 0.95)   # the trainer's parameter EMA (focnerf_amd/ema.py) rides in the update launch of either
+    opt.step(scaler=scaler, ema=ema)               # route — `scaler.step(opt, ema=ema)` under torch's GradScaler — instead of ema.update()
+
 The state is the one `torch.optim.Adam(fused=True, capturable=True)` keeps — per parameter `step` (0-dim fp32 on the device), `exp_avg`,
 `exp_avg_sq`, the same keys in `param_groups` — so state dicts go both ways between the two classes and the reference trainer's full
 checkpoints keep loading; `LossScaler`'s state dict is `torch.amp.GradScaler`'s. There is no fallback: without the library the import fails.
@@ -150,14 +153,18 @@ class FusedAdam(torch.optim.Optimizer):
             self._workspaces[device] = ws
         return ws
 
-    def init_state(self, scaler=None):
-        """Allocate moments, step counters and the workspace now (before a graph capture that has no eager warm-up step)."""
+    def init_state(self, scaler=None, ema=None):
+        """Allocate moments, step counters and the workspace now (before a graph capture that has no eager warm-up step); with `ema`, its
+        device counter and its own workspace too."""
         for group in self.param_groups:
             for p in group["params"]:
                 self._state_of(p)
                 self._workspace(p.device)
                 if scaler is not None:
                     scaler._on(p.device)
+                if ema is not None and p.is_cuda:
+                    ema._on(p.device)
+                    ema._workspace(p.device)
 
     # ---------------------------------------------------------------- step
     def _collect(self):
@@ -201,12 +208,16 @@ class FusedAdam(torch.optim.Optimizer):
         return arr
 
     @torch.no_grad()
-    def step(self, closure=None, *, scaler=None, zero_grads=False):
+    def step(self, closure=None, *, scaler=None, zero_grads=False, ema=None):
         """One step. `scaler`: a `LossScaler` whose scale the grads carry — check, decision, scale update and update, two launches per 16
         tensors, no host synchronisation. Without it: under `torch.amp.GradScaler.step(opt)` the `grad_scale` / `found_inf` torch has set
         on this object decide; otherwise plain Adam. `zero_grads=True` writes zeros to the grads in the same pass — also when the step is
         skipped for an overflow (torch would leave them; they are of no use after a skipped step). Params whose grad is None are left out
-        and their step counters do not advance."""
+        and their step counters do not advance.
+        `ema`: a `ParameterEMA` that takes its update with this step, instead of an `ema.update()` after it — also when the step is skipped
+        for an overflow, as the reference's unconditional call does. The shadows of the step's params are updated inside the update launch;
+        params the EMA tracks and the step leaves out (no grad, not in this optimizer) follow in one more launch per 16 on the same
+        stream; its counter advances once. The launches of the step itself are the same with and without it."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -216,8 +227,12 @@ class FusedAdam(torch.optim.Optimizer):
             raise RuntimeError("FusedAdam: step(scaler=LossScaler) inside torch's GradScaler.step: one scaler at a time")
         if scaler is not None and not isinstance(scaler, LossScaler):
             raise TypeError("FusedAdam: scaler must be a focnerf_amd.optim.LossScaler (torch's GradScaler calls scaler.step(optimizer) itself)")
+        if ema is not None and not hasattr(ema, "_for_step"):
+            raise TypeError("FusedAdam: ema must be a focnerf_amd.ParameterEMA")
         items = self._collect()
         if not items:
+            if ema is not None:
+                ema.update()                    # nothing to step: the EMA's update alone
             return loss
         device = items[0][0].device
         if any(it[0].device != device for it in items):
@@ -231,10 +246,29 @@ class FusedAdam(torch.optim.Optimizer):
         call.zero_grads = 1 if zero_grads else 0
         call.workspace, call.workspace_bytes = ws.data_ptr(), ws.numel() * 4
 
+        riding, behind, by_torch = ema._for_step([it[0] for it in items], device) if ema is not None else ({}, [], [])
+        ema_count = ema._count if ema is not None else None     # on `device` now; None: a constant decay
+        opened = [ema is None]                  # the EMA of this step is opened (counter + 1, 1 - decay_t into the record) exactly once
+
         def run(chunk, phase):
             arr = self._descriptors(chunk) if chunk is not None else None
             call.n_tensors, call.tensors, call.phase = (len(chunk), arr, phase) if chunk is not None else (0, None, phase)
-            check(lib.foc_optim_step(ctypes.byref(call), stream), "optim_step")
+            if ema is None or phase == _PHASE_CHECK:
+                check(lib.foc_optim_step(ctypes.byref(call), stream), "optim_step")
+                return
+            shadows = None
+            if chunk is not None:
+                shadows = (ctypes.c_uint64 * len(chunk))(*[riding[id(it[0])].data_ptr() if id(it[0]) in riding else 0 for it in chunk])
+            advance, opened[0] = (0 if opened[0] else 1), True
+            check(lib.foc_optim_step_ema(ctypes.byref(call), shadows, float(ema.decay), ema_count.data_ptr() if ema_count is not None else None,
+                                         advance, stream), "optim_step_ema")
+
+        def finish():
+            if behind:
+                ema._launch(behind, device, ws, advance=False)
+            if by_torch:
+                ema._torch_rule(by_torch, advanced=True)
+            return loss
 
         if scaler is not None:
             scaler._on(device)
@@ -242,7 +276,7 @@ class FusedAdam(torch.optim.Optimizer):
             call.growth_factor, call.backoff_factor, call.growth_interval = scaler._growth_factor, scaler._backoff_factor, scaler._growth_interval
             if len(chunks) == 1:
                 run(chunks[0], _PHASE_STEP)
-                return loss
+                return finish()
             for chunk in chunks:            # one decision for all groups: every check, the decision, then every update
                 run(chunk, _PHASE_CHECK)
             run(None, _PHASE_DECIDE)
@@ -256,4 +290,4 @@ class FusedAdam(torch.optim.Optimizer):
             call.found_inf = found_inf.data_ptr() if found_inf is not None else None
         for chunk in chunks:
             run(chunk, _PHASE_STEP)
-        return loss
+        return finish()

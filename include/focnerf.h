@@ -1380,6 +1380,44 @@ size_t foc_optim_workspace_bytes(int n_tensors);
 int foc_optim_step(const FocOptimStep *step, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * The parameter EMA (csrc/optim.hip; the reference trainer runs torch_ema's ExponentialMovingAverage.update() after every optimizer
+ * step, nerf/utils.py:739,1125,1256: three torch ops and one temporary per tensor). For a parameter p and its shadow s, both [n] fp32
+ * contiguous:
+ *     n_upd  <- n_upd + 1                                  (only with num_updates; it starts at 0)
+ *     decay_t = min(decay, (1 + n_upd) / (10 + n_upd))     in double; `decay` itself when num_updates is NULL
+ *     omd     = float(1 - decay_t)
+ *     s      <- s - (s - p) * omd                          three fp32 roundings, no contraction
+ * num_updates: one int64 on the device, 8-byte aligned, or NULL. omd is computed once per step on the device and kept in word 7 of
+ * the optimizer workspace (float); nothing reads the counter after the launch that advanced it, so steps capture in a graph.
+ * advance != 0: this call OPENS the step's EMA — it advances the counter (if there is one) and writes omd; advance == 0: the call uses
+ * the omd a call with advance != 0 has left in the same workspace, on the same stream. One step = exactly one call with advance != 0.
+ *
+ * foc_optim_step_ema  foc_optim_step with shadows: `shadow` is a HOST array of step->n_tensors device addresses (0: that tensor has no
+ *     shadow and is updated exactly as foc_optim_step updates it). The update launch applies the rule to the p it has just computed;
+ *     16-byte accesses where param, grad, exp_avg, exp_avg_sq and the shadow are all 16-byte aligned, 4-byte accesses otherwise. A
+ *     SKIPPED step (overflow) leaves params, moments and step counters as they are, and the shadow still moves toward the unchanged
+ *     param by the rule, the counter still advances (the reference calls ema.update() after a skipped scaler.step too). omd is written
+ *     where the step record is: by the check's last workgroup (scale / growth_tracker form), by the one-workgroup record launch (the
+ *     other two forms), or in phase FOC_OPTIM_DECIDE (shadow may be NULL there: tensors are not read). The launches are those of
+ *     foc_optim_step, one for one. A step of more than 16 tensors: advance != 0 in the DECIDE call (scaler form) or in the first
+ *     group's call (other forms), 0 in every other call. FOC_OPTIM_CHECK takes no part in the EMA: advance != 0 there is refused.
+ *     Refused with FOC_E_INVALID before any launch: everything foc_optim_step refuses; a null shadow array in phase FOC_OPTIM_STEP;
+ *     decay outside [0, 1] or not finite; a shadow that is not 4-byte aligned; num_updates not 8-byte aligned.
+ * foc_ema_update  the rule alone, for parameters no optimizer step touches and for a bare update: param, shadow (device addresses)
+ *     and n (element counts) are three HOST arrays of n_tensors (1 .. FOC_OPTIM_MAX_TENSORS) entries; one launch of one workgroup per
+ *     FOC_OPTIM_CHUNK elements that reads p and reads and writes s (16-byte accesses where both are 16-byte aligned). With advance
+ *     != 0 every workgroup derives omd from the counter and the last one to finish stores the advanced counter and omd — no separate
+ *     launch, and a call whose tensors are all empty still advances. workspace: the optimizer's (foc_optim_workspace_bytes, zeroed
+ *     once, one stream at a time). Refused with FOC_E_INVALID before any launch: a null array; n_tensors outside 1 .. 16; decay
+ *     outside [0, 1] or not finite; a null or misaligned pointer (param, shadow: 4 bytes; num_updates: 8; workspace: 4); a negative
+ *     size; a workspace that is too small.
+ * `stream` is a hipStream_t. No order-dependent sums: FOC_DETERMINISTIC changes nothing here and refuses nothing.
+ * --------------------------------------------------------------------------- */
+int foc_optim_step_ema(const FocOptimStep *step, const uint64_t *shadow, double decay, int64_t *num_updates, uint32_t advance, void *stream);
+int foc_ema_update(const uint64_t *param, const uint64_t *shadow, const int64_t *n, int n_tensors, double decay, int64_t *num_updates,
+                   uint32_t advance, void *workspace, uint64_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Training batches and the photometric loss (csrc/batch.hip; no reference binding: the reference builds a batch with torch ops in
  * nerf/provider.py:398-447 NeRFDataset.collate and nerf/utils.py:57-157 get_rays, and its loss in nerf/utils.py:840-899
  * Trainer.train_step). One launch each, no host synchronisation, no float atomics: the same bits on every run, FOC_DETERMINISTIC
