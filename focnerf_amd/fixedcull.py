@@ -68,6 +68,28 @@ class Occupancy:
             densitygrid.grid_update_apply(grid, C, H, sigmas, None, model.density_scale, decay, thresh, bits)
         return cls(bits, C, H, model.bound)
 
+    @torch.no_grad()
+    def pruned(self, keep_largest=1, min_cells=None):
+        """A new `Occupancy` without the grid's floaters: per cascade the bits are unpacked, brought out of Morton order to a 0/1 volume
+        [H,H,H] (`raymarching.morton3D_invert`), filtered by `components.filter_components` at threshold 0.5 — the `keep_largest`
+        largest 26-connected components and / or those of at least `min_cells` cells stay — and packed into a bitfield of its own.
+        Cascades are independent (each holds the whole object at its own resolution; components are never joined across them). Culled
+        renders of the result keep a subset of this grid's samples. `self` is not modified."""
+        from . import raymarching
+        from .components import filter_components
+        C, H, dev = self.cascade, self.grid_size, self.bitfield.device
+        shifts = torch.arange(8, dtype=torch.int32, device=dev)
+        cells = ((self.bitfield.int().view(-1, 1) >> shifts) & 1).view(C, H ** 3)               # Morton order, cell index & 7 = the bit
+        xyz = raymarching.morton3D_invert(torch.arange(H ** 3, dtype=torch.int32, device=dev)).long()
+        lin = (xyz[:, 0] * H + xyz[:, 1]) * H + xyz[:, 2]
+        out = torch.empty_like(cells)
+        for c in range(C):
+            vol = torch.empty(H ** 3, dtype=torch.float32, device=dev)
+            vol[lin] = cells[c].float()
+            out[c] = (filter_components(vol.view(H, H, H), 0.5, keep_largest, min_cells).view(-1)[lin] >= 0.5).int()
+        bits = (out.view(-1, 8) << shifts).sum(-1, dtype=torch.int32).to(torch.uint8)
+        return Occupancy(bits, C, H, self.bound)
+
 
 def _host_floats(values, n, what):
     """`n` floats for a kernel argument block (ctypes array). A tensor is read on the host ONCE and remembered on the tensor object (a

@@ -1281,6 +1281,32 @@ int foc_scene_select(const float *sigma_c, const float *rgb_c, const float *norm
                      uint32_t n, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Connected components of a thresholded volume (csrc/components.hip; no reference binding: the reference hands its mesh to trimesh, where
+ * `split()` finds the floaters on the host). volume: fp32 u[nx, ny, nz], z fastest, the dimensions foc_mc_count serves (each >= 2,
+ * nx * ny * nz <= 2^29); lattice point i is inside iff u[i] >= thr (a NaN is outside): foc_mc_count's rule. Two inside points are
+ * connected when they differ by at most 1 in every coordinate (26-connectivity): the eight corners of a marching cube are mutually
+ * adjacent, so all inside corners of one cube lie in one component, and putting a component's points below the threshold removes exactly
+ * that component's triangles while every other vertex and triangle keeps its bits. A component's label is the SMALLEST LINEAR INDEX among
+ * its points: unique, hence the same bits on every run and in both deterministic modes, whatever order the unions ran in. Integer
+ * atomics only (atomicMin on the parent words, one atomicAdd per tile-local component for the sizes): nothing is refused under
+ * FOC_DETERMINISTIC. FOC_CC_NONE, the label of an outside point, is 0xFFFFFFFF (all bits set; -1 read as int32).
+ * foc_cc_label   labels [n] uint32: the component's smallest linear index, FOC_CC_NONE outside. sizes [n] uint32: the component's point
+ *                count at sizes[root], 0 everywhere else. counts4 [4] uint32 on the device: components, inside points, largest size,
+ *                error flag. workspace: foc_cc_workspace_bytes(nx, ny, nz) device bytes (0 for refused dimensions), 4-byte aligned, no
+ *                initialisation needed. Every find / union loop walks strictly down and is capped at n turns all the same; a loop that
+ *                reaches its cap sets the error flag and leaves (the result is then not to be used) — no loop can spin.
+ * foc_cc_select  out[i] = (labels[i] != FOC_CC_NONE && !keep[labels[i]]) ? fill : volume[i] for n <= 2^29 points; keep [n] uint8 is
+ *                indexed by root. out may be volume.
+ * Refused with FOC_E_INVALID before any launch, the message names the argument: a null pointer, dimensions foc_mc_count refuses, a
+ * non-finite thr, a workspace smaller than foc_cc_workspace_bytes, a NaN fill. No host synchronisation inside either call.
+ * --------------------------------------------------------------------------- */
+uint64_t foc_cc_workspace_bytes(uint32_t nx, uint32_t ny, uint32_t nz);
+int foc_cc_label(const float *volume, uint32_t nx, uint32_t ny, uint32_t nz, float thr, uint32_t *labels, uint32_t *sizes,
+                 void *workspace, uint64_t workspace_bytes, uint32_t *counts4, void *stream);
+int foc_cc_select(const float *volume, const uint32_t *labels, const uint8_t *keep, float fill, float *out, uint32_t n,
+                  void *stream);
+
+/* ---------------------------------------------------------------------------
  * Scoring a combined view (csrc/score.hip; no reference binding: COMBINED.py:335-378 process_images_with_background copies the float
  * image to the host and quantises it with numpy, :267-291 calculate_psnr, :295-332 ssim_rgba / ssim_channel run
  * scipy.ndimage.gaussian_filter forty times per view in float64). H * W in 1 .. 2^30 pixels, B in 1 .. 8 backgrounds, N = H * W,
