@@ -8,6 +8,7 @@ from .combine import Attribution  # noqa: F401  (per-object mattes, depths and t
 from .placement import Placement  # noqa: F401  (rotation, uniform scale and translation of an object in the combined render)
 from .mesh import (density_volume, scene_volume, marching_cubes, extract_geometry, extract_scene_geometry,  # noqa: F401  (triangle meshes
                    write_ply, save_mesh, Mesh, extract_mesh, extract_scene_mesh, read_ply_attributes)      # of objects and placed scenes)
+from .simplify import simplify_mesh, SimplifiedMesh  # noqa: F401  (vertex clustering on the device: meshes with fewer triangles)
 from .components import label_components, filter_components, Components  # noqa: F401  (connected components on the device: meshes and grids without floaters)
 from .query import query_scene, SceneSample  # noqa: F401  (a placed scene at arbitrary points: density, winning object, colour, normal)
 from .score import score_view, ViewScore  # noqa: F401  (PSNR and SSIM of a combined view for every background, on the device)
@@ -22,7 +23,7 @@ from .batch import DeviceDataset, RaySampler, photo_loss  # noqa: F401  (a train
 __all__ = ["raymarching", "gridencoder", "freqencoder", "ffmlp", "activation", "encoding", "shencoder",
            "renderer", "network", "combine", "fixedcull", "use_deterministic", "is_deterministic", "deterministic", "Attribution", "placement", "Placement",
            "mesh", "density_volume", "scene_volume", "marching_cubes", "extract_geometry", "extract_scene_geometry", "write_ply", "save_mesh",
-           "Mesh", "extract_mesh", "extract_scene_mesh", "read_ply_attributes", "components", "label_components", "filter_components", "Components", "query", "query_scene", "SceneSample",
+           "Mesh", "extract_mesh", "extract_scene_mesh", "read_ply_attributes", "simplify", "simplify_mesh", "SimplifiedMesh", "components", "label_components", "filter_components", "Components", "query", "query_scene", "SceneSample",
            "score", "score_view", "ViewScore",
            "normals", "density_gradient", "field_normals", "decode_normal_map", "render_normals", "normal_map_finish",
            "optim", "FusedAdam", "LossScaler", "ema", "ParameterEMA",

@@ -22,12 +22,12 @@
 #include "common.h"
 #include "occ_cell.h"
 #include "fc_place.h"
+#include "ms_scan.h"
 #include "fs_common.h"
 #include "unit_normal.h"
 #define MC_TABLE_ATTR __device__
 #include "mc_table.h"
 
-#define MS_GROUP 64u                       // chunks per wave
 #define MC_MAX_POINTS (1ull << 29)
 
 struct McDim { uint32_t nx, ny, nz, sx, n; };          // sx = ny * nz: the stride of x (y: nz, z: 1)
@@ -60,10 +60,6 @@ __device__ __forceinline__ uint32_t mc_case(const McCell &c, float thr) {
 __device__ __forceinline__ bool mc_crossed(float u0, float u1, float thr) { return (u0 >= thr) != (u1 >= thr); }
 __device__ __forceinline__ bool mc_finite(float v) { return fabsf(v) <= 3.402823466e38f; }     // false for NaN
 
-__device__ __forceinline__ uint64_t ms_shfl64(uint64_t v, uint32_t j) {
-    return ((uint64_t)(uint32_t)__shfl((int)(v >> 32), (int)j, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)v, (int)j, 64);
-}
-
 // the workspace of foc_mc_count / foc_mc_emit: W chunks, G groups
 struct McWs { uint32_t *totals; uint64_t *mx, *my, *mz, *mt; uint32_t *voff, *toff, *gv, *gt, *gb; };
 
@@ -95,54 +91,7 @@ __global__ void __launch_bounds__(256) k_mc_count(const float *__restrict__ vol,
     if (lane == 63) { ws.gv[g] = (uint32_t)vi; ws.gt[g] = (uint32_t)ti; ws.gb[g] = bad_any ? 1u : 0u; }
 }
 
-// ---------------------------------------------------------------- pass 2: one workgroup scans the group totals
-// a and b (b may be null) become exclusive prefix sums in place, c (may be null) is only summed; the first n_out of the three totals go to
-// out_a and out_b (either may be null)
-__global__ void __launch_bounds__(1024) k_ms_scan(uint32_t *__restrict__ a, uint32_t *__restrict__ b, const uint32_t *__restrict__ c, uint32_t n_groups,
-                                                  uint32_t *__restrict__ out_a, uint32_t *__restrict__ out_b, uint32_t n_out) {
-    __shared__ int wave_tot[3][16];
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    uint32_t carry[3] = {0, 0, 0};
-    for (uint32_t base = 0; base < n_groups; base += 1024) {
-        const uint32_t k = base + threadIdx.x;
-        int v[3], incl[3];
-        v[0] = k < n_groups ? (int)a[k] : 0;
-        v[1] = (b && k < n_groups) ? (int)b[k] : 0;
-        v[2] = (c && k < n_groups) ? (int)c[k] : 0;
-#pragma unroll
-        for (int q = 0; q < 3; q++) {
-            incl[q] = wave_incl_sum_i(v[q], (int)lane);
-            if (lane == 63) wave_tot[q][wv] = incl[q];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 3; q++) {
-            int before = 0, all = 0;
-#pragma unroll
-            for (int u = 0; u < 16; u++) { const int t = wave_tot[q][u]; all += t; if (u < (int)wv) before += t; }
-            if (k < n_groups) {
-                if (q == 0) a[k] = carry[0] + (uint32_t)(before + incl[0] - v[0]);
-                if (q == 1 && b) b[k] = carry[1] + (uint32_t)(before + incl[1] - v[1]);
-            }
-            carry[q] += (uint32_t)all;
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x < n_out) {
-        const uint32_t t = threadIdx.x == 0 ? carry[0] : threadIdx.x == 1 ? carry[1] : carry[2];
-        if (out_a) out_a[threadIdx.x] = t;
-        if (out_b) out_b[threadIdx.x] = t;
-    }
-}
-
-// ---------------------------------------------------------------- pass 3: offsets[chunk] += base of the chunk's group
-__global__ void __launch_bounds__(256) k_ms_finish(const uint32_t *__restrict__ base_a, uint32_t *__restrict__ off_a, const uint32_t *__restrict__ base_b,
-                                                   uint32_t *__restrict__ off_b, uint32_t W) {
-    for (uint32_t c = blockIdx.x * 256 + threadIdx.x; c < W; c += gridDim.x * 256) {
-        off_a[c] += base_a[c / MS_GROUP];
-        if (off_b) off_b[c] += base_b[c / MS_GROUP];
-    }
-}
+// passes 2 and 3 (k_ms_scan: one workgroup scans the group totals; k_ms_finish: offsets[chunk] += base of the chunk's group): ms_scan.h
 
 // ---------------------------------------------------------------- marching cubes, emit
 // number of the vertex on the edge of axis `a` owned by lattice point q: (owner, axis) order inside the owner's chunk, after the chunk's offset
@@ -384,9 +333,6 @@ __global__ void __launch_bounds__(256) k_surface_frame(const float *__restrict__
 }
 
 // ---------------------------------------------------------------- host side
-static inline uint32_t ms_chunks(uint64_t n) { return foc_div_up(n, 64); }
-static inline uint32_t ms_groups(uint32_t W) { return foc_div_up(W, MS_GROUP); }
-
 static bool mc_dims_ok(const char *who, uint32_t nx, uint32_t ny, uint32_t nz) {
     if (nx < 2 || ny < 2 || nz < 2) { foc_set_error("%s: every dimension must be >= 2 (got %u x %u x %u)", who, nx, ny, nz); return false; }
     if ((uint64_t)nx * ny > MC_MAX_POINTS || (uint64_t)nx * ny * nz > MC_MAX_POINTS) {

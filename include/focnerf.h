@@ -1307,6 +1307,54 @@ int foc_cc_select(const float *volume, const uint32_t *labels, const uint8_t *ke
                   void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Mesh simplification by vertex clustering on a cell grid (csrc/simplify.hip; no reference binding: the reference hands its mesh to
+ * trimesh, where a user decimates on the host). vertices [V,3] fp32, triangles [F,3] int32, V and F <= 2^31 - 1. The grid: origin3 and
+ * cell3, 3 floats each IN HOST MEMORY (cell finite and > 0 with a finite 1 / cell), and gx, gy, gz >= 1 with gx * gy * gz <= 2^30;
+ * inv = 1.0f / cell in fp32. The definition, which tests/simplify_ref.py states in numpy and the kernels follow bit for bit:
+ *   1. Per axis t = (v - origin) * inv — one fp32 subtraction, one fp32 multiplication, never fused, never a division;
+ *      c = clamp(floor(t), 0, g - 1); r = clamp(t - float(c), 0, 1); cell number k = (cx * gy + cy) * gz + cz. A vertex outside the
+ *      grid belongs to the border cell and counts as lying on its border.
+ *   2. A triangle survives iff its three corners lie in three different cells.
+ *   3. A cell is kept iff a surviving triangle has a corner in it; kept cells are numbered 0 .. Vc - 1 in rising k. vertex_map[v] is the
+ *      number of v's cell, or -1 when that cell is not kept (a vertex no triangle uses; a cell all of whose triangles collapsed): the
+ *      output has no unreferenced vertex.
+ *   4. The vertex of a kept cell is the mean of ALL input vertices in it: per axis q = (int64)(r * 2^30) (the product is exact), S = the
+ *      int64 sum, m = (double)S / (double)count / 2^30, x = fp32(origin + (c + m) * cell) with every double operation rounded on its
+ *      own. members = count.
+ *   5. Normal: per component the int64 sum of (int64)(clamp(n, -1, 1) * 2^30), a non-finite component counting 0; s / sqrt(sx sx + sy sy
+ *      + sz sz) in double, summed left to right, 0 for length 0. Colour: the mean of clamp(c, 0, 1), a NaN counting 0, through the same
+ *      fixed point. Object id: that of the member with the smallest vertex index.
+ *   6. Output triangles: the survivors in input order, renumbered through vertex_map and rotated so that the smallest number stands
+ *      first (orientation is preserved; a closed input gives a closed output, counted with multiplicity).
+ * Integer atomics only (64-bit or / add, 32-bit add / max): nothing depends on the order of arrival, the same bits on every run, and
+ * nothing is refused under FOC_DETERMINISTIC.
+ * foc_simplify_count  fills workspace (foc_simplify_workspace_bytes(V, F, gx, gy, gz) device bytes, 8-byte aligned, no initialisation
+ *                     needed; 0 is returned for sizes that are refused) and writes counts4 [4] uint32 on the device: Vc, Fc, the number
+ *                     of vertices with a non-finite coordinate, the number of triangles with an index outside [0, V). The caller refuses
+ *                     the mesh when either of the last two is not 0. No index is read through before it is range-checked. V = 0 and
+ *                     F = 0 are served (Vc = Fc = 0).
+ * foc_simplify_emit   after the caller read counts4 (its one synchronisation) and found Vc >= 1, Fc >= 1 and no flag, with the SAME
+ *                     mesh, grid and workspace: out_vertices [Vc,3] fp32, members [Vc] int32, vertex_map [V] int32, out_triangles
+ *                     [Fc,3] int32, and for each attribute given (normals / colors [V,3] fp32, object_id [V] int32; NULL in pairs with
+ *                     its output) out_normals / out_colors [Vc,3] fp32, out_object_id [Vc] int32. accum: foc_simplify_accum_bytes(Vc,
+ *                     normals != NULL, colors != NULL) device bytes, 8-byte aligned, zeroed by the call. Nothing is written past Vc / Fc
+ *                     rows (the stores are guarded by the totals kept in the workspace as well).
+ * Refused with FOC_E_INVALID before any launch, the message names the argument: a null pointer, V or F beyond 2^31 - 1, dims outside
+ * the limit, a non-finite origin3, a cell3 that is not finite, not > 0 or whose reciprocal overflows, a workspace or accum smaller than
+ * asked for, attribute pointers not in pairs, and for the emit Vc or Fc of 0 or beyond V / F. No host synchronisation inside.
+ * --------------------------------------------------------------------------- */
+uint64_t foc_simplify_workspace_bytes(uint32_t V, uint32_t F, uint32_t gx, uint32_t gy, uint32_t gz);
+uint64_t foc_simplify_accum_bytes(uint32_t Vc, int normals, int colors);
+int foc_simplify_count(const float *vertices, uint32_t V, const int32_t *triangles, uint32_t F, const float *origin3,
+                       const float *cell3, uint32_t gx, uint32_t gy, uint32_t gz, void *workspace, uint64_t workspace_bytes,
+                       uint32_t *counts4, void *stream);
+int foc_simplify_emit(const float *vertices, uint32_t V, const int32_t *triangles, uint32_t F, const float *normals,
+                      const float *colors, const int32_t *object_id, const float *origin3, const float *cell3, uint32_t gx,
+                      uint32_t gy, uint32_t gz, const void *workspace, void *accum, uint64_t accum_bytes, uint32_t Vc, uint32_t Fc,
+                      float *out_vertices, float *out_normals, float *out_colors, int32_t *out_object_id, int32_t *vertex_map,
+                      int32_t *members, int32_t *out_triangles, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Scoring a combined view (csrc/score.hip; no reference binding: COMBINED.py:335-378 process_images_with_background copies the float
  * image to the host and quantises it with numpy, :267-291 calculate_psnr, :295-332 ssim_rgba / ssim_channel run
  * scipy.ndimage.gaussian_filter forty times per view in float64). H * W in 1 .. 2^30 pixels, B in 1 .. 8 backgrounds, N = H * W,
